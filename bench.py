@@ -11,8 +11,14 @@ value = directed edges collision-checked per second (whole job, all ranks).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4|C3|C5] [--scaling weak|strong]
                     [--obstacles spheres|polygons] [--shard edges|obstacles] [--grid ExO] [--batch B]
+                    [--full] [--dump-outputs DIR]
     (--config C5: one replanning cycle of BASELINE config 5 per step, see bench_c5)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the result line (value, ms_per_step, ...).  --full adds
+everything else: per-kernel times and rooflines, CPU baselines, the other scaling mode, the large batch, the steady
+state, the host-pointer and polygon passes.  --dump-outputs DIR writes the arrays the last timed step returned as
+DIR/<name>.npy (float64; a fixed, seeded sample of each array when they exceed 64 MB together).
 
 Multi-GPU: node SoA and obstacle list are replicated (4.8 MB and 8 KB -- trivially small next
 to 288 GB of HBM).  --scaling weak (default): every rank owns its own batches of B samples.
@@ -42,6 +48,23 @@ FP64_VALU_PEAK_TOPS = 39.3     # 78.6 TFLOP/s FMA-counted vector fp64 => 39.3 T 
 ROBOT_RADIUS = 0.5             # R/experimentsForRRTQX.jl:38
 METRIC = "collision-checked edges/sec + radius-NN queries/sec at N=200k nodes, 256 obs"
 RING = 8                       # pre-generated sample batches per rank
+DUMP_BYTES = 60_000_000        # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SEED = 20240611           # fixed seed of the sample taken of outputs larger than that
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> 1-D tensor or array, what the caller of the timed path receives) as
+    path/<name>.npy in float64 (int32 / int64 indices and uint8 flags are exact in it).  Above DUMP_BYTES every array
+    keeps the same fraction of its entries, chosen by DUMP_SEED: the same positions for the same lengths, run to run."""
+    arrays = {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)).reshape(-1) for k, v in arrays.items()}
+    total = 8 * sum(a.size for a in arrays.values())
+    keep = min(1.0, DUMP_BYTES / max(total, 1))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if keep < 1.0:
+            pos = np.random.default_rng(DUMP_SEED).choice(a.size, int(a.size * keep), replace=False)
+            a = a[np.sort(pos)]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def lib_sha16():
@@ -325,29 +348,21 @@ def bench_c3(args, torch, dist, dev, rank, world):
         compute()
     fence()
     dt = time.perf_counter() - t0
-    ctx.profile(2)
-    for _ in range(2):
-        compute()
-    fence()
-    st = ctx.stats()
-    ctx.profile(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"offsets": d_off, "idx": d_idx[:k_total], "key": d_key[:k_total],
+                                         "cost_out": d_co[:k_total], "cost_in": d_ci[:k_total], "hit_out": d_ho[:k_total],
+                                         "hit_in": d_hi[:k_total], "nearest_idx": d_ni, "nearest_dist": d_nd,
+                                         "sample_unsafe": d_un})
+    if args.full:
+        ctx.profile(2)
+        for _ in range(2):
+            compute()
+        fence()
+        st = ctx.stats()
+        ctx.profile(0)
     e_sum, t_max = parallel.reduce_throughput(2 * k_total * steps, dt, device=dev)
     if rank == 0:
-        # per step: the check launches (both directions, every chunk) and the steering launches, summed
-        dub_ms = st.ms_dubins / 2
-        steer_ms = st.ms_dubins_steer / 2
-        chk_launches = st.launches_dubins // 2
-        # Dubins steering + two-stage check is fp64 arithmetic: ~400 flops per steer plus, per
-        # polyline piece that reaches stage 2, the polygon test.  The steering figure alone is a floor.
         rk = make_run_key(args)
-        d_kernel = "dubins_check_rec_kernel<false>"
-        # the check kernel's own duration: rocprof names it; the family timer covers steer + check launches together
-        tj = load_pmc(d_kernel, rk)
-        if tj:      # the passes average per LAUNCH; a step is chk_launches launches of the kernel
-            tj = dict(tj)
-            for kk in ("SQ_INSTS_VALU_per_launch", "SQ_INSTS_SALU_per_launch", "traffic_bytes_per_launch"):
-                if tj.get(kk) is not None:
-                    tj[kk] = tj[kk] * chk_launches
         out = {
             "metric": METRIC, "value": e_sum / t_max, "unit": "edges/s", "n_gpus": world, "steps": steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * t_max / steps, "higher_is_better": True, "scaling": "weak",
@@ -356,17 +371,32 @@ def bench_c3(args, torch, dist, dev, rank, world):
                        "batch_per_gpu": B, "radius": r, "edge": "DubinsEdge", "min_turning_radius": r_min,
                        "directed_edges_per_step_per_gpu": 2 * k_total},
             "nn_queries_per_s": B * world * steps / t_max,
-            "kernel_ms": {"nn_scan": st.ms_nn_scan / max(st.launches_nn_scan, 1),
-                          "nn_finish": st.ms_nn_finish / 2, "dubins_check": dub_ms, "dubins_steer": steer_ms,
-                          "dubins_check_launches_per_step": chk_launches,
-                          "points": st.ms_points / max(st.launches_points, 1)},
-            "roofline": issue_roofline(d_kernel, tj, dub_ms,
-                                       "; kernel_ms and the instruction counts are the SUM over the check kernel's launches of "
-                                       "one step (both directions, every chunk of 2 M edges); steering is a launch of its own "
-                                       "(kernel_ms.dubins_steer), DESIGN.md 4.6"),
             "run_key": rk, "hip_runtime": _capi.hip_runtime(), "lib_sha16": lib_sha16(), "source_sha16": source_sha16(),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            # per step: the check launches (both directions, every chunk) and the steering launches, summed
+            dub_ms = st.ms_dubins / 2
+            steer_ms = st.ms_dubins_steer / 2
+            chk_launches = st.launches_dubins // 2
+            # Dubins steering + two-stage check is fp64 arithmetic: ~400 flops per steer plus, per
+            # polyline piece that reaches stage 2, the polygon test.  The steering figure alone is a floor.
+            d_kernel = "dubins_check_rec_kernel<false>"
+            # the check kernel's own duration: rocprof names it; the family timer covers steer + check launches together
+            tj = load_pmc(d_kernel, rk)
+            if tj:      # the passes average per LAUNCH; a step is chk_launches launches of the kernel
+                tj = dict(tj)
+                for kk in ("SQ_INSTS_VALU_per_launch", "SQ_INSTS_SALU_per_launch", "traffic_bytes_per_launch"):
+                    if tj.get(kk) is not None:
+                        tj[kk] = tj[kk] * chk_launches
+            out["kernel_ms"] = {"nn_scan": st.ms_nn_scan / max(st.launches_nn_scan, 1),
+                                "nn_finish": st.ms_nn_finish / 2, "dubins_check": dub_ms, "dubins_steer": steer_ms,
+                                "dubins_check_launches_per_step": chk_launches,
+                                "points": st.ms_points / max(st.launches_points, 1)}
+            out["roofline"] = issue_roofline(d_kernel, tj, dub_ms,
+                                             "; kernel_ms and the instruction counts are the SUM over the check kernel's launches "
+                                             "of one step (both directions, every chunk of 2 M edges); steering is a launch of its "
+                                             "own (kernel_ms.dubins_steer), DESIGN.md 4.6")
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_dubins(pts, Q, polys, r, r_min)
         print(json.dumps(out))
     if world > 1:
@@ -500,6 +530,7 @@ def bench_c5(args, torch, dist, dev, rank, world):
 
     phase = {k: 0.0 for k in ("obstacle_appears", "sweep", "block", "cost_update", "extend_preamble", "append")}
     counts = {"sweep_candidates": 0, "edges_blocked": 0, "neighbours": 0}
+    last = {}                                              # host results of the latest cycle (--dump-outputs)
 
     def cycle(i, timed):
         j = appear[i]
@@ -514,7 +545,8 @@ def bench_c5(args, torch, dist, dev, rank, world):
             ctx.graph_edges_block(ids)
         torch.cuda.synchronize()
         t.append(time.perf_counter())
-        ctx.graph_cost_update(root, want_parent=False)
+        lmc, _, _ = ctx.graph_cost_update(root, want_parent=False)
+        last.update(blocked_edges=ids, lmc=lmc)
         t.append(time.perf_counter())
         n_now = N + i * B
         ri = synth.ball_radius(n_now, 4, gamma=100.0, delta=10.0)
@@ -549,29 +581,28 @@ def bench_c5(args, torch, dist, dev, rank, world):
         raise SystemExit(f"candidate capacity too small in a timed cycle: {max(ks)} > {cap}")
     counts["neighbours"] = sum(ks)
     units = counts["sweep_candidates"] + 2 * sum(ks)           # directed Dubins edges put through explicitEdgeCheck
-    # per-family device time of the last cycle's preamble
-    ctx.profile(2)
-    r_last = synth.ball_radius(N + (warm + steps) * B, 4, gamma=100.0, delta=10.0)
-    ctx.extend_candidates_dubins_dev(d_q[0].data_ptr(), B, r_last, rr, r_min, d_off.data_ptr(), d_idx.data_ptr(),
-                                     d_key.data_ptr(), d_co.data_ptr(), d_ci.data_ptr(), None, None, d_ho.data_ptr(),
-                                     d_hi.data_ptr(), cap, d_need.data_ptr() + 8 * (steps + warm), d_ni.data_ptr(), d_nd.data_ptr(),
-                                     d_un.data_ptr())
-    fence()
-    st = ctx.stats()
-    ctx.profile(0)
-    if int(d_need[steps + warm].item()) > cap:
-        raise SystemExit("candidate capacity too small in the profiled pass")
+    if args.dump_outputs and rank == 0:
+        k = ks[-1]
+        dump_outputs(args.dump_outputs, {"blocked_edges": last["blocked_edges"], "lmc": last["lmc"], "offsets": d_off,
+                                         "idx": d_idx[:k], "key": d_key[:k], "cost_out": d_co[:k], "cost_in": d_ci[:k],
+                                         "hit_out": d_ho[:k], "hit_in": d_hi[:k], "nearest_idx": d_ni, "nearest_dist": d_nd,
+                                         "sample_unsafe": d_un})
+    if args.full:
+        # per-family device time of the last cycle's preamble
+        ctx.profile(2)
+        r_last = synth.ball_radius(N + (warm + steps) * B, 4, gamma=100.0, delta=10.0)
+        ctx.extend_candidates_dubins_dev(d_q[0].data_ptr(), B, r_last, rr, r_min, d_off.data_ptr(), d_idx.data_ptr(),
+                                         d_key.data_ptr(), d_co.data_ptr(), d_ci.data_ptr(), None, None, d_ho.data_ptr(),
+                                         d_hi.data_ptr(), cap, d_need.data_ptr() + 8 * (steps + warm), d_ni.data_ptr(),
+                                         d_nd.data_ptr(), d_un.data_ptr())
+        fence()
+        st = ctx.stats()
+        ctx.profile(0)
+        if int(d_need[steps + warm].item()) > cap:
+            raise SystemExit("candidate capacity too small in the profiled pass")
     e_sum, t_max = parallel.reduce_throughput(units, dt, device=dev)
     if rank == 0:
         rk = make_run_key(args)
-        d_kernel = "dubins_check_rec_kernel<true>"
-        tj = load_pmc(d_kernel, rk)
-        chk_launches = int(st.launches_dubins)
-        if tj:
-            tj = dict(tj)
-            for kk in ("SQ_INSTS_VALU_per_launch", "SQ_INSTS_SALU_per_launch", "traffic_bytes_per_launch"):
-                if tj.get(kk) is not None:
-                    tj[kk] = tj[kk] * chk_launches
         out = {
             "metric": METRIC, "value": e_sum / t_max, "unit": "edges/s", "n_gpus": world, "steps": steps, "warmup": warm,
             "ms_per_step": 1e3 * t_max / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -591,15 +622,24 @@ def bench_c5(args, torch, dist, dev, rank, world):
             "per_cycle": {k: v / steps for k, v in counts.items()},
             "initial_solve": {"root": root, "passes": int(passes0), "reachable_nodes": int(np.isfinite(lmc0).sum()),
                               "edges_forward_in_reverse_time": n_valid},
-            "kernel_ms": {"nn_scan": st.ms_nn_scan / max(st.launches_nn_scan, 1), "nn_finish": st.ms_nn_finish,
-                          "dubins_check": st.ms_dubins, "dubins_steer": st.ms_dubins_steer,
-                          "dubins_check_launches": chk_launches, "points": st.ms_points},
-            "roofline": issue_roofline(d_kernel, tj, st.ms_dubins,
-                                       "; kernel_ms and the instruction counts are the SUM over the check kernel's launches of one "
-                                       "preamble (both directions, every chunk of 2 M edges)"),
             "run_key": rk, "hip_runtime": _capi.hip_runtime(), "lib_sha16": lib_sha16(), "source_sha16": source_sha16(),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            d_kernel = "dubins_check_rec_kernel<true>"
+            tj = load_pmc(d_kernel, rk)
+            chk_launches = int(st.launches_dubins)
+            if tj:
+                tj = dict(tj)
+                for kk in ("SQ_INSTS_VALU_per_launch", "SQ_INSTS_SALU_per_launch", "traffic_bytes_per_launch"):
+                    if tj.get(kk) is not None:
+                        tj[kk] = tj[kk] * chk_launches
+            out["kernel_ms"] = {"nn_scan": st.ms_nn_scan / max(st.launches_nn_scan, 1), "nn_finish": st.ms_nn_finish,
+                                "dubins_check": st.ms_dubins, "dubins_steer": st.ms_dubins_steer,
+                                "dubins_check_launches": chk_launches, "points": st.ms_points}
+            out["roofline"] = issue_roofline(d_kernel, tj, st.ms_dubins,
+                                             "; kernel_ms and the instruction counts are the SUM over the check kernel's launches "
+                                             "of one preamble (both directions, every chunk of 2 M edges)")
+        if world == 1 and args.full and not args.no_cpu_baseline:
             act0 = act.copy()
             out["cpu_baseline"] = cpu_baseline_c5(pts, es, ee, polys, kinds, paths, act0, appear[warm], Qs[warm % RING], r,
                                                   r_min, rr, delta)
@@ -676,7 +716,14 @@ def main():
                     help="multi-GPU: what the ranks split -- the sample / candidate-edge batch (default), or the obstacle list "
                          "(every rank checks all edges against its obstacles, flags OR-reduced with all_reduce(MAX))")
     ap.add_argument("--grid", default="", help="multi-GPU: ExO = E edge shards x O obstacle shards (E * O = --gpus)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: per-kernel times and rooflines, CPU baselines, the other scaling mode, "
+                         "large-batch, steady-state, host-pointer and polygon passes (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This happens BEFORE anything touches
     # the GPU (no torch import yet), as a child process -- a process that has initialised HIP must never be replaced.
@@ -733,7 +780,8 @@ def main():
     obs_group = parallel.obstacle_groups(world, E, O, rank)
     use_polys = args.obstacles == "polygons"
     o_lo, o_hi = parallel.shard_range(M, o_idx, O)           # this rank's list positions
-    steady_steps = 0 if (args.no_extras or use_polys or O > 1 or args.batch) else args.steps
+    extras_on = args.full and not args.no_extras
+    steady_steps = 0 if (not extras_on or use_polys or O > 1 or args.batch) else args.steps
     ctx = Context(3, device=local_rank, node_capacity=N)
     stream = torch.cuda.current_stream()
     ctx.set_stream(stream.cuda_stream)          # kernels, events and torch share one stream
@@ -887,16 +935,23 @@ def main():
         edges = sum(2 * k_ring[i % RING] for i in range(steps)) if o_idx == 0 else 0
         return edges, dt, st, k_ring, sample_every
 
-    modes = [args.scaling] + ([("strong" if args.scaling == "weak" else "weak")] if E > 1 else [])
+    # a plain run: the headline mode alone, no events in its timed loop; --full: in-loop kernel events and the other mode
+    modes = [args.scaling] + ([("strong" if args.scaling == "weak" else "weak")] if E > 1 and args.full else [])
     results = {}
     for mode in modes:
         m = make_mode(mode)
-        edges, dt, st, k_ring, sample_every = run_mode(m, args.steps, args.warmup, profile=(mode == modes[0]))
+        edges, dt, st, k_ring, sample_every = run_mode(m, args.steps, args.warmup, profile=args.full and mode == modes[0])
         e_sum, t_max = parallel.reduce_throughput(edges, dt, device=dev)
         results[mode] = {"m": m, "edges": edges, "dt": dt, "st": st, "k_ring": k_ring, "e_sum": e_sum, "t_max": t_max,
                          "sample_every": sample_every}
+        if mode == modes[0] and args.dump_outputs and rank == 0:
+            # the buffers still hold the last timed step (batch (steps - 1) % RING) of this rank
+            b, nb, k = m["buf"], m["nb"], k_ring[(args.steps - 1) % RING]
+            dump_outputs(args.dump_outputs, {"offsets": b.off[:nb + 1], "idx": b.idx[:k], "cost": b.cost[:k],
+                                             "hit_out": b.hout[:k], "hit_in": b.hin[:k], "nearest_idx": b.nidx[:nb],
+                                             "nearest_dist": b.ndist[:nb], "sample_unsafe": b.unsafe[:nb]})
     large = None
-    if not args.no_extras and not args.batch:
+    if extras_on and not args.batch:
         # the same step at a batch that is several grid waves per kernel (B = 131072): strong-sharded over the edge
         # shards when there are any -- at B = 16384 a step is four launch-bound kernels and splitting it removes
         # workgroups, not chain length; this is the line where splitting the batch can pay
@@ -915,7 +970,7 @@ def main():
     k_mean = sum(k_ring) / len(k_ring)
 
     extras = {}
-    if not args.no_extras:
+    if extras_on:
         # per-family device time in a short pass of its own (an event record between two kernels costs
         # ~10 us of pipeline drain, which must not sit inside the timed region)
         ctx.profile(2)
@@ -987,47 +1042,7 @@ def main():
         e_sum, t_max = main_r["e_sum"], main_r["t_max"]
         nb = m["nb"]
         ms_step = 1e3 * t_max / args.steps
-        scan_ms = st.ms_nn_scan / max(st.launches_nn_scan, 1)
-        tile_q = int(st.last_tile_q)   # query copies sharing one streamed pass of the node arrays
-        n_tiles = (nb + tile_q - 1) // tile_q
-        units = int(st.last_scan_units)  # slab-culled scan: (tile, 512-node chunk) pairs actually streamed (last call)
-        k_last = k_ring[(args.steps - 1) % RING]
-        node_visits = units * 512 if units > 0 else n_tiles * N
-        # SURVEY 8(d) contract figure: node passes x 24 B (fp64 x, y, z of every node visit) + queries + hit records
-        bytes_alg = node_visits * 24 + nb * 32 + k_last * 16
-        # what the kernel really requests: the fp32 screen record of a node is 16 B (x, y, z, |p|^2); each entry the
-        # screen leaves over re-reads the fp64 rows of its lane's 8 nodes (3 x 64 B); 16-B hit records out
-        culled = units > 0
-        kernel = (("nn_tile_kernel<3, false>" if use_polys else "nn_tile_kernel<3, true>") if culled
-                  else "nn_scan_f32_kernel<3> + nn_confirm_kernel<3>") if args.nn_filter else "nn_scan_kernel<3>"
-        bytes_req = node_visits * 16 + nb * 48 + k_last * (192 + 16 + 8)
-        # the in-loop figure comes from few launches (every 10th step carries events); the separate pass times EVERY launch
-        scan_ms_loop = scan_ms
-        sep = extras.get("kernel_ms_all", {}).get("nn_scan_separate_pass")
-        if sep:
-            scan_ms = sep
-        alg_gbs = bytes_alg / (scan_ms * 1e-3) / 1e9
-        traffic, traffic_src, frac_traffic, hbm_gbs, issue = None, None, None, None, None
         rk = make_run_key(args)
-        # counters cannot be read inside this process; the committed PMC passes count only when they were taken on
-        # these kernel sources AND this run key (configuration, obstacle list, batch, tuning options)
-        tj = load_pmc(kernel, rk) if world == 1 else None
-        if tj and tj.get("traffic_bytes_per_launch"):
-            traffic = tj["traffic_bytes_per_launch"]
-            traffic_src = f"{tj['file']} (rocprofv3 PMC passes, sources {tj['source_sha16']}, lib match {tj['lib_match']})"
-            hbm_gbs = traffic / (scan_ms * 1e-3) / 1e9
-            frac_traffic = hbm_gbs / HBM_PEAK_GBS
-        issue = issue_block(tj, scan_ms)
-        roof_bf = None
-        bf = extras.get("bf")
-        if bf:
-            nt = (nb + bf["tile_q"] - 1) // bf["tile_q"]
-            by = nt * N * 24 + nb * 32 + k_ring[0] * 16
-            ach = by / (bf["scan_ms"] * 1e-3) / 1e9
-            roof_bf = {"kernel": "nn_scan_f32_kernel<3> + nn_confirm_kernel<3> (RRTX_OPT_NN_CULL=0)", "bound": "hbm",
-                       "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                       "algorithmic_bytes_per_launch": by, "tile_q": bf["tile_q"], "ms": bf["scan_ms"],
-                       "pairs_per_s": nb * N / (bf["scan_ms"] * 1e-3)}
         out = {
             "metric": METRIC,
             "value": e_sum / t_max,
@@ -1058,8 +1073,54 @@ def main():
                                        % max(1, args.exchange_every)))},
             "nn_queries_per_s": (nb * E if modes[0] == "weak" else B) * args.steps / t_max,
             "launches_per_step": 4,
-            "kernel_ms": {"nn_scan": scan_ms, **extras.get("kernel_ms_all", {})},
-            "roofline": {
+            "run_key": rk,
+            "hip_runtime": _capi.hip_runtime(),
+            "lib_sha16": lib_sha16(),
+            "source_sha16": source_sha16(),
+        }
+        if args.full:
+            scan_ms = st.ms_nn_scan / max(st.launches_nn_scan, 1)
+            tile_q = int(st.last_tile_q)   # query copies sharing one streamed pass of the node arrays
+            n_tiles = (nb + tile_q - 1) // tile_q
+            units = int(st.last_scan_units)  # slab-culled scan: (tile, 512-node chunk) pairs actually streamed (last call)
+            k_last = k_ring[(args.steps - 1) % RING]
+            node_visits = units * 512 if units > 0 else n_tiles * N
+            # SURVEY 8(d) contract figure: node passes x 24 B (fp64 x, y, z of every node visit) + queries + hit records
+            bytes_alg = node_visits * 24 + nb * 32 + k_last * 16
+            # what the kernel really requests: the fp32 screen record of a node is 16 B (x, y, z, |p|^2); each entry the
+            # screen leaves over re-reads the fp64 rows of its lane's 8 nodes (3 x 64 B); 16-B hit records out
+            culled = units > 0
+            kernel = (("nn_tile_kernel<3, false>" if use_polys else "nn_tile_kernel<3, true>") if culled
+                      else "nn_scan_f32_kernel<3> + nn_confirm_kernel<3>") if args.nn_filter else "nn_scan_kernel<3>"
+            bytes_req = node_visits * 16 + nb * 48 + k_last * (192 + 16 + 8)
+            # the in-loop figure comes from few launches (every 10th step carries events); the separate pass times EVERY launch
+            scan_ms_loop = scan_ms
+            sep = extras.get("kernel_ms_all", {}).get("nn_scan_separate_pass")
+            if sep:
+                scan_ms = sep
+            alg_gbs = bytes_alg / (scan_ms * 1e-3) / 1e9
+            traffic, traffic_src, frac_traffic, hbm_gbs, issue = None, None, None, None, None
+            # counters cannot be read inside this process; the committed PMC passes count only when they were taken on
+            # these kernel sources AND this run key (configuration, obstacle list, batch, tuning options)
+            tj = load_pmc(kernel, rk) if world == 1 else None
+            if tj and tj.get("traffic_bytes_per_launch"):
+                traffic = tj["traffic_bytes_per_launch"]
+                traffic_src = f"{tj['file']} (rocprofv3 PMC passes, sources {tj['source_sha16']}, lib match {tj['lib_match']})"
+                hbm_gbs = traffic / (scan_ms * 1e-3) / 1e9
+                frac_traffic = hbm_gbs / HBM_PEAK_GBS
+            issue = issue_block(tj, scan_ms)
+            roof_bf = None
+            bf = extras.get("bf")
+            if bf:
+                nt = (nb + bf["tile_q"] - 1) // bf["tile_q"]
+                by = nt * N * 24 + nb * 32 + k_ring[0] * 16
+                ach = by / (bf["scan_ms"] * 1e-3) / 1e9
+                roof_bf = {"kernel": "nn_scan_f32_kernel<3> + nn_confirm_kernel<3> (RRTX_OPT_NN_CULL=0)", "bound": "hbm",
+                           "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                           "algorithmic_bytes_per_launch": by, "tile_q": bf["tile_q"], "ms": bf["scan_ms"],
+                           "pairs_per_s": nb * N / (bf["scan_ms"] * 1e-3)}
+            out["kernel_ms"] = {"nn_scan": scan_ms, **extras.get("kernel_ms_all", {})}
+            out["roofline"] = {
                 "kernel": kernel, "bound": "hbm", "achieved": alg_gbs, "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": alg_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes/launch",
                 "traffic_source": traffic_src,
@@ -1087,13 +1148,8 @@ def main():
                          "(instruction issue + the dependency chain of one workgroup), see DESIGN.md 4.1.  The same kernel "
                          "also decides both collision flags of every neighbour (fused extend path).") if culled else
                         "VALU-issue bound, node arrays are L2-resident; see DESIGN.md",
-            },
-            "roofline_bruteforce": roof_bf,
-            "run_key": rk,
-            "hip_runtime": _capi.hip_runtime(),
-            "lib_sha16": lib_sha16(),
-            "source_sha16": source_sha16(),
-        }
+            }
+            out["roofline_bruteforce"] = roof_bf
         if len(modes) > 1:
             o = results[modes[1]]
             out["other_scaling"] = {"scaling": modes[1], "value": o["e_sum"] / o["t_max"],
@@ -1110,7 +1166,7 @@ def main():
         if steady:
             out["steady_state"] = steady
             out["value_steady"] = steady["value_steady"]
-        if world == 1 and not args.no_extras and not use_polys:
+        if world == 1 and extras_on and not use_polys:
             # the same step through the host-pointer entry point (what a ccall from Julia pays):
             # H2D of the samples, kernels, D2H of lists/costs/flags.  Reported, never `value`.
             ctx.set_stream(None)
@@ -1177,7 +1233,7 @@ def main():
             ctx.set_stream(None)
         if world == 1 and args.agents > 1:
             out["concurrent_agents"] = concurrent_agents(args.agents, torch, dev, pts, sph, r, B, cap, N)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, pts, m["host_q"][0], sph, r, polys=polys_all if use_polys else None)
         print(json.dumps(out))
     if world > 1:

@@ -18,7 +18,8 @@ def test_bench_help_runs_without_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--shard", "--grid", "--obstacles", "--batch"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--shard", "--grid", "--obstacles", "--batch", "--full",
+                 "--dump-outputs"):
         assert flag in r.stdout
 
 

@@ -14,15 +14,15 @@ if has tests; then
   rc=$?; tail -3 $out/pytest_gpu.log; echo "pytest rc=$rc"; [ $rc -ne 0 ] && exit $rc
 fi
 if has bench; then
-  timeout -k 10 500 python3 bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
-  timeout -k 10 500 python3 bench.py --obstacles polygons > $out/bench_poly.json 2> $out/bench_poly.err; echo "bench_poly rc=$?"
-  timeout -k 10 500 python3 bench.py --config C3 --steps 5 --warmup 1 > $out/bench_c3.json 2> $out/bench_c3.err; echo "bench_c3 rc=$?"
-  timeout -k 10 700 python3 bench.py --config C5 --steps 6 --warmup 2 > $out/bench_c5.json 2> $out/bench_c5.err; echo "bench_c5 rc=$?"
+  timeout -k 10 500 python3 bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+  timeout -k 10 500 python3 bench.py --full --obstacles polygons > $out/bench_poly.json 2> $out/bench_poly.err; echo "bench_poly rc=$?"
+  timeout -k 10 500 python3 bench.py --full --config C3 --steps 5 --warmup 1 > $out/bench_c3.json 2> $out/bench_c3.err; echo "bench_c3 rc=$?"
+  timeout -k 10 700 python3 bench.py --full --config C5 --steps 6 --warmup 2 > $out/bench_c5.json 2> $out/bench_c5.err; echo "bench_c5 rc=$?"
 fi
 if has stats; then
   for v in "bench:" "bench_static:--no-extras" "bench_poly:--obstacles polygons --no-extras" "bench_c3:--config C3 --steps 3 --warmup 1" "bench_c5:--config C5 --steps 2 --warmup 1"; do
     name=${v%%:*}; args=${v#*:}
-    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$name -- python3 bench.py --no-cpu-baseline $args > $out/${name}_under_rocprof.json 2> $out/${name}_rocprof.err
+    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$name -- python3 bench.py --full --no-cpu-baseline $args > $out/${name}_under_rocprof.json 2> $out/${name}_rocprof.err
     echo "rocprof $name rc=$?"
     cp $out/trace_$name/*/*_kernel_stats.csv $out/kernel_stats_$name.csv 2>/dev/null; rm -rf $out/trace_$name
   done
@@ -39,7 +39,7 @@ fi
 if has ranks; then
   for v in "2rank_weak:" "2rank_strong:--scaling strong" "2rank_obstacles:--shard obstacles --obstacles polygons" "4rank_grid2x2:--grid 2x2 --obstacles polygons"; do
     name=${v%%:*}; args=${v#*:}; n=${name%%rank*}
-    timeout -k 10 400 python3 bench.py --gpus $n --backend gloo --share-device --no-cpu-baseline --no-extras --steps 8 --warmup 2 $args > $out/bench_$name.json 2> $out/bench_$name.err
+    timeout -k 10 400 python3 bench.py --full --gpus $n --backend gloo --share-device --no-cpu-baseline --no-extras --steps 8 --warmup 2 $args > $out/bench_$name.json 2> $out/bench_$name.err
     echo "ranks $name rc=$?"
   done
 fi

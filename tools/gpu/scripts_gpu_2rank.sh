@@ -7,7 +7,7 @@ timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&
 rc=$?; tail -3 $out/pytest_gpu.log; echo "pytest rc=$rc"; [ $rc -ne 0 ] && exit $rc
 for mode in weak strong; do
   timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus 2 --backend gloo --share-device --scaling $mode --no-cpu-baseline --no-extras > $out/bench_2rank_$mode.json 2> $out/bench_2rank_$mode.err
+    bench.py --full --gpus 2 --backend gloo --share-device --scaling $mode --no-cpu-baseline --no-extras > $out/bench_2rank_$mode.json 2> $out/bench_2rank_$mode.err
   echo "$mode rc=$?"
   python3 -c "
 import json; d=json.loads(open('$out/bench_2rank_$mode.json').read().strip().splitlines()[-1])

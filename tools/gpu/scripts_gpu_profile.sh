@@ -10,13 +10,13 @@ rc=$?
 tail -4 $out/pytest_gpu.log
 echo "pytest rc=$rc"
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 500 python3 bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 500 python3 bench.py --full > $out/bench.json 2> $out/bench.err
 echo "bench rc=$?"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/rocprof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/rocprof.err
 echo "rocprof rc=$?"
 cp $out/trace/*/*_kernel_stats.csv $out/kernel_stats.csv
 rm -rf $out/trace
-timeout -k 10 300 python3 bench.py --config C3 --steps 5 --warmup 1 > $out/bench_c3.json 2> $out/bench_c3.err
+timeout -k 10 300 python3 bench.py --full --config C3 --steps 5 --warmup 1 > $out/bench_c3.json 2> $out/bench_c3.err
 echo "c3 rc=$?"
 python3 - <<PY
 import json
