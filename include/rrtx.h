@@ -121,7 +121,8 @@ int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out);
 /*   RRTX_OPT_BUCKET_MULT (default 2, grows by itself after a call whose lists overflowed): capacity of the
  *   per-query hit buckets of the range search in units of cap / nq; 2, 4, 8 or 16. */
 #define RRTX_OPT_BUCKET_MULT 10
-/*   RRTX_OPT_TUNE (default 0): bit mask of kernel variants under measurement; results are identical. */
+/*   RRTX_OPT_TUNE (default 0): bit mask of kernel variants under measurement; results are identical.  Bit 4:
+ *   the culled range search without ghosts keeps the place pass (RRTX_OPT_LAST_PLACEMENT). */
 #define RRTX_OPT_TUNE 11
 /*   RRTX_OPT_SPACE_HAS_TIME (default 0; dim = 4 only): CSpace.spaceHasTime (R/DRRT_data_structures.jl:330) for the
  *   Dubins entry points.  The third coordinate of [x y t theta] is then time (planning runs in reverse time:
@@ -136,6 +137,9 @@ int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out);
  *   with <= (R/kdTree_general.jl:896).  0 for a context that holds a LATER index range of a tree sharded over
  *   several GPUs (rrtqx_3d_amd/parallel.py): its node 0 is an ordinary node. */
 #define RRTX_OPT_ROOT_RULE 13
+/*   RRTX_OPT_LAST_PLACEMENT (read only): how the last range search ordered its query copies -- 0 no culling (no
+ *   order), 1 the place pass (ghosts, or RRTX_OPT_TUNE bit 4), 2 the tile kernel from the bucket-slot table. */
+#define RRTX_OPT_LAST_PLACEMENT 14
 int rrtx_set_option(rrtx_ctx *ctx, int option, int64_t value);
 /* The value an option currently has (as rrtx_set_option normalised it): callers that size buffers by an
  * option -- the row width of rrtx_dubins_trajectory -- read it here instead of keeping a shadow copy. */

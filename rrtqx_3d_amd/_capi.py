@@ -33,6 +33,7 @@ RRTX_OPT_BUCKET_MULT = 10
 RRTX_OPT_TUNE = 11
 RRTX_OPT_SPACE_HAS_TIME = 12
 RRTX_OPT_ROOT_RULE = 13
+RRTX_OPT_LAST_PLACEMENT = 14
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)

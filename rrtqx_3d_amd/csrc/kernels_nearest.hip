@@ -402,7 +402,7 @@ static int launch_nn_nearest_screened(rrtx_ctx *ctx, const double *q_dev, int nq
                          ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
                          ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec4>(), ctx->ws_copy_meta.as<int2>(), sc,
                          (const unsigned long long *)nullptr, 1, 1, (int *)nullptr, (int2 *)nullptr, PackFused{},
-                         ConfirmArgs{});
+                         ConfirmArgs{}, QSlots{});
       hipLaunchKernelGGL(nn_filter_prep_kernel<4>, pgrid, block, 0, st, ctx->ws_copies.as<QRec4>(), sc,
                          ctx->d_absmax.as<unsigned long long>(), (int)n_copies_max, ctx->origin[0], ctx->origin[1],
                          ctx->origin[2], ctx->origin[3], ctx->ws_copies_f.as<QRecF4>());
@@ -418,7 +418,7 @@ static int launch_nn_nearest_screened(rrtx_ctx *ctx, const double *q_dev, int nq
                          ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
                          ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec3>(), ctx->ws_copy_meta.as<int2>(), sc,
                          (const unsigned long long *)nullptr, 1, 1, (int *)nullptr, (int2 *)nullptr, PackFused{},
-                         ConfirmArgs{});
+                         ConfirmArgs{}, QSlots{});
       hipLaunchKernelGGL(nn_filter_prep_kernel<3>, pgrid, block, 0, st, ctx->ws_copies.as<QRec3>(), sc,
                          ctx->d_absmax.as<unsigned long long>(), (int)n_copies_max, ctx->origin[0], ctx->origin[1],
                          ctx->origin[2], ctx->origin[3], ctx->ws_copies_f.as<QRecF3>());

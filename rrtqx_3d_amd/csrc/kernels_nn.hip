@@ -9,7 +9,9 @@
 //   pack    : queries -> slot table (query + ghosts), copy records, grid bucket and rank of
 //             every copy, the root rule (<= instead of <, R/kdTree_general.jl:896 vs :830),
 //             per-call state
-//   place   : copies in bucket order + their fp32 screen records      (culled search)
+//   place   : copies in bucket order + their fp32 screen records      (culled search with ghosts, or RRTX_OPT_TUNE
+//             bit 4; without ghosts the pack pass writes every copy, its screen record and its owner to slot
+//             (bucket, rank) of a table instead, and each tile finds its own copies there: three launches)
 //   tile    : per tile of 16 copies: groups of eight nodes within reach (cells of the slab index cut
 //             by bins of the third coordinate) -> fp32 screen -> exact confirmation -> hits into the
 //             queries' buckets; on the fused extend() path also the sample check and both edge flags
@@ -283,13 +285,26 @@ __global__ __launch_bounds__(256) void nn_confirm_kernel(ConfirmArgs a, const in
 // MODE 0: the lane's nodes are base + lane + 64 u (index-order arrays); 1: lane-major chunk of the slab
 // index, positions base + 8 lane .. + 7; 2: lane-major GROUPS, every lane its own eight consecutive
 // positions p_lane .. + 7 (lanes outside the wave mask vm hold nothing and file nothing).
-template <int D, int MODE>
+// LQ: the records of copies q0 .. q0 + 15 come from the tile's LDS table lq (padded with never_pass records to 16)
+// instead of copies_f; they are moved to scalar registers like the scalar loads' results.
+template <int D>
+__device__ __forceinline__ typename QRecFT<D>::type uniform_qrecf(const typename QRecFT<D>::type &f) {
+  typename QRecFT<D>::type u = f;
+  u.x = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f.x)));
+  u.y = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f.y)));
+  u.z = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f.z)));
+  if constexpr (D == 4) u.w = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f.w)));
+  u.thr = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f.thr)));
+  return u;
+}
+template <int D, int MODE, bool LQ = false>
 __device__ __forceinline__ void scan_chunk_f32(const float *__restrict__ fx, const float *__restrict__ fy,
                                                const float *__restrict__ fz, const float *__restrict__ fw,
                                                const float *__restrict__ fpp, const int base, const int node_end,
                                                const typename QRecFT<D>::type *__restrict__ copies_f, const int q0,
                                                const int q1, int2 *__restrict__ mine, int &wn,
-                                               const unsigned p_lane = 0u, const unsigned long long vm = ~0ull) {
+                                               const unsigned p_lane = 0u, const unsigned long long vm = ~0ull,
+                                               const typename QRecFT<D>::type *lq = nullptr) {
   const int lane = threadIdx.x & 63;
   const float kInf = __builtin_inff();
   constexpr bool LM = MODE != 0;
@@ -339,7 +354,10 @@ __device__ __forceinline__ void scan_chunk_f32(const float *__restrict__ fx, con
     // multiple of kQPI records that never pass
     typename QRecFT<D>::type c[kQPI];
 #pragma unroll
-    for (int k = 0; k < kQPI; ++k) c[k] = copies_f[q + k];
+    for (int k = 0; k < kQPI; ++k) {
+      if constexpr (LQ) c[k] = uniform_qrecf<D>(lq[q - q0 + k]);
+      else c[k] = copies_f[q + k];
+    }
     unsigned long long mk[kQPI];      // wave masks stay on the SALU (no short-circuit control flow)
     unsigned long long anym = 0ull;
 #pragma unroll
@@ -474,6 +492,9 @@ struct TileLds {
   double lo, hi, ylo, yhi;
   int lcnt[kTileB];
   typename QRecT<D>::type cp[kTileB];
+  // placement in the tile kernel (bucket-slot table): the screen records and owners of the tile's copies
+  typename QRecFT<D>::type cf[kTileB];
+  int own[kTileB];
   BktRec hrec[kTileB][kTbLcap];
   // fused extend() path: per copy (= sample) the spheres its candidate edges can touch, and whether
   // the sample itself is in collision
@@ -559,7 +580,7 @@ struct TileEmit {
         const bool sp = (spill >> u) & 1u;
         if (__ballot(sp) == 0ull) continue;
         int owner = 0, flags = 0;
-        if (sp) owner = meta[q].x;
+        if (sp) owner = meta ? meta[q].x : sm.own[cl];
         if constexpr (EXT) flags = tile_edge_flags<D>(x, sm, sp, cl, id[u], d2[u]);
         emit_hits_grouped(hs, sp, owner, id[u], d2[u], flags);   // at most kTileB queries per wave
       }
@@ -567,7 +588,7 @@ struct TileEmit {
   }
   TileLds<D> &sm;
   const HitSink &hs;
-  const int2 *meta;
+  const int2 *meta;            // owner of a copy (null: sm.own)
   const ExtendDev &x;
   int q0;
   __device__ __forceinline__ void operator()(bool h, int q, int /*owner*/, int id, double d2) const {
@@ -584,7 +605,7 @@ struct TileEmit {
     if (__ballot(spill) != 0ull) {
       // a dense ball (more than kTbLcap hits of one copy in one tile): straight to the bucket
       int owner = 0, flags = 0;
-      if (spill) owner = meta[q].x;
+      if (spill) owner = meta ? meta[q].x : sm.own[cl];
       if constexpr (EXT) flags = tile_edge_flags<D>(x, sm, spill, cl, id, d2);
       emit_hits_grouped(hs, spill, owner, id, d2, flags);   // at most kTileB queries per wave
     }
@@ -644,14 +665,36 @@ __device__ unsigned long long g_tile_clk[4096 * 16];
 #endif
 #define RRTX_TILE_CLK(k) RRTX_TILE_CLK_AT(0, k)
 
-template <int D, bool EXT>
+// Placement of the bucket-slot table (QSlots, nn_device.hpp): the tile finds the copies at its positions itself
+struct TilePlace {
+  const int *qhist;            // copies per bucket (kMaxQBuckets + 1 ints, zero beyond the buckets in use)
+  const void *tab;             // QSlotRec<D>
+  const int2 *spill_key;
+  int n_buckets, capb, spill_base, n_tab;
+};
+
+// Sixteen counters of the bucket histogram per thread: four 16-byte loads in flight instead of up to sixteen
+// dependent 4-byte ones.  Thread t owns buckets [b0, b1).
+__device__ __forceinline__ void load_qhist16(const int *__restrict__ qhist, int per, int b0, int b1, int *h) {
+  static_assert(kMaxQBuckets == 256 * 16, "sixteen counters per thread");
+  if (per == 16) {
+    const int4 *h4 = reinterpret_cast<const int4 *>(qhist + b0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const int4 v4 = h4[k]; h[4 * k] = v4.x; h[4 * k + 1] = v4.y; h[4 * k + 2] = v4.z; h[4 * k + 3] = v4.w; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) h[k] = (b0 + k < b1) ? qhist[b0 + k] : 0;
+  }
+}
+
+template <int D, bool EXT, bool SL>
 __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     const float *__restrict__ fx, const float *__restrict__ fy, const float *__restrict__ fz,
     const float *__restrict__ fw, const float *__restrict__ fpp, int n_nodes, int n_chunks,
     const ChunkExt *__restrict__ chunk_ext, const typename QRecT<D>::type *__restrict__ copies_s, const typename QRecFT<D>::type *__restrict__ copies_f,
     const Scalars *__restrict__ sc, int n_parts, int2 *__restrict__ ev, int slice_cap,
     const ConfirmArgs a, const ConfirmArgs *__restrict__ ca, const TileGrid tg, const ExtendDev x,
-    int *__restrict__ visits, const int n_copies_known) {
+    int *__restrict__ visits, const int n_copies_known, const TilePlace tp) {
   __shared__ TileLds<D> sm;
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -675,14 +718,108 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     const int q1 = min(q0 + kTileB, n_copies);
     int wn = 0;                             // wave-uniform: entries in the slice
 
-    // ---- 1. reach ----
     RRTX_TILE_CLK(0);
+    int slot = -1;                          // SL, wave 0, lane l < q1 - q0: table slot of the copy at position q0 + l
+    if constexpr (SL) {
+      // ---- 0. placement: which copies hold positions [q0, q1) of the bucket order.  Every thread adds up its
+      //      sixteen counters of the bucket histogram; an exclusive scan (DPP within the wave, four wave sums)
+      //      gives each thread the first position of its buckets (list[16 + t]: list is idle until step 2).
+      //      Lane l of wave 0 then finds the thread whose buckets hold position q0 + l (binary search over the
+      //      256 starts), re-reads that thread's counters and picks bucket and rank, hence the slot ----
+      int tq = t;
+      asm volatile("" : "+v"(tq));          // (keeps the per-thread bucket range from living across the tile loop)
+      const int per = (tp.n_buckets + 255) / 256;          // <= 16
+      {
+        const int b0 = min(tq * per, tp.n_buckets), b1 = min(b0 + per, tp.n_buckets);
+        int h[16];
+        load_qhist16(tp.qhist, per, b0, b1, h);
+        int local = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) local += h[k];
+        const int incl = wave_scan_incl<false>(local, 0);
+        if (lane == 63) sm.wcnt[wave] = incl;
+        sm.list[kTileB + tq] = incl - local;              // within the wave; the wave sums are added on use
+      }
+      __syncthreads();
+      RRTX_TILE_CLK(11);
+      if (wave == 0) {
+        const int pos = q0 + lane;
+        int rk = -1, bk = 0;
+        if (pos < q1) {
+          const int w1 = sm.wcnt[0], w2 = w1 + sm.wcnt[1], w3 = w2 + sm.wcnt[2];
+          // start of thread T's buckets (non-decreasing in T); the last T with start <= pos holds pos
+          auto start_of = [&](int T) {
+            const int w = T >> 6;
+            return sm.list[kTileB + T] + (w == 0 ? 0 : (w == 1 ? w1 : (w == 2 ? w2 : w3)));
+          };
+          int T = 0;
+#pragma unroll
+          for (int st = 128; st > 0; st >>= 1)
+            if (start_of(T + st) <= pos) T += st;
+          int p = start_of(T);
+          const int b0 = min(T * per, tp.n_buckets), b1 = min(b0 + per, tp.n_buckets);
+          int h[16];
+          load_qhist16(tp.qhist, per, b0, b1, h);
+#pragma unroll
+          for (int k = 0; k < 16; ++k) {
+            const bool in = pos >= p && pos < p + h[k];
+            bk = in ? b0 + k : bk;
+            rk = in ? pos - p : rk;
+            p += h[k];
+          }
+          if (rk >= 0 && rk < tp.capb) slot = bk * tp.capb + rk;
+        }
+        const unsigned long long need = __ballot(rk >= tp.capb);
+        if (need != 0ull) {
+          // rare (a bucket with more than capb copies): look the spilled positions up by (bucket, rank)
+          // (every (bucket, rank) is on the list once: a position is done when its key is found, and the walk
+          // ends when all of the tile's are)
+          const int n_sp = min(sc->n_spill, n_copies);
+          unsigned long long todo = need;
+          for (int j0 = 0; j0 < n_sp && todo != 0ull; j0 += 64) {
+            const int j = j0 + lane;
+            const int2 key = j < n_sp ? tp.spill_key[j] : make_int2(-1, -1);
+            unsigned long long rem = todo;
+            while (rem != 0ull) {
+              const int l = __ffsll((long long)rem) - 1;
+              rem &= rem - 1ull;
+              const int kb = __builtin_amdgcn_readlane(bk, l), kr = __builtin_amdgcn_readlane(rk, l);
+              const unsigned long long m = __ballot(key.x == kb && key.y == kr);
+              if (m != 0ull) {
+                if (lane == l) slot = tp.spill_base + j0 + __ffsll((long long)m) - 1;
+                todo &= ~(1ull << l);
+              }
+            }
+          }
+        }
+      }
+    }
+
+    // ---- 1. reach ----
     if (t < kTileB) sm.lcnt[t] = 0;
     if (wave == 0) {
       double lo = __builtin_inf(), hi = -__builtin_inf(), ylo = __builtin_inf(), yhi = -__builtin_inf();
       double zlo = __builtin_inf(), zhi = -__builtin_inf();
+      if constexpr (SL) {
+        if (lane >= q1 - q0 && lane < kTileB) sm.cf[lane] = never_pass_qrecf<D>();   // padding of the screen's reads
+      }
       if (q0 + lane < q1) {
-        const typename QRecT<D>::type c = copies_s[q0 + lane];
+        typename QRecT<D>::type c;
+        if constexpr (SL) {
+          if ((unsigned)slot < (unsigned)tp.n_tab) {
+            const QSlotRec<D> rec = static_cast<const QSlotRec<D> *>(tp.tab)[slot];
+            c = rec.q;
+            sm.cf[lane] = rec.f;
+            sm.own[lane] = rec.owner;
+          } else {                          // cannot happen with a consistent histogram: a copy without neighbours
+            c.x = 0.0; c.y = 0.0; c.z = 0.0; c.thr = -1.0;
+            if constexpr (D == 4) { c.w = 0.0; c.pad0 = 0.0; c.pad1 = 0.0; c.pad2 = 0.0; }
+            sm.cf[lane] = never_pass_qrecf<D>();
+            sm.own[lane] = -1;
+          }
+        } else {
+          c = copies_s[q0 + lane];
+        }
         sm.cp[lane] = c;
         if constexpr (EXT) {
           const double rb = x.r_bound >= 0.0 ? x.r_bound : 0.0;
@@ -914,10 +1051,11 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
             const bool valid = gi < G;
             const unsigned p_lane = valid ? 8u * (unsigned)sm.glist[gi] : 0u;
             if (wn + 64 * kTileB > slice_cap) {
-              const TileEmit<D, EXT> emit_now{sm, a.hs, a.meta, x, q0};
+              const TileEmit<D, EXT> emit_now{sm, a.hs, SL ? nullptr : a.meta, x, q0};
               drain_slice_to<D, true>(mine, wn, n_nodes, a, emit_now, sm.cp, q0);
             }
-            scan_chunk_f32<D, 2>(fx, fy, fz, fw, fpp, 0, n_nodes, copies_f, q0, q1, mine, wn, p_lane, __ballot(valid));
+            scan_chunk_f32<D, 2, SL>(fx, fy, fz, fw, fpp, 0, n_nodes, copies_f, q0, q1, mine, wn, p_lane, __ballot(valid),
+                                     sm.cf);
             visited += min(64, G - 64 * u);
           }
         }
@@ -932,10 +1070,11 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
           if (wn + 64 * kTileB > slice_cap) {
             // the slice is nearly full (a screen that passes almost everything: a non-finite or far-away node makes
             // the fp32 bounds useless): confirm it now, through the tile's own emitter -- the hits must carry the edge flags
-            const TileEmit<D, EXT> emit_now{sm, a.hs, a.meta, x, q0};
+            const TileEmit<D, EXT> emit_now{sm, a.hs, SL ? nullptr : a.meta, x, q0};
             drain_slice_to<D, true>(mine, wn, n_nodes, a, emit_now, sm.cp, q0);
           }
-          scan_chunk_f32<D, 1>(fx, fy, fz, fw, fpp, chunk * kChunkF, n_nodes, copies_f, q0, q1, mine, wn);
+          scan_chunk_f32<D, 1, SL>(fx, fy, fz, fw, fpp, chunk * kChunkF, n_nodes, copies_f, q0, q1, mine, wn, 0u, ~0ull,
+                                   sm.cf);
           visited += kChunkF / 8;
         }
         if (ce < n_chunks) {  // (trees beyond kTbList chunks) the list is rebuilt by the next pass
@@ -953,7 +1092,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
     RRTX_TILE_CLK(4);
-    const TileEmit<D, EXT> emit{sm, a.hs, a.meta, x, q0};
+    const TileEmit<D, EXT> emit{sm, a.hs, SL ? nullptr : a.meta, x, q0};
     const int c0 = sm.wcnt[0], c1 = c0 + sm.wcnt[1], c2 = c1 + sm.wcnt[2], total = c2 + sm.wcnt[3];
     for (int e0 = 0; e0 < total; e0 += kScanThreads) {
       const int e = e0 + t;
@@ -979,7 +1118,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
         if (cl < nc) {
           my_n = min(sm.lcnt[cl], kTbLcap);
           if (my_n > 0) {
-            my_owner = a.meta[q0 + cl].x;
+            my_owner = SL ? sm.own[cl] : a.meta[q0 + cl].x;
             my_base = atomicAdd(&a.hs.count[my_owner], my_n);
           }
         }
@@ -1004,7 +1143,10 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     }
     if constexpr (EXT) {
       // explicitPointCheck of the samples (one part of a tile reports them)
-      if (part == 0 && t < q1 - q0 && x.sample_unsafe) x.sample_unsafe[a.meta[q0 + t].x] = sm.sbad[t] ? 1 : 0;
+      if (part == 0 && t < q1 - q0 && x.sample_unsafe) {
+        const int owner = SL ? sm.own[t] : a.meta[q0 + t].x;
+        if (owner >= 0) x.sample_unsafe[owner] = sm.sbad[t] ? 1 : 0;
+      }
     }
     RRTX_TILE_CLK(6);
     __syncthreads();          // LDS is reused by the next tile
@@ -1131,8 +1273,6 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   const size_t n_copies_max = (size_t)nq * n_slots;
   const size_t qrec_bytes = (D == 4) ? sizeof(QRec4) : sizeof(QRec3);
   RRTX_HIP(ctx, ctx->ws_slots.ensure(n_copies_max * sizeof(SlotRec)));
-  RRTX_HIP(ctx, ctx->ws_copies.ensure(n_copies_max * qrec_bytes));
-  RRTX_HIP(ctx, ctx->ws_copy_meta.ensure(n_copies_max * sizeof(int2)));
   RRTX_HIP(ctx, ctx->ws_counts.ensure(((size_t)nq * 3 + 2) * sizeof(int)));
   // two Scalars records used alternately: each call's pack kernel resets the other one
   if (!ctx->ws_scalars.p) {
@@ -1174,6 +1314,17 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   int n_buckets = 1, g2 = 1, g3 = 1;
   int *qhist = nullptr;
   int2 *cbk = nullptr;
+  // culled search without ghosts: the pack pass fills the bucket-slot table and the tile kernel places the
+  // copies itself (three launches); with ghosts, or experiment switch 4, the place pass puts them in order
+  const bool slot_route = use_cull && n_slots == 1 && !(ctx->opt_tune & 4);
+  ctx->last_placement = slot_route ? 2 : (use_cull ? 1 : 0);
+  QSlots qs;
+  std::memset(&qs, 0, sizeof(qs));
+  int n_tab = 0;
+  if (!slot_route) {                      // (the slot route writes neither: its copies live in the table)
+    RRTX_HIP(ctx, ctx->ws_copies.ensure(n_copies_max * qrec_bytes));
+    RRTX_HIP(ctx, ctx->ws_copy_meta.ensure(n_copies_max * sizeof(int2)));
+  }
   if (use_cull) {
     int rc = slab_refresh(ctx, (long long)((n_copies_max + 15) / 16));
     if (rc) return rc;
@@ -1192,10 +1343,26 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
       RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_qhist.p, 0, sizeof(int) * (size_t)(kMaxQBuckets + 1), st));
     }
     RRTX_HIP(ctx, ctx->ws_cb.ensure(sizeof(int2) * n_copies_max));
-    RRTX_HIP(ctx, ctx->ws_copies_s.ensure(n_copies_max * qrec_bytes));
-    RRTX_HIP(ctx, ctx->ws_meta_s.ensure(n_copies_max * sizeof(int2)));
+    if (!slot_route) {
+      RRTX_HIP(ctx, ctx->ws_copies_s.ensure(n_copies_max * qrec_bytes));
+      RRTX_HIP(ctx, ctx->ws_meta_s.ensure(n_copies_max * sizeof(int2)));
+    }
     qhist = ctx->ws_qhist.as<int>();
     cbk = ctx->ws_cb.as<int2>();
+    if (slot_route) {
+      // slots per bucket: the average over the coarser of the two grids with headroom (the rest spills)
+      const long long min_b = std::max(1ll, std::min((long long)g2 * g2, (long long)g3 * g3 * g3));
+      const long long avg = ((long long)n_copies_max + min_b - 1) / min_b;
+      const int capb = (int)std::min(128ll, std::max(8ll, (2 * avg + 8 + 3) / 4 * 4));
+      qs.capb = capb;
+      qs.spill_base = n_buckets * capb;
+      n_tab = qs.spill_base + (int)n_copies_max;
+      const size_t rec_bytes = (D == 4) ? sizeof(QSlotRec<4>) : sizeof(QSlotRec<3>);
+      RRTX_HIP(ctx, ctx->ws_qslot.ensure((size_t)n_tab * rec_bytes));
+      qs.tab = ctx->ws_qslot.p;
+      qs.spill_key = cbk;
+      qs.node_absmax = ctx->d_absmax.as<unsigned long long>();
+    }
   }
   // ---- hit sink: per-query buckets (bkt_mult x the average the caller made room for, at most 16 GiB
   //      in all -- there are 288) + overflow list ----
@@ -1217,8 +1384,9 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   ConfirmArgs ca;
   double *const *pd = use_cull ? ctx->sl_d : ctx->nodes;
   ca.nx = pd[0]; ca.ny = pd[1]; ca.nz = pd[2]; ca.nw = pd[D == 4 ? 3 : 2];
-  ca.copies = use_cull ? ctx->ws_copies_s.p : ctx->ws_copies.p;
-  ca.meta = use_cull ? ctx->ws_meta_s.as<int2>() : ctx->ws_copy_meta.as<int2>();
+  // (slot route: the tile kernel confirms against its copies in LDS and takes the owners from there)
+  ca.copies = slot_route ? nullptr : (use_cull ? ctx->ws_copies_s.p : ctx->ws_copies.p);
+  ca.meta = slot_route ? nullptr : (use_cull ? ctx->ws_meta_s.as<int2>() : ctx->ws_copy_meta.as<int2>());
   ca.slots = ctx->ws_slots.as<SlotRec>();
   ca.pos_id = use_cull ? ctx->sl_id : nullptr;
   ca.n_slots = n_slots;
@@ -1264,7 +1432,7 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
                          ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
                          ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec4>(),
                          ctx->ws_copy_meta.as<int2>(), sc, ctx->d_xrange.as<unsigned long long>(), g2, g3, qhist,
-                         cbk, pf, ca);
+                         cbk, pf, ca, qs);
     else
       hipLaunchKernelGGL(nn_pack_kernel<3>, grid, block, 0, st, q_dev, nq, thr_lt_arr, thr_gt_arr, tlt, tgt,
                          ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2],
@@ -1272,7 +1440,7 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
                          ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
                          ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec3>(),
                          ctx->ws_copy_meta.as<int2>(), sc, ctx->d_xrange.as<unsigned long long>(), g2, g3, qhist,
-                         cbk, pf, ca);
+                         cbk, pf, ca, qs);
   }
   span_end(ctx);
   ctx->scalars_flip = flip;
@@ -1289,7 +1457,7 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   n_seg = (n_nodes + seg_len - 1) / seg_len;
   ctx->last_tile_q = use_cull ? kTileB : tile_q;
 
-  if (use_filter) {
+  if (use_filter && !slot_route) {
     const size_t qf_bytes = (D == 4) ? sizeof(QRecF4) : sizeof(QRecF3);
     RRTX_HIP(ctx, ctx->ws_copies_f.ensure((n_copies_max + kQPI) * qf_bytes));
     span_begin(ctx, KF_NN_FINISH);
@@ -1340,21 +1508,25 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
       tg.n_sorted_chunks = (ctx->ws_slab_params.p && ctx->ws_slab_start.p) ? (int)(ctx->sl_n_sorted / kSlabChunk) : 0;
       tg.kz = ctx->sl_kz > 0 ? ctx->sl_kz : 1;
       tg.groups = (tg.kz > 1 && !(ctx->opt_tune & 2)) ? 1 : 0;     // (experiment switch 2: whole chunks)
-      if (fuse)
-        hipLaunchKernelGGL((nn_tile_kernel<3, true>), dim3((unsigned)nb), block, 0, st, ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2],
-                           ctx->sl_f[wi], ctx->sl_pp, n_nodes, n_chunks, reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),
-                           ctx->ws_copies_s.as<QRec3>(), ctx->ws_copies_f.as<QRecF3>(), sc, n_parts,
-                           ctx->ws_ev_a.as<int2>(), slice_cap, ca, ca_dev, tg, xd, ctx->ws_ev_cnt.as<int>(), n_slots == 1 ? nq : -1);
-      else if (D == 4)
-        hipLaunchKernelGGL((nn_tile_kernel<4, false>), dim3((unsigned)nb), block, 0, st, ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2],
-                           ctx->sl_f[wi], ctx->sl_pp, n_nodes, n_chunks, reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),
-                           ctx->ws_copies_s.as<QRec4>(), ctx->ws_copies_f.as<QRecF4>(), sc, n_parts,
-                           ctx->ws_ev_a.as<int2>(), slice_cap, ca, ca_dev, tg, xd, ctx->ws_ev_cnt.as<int>(), n_slots == 1 ? nq : -1);
-      else
-        hipLaunchKernelGGL((nn_tile_kernel<3, false>), dim3((unsigned)nb), block, 0, st, ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2],
-                           ctx->sl_f[wi], ctx->sl_pp, n_nodes, n_chunks, reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),
-                           ctx->ws_copies_s.as<QRec3>(), ctx->ws_copies_f.as<QRecF3>(), sc, n_parts,
-                           ctx->ws_ev_a.as<int2>(), slice_cap, ca, ca_dev, tg, xd, ctx->ws_ev_cnt.as<int>(), n_slots == 1 ? nq : -1);
+      TilePlace tpl;
+      tpl.qhist = qhist; tpl.tab = qs.tab; tpl.spill_key = qs.spill_key;
+      tpl.n_buckets = n_buckets; tpl.capb = qs.capb; tpl.spill_base = qs.spill_base; tpl.n_tab = n_tab;
+#define RRTX_TILE_LAUNCH(DD, EE, SS)                                                                                   \
+  hipLaunchKernelGGL((nn_tile_kernel<DD, EE, SS>), dim3((unsigned)nb), block, 0, st, ctx->sl_f[0], ctx->sl_f[1],       \
+                     ctx->sl_f[2], ctx->sl_f[wi], ctx->sl_pp, n_nodes, n_chunks,                                       \
+                     reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),                                               \
+                     SS ? nullptr : ctx->ws_copies_s.as<typename QRecT<DD>::type>(),                                   \
+                     SS ? nullptr : ctx->ws_copies_f.as<typename QRecFT<DD>::type>(), sc, n_parts,                     \
+                     ctx->ws_ev_a.as<int2>(), slice_cap, ca, ca_dev, tg, xd, ctx->ws_ev_cnt.as<int>(),                 \
+                     n_slots == 1 ? nq : -1, tpl)
+      if (fuse) {
+        if (slot_route) RRTX_TILE_LAUNCH(3, true, true); else RRTX_TILE_LAUNCH(3, true, false);
+      } else if (D == 4) {
+        if (slot_route) RRTX_TILE_LAUNCH(4, false, true); else RRTX_TILE_LAUNCH(4, false, false);
+      } else {
+        if (slot_route) RRTX_TILE_LAUNCH(3, false, true); else RRTX_TILE_LAUNCH(3, false, false);
+      }
+#undef RRTX_TILE_LAUNCH
     } else if (use_filter) {
       // persistent grid: opt_scan_blocks workgroups (multiple of 8) striding over the work
       unsigned pg = (unsigned)ctx->opt_scan_blocks / 8u * 8u;

@@ -21,6 +21,8 @@ struct Scalars {
   int n_copies;                    // valid query copies
   int n_units;                     // unused (the culled search reports its chunk visits per wave)
   unsigned long long q_absmax;     // bit pattern of max |coordinate| over the query copies
+  int n_spill;                     // copies on the spill list of the bucket-slot table (QSlots)
+  int pad;
 };
 
 // Where confirmed neighbours go.  count[q] hands out slots of query q's bucket (a returning
@@ -78,13 +80,85 @@ __global__ void nn_init_kernel(Scalars *__restrict__ sc, int n_copies_init, int 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int stride = gridDim.x * blockDim.x;
   if (i == 0) {
-    sc->total = 0ull; sc->n_copies = n_copies_init; sc->n_units = 0; sc->q_absmax = 0ull;
+    sc->total = 0ull; sc->n_copies = n_copies_init; sc->n_units = 0; sc->q_absmax = 0ull; sc->n_spill = 0;
     if (ca_dst) *ca_dst = ca;
   }
   for (int k = i; k < n_i32; k += stride) zero_i32[k] = 0;
   for (int k = i; k < n_u64; k += stride) fill_u64[k] = v_u64;
   for (int k = i; k < n_fill_i32; k += stride) fill_i32[k] = v_i32;
 }
+
+// ------------------------------------------------------ fp32 prefilter ------
+// Conservative screen: a pair may only be DROPPED when it provably fails the
+// exact test; pairs that survive are re-tested with the exact unfused fp64
+// arithmetic, which alone decides membership (DESIGN.md, "fp32 prefilter").
+//
+// Norm expansion on coordinates shifted by the context origin o (P = p - o,
+// Q = q - o, p~ = fl32(P), q~ = fl32(Q), eps = 2^-24, C >= max |P_i|, |Q_i|):
+//     t = fma(ax, p~x, fma(ay, p~y, fma(az, p~z, pp))),  a = -2 q~,  pp = fl32(|p~|^2)
+//   |t - (|p~|^2 - 2 q~.p~)| <= K eps C^2      K = D + sum_{k<=D} (D + 2k)  (24 / 40), used: 26 / 42
+//   |q~ - p~| <= |Q - P| + 2 sqrt(D) eps C
+// so whenever the exact fp64 s < thr (=> |Q - P| <= R = sqrt(thr)(1 + 1e-15)):
+//     t <= (R + 2 sqrt(D) eps C)^2 + K eps C^2 - |q~|^2  =: thr'   (rounded UP to fp32)
+// and "t > thr'" proves s >= thr.  Non-finite or huge C disables the screen.
+// The bound uses C only for the one pair (copy, node) being screened, so C may differ from copy to copy:
+// C = max(max |P_i| over ALL nodes, max_i |Q_i| of THIS copy) still bounds |P_i| and |Q_i| of every pair the
+// copy's record screens.  The culled search without ghosts builds each record with its own C in the pack
+// pass (no shared maximum to wait for); the other paths use the maximum over all copies (q_absmax).
+template <int D>
+__device__ __forceinline__ typename QRecFT<D>::type make_qrecf(const typename QRecT<D>::type &c, double C, double ox,
+                                                               double oy, double oz, double ow) {
+  const float qx = (float)(c.x - ox), qy = (float)(c.y - oy), qz = (float)(c.z - oz);
+  float qw = 0.f;
+  double qq = (double)qx * (double)qx + (double)qy * (double)qy + (double)qz * (double)qz;
+  if constexpr (D == 4) { qw = (float)(c.w - ow); qq += (double)qw * (double)qw; }
+  float thr_f;
+  if (!(C <= 1e15)) {
+    thr_f = __builtin_inff();              // non-finite or huge coordinates: screen nothing
+  } else if (!(c.thr > 0.0)) {
+    thr_f = -__builtin_inff();              // exact test can never pass (s >= 0 >= thr, or thr NaN)
+  } else {
+    const double eps = 5.9604644775390625e-08;   // 2^-24
+    const double K = (D == 4) ? 42.0 : 26.0;
+    const double two_sqrt_d = (D == 4) ? 4.0 : 3.4641016151377544;
+    const double R = sqrt_rn(c.thr) * (1.0 + 1e-15);
+    const double b = R + two_sqrt_d * eps * C * (1.0 + 1e-6);
+    const double T = b * b * (1.0 + 1e-12) + K * eps * C * C + 1e-30 - qq * (1.0 - 1e-14);
+    thr_f = __double2float_ru(T);
+    if (thr_f != thr_f) thr_f = __builtin_inff();
+  }
+  typename QRecFT<D>::type f;
+  f.x = -2.0f * qx; f.y = -2.0f * qy; f.z = -2.0f * qz;
+  if constexpr (D == 4) { f.w = -2.0f * qw; f.pad0 = 0.f; f.pad1 = 0.f; f.pad2 = 0.f; }
+  f.thr = thr_f;
+  return f;
+}
+
+template <int D>
+__device__ __forceinline__ typename QRecFT<D>::type never_pass_qrecf() {
+  typename QRecFT<D>::type f;
+  f.x = 0.f; f.y = 0.f; f.z = 0.f;
+  if constexpr (D == 4) { f.w = 0.f; f.pad0 = 0.f; f.pad1 = 0.f; f.pad2 = 0.f; }
+  f.thr = -__builtin_inff();
+  return f;
+}
+
+// Bucket-slot table of the culled search without ghosts: the pack pass writes copy i of bucket b with rank r
+// (drawn by atomicAdd on qhist[b]) to tab[b * capb + r], with its fp32 screen record and its owner; ranks >= capb
+// go to the spill list tab[spill_base + j], tagged spill_key[j] = (b, r).  The tile kernel finds the copies at
+// its own positions from the bucket histogram (tile_place), so no pass has to put the copies in bucket order.
+template <int D>
+struct alignas(64) QSlotRec {
+  typename QRecT<D>::type q;
+  typename QRecFT<D>::type f;
+  int owner;
+};
+struct QSlots {
+  void *tab;                              // QSlotRec<D>[spill_base + n_copies]; null: copies + meta + cb (place pass)
+  int2 *spill_key;                        // (bucket, rank) of spill entry j
+  const unsigned long long *node_absmax;  // per-copy screen bound (make_qrecf)
+  int capb, spill_base;
+};
 
 // ---------------------------------------------------------------- pack ------
 // What the radius search folds into the pack pass (all null / zero for the nearest search):
@@ -137,14 +211,15 @@ __global__ void nn_pack_kernel(const double *__restrict__ q, int nq, const doubl
                                SlotRec *__restrict__ slots, typename QRecT<D>::type *__restrict__ copies,
                                int2 *__restrict__ meta, Scalars *__restrict__ sc,
                                const unsigned long long *__restrict__ xrange, int g2, int g3,
-                               int *__restrict__ qhist, int2 *__restrict__ cb, PackFused pf, ConfirmArgs ca) {
+                               int *__restrict__ qhist, int2 *__restrict__ cb, PackFused pf, ConfirmArgs ca,
+                               QSlots qs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool act = i < nq;
   if (i == 0 && pf.count) {
     pf.count[nq] = 0;
     *pf.ca_dst = ca;
     Scalars *nx_sc = pf.sc_next;
-    nx_sc->total = 0ull; nx_sc->n_copies = 0; nx_sc->n_units = 0; nx_sc->q_absmax = 0ull;
+    nx_sc->total = 0ull; nx_sc->n_copies = 0; nx_sc->n_units = 0; nx_sc->q_absmax = 0ull; nx_sc->n_spill = 0;
     if (n_wraps == 0) sc->n_copies = nq;       // nobody counts copies then: one per query
   }
   unsigned long long am = 0ull;                // max |copy - origin| feeds the prefilter's rounding bound
@@ -213,12 +288,42 @@ __global__ void nn_pack_kernel(const double *__restrict__ q, int nq, const doubl
       if (n_wraps > 0) slots[(size_t)i * n_slots + k] = sr;   // only the ghost rules read the table
       if (valid) {
         const double og[4] = {ox, oy, oz, ow};
-        for (int c2 = 0; c2 < D; ++c2) am = max(am, (unsigned long long)__double_as_longlong(fabs(g[c2] - og[c2])));
-        int pos = (n_wraps == 0) ? i : atomicAdd(&sc->n_copies, 1);
+        unsigned long long amc = 0ull;
+        for (int c2 = 0; c2 < D; ++c2) amc = max(amc, (unsigned long long)__double_as_longlong(fabs(g[c2] - og[c2])));
         typename QRecT<D>::type qr;
         qr.x = g[0]; qr.y = g[1]; qr.z = g[2];
         if constexpr (D == 4) { qr.w = g[3]; qr.pad0 = 0.0; qr.pad1 = 0.0; qr.pad2 = 0.0; }
         qr.thr = tlt;
+        if (qs.tab) {
+          // bucket-slot table (culled search, no ghosts: one copy per query, k == 0 for every lane): the copy's
+          // screen record carries its own bound, so there is no shared maximum to update
+          QSlotRec<D> rec;
+          rec.q = qr;
+          rec.f = make_qrecf<D>(qr, __longlong_as_double((long long)max(*qs.node_absmax, amc)), ox, oy, oz, ow);
+          rec.owner = i;
+          const int b = query_bucket(qg, g[0], g[1], g[2]);
+          const int r = atomicAdd(&qhist[b], 1);
+          QSlotRec<D> *tab = static_cast<QSlotRec<D> *>(qs.tab);
+          const bool sp = r >= qs.capb;
+          if (!sp) tab[(size_t)b * qs.capb + r] = rec;
+          // ranks beyond the bucket's slots: spill list, one counter update per wave
+          const unsigned long long m = __ballot(sp);
+          if (m != 0ull) {
+            const int lane = threadIdx.x & 63;
+            const int leader = __ffsll((long long)m) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&sc->n_spill, __popcll(m));
+            base = __shfl(base, leader);
+            if (sp) {
+              const int j = base + __popcll(m & ((1ull << lane) - 1ull));
+              tab[(size_t)qs.spill_base + j] = rec;
+              qs.spill_key[j] = make_int2(b, r);
+            }
+          }
+          continue;
+        }
+        am = max(am, amc);
+        int pos = (n_wraps == 0) ? i : atomicAdd(&sc->n_copies, 1);
         copies[pos] = qr;
         meta[pos] = make_int2(i, k);
         if (qhist) {
@@ -322,57 +427,6 @@ struct GlobalEmit {
     emit_hit(hs, h, owner, id, d2);
   }
 };
-
-// ------------------------------------------------------ fp32 prefilter ------
-// Conservative screen: a pair may only be DROPPED when it provably fails the
-// exact test; pairs that survive are re-tested with the exact unfused fp64
-// arithmetic, which alone decides membership (DESIGN.md, "fp32 prefilter").
-//
-// Norm expansion on coordinates shifted by the context origin o (P = p - o,
-// Q = q - o, p~ = fl32(P), q~ = fl32(Q), eps = 2^-24, C >= max |P_i|, |Q_i|):
-//     t = fma(ax, p~x, fma(ay, p~y, fma(az, p~z, pp))),  a = -2 q~,  pp = fl32(|p~|^2)
-//   |t - (|p~|^2 - 2 q~.p~)| <= K eps C^2      K = D + sum_{k<=D} (D + 2k)  (24 / 40), used: 26 / 42
-//   |q~ - p~| <= |Q - P| + 2 sqrt(D) eps C
-// so whenever the exact fp64 s < thr (=> |Q - P| <= R = sqrt(thr)(1 + 1e-15)):
-//     t <= (R + 2 sqrt(D) eps C)^2 + K eps C^2 - |q~|^2  =: thr'   (rounded UP to fp32)
-// and "t > thr'" proves s >= thr.  Non-finite or huge C disables the screen.
-template <int D>
-__device__ __forceinline__ typename QRecFT<D>::type make_qrecf(const typename QRecT<D>::type &c, double C, double ox,
-                                                               double oy, double oz, double ow) {
-  const float qx = (float)(c.x - ox), qy = (float)(c.y - oy), qz = (float)(c.z - oz);
-  float qw = 0.f;
-  double qq = (double)qx * (double)qx + (double)qy * (double)qy + (double)qz * (double)qz;
-  if constexpr (D == 4) { qw = (float)(c.w - ow); qq += (double)qw * (double)qw; }
-  float thr_f;
-  if (!(C <= 1e15)) {
-    thr_f = __builtin_inff();              // non-finite or huge coordinates: screen nothing
-  } else if (!(c.thr > 0.0)) {
-    thr_f = -__builtin_inff();              // exact test can never pass (s >= 0 >= thr, or thr NaN)
-  } else {
-    const double eps = 5.9604644775390625e-08;   // 2^-24
-    const double K = (D == 4) ? 42.0 : 26.0;
-    const double two_sqrt_d = (D == 4) ? 4.0 : 3.4641016151377544;
-    const double R = sqrt_rn(c.thr) * (1.0 + 1e-15);
-    const double b = R + two_sqrt_d * eps * C * (1.0 + 1e-6);
-    const double T = b * b * (1.0 + 1e-12) + K * eps * C * C + 1e-30 - qq * (1.0 - 1e-14);
-    thr_f = __double2float_ru(T);
-    if (thr_f != thr_f) thr_f = __builtin_inff();
-  }
-  typename QRecFT<D>::type f;
-  f.x = -2.0f * qx; f.y = -2.0f * qy; f.z = -2.0f * qz;
-  if constexpr (D == 4) { f.w = -2.0f * qw; f.pad0 = 0.f; f.pad1 = 0.f; f.pad2 = 0.f; }
-  f.thr = thr_f;
-  return f;
-}
-
-template <int D>
-__device__ __forceinline__ typename QRecFT<D>::type never_pass_qrecf() {
-  typename QRecFT<D>::type f;
-  f.x = 0.f; f.y = 0.f; f.z = 0.f;
-  if constexpr (D == 4) { f.w = 0.f; f.pad0 = 0.f; f.pad1 = 0.f; f.pad2 = 0.f; }
-  f.thr = -__builtin_inff();
-  return f;
-}
 
 template <int D>
 __global__ void nn_filter_prep_kernel(const typename QRecT<D>::type *__restrict__ copies,

@@ -489,7 +489,7 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_out_u8b, &ctx->ws_out_i32, &ctx->ws_out_f64, &ctx->ws_partial, &ctx->ws_thr, &ctx->ws_mask, &ctx->ws_i32a, &ctx->ws_i32b,
                     &ctx->ws_slab_hist, &ctx->ws_slab_start, &ctx->ws_slab_sr, &ctx->ws_slab_params, &ctx->ws_run_hist, &ctx->ws_run_sr,
                     &ctx->ws_copies_s,
-                    &ctx->ws_meta_s, &ctx->ws_cb, &ctx->ws_qhist, &ctx->ws_bkt,
+                    &ctx->ws_meta_s, &ctx->ws_cb, &ctx->ws_qhist, &ctx->ws_qslot, &ctx->ws_bkt,
                     &ctx->ws_ev_a, &ctx->ws_ev_cnt, &ctx->ws_confirm_args, &ctx->ws_sph_lists, &ctx->ws_poly_lists, &ctx->d_sph_sample,
                     &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
@@ -600,6 +600,7 @@ int rrtx_get_option(rrtx_ctx *ctx, int option, int64_t *value) {
     case RRTX_OPT_SPACE_HAS_TIME: *value = ctx->opt_space_has_time ? 1 : 0; return RRTX_OK;
     case RRTX_OPT_NEAREST_REC_CAP: *value = (int64_t)ctx->opt_nearest_rec_cap; return RRTX_OK;
     case RRTX_OPT_BUCKET_MULT: *value = ctx->bkt_mult; return RRTX_OK;
+    case RRTX_OPT_LAST_PLACEMENT: *value = ctx->last_placement; return RRTX_OK;
     default: return fail(ctx, RRTX_E_INVALID, "get_option: unknown option %d", option);
   }
 }

@@ -200,6 +200,7 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_copy_meta;// int32 owner, slot per copy
   rrtx::DevBuf ws_copies_s, ws_meta_s;  // copies / meta in bucket order (culled scan)
   rrtx::DevBuf ws_cb, ws_qhist;         // (bucket, rank) per copy; bucket histogram
+  rrtx::DevBuf ws_qslot;                // bucket-slot table of the culled search without ghosts (QSlots)
   rrtx::DevBuf ws_bkt;      // per-query hit buckets (16-byte records)
   int bkt_mult = 2;         // bucket capacity in units of the average list length the caller made room for
   unsigned *mailbox = nullptr;   // host-mapped words the finish kernel reports to: [0] overflow records of a call
@@ -242,6 +243,7 @@ struct rrtx_ctx {
   int64_t last_pairs = 0, last_neighbors = 0;
   int last_tile_q = 0;
   bool last_culled = false;         // the last range search used the slab-culled scan
+  int last_placement = 0;           // RRTX_OPT_LAST_PLACEMENT of the last range search
   int64_t last_sweep_candidates = 0;
   int last_visit_slices = 0;        // entries of ws_ev_cnt holding its per-wave chunk counts
 };

@@ -18,7 +18,7 @@ cfg = synth.CONFIGS["C4"]
 pts, Q = synth.nodes(cfg.n_nodes, 3), synth.queries(cfg.batch, 3)
 r = synth.ball_radius(cfg.n_nodes, 3)
 names = ["start", "reach", "list+sample pass", "screen (wave 0)", "fence+barrier", "confirm", "hand-out", "end",
-         "  wave 0 list done", "  wave 1 tail done", "  wave 2 sample done"]
+         "  wave 0 list done", "  wave 1 tail done", "  wave 2 sample done", "  placement scan"]
 with Context(3, node_capacity=cfg.n_nodes) as ctx:
     if len(sys.argv) > 1:
         ctx.set_option(_capi.RRTX_OPT_TUNE, int(sys.argv[1]))
@@ -44,6 +44,7 @@ with Context(3, node_capacity=cfg.n_nodes) as ctx:
     rel = (clk - clk[:, :1]) / 100.0            # us since the workgroup's own start
     print(f"{n_wg} workgroups, {len(out['idx'])} neighbours; workgroup starts spread over {(clk[:, 0].max() - t0) / 100.0:.2f} us; "
           f"last end {(clk[:, 7].max() - t0) / 100.0:.2f} us after the first start")
-    for k in (1, 8, 9, 10, 2, 3, 4, 5, 6, 7):
+    ks = (11, 1, 8, 9, 10, 2, 3, 4, 5, 6, 7) if clk[:, 11].any() else (1, 8, 9, 10, 2, 3, 4, 5, 6, 7)
+    for k in ks:
         d = rel[:, k]
         print(f"  {names[k]:18s} mean {d.mean():6.2f}  median {np.median(d):6.2f}  p95 {np.percentile(d, 95):6.2f}  max {d.max():6.2f}")
