@@ -49,6 +49,18 @@ class Context:
         if rc != _capi.RRTX_OK:
             raise RrtxError(rc, self._lib.rrtx_last_error(self._h).decode())
 
+    def _two_call(self, cap: int, call):
+        """The two-call pattern: call(cap, needed) allocates room for cap entries and makes the C call with `needed`
+        as its count output, returning (rc, arrays); RRTX_E_CAPACITY repeats it with cap = needed.
+        Returns (needed, arrays)."""
+        while True:
+            needed = C.c_int64()
+            rc, arrays = call(cap, C.byref(needed))
+            if rc != _capi.RRTX_E_CAPACITY:
+                self._check(rc)
+                return int(needed.value), arrays
+            cap = int(needed.value)
+
     @property
     def handle(self):
         return self._h
@@ -172,19 +184,14 @@ class Context:
         if cap is None:
             cap = max(64 * nq, 1024)
         offsets = np.empty(nq + 1, dtype=np.int64)
-        while True:
+
+        def call(cap, needed):
             idx = np.empty(cap, dtype=np.int32)
             dist = np.empty(cap, dtype=np.float64)
-            needed = C.c_int64()
-            rc = self._lib.rrtx_nn_radius(self._h, _capi._ptr(q), _capi._ptr(r_arr), stride, nq,
-                                          _capi._ptr(offsets), _capi._ptr(idx), _capi._ptr(dist), cap,
-                                          C.byref(needed))
-            if rc == _capi.RRTX_E_CAPACITY:
-                cap = int(needed.value)     # two-call pattern
-                continue
-            self._check(rc)
-            n = int(needed.value)
-            return offsets, idx[:n], dist[:n]
+            return self._lib.rrtx_nn_radius(self._h, _capi._ptr(q), _capi._ptr(r_arr), stride, nq, _capi._ptr(offsets),
+                                            _capi._ptr(idx), _capi._ptr(dist), cap, needed), (idx, dist)
+        n, (idx, dist) = self._two_call(cap, call)
+        return offsets, idx[:n], dist[:n]
 
     # ---- collision ---------------------------------------------------------------------
     def edges_check(self, p0, p1, robot_radius: float, kind: int = 0, obstacle: int = -1,
@@ -273,16 +280,13 @@ class Context:
         off = np.empty(ne + 1, dtype=np.int64)
         cap = max(64 * ne, 64)
         cols = 3 if self.space_has_time else 2
-        while True:
+
+        def call(cap, needed):
             xy = np.empty((cap, cols), dtype=np.float64)
-            needed = C.c_int64()
-            rc = self._lib.rrtx_dubins_trajectory(self._h, _capi._ptr(s), _capi._ptr(g), ne, r_min, _capi._ptr(off),
-                                                  _capi._ptr(xy), cols, cap, C.byref(needed))
-            if rc == _capi.RRTX_E_CAPACITY:
-                cap = int(needed.value)
-                continue
-            self._check(rc)
-            return off, xy[: int(needed.value)]
+            return self._lib.rrtx_dubins_trajectory(self._h, _capi._ptr(s), _capi._ptr(g), ne, r_min, _capi._ptr(off),
+                                                    _capi._ptr(xy), cols, cap, needed), xy
+        n, xy = self._two_call(cap, call)
+        return off, xy[:n]
 
     def detmath_eval(self, op: int, x, y=None):
         """include/rrtx_detmath.h on the device, element-wise: 0 sin(x), 1 cos(x), 2 atan2(y, x), 3 acos(x)."""
@@ -334,23 +338,19 @@ class Context:
         nidx = np.empty(nq, dtype=np.int32)
         ndist = np.empty(nq, dtype=np.float64)
         unsafe = np.empty(nq, dtype=np.uint8)
-        while True:
+
+        def call(cap, needed):
             idx = np.empty(cap, dtype=np.int32)
             cost = np.empty(cap, dtype=np.float64)
             hout = np.empty(cap, dtype=np.uint8)
             hin = np.empty(cap, dtype=np.uint8)
-            needed = C.c_int64()
-            rc = self._lib.rrtx_extend_candidates(self._h, _capi._ptr(q), nq, r, robot_radius, _capi._ptr(offsets),
-                                                  _capi._ptr(idx), _capi._ptr(cost), _capi._ptr(hout),
-                                                  _capi._ptr(hin), cap, C.byref(needed), _capi._ptr(nidx),
-                                                  _capi._ptr(ndist), _capi._ptr(unsafe))
-            if rc == _capi.RRTX_E_CAPACITY:
-                cap = int(needed.value)
-                continue
-            self._check(rc)
-            n = int(needed.value)
-            return dict(offsets=offsets, idx=idx[:n], cost=cost[:n], hit_out=hout[:n], hit_in=hin[:n],
-                        nearest_idx=nidx, nearest_dist=ndist, sample_unsafe=unsafe)
+            return self._lib.rrtx_extend_candidates(self._h, _capi._ptr(q), nq, r, robot_radius, _capi._ptr(offsets),
+                                                    _capi._ptr(idx), _capi._ptr(cost), _capi._ptr(hout),
+                                                    _capi._ptr(hin), cap, needed, _capi._ptr(nidx), _capi._ptr(ndist),
+                                                    _capi._ptr(unsafe)), (idx, cost, hout, hin)
+        n, (idx, cost, hout, hin) = self._two_call(cap, call)
+        return dict(offsets=offsets, idx=idx[:n], cost=cost[:n], hit_out=hout[:n], hit_in=hin[:n],
+                    nearest_idx=nidx, nearest_dist=ndist, sample_unsafe=unsafe)
 
     def extend_candidates_dubins(self, q, r: float, robot_radius: float, r_min: float, cap: Optional[int] = None):
         """Fused extend() preamble for Edge = DubinsEdge (dim 4, theta wrapped, polygon obstacles)."""
@@ -362,7 +362,8 @@ class Context:
         nidx = np.empty(nq, dtype=np.int32)
         ndist = np.empty(nq, dtype=np.float64)
         unsafe = np.empty(nq, dtype=np.uint8)
-        while True:
+
+        def call(cap, needed):
             idx = np.empty(cap, dtype=np.int32)
             key = np.empty(cap, dtype=np.float64)
             co = np.empty(cap, dtype=np.float64)
@@ -371,19 +372,15 @@ class Context:
             wi = np.empty((cap, 3), dtype=np.uint8)
             ho = np.empty(cap, dtype=np.uint8)
             hi = np.empty(cap, dtype=np.uint8)
-            needed = C.c_int64()
-            rc = self._lib.rrtx_extend_candidates_dubins(
+            return self._lib.rrtx_extend_candidates_dubins(
                 self._h, _capi._ptr(q), nq, r, robot_radius, r_min, _capi._ptr(offsets), _capi._ptr(idx),
                 _capi._ptr(key), _capi._ptr(co), _capi._ptr(ci), _capi._ptr(wo), _capi._ptr(wi), _capi._ptr(ho),
-                _capi._ptr(hi), cap, C.byref(needed), _capi._ptr(nidx), _capi._ptr(ndist), _capi._ptr(unsafe))
-            if rc == _capi.RRTX_E_CAPACITY:
-                cap = int(needed.value)
-                continue
-            self._check(rc)
-            n = int(needed.value)
-            return dict(offsets=offsets, idx=idx[:n], key=key[:n], cost_out=co[:n], cost_in=ci[:n],
-                        word_out=wo[:n].view("S3").ravel(), word_in=wi[:n].view("S3").ravel(), hit_out=ho[:n],
-                        hit_in=hi[:n], nearest_idx=nidx, nearest_dist=ndist, sample_unsafe=unsafe)
+                _capi._ptr(hi), cap, needed, _capi._ptr(nidx), _capi._ptr(ndist),
+                _capi._ptr(unsafe)), (idx, key, co, ci, wo, wi, ho, hi)
+        n, (idx, key, co, ci, wo, wi, ho, hi) = self._two_call(cap, call)
+        return dict(offsets=offsets, idx=idx[:n], key=key[:n], cost_out=co[:n], cost_in=ci[:n],
+                    word_out=wo[:n].view("S3").ravel(), word_in=wi[:n].view("S3").ravel(), hit_out=ho[:n],
+                    hit_in=hi[:n], nearest_idx=nidx, nearest_dist=ndist, sample_unsafe=unsafe)
 
     # ---- device-pointer variants (pointers are ints, e.g. torch.Tensor.data_ptr()) ----------------
     def nn_nearest_dev(self, q_ptr: int, nq: int, idx_ptr: int, dist_ptr: int):
@@ -474,16 +471,13 @@ class Context:
         search_range of sphere `obstacle` and collide with it."""
         if cap is None:
             cap = 4096
-        while True:
+
+        def call(cap, needed):
             ids = np.empty(max(cap, 1), dtype=np.int32)
-            needed = C.c_int64()
-            rc = self._lib.rrtx_obstacle_sweep(self._h, obstacle, search_range, robot_radius, _capi._ptr(ids), cap,
-                                               C.byref(needed))
-            if rc == _capi.RRTX_E_CAPACITY:
-                cap = int(needed.value)
-                continue
-            self._check(rc)
-            return ids[:int(needed.value)]
+            return self._lib.rrtx_obstacle_sweep(self._h, obstacle, search_range, robot_radius, _capi._ptr(ids), cap,
+                                                 needed), ids
+        n, ids = self._two_call(cap, call)
+        return ids[:n]
 
     def obstacle_sweep_polygon(self, obstacle: int, robot_radius: float, delta: float, r_min: float = 0.0,
                                remove: bool = False, cap: Optional[int] = None):
@@ -493,16 +487,13 @@ class Context:
         context, DubinsEdge (r_min) in a dim = 4 one."""
         if cap is None:
             cap = 4096
-        while True:
+
+        def call(cap, needed):
             ids = np.empty(max(cap, 1), dtype=np.int32)
-            needed = C.c_int64()
-            rc = self._lib.rrtx_obstacle_sweep_polygon(self._h, obstacle, robot_radius, delta, r_min, 1 if remove else 0,
-                                                       _capi._ptr(ids), cap, C.byref(needed))
-            if rc == _capi.RRTX_E_CAPACITY:
-                cap = int(needed.value)
-                continue
-            self._check(rc)
-            return ids[:int(needed.value)]
+            return self._lib.rrtx_obstacle_sweep_polygon(self._h, obstacle, robot_radius, delta, r_min, 1 if remove else 0,
+                                                         _capi._ptr(ids), cap, needed), ids
+        n, ids = self._two_call(cap, call)
+        return ids[:n]
 
     def dubins_edges_check_obstacle(self, s, g, r_min: float, robot_radius: float, obstacle: int):
         """explicitEdgeCheck(S, edge::DubinsEdge, ob) against polygon `obstacle` alone."""

@@ -378,9 +378,44 @@ static void arena_flush(rrtx_ctx *ctx) {
 }
 
 // stage a host array on the device workspace `buf`
-int stage_in(rrtx_ctx *ctx, DevBuf &buf, const void *host, size_t bytes) {
-  RRTX_HIP(ctx, buf.ensure(bytes ? bytes : 8));
-  if (bytes) RRTX_HIP(ctx, hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+hipError_t stage_in(rrtx_ctx *ctx, DevBuf &buf, const void *host, size_t bytes) {
+  hipError_t e = buf.ensure(bytes ? bytes : 8);
+  if (e == hipSuccess && bytes) e = hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, ctx->stream);
+  return e;
+}
+// two host arrays of the same size (the endpoints of a batch of edges) -> ws_q, ws_q2
+hipError_t stage_pair(rrtx_ctx *ctx, const double *s, const double *g, size_t bytes) {
+  hipError_t e = stage_in(ctx, ctx->ws_q, s, bytes);
+  return e != hipSuccess ? e : stage_in(ctx, ctx->ws_q2, g, bytes);
+}
+// queue the copy of a device result straight into caller memory; an output the caller did not ask for (null) or an
+// empty one is skipped.  The caller synchronises once all its copies are queued.
+hipError_t copy_out(rrtx_ctx *ctx, void *dst, const void *src_dev, size_t bytes) {
+  return dst && bytes ? hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+}
+// the entry count of a two-call entry point, read back after whatever the caller has queued before it
+hipError_t read_count(rrtx_ctx *ctx, const void *count_dev, int64_t *count) {
+  hipError_t e = hipMemcpyAsync(count, count_dev, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
+  return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+}
+// the capacity step of a two-call entry point: report the count, and refuse it above cap before any entry is copied
+int check_capacity(rrtx_ctx *ctx, const char *fn, const char *noun, int64_t count, int64_t cap, int64_t *needed) {
+  if (needed) *needed = count;
+  if (count > cap) return fail(ctx, RRTX_E_CAPACITY, "%s: %lld %s, capacity %lld", fn, (long long)count, noun, (long long)cap);
+  return RRTX_OK;
+}
+// samples with an empty ball (nearest index -1): resolve with the full nearest scan
+int nearest_fallback(rrtx_ctx *ctx, const double *q, int nq, int dim, int32_t *nearest_idx, double *nearest_dist) {
+  std::vector<int> miss;
+  for (int i = 0; i < nq; ++i) if (nearest_idx[i] < 0) miss.push_back(i);
+  if (miss.empty()) return RRTX_OK;
+  std::vector<double> mq(miss.size() * (size_t)dim);
+  for (size_t k = 0; k < miss.size(); ++k) std::memcpy(&mq[k * dim], q + (size_t)miss[k] * dim, sizeof(double) * dim);
+  std::vector<int32_t> mi(miss.size());
+  std::vector<double> md(miss.size());
+  int rc = rrtx_nn_nearest(ctx, mq.data(), (int)miss.size(), mi.data(), md.data());
+  if (rc) return rc;
+  for (size_t k = 0; k < miss.size(); ++k) { nearest_idx[miss[k]] = mi[k]; nearest_dist[miss[k]] = md[k]; }
   return RRTX_OK;
 }
 // the samples of a batched call: through the pinned arena when they are small (one host memcpy of cache-resident data,
@@ -638,12 +673,16 @@ int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out) {
 // ---- tree ---------------------------------------------------------------------------
 int64_t rrtx_nodes_count(rrtx_ctx *ctx) { return ctx ? ctx->n_nodes : 0; }
 
+static int nodes_append_args(rrtx_ctx *ctx, const double *pos, int64_t n) {
+  if (n < 0 || (n > 0 && !pos)) return fail(ctx, RRTX_E_INVALID, "nodes_append: bad arguments");
+  return RRTX_OK;
+}
+
 int rrtx_nodes_append_dev(rrtx_ctx *ctx, const double *pos_dev, int64_t n) {
   CHECK_CTX(ctx);
-  if (n < 0 || (n > 0 && !pos_dev)) return fail(ctx, RRTX_E_INVALID, "nodes_append: bad arguments");
-  if (n == 0) return RRTX_OK;
-  int rc = grow_nodes(ctx, ctx->n_nodes + n);
-  if (rc) return rc;
+  int rc = nodes_append_args(ctx, pos_dev, n);
+  if (rc || n == 0) return rc;
+  if ((rc = grow_nodes(ctx, ctx->n_nodes + n))) return rc;
   if (!ctx->origin_set) {
     // origin of the fp32 shadow = the first node (the tree root); one small read-back, once per ctx
     double first[4] = {0, 0, 0, 0};
@@ -678,11 +717,11 @@ int rrtx_nodes_append_dev(rrtx_ctx *ctx, const double *pos_dev, int64_t n) {
 
 int rrtx_nodes_append(rrtx_ctx *ctx, const double *pos, int64_t n, int64_t *first_index) {
   CHECK_CTX(ctx);
-  if (n < 0 || (n > 0 && !pos)) return fail(ctx, RRTX_E_INVALID, "nodes_append: bad arguments");
+  int rc = nodes_append_args(ctx, pos, n);
+  if (rc) return rc;
   if (first_index) *first_index = ctx->n_nodes;
   if (n == 0) return RRTX_OK;
-  int rc = stage_in(ctx, ctx->ws_q, pos, sizeof(double) * (size_t)n * ctx->dim);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, pos, sizeof(double) * (size_t)n * ctx->dim));
   rc = rrtx_nodes_append_dev(ctx, ctx->ws_q.as<double>(), n);
   if (rc) return rc;
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -788,73 +827,88 @@ int rrtx_polygon_paths_set(rrtx_ctx *ctx, const int32_t *path_off, const double 
 }
 
 // ---- nearest neighbours ----------------------------------------------------------------
+// (argument checks shared by each host-pointer entry point and its _dev twin)
+static int nn_nearest_args(rrtx_ctx *ctx, const double *q, int nq, const int32_t *idx, const double *dist) {
+  if (nq < 0 || (nq > 0 && (!q || !idx || !dist))) return fail(ctx, RRTX_E_INVALID, "nn_nearest: bad arguments");
+  return RRTX_OK;
+}
+
 int rrtx_nn_nearest_dev(rrtx_ctx *ctx, const double *q, int nq, int32_t *idx, double *dist) {
   CHECK_CTX(ctx);
-  if (nq < 0 || (nq > 0 && (!q || !idx || !dist))) return fail(ctx, RRTX_E_INVALID, "nn_nearest: bad arguments");
-  return launch_nn_nearest(ctx, q, nq, idx, dist);
+  int rc = nn_nearest_args(ctx, q, nq, idx, dist);
+  return rc ? rc : launch_nn_nearest(ctx, q, nq, idx, dist);
 }
 
 int rrtx_nn_nearest(rrtx_ctx *ctx, const double *q, int nq, int32_t *idx, double *dist) {
   CHECK_CTX(ctx);
-  if (nq < 0 || (nq > 0 && (!q || !idx || !dist))) return fail(ctx, RRTX_E_INVALID, "nn_nearest: bad arguments");
-  if (nq == 0) return RRTX_OK;
-  int rc = stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim);
-  if (rc) return rc;
+  int rc = nn_nearest_args(ctx, q, nq, idx, dist);
+  if (rc || nq == 0) return rc;
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim));
   RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)nq));
   RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)nq));
   rc = launch_nn_nearest(ctx, ctx->ws_q.as<double>(), nq, ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_dist.as<double>());
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipMemcpyAsync(dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)nq));
+  RRTX_HIP(ctx, copy_out(ctx, dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)nq));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
+}
+
+static int nn_knearest_args(rrtx_ctx *ctx, const double *q, int nq, const int32_t *idx, const double *dist,
+                            const int32_t *count) {
+  if (nq < 0 || (nq > 0 && (!q || !idx || !dist || !count)))
+    return fail(ctx, RRTX_E_INVALID, "nn_knearest: bad arguments");
   return RRTX_OK;
 }
 
 int rrtx_nn_knearest_dev(rrtx_ctx *ctx, const double *q, int nq, int k, int32_t *idx, double *dist, int32_t *count) {
   CHECK_CTX(ctx);
-  if (nq < 0 || (nq > 0 && (!q || !idx || !dist || !count)))
-    return fail(ctx, RRTX_E_INVALID, "nn_knearest: bad arguments");
-  return launch_nn_knearest(ctx, q, nq, k, idx, dist, count);
+  int rc = nn_knearest_args(ctx, q, nq, idx, dist, count);
+  return rc ? rc : launch_nn_knearest(ctx, q, nq, k, idx, dist, count);
 }
 
 int rrtx_nn_knearest(rrtx_ctx *ctx, const double *q, int nq, int k, int32_t *idx, double *dist, int32_t *count) {
   CHECK_CTX(ctx);
-  if (nq < 0 || (nq > 0 && (!q || !idx || !dist || !count)))
-    return fail(ctx, RRTX_E_INVALID, "nn_knearest: bad arguments");
-  if (nq == 0) return RRTX_OK;
+  int rc = nn_knearest_args(ctx, q, nq, idx, dist, count);
+  if (rc || nq == 0) return rc;
   const size_t stride = (size_t)(k < 2 ? 2 : k);
-  int rc = stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim));
   RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * ((size_t)nq * stride + (size_t)nq)));
   RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)nq * stride));
   int32_t *idx_dev = ctx->ws_out_idx.as<int32_t>();
   int32_t *count_dev = idx_dev + (size_t)nq * stride;
   rc = launch_nn_knearest(ctx, ctx->ws_q.as<double>(), nq, k, idx_dev, ctx->ws_out_dist.as<double>(), count_dev);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(idx, idx_dev, sizeof(int32_t) * (size_t)nq * stride, hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipMemcpyAsync(dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)nq * stride, hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipMemcpyAsync(count, count_dev, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, idx, idx_dev, sizeof(int32_t) * (size_t)nq * stride));
+  RRTX_HIP(ctx, copy_out(ctx, dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)nq * stride));
+  RRTX_HIP(ctx, copy_out(ctx, count, count_dev, sizeof(int32_t) * (size_t)nq));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
+}
+
+// (the _dev form takes one radius: r points at it, r_stride = 0)
+static int nn_radius_args(rrtx_ctx *ctx, const double *q, const double *r, int r_stride, int nq, const int64_t *offsets,
+                          const int32_t *idx, const double *dist, int64_t cap) {
+  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !r || !offsets)) || (cap > 0 && (!idx || !dist)) ||
+      (r_stride != 0 && r_stride != 1))
+    return fail(ctx, RRTX_E_INVALID, "nn_radius: bad arguments");
   return RRTX_OK;
 }
 
 int rrtx_nn_radius_dev(rrtx_ctx *ctx, const double *q, double r, int nq, int64_t *offsets, int32_t *idx,
                        double *dist, int64_t cap, int64_t *needed_dev) {
   CHECK_CTX(ctx);
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && (!idx || !dist)))
-    return fail(ctx, RRTX_E_INVALID, "nn_radius: bad arguments");
-  return launch_nn_radius(ctx, q, nullptr, r, nq, offsets, idx, dist, cap, needed_dev);
+  int rc = nn_radius_args(ctx, q, &r, 0, nq, offsets, idx, dist, cap);
+  return rc ? rc : launch_nn_radius(ctx, q, nullptr, r, nq, offsets, idx, dist, cap, needed_dev);
 }
 
 int rrtx_nn_radius(rrtx_ctx *ctx, const double *q, const double *r, int r_stride, int nq, int64_t *offsets,
                    int32_t *idx, double *dist, int64_t cap, int64_t *needed) {
   CHECK_CTX(ctx);
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !r || !offsets)) || (cap > 0 && (!idx || !dist)) ||
-      (r_stride != 0 && r_stride != 1))
-    return fail(ctx, RRTX_E_INVALID, "nn_radius: bad arguments");
-  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
-  int rc = stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim);
+  int rc = nn_radius_args(ctx, q, r, r_stride, nq, offsets, idx, dist, cap);
   if (rc) return rc;
+  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim));
   const double *thr_dev = nullptr;
   if (r_stride == 1) {
     std::vector<double> thr(2 * (size_t)nq);
@@ -863,8 +917,7 @@ int rrtx_nn_radius(rrtx_ctx *ctx, const double *q, const double *r, int r_stride
       if (!(r[i] == last_r)) { last_r = r[i]; lt = thr_first_ge(r[i]); gt = thr_first_gt(r[i]); }
       thr[i] = lt; thr[(size_t)nq + i] = gt;
     }
-    rc = stage_in(ctx, ctx->ws_thr, thr.data(), sizeof(double) * thr.size());
-    if (rc) return rc;
+    RRTX_HIP(ctx, stage_in(ctx, ctx->ws_thr, thr.data(), sizeof(double) * thr.size()));
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // thr goes out of scope
     thr_dev = ctx->ws_thr.as<double>();
   }
@@ -878,27 +931,31 @@ int rrtx_nn_radius(rrtx_ctx *ctx, const double *q, const double *r, int r_stride
                         ctx->ws_out_dist.as<double>(), cap, needed_dev);
   if (rc) return rc;
   int64_t total = 0;
-  RRTX_HIP(ctx, hipMemcpyAsync(offsets, off_dev, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipMemcpyAsync(&total, needed_dev, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (needed) *needed = total;
+  RRTX_HIP(ctx, copy_out(ctx, offsets, off_dev, sizeof(int64_t) * ((size_t)nq + 1)));
+  RRTX_HIP(ctx, read_count(ctx, needed_dev, &total));
   ctx->last_neighbors = total;
-  if (total > cap) return fail(ctx, RRTX_E_CAPACITY, "nn_radius: %lld neighbours, capacity %lld", (long long)total, (long long)cap);
+  if ((rc = check_capacity(ctx, "nn_radius", "neighbours", total, cap, needed))) return rc;
   if (total > 0) {
-    RRTX_HIP(ctx, hipMemcpyAsync(idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipMemcpyAsync(dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    RRTX_HIP(ctx, copy_out(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total));
+    RRTX_HIP(ctx, copy_out(ctx, dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)total));
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return RRTX_OK;
 }
 
 // ---- collision ----------------------------------------------------------------------------
+static int edges_check_args(rrtx_ctx *ctx, int kind, const double *p0, const double *p1, int64_t ne, const uint8_t *hit) {
+  if (ne < 0 || (ne > 0 && (!p0 || !p1 || !hit)) || (kind != 0 && kind != 1))
+    return fail(ctx, RRTX_E_INVALID, "edges_check: bad arguments");
+  return RRTX_OK;
+}
+
 int rrtx_edges_check_dev(rrtx_ctx *ctx, int kind, const double *p0, const double *p1, int64_t ne,
                          double robot_radius, int obstacle_or_minus1, int obs_begin, int obs_end, uint8_t *hit,
                          int32_t *first_hit) {
   CHECK_CTX(ctx);
-  if (ne < 0 || (ne > 0 && (!p0 || !p1 || !hit)) || (kind != 0 && kind != 1))
-    return fail(ctx, RRTX_E_INVALID, "edges_check: bad arguments");
+  int rc = edges_check_args(ctx, kind, p0, p1, ne, hit);
+  if (rc) return rc;
   if (kind == 0)
     return launch_edges_spheres(ctx, p0, p1, ne, robot_radius, obstacle_or_minus1, obs_begin, obs_end, hit, first_hit);
   return launch_edges_polygons(ctx, p0, p1, ne, robot_radius, obstacle_or_minus1, obs_begin, obs_end, hit, first_hit);
@@ -907,23 +964,17 @@ int rrtx_edges_check_dev(rrtx_ctx *ctx, int kind, const double *p0, const double
 int rrtx_edges_check(rrtx_ctx *ctx, int kind, const double *p0, const double *p1, int64_t ne, double robot_radius,
                      int obstacle_or_minus1, uint8_t *hit, int32_t *first_hit) {
   CHECK_CTX(ctx);
-  if (ne < 0 || (ne > 0 && (!p0 || !p1 || !hit)) || (kind != 0 && kind != 1))
-    return fail(ctx, RRTX_E_INVALID, "edges_check: bad arguments");
-  if (ne == 0) return RRTX_OK;
-  const size_t pb = sizeof(double) * (size_t)ne * ctx->dim;
-  int rc = stage_in(ctx, ctx->ws_q, p0, pb);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_q2, p1, pb);
-  if (rc) return rc;
+  int rc = edges_check_args(ctx, kind, p0, p1, ne, hit);
+  if (rc || ne == 0) return rc;
+  RRTX_HIP(ctx, stage_pair(ctx, p0, p1, sizeof(double) * (size_t)ne * ctx->dim));
   RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)ne));
   rc = rrtx_edges_check_dev(ctx, kind, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, robot_radius,
                             obstacle_or_minus1, -1, -1, ctx->ws_out_u8a.as<uint8_t>(),
                             first_hit ? ctx->ws_out_i32.as<int32_t>() : nullptr);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(hit, ctx->ws_out_u8a.p, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (first_hit)
-    RRTX_HIP(ctx, hipMemcpyAsync(first_hit, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, hit, ctx->ws_out_u8a.p, (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, first_hit, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -939,19 +990,16 @@ int rrtx_edges_check_idx(rrtx_ctx *ctx, const int32_t *start_idx, const int32_t 
     if (start_idx[i] < 0 || start_idx[i] >= ctx->n_nodes || end_idx[i] < 0 || end_idx[i] >= ctx->n_nodes)
       return fail(ctx, RRTX_E_INVALID, "edges_check_idx: edge %lld references a node outside [0, %lld)",
                   (long long)i, (long long)ctx->n_nodes);
-  int rc = stage_in(ctx, ctx->ws_i32a, start_idx, sizeof(int32_t) * (size_t)ne);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_i32b, end_idx, sizeof(int32_t) * (size_t)ne);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_i32a, start_idx, sizeof(int32_t) * (size_t)ne));
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_i32b, end_idx, sizeof(int32_t) * (size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)ne));
-  rc = launch_edges_spheres(ctx, nullptr, nullptr, ne, robot_radius, obstacle_or_minus1, -1, -1,
-                            ctx->ws_out_u8a.as<uint8_t>(), first_hit ? ctx->ws_out_i32.as<int32_t>() : nullptr,
-                            ctx->ws_i32a.as<int32_t>(), ctx->ws_i32b.as<int32_t>(), obstacle_mask);
+  int rc = launch_edges_spheres(ctx, nullptr, nullptr, ne, robot_radius, obstacle_or_minus1, -1, -1,
+                                ctx->ws_out_u8a.as<uint8_t>(), first_hit ? ctx->ws_out_i32.as<int32_t>() : nullptr,
+                                ctx->ws_i32a.as<int32_t>(), ctx->ws_i32b.as<int32_t>(), obstacle_mask);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(hit, ctx->ws_out_u8a.p, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (first_hit)
-    RRTX_HIP(ctx, hipMemcpyAsync(first_hit, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, hit, ctx->ws_out_u8a.p, (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, first_hit, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -1020,28 +1068,32 @@ int rrtx_graph_edges_block(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
 }
 
 namespace {
-int graph_cost_host(rrtx_ctx *ctx, const char *fn, int root_idx, bool update, double *lmc, int32_t *parent_edge, int32_t *passes) {
+int graph_cost_args(rrtx_ctx *ctx, const char *fn, int root_idx, const double *lmc) {
   if (!lmc) return fail(ctx, RRTX_E_INVALID, "%s: lmc is NULL", fn);
   if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "%s on an empty tree", fn);
   if (root_idx < 0 || root_idx >= ctx->n_nodes) return fail(ctx, RRTX_E_INVALID, "%s: root %d out of range", fn, root_idx);
+  return RRTX_OK;
+}
+
+int graph_cost_host(rrtx_ctx *ctx, const char *fn, int root_idx, bool update, double *lmc, int32_t *parent_edge, int32_t *passes) {
+  int rc = graph_cost_args(ctx, fn, root_idx, lmc);
+  if (rc) return rc;
   const size_t n = (size_t)ctx->n_nodes;
   RRTX_HIP(ctx, ctx->ws_out_f64.ensure(sizeof(double) * n));
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * n));
   int np = 0;
-  int rc = launch_graph_cost(ctx, root_idx, update, ctx->ws_out_f64.as<double>(), parent_edge ? ctx->ws_out_i32.as<int32_t>() : nullptr, &np);
+  rc = launch_graph_cost(ctx, root_idx, update, ctx->ws_out_f64.as<double>(), parent_edge ? ctx->ws_out_i32.as<int32_t>() : nullptr, &np);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(lmc, ctx->ws_out_f64.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (parent_edge) RRTX_HIP(ctx, hipMemcpyAsync(parent_edge, ctx->ws_out_i32.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, lmc, ctx->ws_out_f64.p, sizeof(double) * n));
+  RRTX_HIP(ctx, copy_out(ctx, parent_edge, ctx->ws_out_i32.p, sizeof(int32_t) * n));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (passes) *passes = np;
   return RRTX_OK;
 }
 
 int graph_cost_dev(rrtx_ctx *ctx, const char *fn, int root_idx, bool update, double *lmc_dev, int32_t *parent_edge_dev) {
-  if (!lmc_dev) return fail(ctx, RRTX_E_INVALID, "%s: lmc is NULL", fn);
-  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "%s on an empty tree", fn);
-  if (root_idx < 0 || root_idx >= ctx->n_nodes) return fail(ctx, RRTX_E_INVALID, "%s: root %d out of range", fn, root_idx);
-  return launch_graph_cost(ctx, root_idx, update, lmc_dev, parent_edge_dev, nullptr);
+  int rc = graph_cost_args(ctx, fn, root_idx, lmc_dev);
+  return rc ? rc : launch_graph_cost(ctx, root_idx, update, lmc_dev, parent_edge_dev, nullptr);
 }
 }  // namespace
 
@@ -1150,13 +1202,13 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
   if (rc) return rc;
   // ---- the out-edges (and parent edges) of those nodes; removeObstacle looks at blocked ones only ----
   RRTX_HIP(ctx, ctx->ws_i32a.ensure(sizeof(int32_t) * (size_t)ne));
-  long long *total_dev = nullptr, n_c = 0;
+  long long *total_dev = nullptr;
+  int64_t n_c = 0;
   span_begin(ctx, KF_EDGES);
   rc = launch_sweep_select(ctx, mode == 1 ? 1 : 0, ctx->ws_i32a.as<int32_t>(), ne, &total_dev);
   span_end(ctx);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(&n_c, total_dev, sizeof(n_c), hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  RRTX_HIP(ctx, read_count(ctx, total_dev, &n_c));
   ctx->last_sweep_candidates = n_c;
   if (n_c == 0) return RRTX_OK;
   // ---- explicitEdgeCheck(S, edge, ob) of every candidate; removeObstacle: and against every OTHER obstacle in use ----
@@ -1190,13 +1242,11 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
                            ctx->ws_out_i32.as<int32_t>(), cap, &total_dev);
   span_end(ctx);
   if (rc) return rc;
-  long long total = 0;
-  RRTX_HIP(ctx, hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (needed) *needed = total;
-  if (total > cap) return fail(ctx, RRTX_E_CAPACITY, "obstacle_sweep_polygon: %lld edges, capacity %lld", total, (long long)cap);
+  int64_t total = 0;
+  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));
+  if ((rc = check_capacity(ctx, "obstacle_sweep_polygon", "edges", total, cap, needed))) return rc;
   if (total > 0) {
-    RRTX_HIP(ctx, hipMemcpyAsync(edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return RRTX_OK;
@@ -1213,16 +1263,12 @@ int rrtx_dubins_edges_check_obstacle(rrtx_ctx *ctx, const double *s, const doubl
   int pb, pe;
   packed_range(active_positions(ctx->poly_active), obstacle, obstacle + 1, pb, pe);
   if (pe <= pb) { std::memset(hit, 0, (size_t)ne); return RRTX_OK; }          // not in use: collides with nothing
-  const size_t pbytes = sizeof(double) * (size_t)ne * 4;
-  int rc = stage_in(ctx, ctx->ws_q, s, pbytes);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_q2, g, pbytes);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_pair(ctx, s, g, sizeof(double) * (size_t)ne * 4));
   RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)ne));
-  rc = launch_dubins_edges_check(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min, robot_radius, nullptr, nullptr,
-                                 ctx->ws_out_u8b.as<uint8_t>(), nullptr, pb, pe);
+  int rc = launch_dubins_edges_check(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min, robot_radius, nullptr,
+                                     nullptr, ctx->ws_out_u8b.as<uint8_t>(), nullptr, pb, pe);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(hit, ctx->ws_out_u8b.p, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, hit, ctx->ws_out_u8b.p, (size_t)ne));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -1245,23 +1291,27 @@ int rrtx_obstacle_sweep(rrtx_ctx *ctx, int obstacle, double search_range, double
   int rc = launch_obstacle_sweep(ctx, c, thr_first_ge(search_range), thr_first_gt(search_range), ob,
                                  ctx->sph_active[obstacle] ? 1 : 0, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev);
   if (rc) return rc;
-  long long total = 0;
-  RRTX_HIP(ctx, hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (needed) *needed = total;
-  if (total > cap) return fail(ctx, RRTX_E_CAPACITY, "obstacle_sweep: %lld colliding edges, capacity %lld", total, (long long)cap);
+  int64_t total = 0;
+  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));
+  if ((rc = check_capacity(ctx, "obstacle_sweep", "colliding edges", total, cap, needed))) return rc;
   if (total > 0) {
-    RRTX_HIP(ctx, hipMemcpyAsync(edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return RRTX_OK;
+}
+
+static int points_check_args(rrtx_ctx *ctx, int kind, const double *p, int64_t np, const uint8_t *unsafe) {
+  if (np < 0 || (np > 0 && (!p || !unsafe)) || (kind != 0 && kind != 1))
+    return fail(ctx, RRTX_E_INVALID, "points_check: bad arguments");
   return RRTX_OK;
 }
 
 int rrtx_points_check_dev(rrtx_ctx *ctx, int kind, const double *p, int64_t np, double robot_radius, int quick,
                           uint8_t *unsafe, double *clearance) {
   CHECK_CTX(ctx);
-  if (np < 0 || (np > 0 && (!p || !unsafe)) || (kind != 0 && kind != 1))
-    return fail(ctx, RRTX_E_INVALID, "points_check: bad arguments");
+  int rc = points_check_args(ctx, kind, p, np, unsafe);
+  if (rc) return rc;
   if (kind == 0) return launch_points_spheres(ctx, p, np, robot_radius, quick, unsafe, clearance);
   return launch_points_polygons(ctx, p, np, robot_radius, unsafe, clearance);
 }
@@ -1269,20 +1319,17 @@ int rrtx_points_check_dev(rrtx_ctx *ctx, int kind, const double *p, int64_t np, 
 int rrtx_points_check(rrtx_ctx *ctx, int kind, const double *p, int64_t np, double robot_radius, int quick,
                       uint8_t *unsafe, double *clearance) {
   CHECK_CTX(ctx);
-  if (np < 0 || (np > 0 && (!p || !unsafe)) || (kind != 0 && kind != 1))
-    return fail(ctx, RRTX_E_INVALID, "points_check: bad arguments");
-  if (np == 0) return RRTX_OK;
-  int rc = stage_in(ctx, ctx->ws_q, p, sizeof(double) * (size_t)np * ctx->dim);
-  if (rc) return rc;
+  int rc = points_check_args(ctx, kind, p, np, unsafe);
+  if (rc || np == 0) return rc;
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, p, sizeof(double) * (size_t)np * ctx->dim));
   RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)np));
   RRTX_HIP(ctx, ctx->ws_out_f64.ensure(sizeof(double) * (size_t)np));
   // (no certificate wanted: the polygon check then only walks the obstacles near each point)
   rc = rrtx_points_check_dev(ctx, kind, ctx->ws_q.as<double>(), np, robot_radius, quick,
                              ctx->ws_out_u8a.as<uint8_t>(), clearance ? ctx->ws_out_f64.as<double>() : nullptr);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(unsafe, ctx->ws_out_u8a.p, (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
-  if (clearance)
-    RRTX_HIP(ctx, hipMemcpyAsync(clearance, ctx->ws_out_f64.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, unsafe, ctx->ws_out_u8a.p, (size_t)np));
+  RRTX_HIP(ctx, copy_out(ctx, clearance, ctx->ws_out_f64.p, sizeof(double) * (size_t)np));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -1292,18 +1339,14 @@ int rrtx_simple_steer(rrtx_ctx *ctx, const double *s, const double *g, int64_t n
   CHECK_CTX(ctx);
   if (ne < 0 || (ne > 0 && (!s || !g))) return fail(ctx, RRTX_E_INVALID, "simple_steer: bad arguments");
   if (ne == 0) return RRTX_OK;
-  const size_t pb = sizeof(double) * (size_t)ne * ctx->dim;
-  int rc = stage_in(ctx, ctx->ws_q, s, pb);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_q2, g, pb);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_pair(ctx, s, g, sizeof(double) * (size_t)ne * ctx->dim));
   RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_f64.ensure(sizeof(double) * (size_t)ne));
-  rc = launch_simple_steer(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, ctx->ws_out_dist.as<double>(),
-                           ctx->ws_out_f64.as<double>());
+  int rc = launch_simple_steer(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, ctx->ws_out_dist.as<double>(),
+                               ctx->ws_out_f64.as<double>());
   if (rc) return rc;
-  if (dist) RRTX_HIP(ctx, hipMemcpyAsync(dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (wdist) RRTX_HIP(ctx, hipMemcpyAsync(wdist, ctx->ws_out_f64.p, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, dist, ctx->ws_out_dist.p, sizeof(double) * (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, wdist, ctx->ws_out_f64.p, sizeof(double) * (size_t)ne));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -1315,15 +1358,12 @@ static int dubins_common(rrtx_ctx *ctx, const double *s, const double *g, int64_
     return fail(ctx, RRTX_E_INVALID, "dubins: bad arguments");
   if (ne == 0) return RRTX_OK;
   if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "Dubins steering needs a dim=4 [x y t theta] context");
-  const size_t pb = sizeof(double) * (size_t)ne * 4;
-  int rc = stage_in(ctx, ctx->ws_q, s, pb);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_q2, g, pb);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_pair(ctx, s, g, sizeof(double) * (size_t)ne * 4));
   RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(3 * (size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)ne));
+  int rc;
   if (check)
     rc = launch_dubins_edges_check(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min, robot_radius,
                                    ctx->ws_out_dist.as<double>(), ctx->ws_out_u8a.as<uint8_t>(),
@@ -1332,13 +1372,10 @@ static int dubins_common(rrtx_ctx *ctx, const double *s, const double *g, int64_
     rc = launch_dubins_steer(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min,
                              ctx->ws_out_dist.as<double>(), ctx->ws_out_u8a.as<uint8_t>());
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (word) RRTX_HIP(ctx, hipMemcpyAsync(word, ctx->ws_out_u8a.p, 3 * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (check) {
-    RRTX_HIP(ctx, hipMemcpyAsync(hit, ctx->ws_out_u8b.p, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-    if (traj_len)
-      RRTX_HIP(ctx, hipMemcpyAsync(traj_len, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  RRTX_HIP(ctx, copy_out(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, word, ctx->ws_out_u8a.p, 3 * (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, hit, ctx->ws_out_u8b.p, (size_t)ne));                  // (null unless check)
+  RRTX_HIP(ctx, copy_out(ctx, traj_len, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -1362,22 +1399,19 @@ int rrtx_dubins_steer_full(rrtx_ctx *ctx, const double *s, const double *g, int6
   if (ne < 0 || (ne > 0 && (!s || !g))) return fail(ctx, RRTX_E_INVALID, "dubins_steer_full: bad arguments");
   if (ne == 0) return RRTX_OK;
   if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "Dubins steering needs a dim=4 [x y t theta] context");
-  const size_t pb = sizeof(double) * (size_t)ne * 4;
-  int rc = stage_in(ctx, ctx->ws_q, s, pb);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_q2, g, pb);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_pair(ctx, s, g, sizeof(double) * (size_t)ne * 4));
   RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * 3 * (size_t)ne));
   RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(4 * (size_t)ne));
   double *d_dist = ctx->ws_out_dist.as<double>(), *d_w = d_dist + ne, *d_v = d_w + ne;
   uint8_t *d_word = ctx->ws_out_u8a.as<uint8_t>(), *d_valid = d_word + 3 * (size_t)ne;
-  rc = launch_dubins_steer(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min, d_dist, d_word, d_w, d_v, d_valid);
+  int rc = launch_dubins_steer(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min, d_dist, d_word, d_w, d_v,
+                               d_valid);
   if (rc) return rc;
-  if (dist) RRTX_HIP(ctx, hipMemcpyAsync(dist, d_dist, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (wdist) RRTX_HIP(ctx, hipMemcpyAsync(wdist, d_w, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (velocity) RRTX_HIP(ctx, hipMemcpyAsync(velocity, d_v, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (word) RRTX_HIP(ctx, hipMemcpyAsync(word, d_word, 3 * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
-  if (valid_move) RRTX_HIP(ctx, hipMemcpyAsync(valid_move, d_valid, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, dist, d_dist, sizeof(double) * (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, wdist, d_w, sizeof(double) * (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, velocity, d_v, sizeof(double) * (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, word, d_word, 3 * (size_t)ne));
+  RRTX_HIP(ctx, copy_out(ctx, valid_move, d_valid, (size_t)ne));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -1398,34 +1432,28 @@ int rrtx_dubins_trajectory(rrtx_ctx *ctx, const double *s, const double *g, int6
                 "the caller's buffer was sized for %d", ctx->opt_space_has_time ? 3 : 2, ctx->opt_space_has_time ? 1 : 0, cols_in);
   if (ne == 0) { if (needed_rows) *needed_rows = 0; if (traj_off) traj_off[0] = 0; return RRTX_OK; }
   if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "Dubins steering needs a dim=4 [x y t theta] context");
-  const size_t pb = sizeof(double) * (size_t)ne * 4;
-  int rc = stage_in(ctx, ctx->ws_q, s, pb);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_q2, g, pb);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_pair(ctx, s, g, sizeof(double) * (size_t)ne * 4));
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)ne));
   // pass 1: rows per edge
-  rc = launch_dubins_trajectory(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min, nullptr, nullptr, 0,
-                                ctx->ws_out_i32.as<int32_t>());
+  int rc = launch_dubins_trajectory(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min, nullptr, nullptr, 0,
+                                    ctx->ws_out_i32.as<int32_t>());
   if (rc) return rc;
   std::vector<int32_t> len((size_t)ne);
-  RRTX_HIP(ctx, hipMemcpyAsync(len.data(), ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, len.data(), ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)ne));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   traj_off[0] = 0;
   for (int64_t i = 0; i < ne; ++i) traj_off[i + 1] = traj_off[i] + len[(size_t)i];
   const int64_t total = traj_off[ne];
-  if (needed_rows) *needed_rows = total;
-  if (total > cap_rows) return fail(ctx, RRTX_E_CAPACITY, "dubins_trajectory: %lld rows, capacity %lld", (long long)total, (long long)cap_rows);
+  if ((rc = check_capacity(ctx, "dubins_trajectory", "rows", total, cap_rows, needed_rows))) return rc;
   if (total == 0) return RRTX_OK;
   // pass 2: write the polylines
-  rc = stage_in(ctx, ctx->ws_out_off, traj_off, sizeof(int64_t) * ((size_t)ne + 1));
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_out_off, traj_off, sizeof(int64_t) * ((size_t)ne + 1)));
   const size_t cols = ctx->opt_space_has_time ? 3 : 2;      // (x, y) or, in a space with time, (x, y, t)
   RRTX_HIP(ctx, ctx->ws_out_f64.ensure(sizeof(double) * cols * (size_t)total));
   rc = launch_dubins_trajectory(ctx, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), ne, r_min,
                                 ctx->ws_out_off.as<int64_t>(), ctx->ws_out_f64.as<double>(), total, nullptr);
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(traj_xy, ctx->ws_out_f64.p, sizeof(double) * cols * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, traj_xy, ctx->ws_out_f64.p, sizeof(double) * cols * (size_t)total));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -1436,26 +1464,30 @@ int rrtx_detmath_eval(rrtx_ctx *ctx, int op, const double *x, const double *y, i
     return fail(ctx, RRTX_E_INVALID, "detmath_eval: bad arguments");
   if (n == 0) return RRTX_OK;
   const size_t pb = sizeof(double) * (size_t)n;
-  int rc = stage_in(ctx, ctx->ws_q, x, pb);
-  if (rc) return rc;
-  rc = stage_in(ctx, ctx->ws_q2, y ? y : x, pb);
-  if (rc) return rc;
+  RRTX_HIP(ctx, stage_pair(ctx, x, y ? y : x, pb));
   RRTX_HIP(ctx, ctx->ws_out_dist.ensure(pb));
-  rc = launch_detmath_eval(ctx, op, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), n, ctx->ws_out_dist.as<double>());
+  int rc = launch_detmath_eval(ctx, op, ctx->ws_q.as<double>(), ctx->ws_q2.as<double>(), n, ctx->ws_out_dist.as<double>());
   if (rc) return rc;
-  RRTX_HIP(ctx, hipMemcpyAsync(out, ctx->ws_out_dist.p, pb, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, out, ctx->ws_out_dist.p, pb));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
 
 // ---- fused extend() preamble ------------------------------------------------------------------
+static int extend_candidates_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,
+                                  const double *cost, const uint8_t *hit_out, const uint8_t *hit_in, int64_t cap) {
+  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))
+    return fail(ctx, RRTX_E_INVALID, "extend_candidates: bad arguments");
+  return RRTX_OK;
+}
+
 int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
                                int64_t *offsets, int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in,
                                int64_t cap, int64_t *needed_dev, int32_t *nearest_idx, double *nearest_dist,
                                uint8_t *sample_unsafe) {
   CHECK_CTX(ctx);
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))
-    return fail(ctx, RRTX_E_INVALID, "extend_candidates: bad arguments");
+  int rc = extend_candidates_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
+  if (rc) return rc;
   if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_candidates is the SimpleEdge (dim=3) path");
   if (ctx->n_wraps != 0)
     return fail(ctx, RRTX_E_STATE, "extend_candidates reads kdFindNearest off the range lists, which is only valid "
@@ -1467,7 +1499,7 @@ int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r,
   // (kernels_finish.hip), so no -1 reaches the caller.
   if (ctx->opt_extend_polygons) {
     RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
-    int rc = launch_nn_radius(ctx, q, nullptr, r, nq, offsets, idx, cost, cap, needed_dev,
+    rc = launch_nn_radius(ctx, q, nullptr, r, nq, offsets, idx, cost, cap, needed_dev,
                               ctx->ws_owner.as<int32_t>(), want_nearest ? nearest_idx : nullptr,
                               want_nearest ? nearest_dist : nullptr);
     if (rc) return rc;
@@ -1477,7 +1509,7 @@ int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r,
   // sphere list: in the culled search the sample pass and both directed edges of every neighbour are
   // decided where the neighbour is found (kernels_nn.hip, TileEmit) and the finish kernel hands out
   // the flags; the other search paths (small trees, culling off) run the two kernels of their own
-  int rc = sync_spheres(ctx, robot_radius);
+  rc = sync_spheres(ctx, robot_radius);
   if (rc) return rc;
   RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
   ExtendFuse ef;
@@ -1495,8 +1527,8 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
                            int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap,
                            int64_t *needed, int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe) {
   CHECK_CTX(ctx);
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))
-    return fail(ctx, RRTX_E_INVALID, "extend_candidates: bad arguments");
+  int rc = extend_candidates_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
+  if (rc) return rc;
   if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
   // ONE small device block for everything that is per sample -- [offsets (nq + 1) | count | nearest_dist (nq) |
   // nearest_idx (nq) | sample_unsafe (nq)] -- so that it leaves in one transfer; the per-entry arrays follow once the
@@ -1504,7 +1536,7 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
   const int64_t dcap = cap > 0 ? cap : 1;
   const size_t o_cnt = sizeof(int64_t) * ((size_t)nq + 1), o_nd = o_cnt + sizeof(int64_t), o_ni = o_nd + sizeof(double) * (size_t)nq,
                o_un = o_ni + sizeof(int32_t) * (size_t)nq, small_bytes = o_un + (size_t)nq;
-  int rc = arena_begin(ctx, small_bytes + sizeof(double) * (size_t)nq * ctx->dim + 256);
+  rc = arena_begin(ctx, small_bytes + sizeof(double) * (size_t)nq * ctx->dim + 256);
   if (rc) return rc;
   rc = stage_in_small(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim);
   if (rc) return rc;
@@ -1533,9 +1565,8 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
   int64_t total = 0;
   std::memcpy(offsets, host_blk, o_cnt);
   std::memcpy(&total, host_blk + o_cnt, sizeof(int64_t));
-  if (needed) *needed = total;
   ctx->last_neighbors = total;
-  if (total > cap) return fail(ctx, RRTX_E_CAPACITY, "extend_candidates: %lld neighbours, capacity %lld", (long long)total, (long long)cap);
+  if ((rc = check_capacity(ctx, "extend_candidates", "neighbours", total, cap, needed))) return rc;
   if (total > 0) {
     if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)total))) return rc;
     if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
@@ -1552,21 +1583,16 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     arena_flush(ctx);
   }
-  if (nearest_idx && nearest_dist) {
-    // samples with an empty ball: resolve with the full nearest scan
-    std::vector<int> miss;
-    for (int i = 0; i < nq; ++i) if (nearest_idx[i] < 0) miss.push_back(i);
-    if (!miss.empty()) {
-      std::vector<double> mq(miss.size() * (size_t)ctx->dim);
-      for (size_t k = 0; k < miss.size(); ++k)
-        std::memcpy(&mq[k * ctx->dim], q + (size_t)miss[k] * ctx->dim, sizeof(double) * ctx->dim);
-      std::vector<int32_t> mi(miss.size());
-      std::vector<double> md(miss.size());
-      rc = rrtx_nn_nearest(ctx, mq.data(), (int)miss.size(), mi.data(), md.data());
-      if (rc) return rc;
-      for (size_t k = 0; k < miss.size(); ++k) { nearest_idx[miss[k]] = mi[k]; nearest_dist[miss[k]] = md[k]; }
-    }
-  }
+  return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
+}
+
+static int extend_dubins_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,
+                              const double *key, const double *cost_out, const double *cost_in, const uint8_t *hit_out,
+                              const uint8_t *hit_in, int64_t cap) {
+  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) ||
+      (cap > 0 && (!idx || !key || !cost_out || !cost_in || !hit_out || !hit_in)))
+    return fail(ctx, RRTX_E_INVALID, "extend_candidates_dubins: bad arguments");
+  if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "extend_candidates_dubins needs a dim=4 [x y t theta] context");
   return RRTX_OK;
 }
 
@@ -1576,18 +1602,15 @@ int rrtx_extend_candidates_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, do
                                       uint8_t *hit_in, int64_t cap, int64_t *needed_dev, int32_t *nearest_idx,
                                       double *nearest_dist, uint8_t *sample_unsafe) {
   CHECK_CTX(ctx);
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) ||
-      (cap > 0 && (!idx || !key || !cost_out || !cost_in || !hit_out || !hit_in)))
-    return fail(ctx, RRTX_E_INVALID, "extend_candidates_dubins: bad arguments");
-  if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "extend_candidates_dubins needs a dim=4 [x y t theta] context");
-  if (nq == 0) return RRTX_OK;
+  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
+  if (rc || nq == 0) return rc;
   RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
   const bool want_nearest = nearest_idx && nearest_dist;
   // with wrapped dimensions a list key is the distance to the copy that found the node FIRST
   // (addToRangeList), not the minimum over the copies, so kdFindNearest cannot be read off the list
   const bool nearest_from_list = want_nearest && ctx->n_wraps == 0;
-  int rc = launch_nn_radius(ctx, q, nullptr, r, nq, offsets, idx, key, cap, needed_dev, ctx->ws_owner.as<int32_t>(),
-                            nearest_from_list ? nearest_idx : nullptr, nearest_from_list ? nearest_dist : nullptr);
+  rc = launch_nn_radius(ctx, q, nullptr, r, nq, offsets, idx, key, cap, needed_dev, ctx->ws_owner.as<int32_t>(),
+                        nearest_from_list ? nearest_idx : nullptr, nearest_from_list ? nearest_dist : nullptr);
   if (rc) return rc;
   rc = launch_candidate_dubins(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, r_min, robot_radius, cost_out,
                                cost_in, word_out, word_in, hit_out, hit_in);
@@ -1609,13 +1632,10 @@ int rrtx_extend_candidates_dubins(rrtx_ctx *ctx, const double *q, int nq, double
                                   uint8_t *hit_in, int64_t cap, int64_t *needed, int32_t *nearest_idx,
                                   double *nearest_dist, uint8_t *sample_unsafe) {
   CHECK_CTX(ctx);
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) ||
-      (cap > 0 && (!idx || !key || !cost_out || !cost_in || !hit_out || !hit_in)))
-    return fail(ctx, RRTX_E_INVALID, "extend_candidates_dubins: bad arguments");
-  if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "extend_candidates_dubins needs a dim=4 [x y t theta] context");
-  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
-  int rc = stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * 4);
+  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
   if (rc) return rc;
+  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * 4));
   const int64_t dcap = cap > 0 ? cap : 1;
   const bool want_nearest = nearest_idx && nearest_dist;
   RRTX_HIP(ctx, ctx->ws_out_off.ensure(sizeof(int64_t) * ((size_t)nq + 2)));
@@ -1637,43 +1657,26 @@ int rrtx_extend_candidates_dubins(rrtx_ctx *ctx, const double *q, int nq, double
                                          sample_unsafe ? unsafe_dev : nullptr);
   if (rc) return rc;
   int64_t total = 0;
-  RRTX_HIP(ctx, hipMemcpyAsync(offsets, off_dev, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipMemcpyAsync(&total, needed_dev, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (needed) *needed = total;
+  RRTX_HIP(ctx, copy_out(ctx, offsets, off_dev, sizeof(int64_t) * ((size_t)nq + 1)));
+  RRTX_HIP(ctx, read_count(ctx, needed_dev, &total));
   ctx->last_neighbors = total;
-  if (total > cap) return fail(ctx, RRTX_E_CAPACITY, "extend_candidates_dubins: %lld neighbours, capacity %lld", (long long)total, (long long)cap);
+  if ((rc = check_capacity(ctx, "extend_candidates_dubins", "neighbours", total, cap, needed))) return rc;
   const size_t n = (size_t)total;
-  if (n > 0) {
-    RRTX_HIP(ctx, hipMemcpyAsync(idx, ctx->ws_out_idx.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipMemcpyAsync(key, key_dev, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipMemcpyAsync(cost_out, co_dev, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipMemcpyAsync(cost_in, ci_dev, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (word_out) RRTX_HIP(ctx, hipMemcpyAsync(word_out, wo_dev, 3 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (word_in) RRTX_HIP(ctx, hipMemcpyAsync(word_in, wi_dev, 3 * n, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipMemcpyAsync(hit_out, ho_dev, n, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipMemcpyAsync(hit_in, hi_dev, n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (sample_unsafe) RRTX_HIP(ctx, hipMemcpyAsync(sample_unsafe, unsafe_dev, (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, copy_out(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * n));
+  RRTX_HIP(ctx, copy_out(ctx, key, key_dev, sizeof(double) * n));
+  RRTX_HIP(ctx, copy_out(ctx, cost_out, co_dev, sizeof(double) * n));
+  RRTX_HIP(ctx, copy_out(ctx, cost_in, ci_dev, sizeof(double) * n));
+  RRTX_HIP(ctx, copy_out(ctx, word_out, wo_dev, 3 * n));
+  RRTX_HIP(ctx, copy_out(ctx, word_in, wi_dev, 3 * n));
+  RRTX_HIP(ctx, copy_out(ctx, hit_out, ho_dev, n));
+  RRTX_HIP(ctx, copy_out(ctx, hit_in, hi_dev, n));
+  RRTX_HIP(ctx, copy_out(ctx, sample_unsafe, unsafe_dev, (size_t)nq));
   if (want_nearest) {
-    RRTX_HIP(ctx, hipMemcpyAsync(nearest_idx, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipMemcpyAsync(nearest_dist, ctx->ws_out_f64.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    RRTX_HIP(ctx, copy_out(ctx, nearest_idx, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)nq));
+    RRTX_HIP(ctx, copy_out(ctx, nearest_dist, ctx->ws_out_f64.p, sizeof(double) * (size_t)nq));
   }
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (want_nearest) {
-    std::vector<int> miss;
-    for (int i = 0; i < nq; ++i) if (nearest_idx[i] < 0) miss.push_back(i);
-    if (!miss.empty()) {
-      std::vector<double> mq(miss.size() * 4);
-      for (size_t k = 0; k < miss.size(); ++k) std::memcpy(&mq[k * 4], q + (size_t)miss[k] * 4, sizeof(double) * 4);
-      std::vector<int32_t> mi(miss.size());
-      std::vector<double> md(miss.size());
-      rc = rrtx_nn_nearest(ctx, mq.data(), (int)miss.size(), mi.data(), md.data());
-      if (rc) return rc;
-      for (size_t k = 0; k < miss.size(); ++k) { nearest_idx[miss[k]] = mi[k]; nearest_dist[miss[k]] = md[k]; }
-    }
-  }
-  return RRTX_OK;
+  return want_nearest ? nearest_fallback(ctx, q, nq, 4, nearest_idx, nearest_dist) : RRTX_OK;
 }
 
 int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit_in, const int64_t *n_valid_dev,
