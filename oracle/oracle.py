@@ -159,6 +159,14 @@ def lib() -> C.CDLL:
     L.orc_extend_batch_polygons.restype = C.c_int64
     L.orc_extend_batch_polygons.argtypes = [C.c_void_p, C.POINTER(Polygon), C.c_int, c_double_p, C.c_int64,
                                             C.c_double, C.c_double, c_int64_p, c_int64_p, c_int64_p]
+    vp = C.c_void_p
+    L.orc_dubins_edges_batch.restype = C.c_int
+    L.orc_dubins_edges_batch.argtypes = [vp, vp, C.c_int64, C.c_double, C.c_double, C.POINTER(Polygon), C.c_int, C.c_int,
+                                         C.c_int, C.c_double, C.c_double] + [vp] * 10
+    L.orc_dubins_candidates_batch.restype = C.c_int
+    L.orc_dubins_candidates_batch.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                              C.POINTER(Polygon), C.c_int, C.c_int, C.c_int, C.c_double,
+                                              C.c_double] + [vp] * 6
     _lib = L
     return L
 
@@ -653,3 +661,110 @@ def extend_batch_spheres(tree: KDTree, spheres, m, queries: np.ndarray, r: float
     e = lib().orc_extend_batch_spheres(tree.handle, spheres, m, _dp(q), nq, r, robot_radius,
                                        nearest.ctypes.data_as(c_int64_p), C.byref(nn), C.byref(nh))
     return e, nn.value, nh.value, nearest
+
+
+# ---- batched Dubins edges (orc_dubins_edges_batch / orc_dubins_candidates_batch) ----------------------------------
+MAX_THREADS = 16
+
+
+def _n_threads(threads) -> int:
+    if threads is None:
+        try:
+            threads = len(os.sched_getaffinity(0))
+        except AttributeError:
+            threads = 1
+    return max(1, min(MAX_THREADS, int(threads)))
+
+
+def _at(a, i: int = 0, row: int = 1):
+    """address of element i * row of a C-contiguous array (None for None)"""
+    if a is None:
+        return None
+    assert a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data + i * row * a.itemsize
+
+
+def _run_ranges(n: int, threads, fn):
+    """fn(i0, i1) over [0, n) split into contiguous ranges, on up to MAX_THREADS threads (ctypes drops the GIL)"""
+    k = min(_n_threads(threads), max(1, n // 1024))
+    bounds = [n * j // k for j in range(k + 1)]
+    if k == 1:
+        rcs = [fn(0, n)]
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(k) as ex:
+            rcs = list(ex.map(lambda j: fn(bounds[j], bounds[j + 1]), range(k)))
+    for rc in rcs:
+        if rc == -1:
+            raise ValueError("the oracle has no Dubins check without time for a list with active moving obstacles")
+        if rc != 0:
+            raise RuntimeError(f"oracle Dubins batch failed ({rc})")
+
+
+def _poly_args(ps):
+    return (ps.arr, ps.m) if ps is not None else ((Polygon * 1)(), 0)
+
+
+def dubins_edges_batch(S, G, r_min: float, ps: "PolygonSet" = None, robot_radius: float = 0.0, has_time: bool = False,
+                       piecewise: bool = False, v_min: float = 0.0, v_max: float = 0.0, traj=None, threads=None) -> dict:
+    """Every directed edge S[i] -> G[i] through the per-edge Dubins functions (dubins_steer / dubins_steer_time,
+    dubins_edge_check_polygons[_time], dubins_valid_move_time), in C.  Returns dict(cost, wdist, velocity, word
+    (S3), traj_len, hit, first_hit, valid_move); without ps the check is skipped (hit 0).  traj: True or a boolean
+    mask -- also traj_off (n + 1, rows) and traj (rows of 2, or 3 with time) for those edges (zero rows for the
+    others)."""
+    S = np.ascontiguousarray(S, dtype=np.float64).reshape(-1, 4)
+    G = np.ascontiguousarray(G, dtype=np.float64).reshape(-1, 4)
+    assert S.shape == G.shape
+    n = S.shape[0]
+    arr, m = _poly_args(ps)
+    L = lib()
+    out = dict(cost=np.empty(n), wdist=np.empty(n), velocity=np.empty(n), word=np.zeros((n, 3), dtype=np.uint8),
+               traj_len=np.empty(n, dtype=np.int32), hit=np.zeros(n, dtype=np.uint8),
+               first_hit=np.full(n, -1, dtype=np.int32), valid_move=np.empty(n, dtype=np.uint8))
+    chk = ps is not None
+
+    def run(i0, i1, off=None, rows=None):
+        return L.orc_dubins_edges_batch(
+            _at(S, i0, 4), _at(G, i0, 4), i1 - i0, r_min, robot_radius, arr, m, int(has_time), int(piecewise), v_min,
+            v_max, _at(out["cost"], i0), _at(out["wdist"], i0), _at(out["velocity"], i0), _at(out["word"], i0, 3),
+            _at(out["traj_len"], i0), _at(out["hit"], i0) if chk else None, _at(out["first_hit"], i0) if chk else None,
+            _at(out["valid_move"], i0), _at(off, i0), _at(rows))
+    _run_ranges(n, threads, run)
+    out["word"] = out["word"].view("S3").ravel()
+    if traj is not None and traj is not False:
+        mask = np.ones(n, dtype=bool) if traj is True else np.asarray(traj, dtype=bool).reshape(n)
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.where(mask, out["traj_len"], 0), out=off[1:])
+        rows = np.zeros((max(int(off[-1]), 1), 3 if has_time else 2))
+        arr0, m0 = _poly_args(None)
+        _run_ranges(n, threads, lambda i0, i1: L.orc_dubins_edges_batch(
+            _at(S, i0, 4), _at(G, i0, 4), i1 - i0, r_min, robot_radius, arr0, m0, int(has_time), int(piecewise), v_min,
+            v_max, None, None, None, None, None, None, None, None, _at(off, i0), _at(rows)))
+        out["traj_off"], out["traj"] = off, rows[: int(off[-1])]
+    return out
+
+
+def dubins_candidates_batch(Q, offsets, idx, nodes, r_min: float, ps: "PolygonSet", robot_radius: float,
+                            has_time: bool = False, piecewise: bool = False, v_min: float = 0.0, v_max: float = 0.0,
+                            threads=None) -> dict:
+    """The candidate Dubins edges of extend() for CSR entries (sample of the offsets range, node idx[e]), both
+    directions, in C: dict(cost_out, cost_in, hit_out, hit_in, traj_len_out, traj_len_in); the hit bytes are
+    rrtx_extend_candidates_dubins's flags (bit 0 collision, bit 1 invalid move with time)."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, 4)
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 4)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    nq = Q.shape[0]
+    assert offsets.shape == (nq + 1,) and int(offsets[-1]) == idx.shape[0]
+    assert idx.size == 0 or (0 <= idx.min() and idx.max() < nodes.shape[0])
+    n = idx.shape[0]
+    arr, m = ps.arr, ps.m
+    L = lib()
+    out = dict(cost_out=np.empty(n), cost_in=np.empty(n), hit_out=np.empty(n, dtype=np.uint8),
+               hit_in=np.empty(n, dtype=np.uint8), traj_len_out=np.empty(n, dtype=np.int32),
+               traj_len_in=np.empty(n, dtype=np.int32))
+    _run_ranges(n, threads, lambda e0, e1: L.orc_dubins_candidates_batch(
+        _at(Q), nq, _at(offsets), _at(idx), _at(nodes), e0, e1, r_min, robot_radius, arr, m, int(has_time),
+        int(piecewise), v_min, v_max, _at(out["cost_out"]), _at(out["cost_in"]), _at(out["hit_out"]),
+        _at(out["hit_in"]), _at(out["traj_len_out"]), _at(out["traj_len_in"])))
+    return out

@@ -1397,6 +1397,124 @@ int orc_dubins_edge_check_polygons_time(const orc_polygon *obs, int m, const dou
   return 0;
 }
 
+/* ---- batched Dubins edges: loops over the per-edge functions above, no geometry of their own ---- */
+typedef struct { double *rows; int cap; } dub_scratch;   /* cap rows of 3 doubles (wide enough for either width) */
+
+/* one directed edge: steer into the scratch (grown until it holds every row), validMove, the two-stage check.
+ * Returns 0, -1 where the check has no branch for the list (moving obstacles without time), -3 out of memory. */
+static int dubins_one(const double *s, const double *g, double r_min, double robot_radius, const orc_polygon *obs, int m,
+                      int has_time, int piecewise, double v_min, double v_max, dub_scratch *sc, double *cost,
+                      double *wdist, double *vel, char word[4], int *tl, int *hit, int32_t *fh, int *valid) {
+  for (;;) {
+    memset(word, 0, 4);
+    if (has_time) {
+      if (piecewise) orc_dubins_steer_time_pw(s, g, r_min, cost, wdist, vel, word, sc->rows, sc->cap, tl);
+      else orc_dubins_steer_time(s, g, r_min, cost, wdist, vel, word, sc->rows, sc->cap, tl);
+    } else {
+      orc_dubins_steer(s, g, r_min, cost, word, sc->rows, sc->cap, tl);
+      *wdist = *cost;
+      *vel = NAN;
+    }
+    if (*tl <= sc->cap) break;
+    const int cap = *tl > 2 * sc->cap ? *tl : 2 * sc->cap;
+    double *p = (double *)realloc(sc->rows, sizeof(double) * 3 * (size_t)cap);
+    if (!p) return -3;
+    sc->rows = p;
+    sc->cap = cap;
+  }
+  *valid = has_time ? orc_dubins_valid_move_time(s, g, *vel, v_min, v_max) : 1;
+  const int h = has_time ? orc_dubins_edge_check_polygons_time(obs, m, s, g, sc->rows, *tl, robot_radius, r_min, fh)
+                         : orc_dubins_edge_check_polygons(obs, m, s, g, sc->rows, *tl, robot_radius, r_min, fh);
+  if (h < 0) return -1;
+  *hit = h;
+  return 0;
+}
+
+/* starts below the longest polylines (three arcs of up to 64 rows) so that the growth path runs on every batch */
+static int dub_scratch_init(dub_scratch *sc) {
+  sc->cap = 64;
+  sc->rows = (double *)malloc(sizeof(double) * 3 * (size_t)sc->cap);
+  return sc->rows ? 0 : -3;
+}
+
+int orc_dubins_edges_batch(const double *s, const double *g, int64_t n, double r_min, double robot_radius,
+                           const orc_polygon *obs, int m, int has_time, int piecewise, double v_min, double v_max,
+                           double *cost, double *wdist, double *velocity, char *word, int32_t *traj_len, uint8_t *hit,
+                           int32_t *first_hit, uint8_t *valid_move, const int64_t *traj_off, double *traj_rows) {
+  dub_scratch sc;
+  if (dub_scratch_init(&sc)) return -3;
+  const int cols = has_time ? 3 : 2;
+  int rc = 0;
+  for (int64_t i = 0; i < n && rc == 0; ++i) {
+    double c, w, v;
+    char wd[4];
+    int tl, h, ok;
+    int32_t fh = -1;
+    rc = dubins_one(s + 4 * i, g + 4 * i, r_min, robot_radius, obs, m, has_time, piecewise, v_min, v_max, &sc, &c, &w,
+                    &v, wd, &tl, &h, &fh, &ok);
+    if (rc) break;
+    if (cost) cost[i] = c;
+    if (wdist) wdist[i] = w;
+    if (velocity) velocity[i] = v;
+    if (word) memcpy(word + 3 * i, wd, 3);
+    if (traj_len) traj_len[i] = tl;
+    if (hit) hit[i] = (uint8_t)h;
+    if (first_hit) first_hit[i] = fh;
+    if (valid_move) valid_move[i] = (uint8_t)ok;
+    if (traj_off && traj_off[i + 1] != traj_off[i]) {
+      if (traj_off[i + 1] - traj_off[i] != tl) { rc = -2; break; }
+      for (int k = 0; k < tl; ++k)
+        memcpy(traj_rows + (size_t)cols * (size_t)(traj_off[i] + k), sc.rows + (size_t)cols * (size_t)k,
+               sizeof(double) * (size_t)cols);
+    }
+  }
+  free(sc.rows);
+  return rc;
+}
+
+int orc_dubins_candidates_batch(const double *q, int64_t nq, const int64_t *offsets, const int32_t *idx,
+                                const double *nodes, int64_t e_begin, int64_t e_end, double r_min, double robot_radius,
+                                const orc_polygon *obs, int m, int has_time, int piecewise, double v_min, double v_max,
+                                double *cost_out, double *cost_in, uint8_t *flag_out, uint8_t *flag_in,
+                                int32_t *tl_out, int32_t *tl_in) {
+  if (e_begin == e_end) return 0;
+  if (nq <= 0 || e_begin < 0 || e_begin > e_end || e_end > offsets[nq]) return -2;
+  dub_scratch sc;
+  if (dub_scratch_init(&sc)) return -3;
+  int64_t lo = 0, hi = nq;                             /* owner of e_begin: the first sample whose entries end past it */
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (offsets[mid + 1] <= e_begin) lo = mid + 1; else hi = mid;
+  }
+  int64_t qi = lo;
+  int rc = 0;
+  for (int64_t e = e_begin; e < e_end && rc == 0; ++e) {
+    while (offsets[qi + 1] <= e) ++qi;
+    const double *a = q + 4 * qi, *b = nodes + 4 * (int64_t)idx[e];
+    for (int dir = 0; dir < 2 && rc == 0; ++dir) {
+      double c, w, v;
+      char wd[4];
+      int tl, h, ok;
+      int32_t fh;
+      rc = dubins_one(dir ? b : a, dir ? a : b, r_min, robot_radius, obs, m, has_time, piecewise, v_min, v_max, &sc, &c,
+                      &w, &v, wd, &tl, &h, &fh, &ok);
+      if (rc) break;
+      const uint8_t flag = (uint8_t)(h | (has_time && !ok ? 2 : 0));
+      if (dir == 0) {
+        if (cost_out) cost_out[e] = c;
+        if (flag_out) flag_out[e] = flag;
+        if (tl_out) tl_out[e] = tl;
+      } else {
+        if (cost_in) cost_in[e] = c;
+        if (flag_in) flag_in[e] = flag;
+        if (tl_in) tl_in[e] = tl;
+      }
+    }
+  }
+  free(sc.rows);
+  return rc;
+}
+
 /* ------------------------------------------------------------------------ */
 /* CPU baseline: the per-sample inner loop of extend/findBestParent          */
 /* R/rrtqx.jl:926 (kdFindNearest), R/DRRT_Q.jl:2551 (kdFindWithinRange),     */

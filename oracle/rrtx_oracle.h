@@ -150,6 +150,29 @@ int orc_dubins_valid_move_time(const double *s, const double *g, double velocity
 int orc_dubins_edge_check_polygons_time(const orc_polygon *obs, int m, const double *s, const double *g,
                                         const double *traj3, int traj_len, double robot_radius, double r_min,
                                         int32_t *first_hit);
+/* Batched forms of the Dubins functions above: plain loops over them, no geometry or arithmetic of their own.
+ * n directed edges s[i] -> g[i] (rows of [x y t theta]).  has_time: orc_dubins_steer_time (piecewise = 0, the
+ * reference's running-sum time column) or orc_dubins_steer_time_pw (piecewise = 1), validMove with v_min / v_max
+ * and the check with time; otherwise orc_dubins_steer (wdist = cost, velocity = NaN, every move valid).  Every
+ * output is optional (NULL): cost (edge.dist with time), wdist, velocity, word (3 bytes per edge, no NUL),
+ * traj_len, hit, first_hit, valid_move.  The trajectory scratch grows until it holds every row.  traj_off (n + 1
+ * offsets in rows, or NULL) / traj_rows: edge i with traj_off[i + 1] > traj_off[i] gets its rows, (x, y) or
+ * (x, y, t), at row traj_off[i]; the slot must be exactly traj_len rows.  Returns 0; -1 where the check has no
+ * branch for the list (moving obstacles without time), -2 a trajectory slot of the wrong size, -3 out of memory. */
+int orc_dubins_edges_batch(const double *s, const double *g, int64_t n, double r_min, double robot_radius,
+                           const orc_polygon *obs, int m, int has_time, int piecewise, double v_min, double v_max,
+                           double *cost, double *wdist, double *velocity, char *word, int32_t *traj_len, uint8_t *hit,
+                           int32_t *first_hit, uint8_t *valid_move, const int64_t *traj_off, double *traj_rows);
+/* The candidate edges of extend() with DubinsEdge: CSR entry e in [e_begin, e_end) pairs the sample q[owner] (the
+ * sample whose offsets range holds e) with node idx[e] (rows of 4 in nodes); both directed edges, sample -> node
+ * (_out) and node -> sample (_in), as orc_dubins_edges_batch computes them.  flag = hit | 2 * (has_time and not
+ * validMove), the byte rrtx_extend_candidates_dubins writes.  Outputs are indexed by e and optional.  Returns as
+ * orc_dubins_edges_batch; -2 for a range outside [0, offsets[nq]]. */
+int orc_dubins_candidates_batch(const double *q, int64_t nq, const int64_t *offsets, const int32_t *idx,
+                                const double *nodes, int64_t e_begin, int64_t e_end, double r_min, double robot_radius,
+                                const orc_polygon *obs, int m, int has_time, int piecewise, double v_min, double v_max,
+                                double *cost_out, double *cost_in, uint8_t *flag_out, uint8_t *flag_in,
+                                int32_t *tl_out, int32_t *tl_in);
 /* the shared deterministic transcendentals of include/rrtx_detmath.h, element-wise (tests compare them with
  * libm here and with the device's build of the same header bit for bit).
  * op: 0 sin(x)  1 cos(x)  2 atan2(y, x)  3 acos(x);  returns 1 in the ORC_LIBM_TRIG build, else 0 */

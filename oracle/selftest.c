@@ -87,6 +87,40 @@ int main(void) {
     bad += !(cost > 0) || tl > 1024;
     (void)orc_dubins_edge_check_polygons(&pg, 1, s, g, traj, tl, 0.5, 1.0, &fh);
   }
+  {
+    /* the batched forms: growing trajectory scratch, trajectory CSR, the candidate loop */
+    enum { NB = 300 };
+    static double bs[4 * NB], bg[4 * NB], bc[NB], bw[NB], bv[NB], brows[3 * 200 * NB], nodes[4 * 50], qs[4 * 6];
+    static char bwd[3 * NB];
+    static int32_t btl[NB], bfh[NB];
+    static uint8_t bh[NB], bok[NB];
+    static int64_t boff[NB + 1], coff[7];
+    for (int i = 0; i < NB; ++i) {
+      double *s = bs + 4 * i, *g = bg + 4 * i;
+      s[0] = 20 * frand(&seed); s[1] = 20 * frand(&seed); s[2] = 30; s[3] = 6.28 * frand(&seed);
+      g[0] = s[0] + 3 * (frand(&seed) - .5); g[1] = s[1] + 3 * (frand(&seed) - .5); g[2] = 28; g[3] = 6.28 * frand(&seed);
+    }
+    for (int t3 = 0; t3 < 2; ++t3) {
+      bad += orc_dubins_edges_batch(bs, bg, NB, 1.0, 0.5, &pg, 1, t3, t3, 5.0, 30.0, bc, bw, bv, bwd, btl, bh, bfh, bok,
+                                    NULL, NULL) != 0;
+      boff[0] = 0;
+      for (int i = 0; i < NB; ++i) boff[i + 1] = boff[i] + ((i % 3) ? btl[i] : 0);
+      bad += orc_dubins_edges_batch(bs, bg, NB, 1.0, 0.5, &pg, 1, t3, 0, 5.0, 30.0, NULL, NULL, NULL, NULL, NULL, NULL,
+                                    NULL, NULL, boff, brows) != 0;
+    }
+    bad += orc_dubins_edges_batch(bs, bg, NB, 1.0, 0.5, &mv, 1, 0, 0, 0, 0, bc, NULL, NULL, NULL, NULL, NULL, NULL, NULL,
+                                  NULL, NULL) != -1;
+    for (int i = 0; i < 50; ++i) { nodes[4 * i] = 20 * frand(&seed); nodes[4 * i + 1] = 20 * frand(&seed); nodes[4 * i + 2] = 25; nodes[4 * i + 3] = 6.28 * frand(&seed); }
+    for (int i = 0; i < 6; ++i) { qs[4 * i] = 20 * frand(&seed); qs[4 * i + 1] = 20 * frand(&seed); qs[4 * i + 2] = 30; qs[4 * i + 3] = 6.28 * frand(&seed); }
+    coff[0] = 0;
+    for (int i = 0; i < 6; ++i) coff[i + 1] = coff[i] + (i == 2 ? 0 : 40);
+    int32_t cidx[200];
+    for (int e = 0; e < 200; ++e) cidx[e] = (int32_t)(50 * frand(&seed));
+    bad += orc_dubins_candidates_batch(qs, 6, coff, cidx, nodes, 37, 200, 1.0, 0.5, &mv, 1, 1, 1, 5.0, 30.0, bc, bw, bh,
+                                       bok, btl, bfh) != 0;
+    bad += orc_dubins_candidates_batch(qs, 6, coff, cidx, nodes, 0, 201, 1.0, 0.5, &mv, 1, 1, 1, 5.0, 30.0, bc, bw, bh,
+                                       bok, btl, bfh) != -2;
+  }
   printf(bad ? "selftest FAILED (%d)\n" : "selftest ok\n", bad);
   return bad != 0;
 }

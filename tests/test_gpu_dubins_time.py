@@ -92,16 +92,17 @@ def test_dubins_edges_check_with_time_static_and_moving(oracle):
             ctx.dubins_edges_check(s[:8], g[:8], RMIN, RR)
         ctx.set_space_has_time(True)
         cost, word, hit, tl = ctx.dubins_edges_check(s, g, RMIN, RR)
-        ref_flips = 0
+        ref_flips = ref_compared = 0
         for k in range(len(s)):
             d, w, v, wd, tr = oracle.dubins_steer_time(s[k], g[k], RMIN, piecewise=True)
             assert cost[k] == d and word[k].decode() == wd and tl[k] == len(tr), k
             h, _ = oracle.dubins_edge_check_polygons_time(ps, s[k], g[k], tr, RR, RMIN)
             assert bool(hit[k]) == h, k
-            if k % 5 == 0:      # the reference's running-sum time column gives the same booleans on these scenes
-                tr_ref = oracle.dubins_steer_time(s[k], g[k], RMIN)[4]
-                ref_flips += oracle.dubins_edge_check_polygons_time(ps, s[k], g[k], tr_ref, RR, RMIN)[0] != h
-        assert ref_flips == 0
+            # the reference's running-sum time column gives the same booleans on every edge of these scenes
+            tr_ref = oracle.dubins_steer_time(s[k], g[k], RMIN)[4]
+            ref_flips += oracle.dubins_edge_check_polygons_time(ps, s[k], g[k], tr_ref, RR, RMIN)[0] != h
+            ref_compared += 1
+        assert ref_flips == 0 and ref_compared == len(s) == 2500
         assert 0.05 < hit.mean() < 0.9
         # the moving ones matter: with them switched off fewer edges collide
         act2 = active.copy(); act2[:m] = 0
