@@ -160,6 +160,17 @@ def lib() -> C.CDLL:
     L.orc_extend_batch_polygons.argtypes = [C.c_void_p, C.POINTER(Polygon), C.c_int, c_double_p, C.c_int64,
                                             C.c_double, C.c_double, c_int64_p, c_int64_p, c_int64_p]
     vp = C.c_void_p
+    L.orc_range_batch.restype = C.c_int64
+    L.orc_range_batch.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int64] + [vp] * 5
+    L.orc_knearest_batch.restype = C.c_int
+    L.orc_knearest_batch.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.orc_simple_candidates_batch.restype = C.c_int
+    L.orc_simple_candidates_batch.argtypes = [vp, C.c_int64, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int,
+                                              C.c_double] + [vp] * 6
+    L.orc_edges_check_batch.restype = None
+    L.orc_edges_check_batch.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp]
+    L.orc_points_check_batch.restype = None
+    L.orc_points_check_batch.argtypes = [vp, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp]
     L.orc_dubins_edges_batch.restype = C.c_int
     L.orc_dubins_edges_batch.argtypes = [vp, vp, C.c_int64, C.c_double, C.c_double, C.POINTER(Polygon), C.c_int, C.c_int,
                                          C.c_int, C.c_double, C.c_double] + [vp] * 10
@@ -684,16 +695,18 @@ def _at(a, i: int = 0, row: int = 1):
     return a.ctypes.data + i * row * a.itemsize
 
 
-def _run_ranges(n: int, threads, fn):
-    """fn(i0, i1) over [0, n) split into contiguous ranges, on up to MAX_THREADS threads (ctypes drops the GIL)"""
-    k = min(_n_threads(threads), max(1, n // 1024))
+def _run_ranges(n: int, threads, fn, per_thread: int = 1024, worker: bool = False):
+    """fn(i0, i1) over [0, n) split into contiguous ranges of at least per_thread items, on up to MAX_THREADS threads
+    (ctypes drops the GIL); worker=True calls fn(j, i0, i1) with the range's number j < _n_threads(threads)"""
+    k = min(_n_threads(threads), max(1, n // per_thread))
     bounds = [n * j // k for j in range(k + 1)]
+    call = (lambda j: fn(j, bounds[j], bounds[j + 1])) if worker else (lambda j: fn(bounds[j], bounds[j + 1]))
     if k == 1:
-        rcs = [fn(0, n)]
+        rcs = [call(0)]
     else:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(k) as ex:
-            rcs = list(ex.map(lambda j: fn(bounds[j], bounds[j + 1]), range(k)))
+            rcs = list(ex.map(call, range(k)))
     for rc in rcs:
         if rc == -1:
             raise ValueError("the oracle has no Dubins check without time for a list with active moving obstacles")
@@ -768,3 +781,265 @@ def dubins_candidates_batch(Q, offsets, idx, nodes, r_min: float, ps: "PolygonSe
         int(piecewise), v_min, v_max, _at(out["cost_out"]), _at(out["cost_in"]), _at(out["hit_out"]),
         _at(out["hit_in"]), _at(out["traj_len_out"]), _at(out["traj_len_in"])))
     return out
+
+
+# ---- batched search and SimpleEdge checks (orc_range_batch, orc_knearest_batch, orc_simple_candidates_batch,
+#      orc_edges_check_batch, orc_points_check_batch) ------------------------------------------------------------------
+RANGE_SLICE = 64           # samples per orc_range_batch call: a capacity retry repeats one slice, not a thread's range
+
+
+class TreeSet:
+    """One KDTree per worker thread over the same points, built in insertion order: the range and k-nearest
+    searches mark the nodes they visit in the tree, so two threads never search one tree."""
+
+    def __init__(self, d: int, pts=None, threads=None, wraps=None, wrap_points=None):
+        self.d = d
+        self.trees = [KDTree(d, wraps, wrap_points) for _ in range(_n_threads(threads))]
+        if pts is not None:
+            self.insert_many(pts)
+
+    def insert_many(self, pts):
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, self.d)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(len(self.trees)) as ex:
+            list(ex.map(lambda t: t.insert_many(pts), self.trees))
+
+    @property
+    def size(self) -> int:
+        return self.trees[0].size
+
+
+def _tree_list(trees):
+    return trees.trees if isinstance(trees, TreeSet) else [trees]
+
+
+def range_batch(trees, Q, r, per_sample: float = 64.0, nearest: bool = True, slice_size: int = RANGE_SLICE) -> dict:
+    """kdFindWithinRange (r: scalar or one radius per sample) and kdFindNearest for every sample, in C, on the trees
+    of a TreeSet (one per thread) or on one KDTree: dict(offsets, idx, key, nearest_idx, nearest_dist, retries) --
+    CSR with each list in ascending node index, as the device returns it.  per_sample seeds each slice's capacity
+    (a device count may seed it; the result never depends on it): a slice that needs more is searched again with
+    the size it needs, counted in retries."""
+    ts = _tree_list(trees)
+    d = ts[0].d
+    Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, d)
+    nq = Q.shape[0]
+    rr = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+    stride = 0 if rr.size == 1 else 1
+    if stride and rr.size != nq:
+        raise ValueError("r must be a scalar or have one entry per sample")
+    nidx = np.empty(nq, dtype=np.int64)
+    ndist = np.empty(nq, dtype=np.float64)
+    n_slices = (nq + slice_size - 1) // slice_size
+    parts = [None] * n_slices
+    retries = [0] * len(ts)
+    L = lib()
+
+    def run(j, s0, s1):
+        t = ts[j].handle
+        for s in range(s0, s1):
+            a = s * slice_size
+            n = min(nq, a + slice_size) - a
+            cap = int(per_sample * n) + 64
+            while True:
+                off = np.empty(n + 1, dtype=np.int64)
+                idx = np.empty(cap, dtype=np.int32)
+                key = np.empty(cap, dtype=np.float64)
+                need = L.orc_range_batch(t, _at(Q, a, d), n, _at(rr, a * stride), stride, cap, _at(off), _at(idx),
+                                         _at(key), _at(nidx, a) if nearest else None, _at(ndist, a) if nearest else None)
+                if need < 0:
+                    raise MemoryError("orc_range_batch")
+                if need <= cap:
+                    break
+                cap = int(need)
+                retries[j] += 1
+            parts[s] = (np.diff(off), idx[:need], key[:need])
+        return 0
+    _run_ranges(n_slices, len(ts), run, per_thread=1, worker=True)
+    offsets = np.zeros(nq + 1, dtype=np.int64)
+    if n_slices:
+        np.cumsum(np.concatenate([p[0] for p in parts]), out=offsets[1:])
+    out = dict(offsets=offsets,
+               idx=np.concatenate([p[1] for p in parts]) if n_slices else np.empty(0, dtype=np.int32),
+               key=np.concatenate([p[2] for p in parts]) if n_slices else np.empty(0), retries=sum(retries))
+    if nearest:
+        out["nearest_idx"], out["nearest_dist"] = nidx, ndist
+    return out
+
+
+def knearest_batch(trees, k: int, Q) -> tuple:
+    """kdFindKNearest for every sample, in C: (idx, key, count), rows max(k, 2) wide in heap order, count[i] of row i
+    filled; raises where the reference does (wrapped space)."""
+    ts = _tree_list(trees)
+    d = ts[0].d
+    Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, d)
+    nq = Q.shape[0]
+    w = max(int(k), 2)
+    idx = np.full((nq, w), -1, dtype=np.int32)
+    key = np.full((nq, w), np.nan)
+    count = np.empty(nq, dtype=np.int32)
+    L = lib()
+
+    def run(j, i0, i1):
+        rc = L.orc_knearest_batch(ts[j].handle, int(k), _at(Q, i0, d), i1 - i0, w, _at(idx, i0, w), _at(key, i0, w),
+                                  _at(count, i0))
+        if rc == -1:
+            raise RuntimeError("knn search has not been implimented for wrapped space")
+        return rc
+    _run_ranges(nq, len(ts), run, per_thread=64, worker=True)
+    return idx, key, count
+
+
+def _obs_args(obs):
+    """(spheres, polygons, m) for the batch functions: obs is a PolygonSet or make_spheres()'s (array, m)"""
+    if isinstance(obs, PolygonSet):
+        return None, C.addressof(obs.arr), obs.m
+    arr, m = obs
+    return C.addressof(arr), None, m
+
+
+def candidates_batch(Q, offsets, idx, nodes, obs, robot_radius: float, threads=None) -> dict:
+    """The SimpleEdge candidate edges of extend() for CSR entries (sample of the offsets range, node idx[e]), both
+    directions, in C: dict(cost_out, cost_in, hit_out, hit_in, first_hit_out, first_hit_in)."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+    d = nodes.shape[1]
+    Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, d)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    nq = Q.shape[0]
+    assert offsets.shape == (nq + 1,) and int(offsets[-1]) == idx.shape[0]
+    assert idx.size == 0 or (0 <= idx.min() and idx.max() < nodes.shape[0])
+    n = idx.shape[0]
+    sph, poly, m = _obs_args(obs)
+    out = dict(cost_out=np.empty(n), cost_in=np.empty(n), hit_out=np.empty(n, dtype=np.uint8),
+               hit_in=np.empty(n, dtype=np.uint8), first_hit_out=np.empty(n, dtype=np.int32),
+               first_hit_in=np.empty(n, dtype=np.int32))
+    L = lib()
+
+    def run(e0, e1):
+        return L.orc_simple_candidates_batch(_at(Q), nq, d, _at(offsets), _at(idx), _at(nodes), e0, e1, sph, poly, m,
+                                             robot_radius, *(_at(out[k]) for k in ("cost_out", "cost_in", "hit_out",
+                                                                                    "hit_in", "first_hit_out",
+                                                                                    "first_hit_in")))
+    if n:
+        _run_ranges(n, threads, run)
+    return out
+
+
+def edges_check_batch(obs, P0, P1, robot_radius: float, threads=None):
+    """explicitEdgeCheck over the list for every directed edge P0[i] -> P1[i], in C: (hit, first_hit)"""
+    P0 = np.ascontiguousarray(P0, dtype=np.float64)
+    P1 = np.ascontiguousarray(P1, dtype=np.float64)
+    assert P0.shape == P1.shape and P0.ndim == 2
+    n, d = P0.shape
+    sph, poly, m = _obs_args(obs)
+    hit = np.empty(n, dtype=np.uint8)
+    first = np.empty(n, dtype=np.int32)
+    L = lib()
+    _run_ranges(n, threads, lambda i0, i1: L.orc_edges_check_batch(_at(P0, i0, d), _at(P1, i0, d), i1 - i0, d, sph,
+                                                                   poly, m, robot_radius, _at(hit, i0),
+                                                                   _at(first, i0)) or 0)
+    return hit, first
+
+
+def points_check_batch(obs, P, robot_radius: float, quick: bool = True, threads=None):
+    """explicitPointCheck over the list for every point, in C (quick pass first for spheres): (unsafe, clearance)"""
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    n, d = P.shape
+    sph, poly, m = _obs_args(obs)
+    unsafe = np.empty(n, dtype=np.uint8)
+    clr = np.empty(n, dtype=np.float64)
+    L = lib()
+    _run_ranges(n, threads, lambda i0, i1: L.orc_points_check_batch(_at(P, i0, d), i1 - i0, d, sph, poly, m,
+                                                                    robot_radius, int(quick), _at(unsafe, i0),
+                                                                    _at(clr, i0)) or 0)
+    return unsafe, clr
+
+
+def extend_candidates_batch(trees, Q, r: float, nodes, obs, robot_radius: float, rng: dict = None,
+                            per_sample: float = 64.0, threads=None) -> dict:
+    """What rrtx_extend_candidates returns, from the oracle: range_batch (or a given result of it for the same
+    samples, radius and tree), the candidate edges of every entry and the sample check.  Keys of the device call
+    (offsets, idx, cost, hit_out, hit_in, nearest_idx, nearest_dist, sample_unsafe) plus key, cost_in,
+    first_hit_out, first_hit_in."""
+    if rng is None:
+        rng = range_batch(trees, Q, r, per_sample=per_sample)
+    c = candidates_batch(Q, rng["offsets"], rng["idx"], nodes, obs, robot_radius, threads=threads)
+    unsafe, _ = points_check_batch(obs, np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, nodes.shape[1]),
+                                   robot_radius, quick=True, threads=threads)
+    return dict(offsets=rng["offsets"], idx=rng["idx"], cost=c["cost_out"], hit_out=c["hit_out"], hit_in=c["hit_in"],
+                nearest_idx=rng["nearest_idx"], nearest_dist=rng["nearest_dist"], sample_unsafe=unsafe,
+                key=rng["key"], cost_in=c["cost_in"], first_hit_out=c["first_hit_out"],
+                first_hit_in=c["first_hit_in"])
+
+
+# ---- comparing device results with these, naming the first difference -----------------------------------------------
+ENTRY_FIELDS = ("idx", "key", "cost", "cost_in", "hit_out", "hit_in", "first_hit_out", "first_hit_in")
+SAMPLE_FIELDS = ("nearest_idx", "nearest_dist", "sample_unsafe")
+
+
+def take_samples(res: dict, sel) -> dict:
+    """The rows sel of a CSR result (offsets + ENTRY_FIELDS + SAMPLE_FIELDS that it has), as a CSR of its own"""
+    off = np.asarray(res["offsets"], dtype=np.int64)
+    sel = np.asarray(sel, dtype=np.int64)
+    counts = off[sel + 1] - off[sel]
+    new_off = np.zeros(len(sel) + 1, dtype=np.int64)
+    np.cumsum(counts, out=new_off[1:])
+    ent = np.repeat(off[sel], counts) + (np.arange(int(new_off[-1])) - np.repeat(new_off[:-1], counts))
+    out = {"offsets": new_off}
+    for k, v in res.items():
+        if k in ENTRY_FIELDS:
+            out[k] = np.asarray(v)[ent]
+        elif k in SAMPLE_FIELDS:
+            out[k] = np.asarray(v)[sel]
+    return out
+
+
+def _bits_equal(a, b) -> np.ndarray:
+    """element-wise: equal values with equal signs (0.0 vs -0.0 differ), or both NaN"""
+    if a.dtype.kind == "f" or b.dtype.kind == "f":
+        a, b = a.astype(np.float64), b.astype(np.float64)
+        return ((a == b) & (np.signbit(a) == np.signbit(b))) | (np.isnan(a) & np.isnan(b))
+    return a == b
+
+
+def assert_same_results(dev: dict, ref: dict, fields, names=None, label: str = ""):
+    """dev == ref bit for bit in every field named (offsets, ENTRY_FIELDS, SAMPLE_FIELDS) of the CSR; on a
+    difference, raise naming the first differing sample (names[i] for row i, default i), the field and both values."""
+    off = np.asarray(ref["offsets"], dtype=np.int64)
+    n = len(off) - 1
+    names = np.arange(n) if names is None else np.asarray(names)
+    if "offsets" in fields:
+        od = np.asarray(dev["offsets"], dtype=np.int64)
+        if od.shape != off.shape:
+            raise AssertionError(f"{label}offsets: {len(od) - 1} samples on the device, {n} in the oracle")
+        cd, cr = np.diff(od), np.diff(off)
+        bad = np.flatnonzero(cd != cr)
+        if bad.size:
+            i = int(bad[0])
+            a = np.asarray(dev["idx"])[od[i]:od[i + 1]] if "idx" in dev else np.zeros(0)
+            b = np.asarray(ref["idx"])[off[i]:off[i + 1]] if "idx" in ref else np.zeros(0)
+            k = min(len(a), len(b))
+            j = int(np.flatnonzero(a[:k] != b[:k])[0]) if (a[:k] != b[:k]).any() else k
+            da = int(a[j]) if j < len(a) else None
+            db = int(b[j]) if j < len(b) else None
+            raise AssertionError(f"{label}sample {names[i]}: field idx: {cd[i]} neighbours on the device, {cr[i]} in the "
+                                 f"oracle; first difference at entry {j}: device node {da}, oracle node {db}")
+        if not np.array_equal(od, off):
+            raise AssertionError(f"{label}offsets: device offsets do not start at 0")
+    for k in fields:
+        if k == "offsets":
+            continue
+        a, b = np.asarray(dev[k]), np.asarray(ref[k])
+        if a.shape != b.shape:
+            raise AssertionError(f"{label}field {k}: shape {a.shape} on the device, {b.shape} in the oracle")
+        ok = _bits_equal(a, b)
+        if ok.all():
+            continue
+        e = np.unravel_index(int(np.flatnonzero(~ok.ravel())[0]), a.shape)
+        if k in SAMPLE_FIELDS or k not in ENTRY_FIELDS:
+            where = f"sample {names[e[0]]}" + (f" column {e[1]}" if len(e) > 1 else "")
+        else:
+            s = int(np.searchsorted(off, e[0], side="right") - 1)
+            where = f"sample {names[s]} entry {e[0] - off[s]} (node {np.asarray(ref['idx'])[e[0]] if 'idx' in ref else '?'})"
+        raise AssertionError(f"{label}{where}: field {k}: device {a[e]!r}, oracle {b[e]!r} "
+                             f"({int((~ok).sum())} of {ok.size} differ)")

@@ -1515,6 +1515,121 @@ int orc_dubins_candidates_batch(const double *q, int64_t nq, const int64_t *offs
   return rc;
 }
 
+/* ---- batched range search, nearest, k nearest and SimpleEdge checks: loops over the per-query functions above,
+ * no geometry of their own.  The searches mark nodes in the tree (in_heap): one tree per calling thread. ---- */
+typedef struct { int32_t idx; double key; } range_entry;
+
+static int range_entry_cmp(const void *a, const void *b) {
+  const int32_t x = ((const range_entry *)a)->idx, y = ((const range_entry *)b)->idx;
+  return (x > y) - (x < y);
+}
+
+int64_t orc_range_batch(orc_kd *t, const double *q, int64_t nq, const double *r, int64_t r_stride, int64_t cap,
+                        int64_t *offsets, int32_t *idx, double *key, int64_t *nearest_idx, double *nearest_dist) {
+  range_entry *sc = NULL;
+  int64_t sc_cap = 0, total = 0;
+  if (offsets) offsets[0] = 0;
+  for (int64_t i = 0; i < nq; ++i) {
+    const double *qi = q + i * t->d;
+    if (nearest_idx || nearest_dist) {
+      int64_t ni;
+      double nd;
+      orc_kd_nearest(t, qi, &ni, &nd);
+      if (nearest_idx) nearest_idx[i] = ni;
+      if (nearest_dist) nearest_dist[i] = nd;
+    }
+    if (!offsets) continue;
+    orc_list *l = orc_kd_find_within_range(t, r[i * r_stride], qi);
+    const int64_t n = orc_list_length(l);
+    if (total + n <= cap && n > 0) {
+      if (n > sc_cap) {
+        range_entry *p = (range_entry *)realloc(sc, sizeof(range_entry) * (size_t)n);
+        if (!p) { orc_kd_empty_range_list(t, l); free(sc); return -3; }
+        sc = p;
+        sc_cap = n;
+      }
+      int32_t *li = idx + total;
+      double *lk = key + total;
+      orc_list_read(l, n, li, lk);
+      for (int64_t k = 0; k < n; ++k) { sc[k].idx = li[k]; sc[k].key = lk[k]; }
+      qsort(sc, (size_t)n, sizeof(range_entry), range_entry_cmp);
+      for (int64_t k = 0; k < n; ++k) { li[k] = sc[k].idx; lk[k] = sc[k].key; }
+    }
+    orc_kd_empty_range_list(t, l);
+    total += n;
+    offsets[i + 1] = total;
+  }
+  free(sc);
+  return total;
+}
+
+int orc_knearest_batch(orc_kd *t, int64_t k, const double *q, int64_t nq, int64_t stride, int32_t *idx, double *key,
+                       int32_t *count) {
+  if (stride < (k > 2 ? k : 2)) return -2;
+  for (int64_t i = 0; i < nq; ++i) {
+    const int64_t n = orc_kd_knearest(t, k, q + i * t->d, stride, idx + i * stride, key + i * stride);
+    if (n < 0) return -1;
+    count[i] = (int32_t)n;
+  }
+  return 0;
+}
+
+/* one directed edge against the list: spheres where given, else polygons */
+static uint8_t simple_edge_check(const orc_sphere *sph, const orc_polygon *poly, int m, const double *a,
+                                 const double *b, double robot_radius, int32_t *fh) {
+  return (uint8_t)(sph ? orc_edge_check_spheres(sph, m, a, b, robot_radius, fh)
+                       : orc_edge_check_polygons(poly, m, a, b, robot_radius, fh));
+}
+
+int orc_simple_candidates_batch(const double *q, int64_t nq, int d, const int64_t *offsets, const int32_t *idx,
+                                const double *nodes, int64_t e_begin, int64_t e_end, const orc_sphere *sph,
+                                const orc_polygon *poly, int m, double robot_radius, double *cost_out,
+                                double *cost_in, uint8_t *hit_out, uint8_t *hit_in, int32_t *fh_out, int32_t *fh_in) {
+  if (e_begin == e_end) return 0;
+  if (nq <= 0 || e_begin < 0 || e_begin > e_end || e_end > offsets[nq]) return -2;
+  int64_t lo = 0, hi = nq;                             /* owner of e_begin: the first sample whose entries end past it */
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (offsets[mid + 1] <= e_begin) lo = mid + 1; else hi = mid;
+  }
+  int64_t qi = lo;
+  for (int64_t e = e_begin; e < e_end; ++e) {
+    while (offsets[qi + 1] <= e) ++qi;
+    const double *a = q + d * qi, *b = nodes + d * (int64_t)idx[e];
+    int32_t fo, fi;
+    const uint8_t ho = simple_edge_check(sph, poly, m, a, b, robot_radius, &fo);
+    const uint8_t hn = simple_edge_check(sph, poly, m, b, a, robot_radius, &fi);
+    if (cost_out) cost_out[e] = orc_euclid(a, b, d);   /* calculateTrajectory newNode -> near */
+    if (cost_in) cost_in[e] = orc_euclid(b, a, d);     /* near -> newNode */
+    if (hit_out) hit_out[e] = ho;
+    if (hit_in) hit_in[e] = hn;
+    if (fh_out) fh_out[e] = fo;
+    if (fh_in) fh_in[e] = fi;
+  }
+  return 0;
+}
+
+void orc_edges_check_batch(const double *p0, const double *p1, int64_t n, int d, const orc_sphere *sph,
+                           const orc_polygon *poly, int m, double robot_radius, uint8_t *hit, int32_t *first_hit) {
+  for (int64_t i = 0; i < n; ++i) {
+    int32_t fh;
+    const uint8_t h = simple_edge_check(sph, poly, m, p0 + d * i, p1 + d * i, robot_radius, &fh);
+    if (hit) hit[i] = h;
+    if (first_hit) first_hit[i] = fh;
+  }
+}
+
+void orc_points_check_batch(const double *p, int64_t n, int d, const orc_sphere *sph, const orc_polygon *poly, int m,
+                            double robot_radius, int quick, uint8_t *unsafe, double *clearance) {
+  for (int64_t i = 0; i < n; ++i) {
+    double cl = 0.0;
+    const int u = sph ? orc_point_check_spheres(sph, m, p + d * i, robot_radius, quick, &cl)
+                      : orc_point_check_polygons(poly, m, p + d * i, robot_radius, &cl);
+    if (unsafe) unsafe[i] = (uint8_t)u;
+    if (clearance) clearance[i] = cl;
+  }
+}
+
 /* ------------------------------------------------------------------------ */
 /* CPU baseline: the per-sample inner loop of extend/findBestParent          */
 /* R/rrtqx.jl:926 (kdFindNearest), R/DRRT_Q.jl:2551 (kdFindWithinRange),     */

@@ -173,6 +173,34 @@ int orc_dubins_candidates_batch(const double *q, int64_t nq, const int64_t *offs
                                 const orc_polygon *obs, int m, int has_time, int piecewise, double v_min, double v_max,
                                 double *cost_out, double *cost_in, uint8_t *flag_out, uint8_t *flag_in,
                                 int32_t *tl_out, int32_t *tl_in);
+/* Batched forms of the search and SimpleEdge functions: plain loops over them, no geometry of their own.  The range
+ * and k-nearest searches mark nodes in t (in_heap): a tree serves one thread at a time.
+ * orc_range_batch: per query q[i] (rows of t->d), orc_kd_nearest (nearest_idx / nearest_dist, optional) and, with
+ * offsets, orc_kd_find_within_range at radius r[i * r_stride] read with orc_list_read into CSR: offsets (nq + 1,
+ * from 0) always, idx / key of every list that ends within cap entries, each list in ascending node index.  Returns
+ * the entries the lists need (more than cap: call again with that many), -3 out of memory. */
+int64_t orc_range_batch(orc_kd *t, const double *q, int64_t nq, const double *r, int64_t r_stride, int64_t cap,
+                        int64_t *offsets, int32_t *idx, double *key, int64_t *nearest_idx, double *nearest_dist);
+/* orc_kd_knearest per query into rows of stride (>= max(k, 2)) in heap order, count[i] of row i filled.  Returns 0,
+ * -1 where orc_kd_knearest does (wrapped space), -2 for a stride below max(k, 2). */
+int orc_knearest_batch(orc_kd *t, int64_t k, const double *q, int64_t nq, int64_t stride, int32_t *idx, double *key,
+                       int32_t *count);
+/* The candidate edges of extend() with SimpleEdge: CSR entry e in [e_begin, e_end) pairs the sample q[owner] with
+ * node idx[e] (rows of d in q and nodes): cost orc_euclid (calculateTrajectory) and the list check with its first
+ * hit in both directions, sample -> node (_out) and node -> sample (_in).  The list is sph (orc_edge_check_spheres)
+ * where non-NULL, else poly (orc_edge_check_polygons).  Outputs are indexed by e and optional.  Returns 0, -2 for a
+ * range outside [0, offsets[nq]]. */
+int orc_simple_candidates_batch(const double *q, int64_t nq, int d, const int64_t *offsets, const int32_t *idx,
+                                const double *nodes, int64_t e_begin, int64_t e_end, const orc_sphere *sph,
+                                const orc_polygon *poly, int m, double robot_radius, double *cost_out,
+                                double *cost_in, uint8_t *hit_out, uint8_t *hit_in, int32_t *fh_out, int32_t *fh_in);
+/* directed edges p0[i] -> p1[i] (rows of d) against the list as above: hit and first hit, each optional */
+void orc_edges_check_batch(const double *p0, const double *p1, int64_t n, int d, const orc_sphere *sph,
+                           const orc_polygon *poly, int m, double robot_radius, uint8_t *hit, int32_t *first_hit);
+/* points p[i] (rows of d): orc_point_check_spheres (with quick) where sph is non-NULL, else
+ * orc_point_check_polygons; unsafe and clearance optional */
+void orc_points_check_batch(const double *p, int64_t n, int d, const orc_sphere *sph, const orc_polygon *poly, int m,
+                            double robot_radius, int quick, uint8_t *unsafe, double *clearance);
 /* the shared deterministic transcendentals of include/rrtx_detmath.h, element-wise (tests compare them with
  * libm here and with the device's build of the same header bit for bit).
  * op: 0 sin(x)  1 cos(x)  2 atan2(y, x)  3 acos(x);  returns 1 in the ORC_LIBM_TRIG build, else 0 */

@@ -121,6 +121,51 @@ int main(void) {
     bad += orc_dubins_candidates_batch(qs, 6, coff, cidx, nodes, 0, 201, 1.0, 0.5, &mv, 1, 1, 1, 5.0, 30.0, bc, bw, bh,
                                        bok, btl, bfh) != -2;
   }
+  {
+    /* batched search and SimpleEdge checks: capacity retry, per-query radii, a wrapped tree, k nearest */
+    enum { NN = 2000, NQ = 40 };
+    static double pts[3 * NN], qs3[3 * NQ], rad[NQ], key[64 * NQ * 4], cout_[64 * NQ * 4], cin_[64 * NQ * 4], clr3[NQ];
+    static int32_t idx[64 * NQ * 4], fo[64 * NQ * 4], fi[64 * NQ * 4], kcnt[NQ];
+    static int64_t off[NQ + 1], nidx[NQ];
+    static uint8_t ho[64 * NQ * 4], hi[64 * NQ * 4], uns[NQ];
+    static double ndist[NQ];
+    orc_kd *bt = orc_kd_create(3);
+    for (int i = 0; i < 3 * NN; ++i) pts[i] = frand(&seed);
+    orc_kd_insert_many(bt, pts, NN);
+    for (int i = 0; i < 3 * NQ; ++i) qs3[i] = frand(&seed);
+    for (int i = 0; i < NQ; ++i) rad[i] = (i % 5) ? 0.12 * frand(&seed) : 0.0;
+    const int64_t need = orc_range_batch(bt, qs3, NQ, rad, 1, 8, off, idx, key, nidx, ndist);
+    bad += !(need > 8) || off[NQ] != need;
+    bad += orc_range_batch(bt, qs3, NQ, rad, 1, need, off, idx, key, nidx, ndist) != need;
+    for (int i = 0; i < NQ; ++i)
+      for (int64_t e = off[i] + 1; e < off[i + 1]; ++e) bad += !(idx[e - 1] < idx[e]);
+    bad += orc_range_batch(bt, qs3, NQ, rad, 0, 0, NULL, NULL, NULL, nidx, ndist) != 0;
+    bad += orc_simple_candidates_batch(qs3, NQ, 3, off, idx, pts, 3, need, sp, NULL, 4, 0.5, cout_, cin_, ho, hi, fo,
+                                       fi) != 0;
+    bad += orc_simple_candidates_batch(qs3, NQ, 3, off, idx, pts, 0, need, NULL, &pg, 1, 0.5, cout_, cin_, ho, hi, fo,
+                                       fi) != 0;
+    bad += orc_simple_candidates_batch(qs3, NQ, 3, off, idx, pts, 0, need + 1, sp, NULL, 4, 0.5, cout_, cin_, ho, hi,
+                                       fo, fi) != -2;
+    orc_edges_check_batch(pts, pts + 3, NN - 1, 3, sp, NULL, 4, 0.5, ho, fo);
+    orc_edges_check_batch(pts, pts + 3, NN - 1, 3, NULL, &mv, 1, 0.5, ho, NULL);
+    orc_points_check_batch(qs3, NQ, 3, sp, NULL, 4, 0.5, 1, uns, clr3);
+    orc_points_check_batch(qs3, NQ, 3, NULL, &pg, 1, 0.5, 0, uns, NULL);
+    bad += orc_knearest_batch(bt, 5, qs3, NQ, 5, idx, key, kcnt) != 0 || kcnt[0] != 5;
+    bad += orc_knearest_batch(bt, 1, qs3, NQ, 1, idx, key, kcnt) != -2;
+    orc_kd_destroy(bt);
+    orc_kd *wt = orc_kd_create(4);
+    int wd1[1] = {3}; double wp1[1] = {2.0 * 3.141592653589793};
+    orc_kd_set_wraps(wt, 1, wd1, wp1);
+    static double pts4[4 * NN], qs4[4 * NQ];
+    for (int i = 0; i < NN; ++i) { pts4[4 * i] = 10 * frand(&seed); pts4[4 * i + 1] = 10 * frand(&seed); pts4[4 * i + 2] = 0; pts4[4 * i + 3] = wp1[0] * frand(&seed); }
+    for (int i = 0; i < NQ; ++i) { qs4[4 * i] = 10 * frand(&seed); qs4[4 * i + 1] = 10 * frand(&seed); qs4[4 * i + 2] = 0; qs4[4 * i + 3] = wp1[0] * frand(&seed); }
+    orc_kd_insert_many(wt, pts4, NN);
+    double r4 = 0.6;
+    const int64_t need4 = orc_range_batch(wt, qs4, NQ, &r4, 0, 0, off, NULL, NULL, NULL, NULL);
+    bad += need4 > 64 * NQ * 4 || orc_range_batch(wt, qs4, NQ, &r4, 0, need4, off, idx, key, nidx, ndist) != need4;
+    bad += orc_knearest_batch(wt, 3, qs4, NQ, 3, idx, key, kcnt) != -1;
+    orc_kd_destroy(wt);
+  }
   printf(bad ? "selftest FAILED (%d)\n" : "selftest ok\n", bad);
   return bad != 0;
 }

@@ -48,3 +48,9 @@ def test_plain_run_dumps_the_last_timed_step(oracle, tmp_path):
         o = np.argsort(ri)
         assert np.array_equal(d["idx"][off[i]:off[i + 1]], ri[o].astype(np.float64)), f"neighbour set of sample {i}"
         assert np.array_equal(d["cost"][off[i]:off[i + 1]], rk[o]), f"edge costs of sample {i}"
+    # all eight arrays, every sample, against the oracle's extend() preamble of that step (C4's 256 spheres)
+    ref = oracle.extend_candidates_batch(oracle.TreeSet(3, pts), Q, rad, pts, oracle.make_spheres(synth.spheres(cfg.n_obstacles)),
+                                         0.5, per_sample=40)
+    oracle.assert_same_results(d, ref, tuple(sorted(d)), label="bench dump: ")
+    assert k > 20 * B and 0 < ref["hit_out"].sum() < k and 0 < ref["sample_unsafe"].sum() < B
+    print(f"\nbench dump: {B} samples, {k} entries, all eight arrays against the oracle")

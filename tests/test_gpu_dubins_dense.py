@@ -3,7 +3,8 @@
 rrtqx_3d_amd/csrc/kernels_dubins.hip), so each call here holds more than 2^21 CSR entries and the later chunks are
 compared too.  The oracle side is the batched form of the per-edge functions (oracle.dubins_edges_batch /
 dubins_candidates_batch, held equal to the per-edge wrappers by tests/test_oracle_dubins_batch.py).  Every comparison
-is == on doubles and bytes; every test asserts how many directed edges it compared."""
+is == on doubles and bytes; every test asserts how many directed edges it compared.  The CSR the preamble builds is
+compared with the oracle's range search (oracle.range_batch) entry for entry first."""
 import math
 
 import numpy as np
@@ -63,6 +64,11 @@ def test_c3_every_dubins_edge(oracle):
         off, idx = out["offsets"], out["idx"]
         n = len(idx)
         assert n == C3_ENTRIES > CHUNK
+        # the preamble's CSR is the oracle's range search, entry for entry (the checks below take it as given)
+        trees = oracle.TreeSet(4, pts, wraps=[3], wrap_points=[2.0 * math.pi])
+        rng = oracle.range_batch(trees, Q, r, per_sample=1500, nearest=False)
+        del trees
+        oracle.assert_same_results(out, rng, ("offsets", "idx", "key"), label="C3 Dubins preamble CSR: ")
         owner = np.repeat(np.arange(len(Q)), np.diff(off))
         s = np.concatenate([Q[owner], pts[idx]])                 # sample -> node, then node -> sample
         g = np.concatenate([pts[idx], Q[owner]])
@@ -116,6 +122,11 @@ def test_c5_every_dubins_edge_with_time(oracle):
             off, idx = out["offsets"], out["idx"]
             n = len(idx)
             assert n == C5_ENTRIES > CHUNK
+            if first is None:                                # the preamble's CSR is the oracle's range search
+                trees = oracle.TreeSet(4, pts, wraps=[3], wrap_points=[2.0 * math.pi])
+                rng = oracle.range_batch(trees, Q, r, per_sample=2400, nearest=False)
+                del trees
+                oracle.assert_same_results(out, rng, ("offsets", "idx", "key"), label="C5 Dubins preamble CSR: ")
             first = out if first is None else first
             assert np.array_equal(idx, first["idx"]) and np.array_equal(out["cost_out"], first["cost_out"])
             ps = oracle.PolygonSet(polys, kinds=kinds, paths=paths, active=act)
