@@ -140,6 +140,10 @@ int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out);
 /*   RRTX_OPT_LAST_PLACEMENT (read only): how the last range search ordered its query copies -- 0 no culling (no
  *   order), 1 the place pass (ghosts, or RRTX_OPT_TUNE bit 4), 2 the tile kernel from the bucket-slot table. */
 #define RRTX_OPT_LAST_PLACEMENT 14
+/*   RRTX_OPT_SELECT_LIST_CAP: entries the context-owned neighbour lists of rrtx_extend_select have room for.  The call
+ *   sizes them itself (from what the last calls produced; a call that produces more grows them and runs once more);
+ *   reading tells what it settled on, setting forces a starting value (testing). */
+#define RRTX_OPT_SELECT_LIST_CAP 15
 int rrtx_set_option(rrtx_ctx *ctx, int option, int64_t value);
 /* The value an option currently has (as rrtx_set_option normalised it): callers that size buffers by an
  * option -- the row width of rrtx_dubins_trajectory -- read it here instead of keeping a shadow copy. */
@@ -425,6 +429,65 @@ int rrtx_graph_cost_update_dev(rrtx_ctx *ctx, int root_idx, double *lmc_dev, int
 
 int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit_in,
                        const int64_t *n_valid_dev, int64_t cap, uint64_t *words);
+
+/* ---- parent and rewire selection over the extend lists ------------------------ */
+/* findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) for a whole batch, over the
+ * CSR lists rrtx_extend_candidates* wrote and rrtLMC of every node (lmc: one double per node, at least
+ * rrtx_nodes_count long).  Exact, no tolerance: every output is an input value, an index or one rounded fp64 addition.
+ * Per sample s, over its entries e in list order (ascending node index):
+ *   status[s]       RRTX_SEL_UNSAFE     sample_unsafe is given and sample_unsafe[s] != 0: nothing else is computed
+ *                                       (the driver skips extend for such a sample, R/rrtqx.jl:940);
+ *                   RRTX_SEL_EMPTY      the list has no entry (the closestNode rule, :1931-1935, stays with the caller);
+ *                   RRTX_SEL_NO_PARENT  no entry was adopted;
+ *                   RRTX_SEL_OK         otherwise;
+ *                   RRTX_SEL_OVERFLOW   (every sample) the extend call produced more entries than its cap.
+ *   parent          best = +Inf; for each entry with hit_out[e] == 0 (the Dubins-with-time byte also carries !validMove:
+ *                   the test is "byte is zero"): cand = lmc[idx[e]] + cost_out[e]; adopted when best > cand.  A NaN or
+ *                   +Inf candidate is never adopted (an orphan is never a parent); of exactly equal candidates the
+ *                   lowest list position wins.  parent_idx[s] = idx of the winner, parent_entry[s] = its CSR
+ *                   position, lmc_new[s] = best; -1, -1, +Inf unless status[s] is RRTX_SEL_OK.
+ *   rewire          (RRTX_SEL_OK only) every entry with hit_in[e] == 0, idx[e] != parent_idx[s] and
+ *                   lmc[idx[e]] > lmc_new[s] + cost_in[e], as (rw_node = idx[e], rw_value = lmc_new[s] + cost_in[e]) in
+ *                   list order: a second CSR rw_offsets[nq + 1], rw_node, rw_value with the two-call capacity pattern.
+ * For SimpleEdge lists pass the one cost array as cost_out and cost_in.  The kd-tree root needs no special case:
+ * lmc[root] = 0 never exceeds a non-negative sum.  Samples of one batch do not see each other -- the lists are against
+ * the tree as it stood, as in rrtx_extend_candidates -- so a node may appear in the rewire lists of several samples;
+ * settling that is the caller's bookkeeping. */
+#define RRTX_SEL_OK 0
+#define RRTX_SEL_NO_PARENT 1
+#define RRTX_SEL_EMPTY 2
+#define RRTX_SEL_UNSAFE 3
+#define RRTX_SEL_OVERFLOW 4
+/* Device-pointer form: only enqueues, never waits on the stream.  cap and n_valid_dev are the capacity the extend call
+ * was given and the count it left on the device (needed_dev): with *n_valid_dev > cap every status is
+ * RRTX_SEL_OVERFLOW and nothing else is written; no list entry at or beyond cap is read.  *rw_needed_dev receives the
+ * number of rewire entries; entries at or beyond rw_cap are not written.  sample_unsafe may be NULL.  lmc == NULL
+ * selects the context's own array (rrtx_node_cost_set), which may first have to grow with the nodes (that growth
+ * waits on the stream once). */
+int rrtx_extend_select_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
+                           const double *cost_in, const uint8_t *hit_out, const uint8_t *hit_in,
+                           const int64_t *n_valid_dev, int64_t cap, const uint8_t *sample_unsafe, const double *lmc,
+                           int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
+                           int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
+                           int64_t *rw_needed_dev);
+/* The context's own rrtLMC array on the device: one double per node, +Inf for a node never set, growing with
+ * rrtx_nodes_append.  Writes lmc[0 .. n) to nodes first_index .. first_index + n - 1 (host pointer; the nodes must
+ * exist), so a host planner uploads the few values a step changed instead of all of them. */
+int rrtx_node_cost_set(rrtx_ctx *ctx, int64_t first_index, const double *lmc, int64_t n);
+/* Host-pointer form for SimpleEdge (dim == 3, no wraps; spheres or polygons by RRTX_OPT_EXTEND_OBSTACLES): runs
+ * rrtx_extend_candidates into buffers the context owns, then the selection, and returns the per-sample results and the
+ * rewire lists only.  lmc: rrtLMC of every node (rrtx_nodes_count doubles), or NULL for the context's own array.
+ * parent_entry is a position in the lists of THIS call (useful with the optional list outputs).  rw_* follow the two-call
+ * pattern: with more than rw_cap rewire entries the call returns RRTX_E_CAPACITY with *rw_needed set (the per-sample
+ * outputs and rw_offsets are valid).  nearest_idx / nearest_dist / sample_unsafe may be NULL (the samples are checked
+ * either way: an unsafe sample has status RRTX_SEL_UNSAFE).  The neighbour lists themselves stay on the device unless
+ * offsets is non-NULL: then offsets, idx, cost, hit_out, hit_in (room for cap entries, all non-NULL) and *needed receive
+ * them as rrtx_extend_candidates would, RRTX_E_CAPACITY included. */
+int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, const double *lmc,
+                       int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
+                       int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap, int64_t *rw_needed,
+                       int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe, int64_t *offsets,
+                       int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
 
 #ifdef __cplusplus
 }

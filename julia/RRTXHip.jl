@@ -399,6 +399,74 @@ function extend_candidates(tree::HipTree, S::TS, positions::Array{Float64,2}, hy
 end
 
 # ---------------------------------------------------------------------------
+# findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) on the device, for a batch of
+# samples: what comes back per sample is a status, a parent, the sample's rrtLMC and the neighbours to rewire -- the
+# neighbour lists themselves stay on the device.  setNodeCosts uploads rrtLMC of the nodes a step changed
+# (0-based first index; a node never set reads as Inf); extendSelect reads that array.  A sample with an empty ball
+# (status RRTX_SEL_EMPTY) keeps the closestNode rule of findBestParent (:1931-1935) on the host: nearestIdx says which
+# node.  Samples of one batch do not see each other.
+const RRTX_SEL_OK = UInt8(0)
+const RRTX_SEL_NO_PARENT = UInt8(1)
+const RRTX_SEL_EMPTY = UInt8(2)
+const RRTX_SEL_UNSAFE = UInt8(3)
+const RRTX_SEL_OVERFLOW = UInt8(4)
+
+function setNodeCosts(tree::HipTree, firstIndex::Int, lmc::Vector{Float64})
+  GC.@preserve lmc rrtx_check(tree, ccall((:rrtx_node_cost_set, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Int64), tree.ctx, firstIndex, lmc, length(lmc)))
+end
+
+struct ExtendSelection
+  status::Vector{UInt8}       # RRTX_SEL_*
+  parentIdx::Vector{Int32}    # 0-based node index of the parent (-1 unless RRTX_SEL_OK)
+  lmcNew::Vector{Float64}     # rrtLMC of the new node through that parent (Inf unless RRTX_SEL_OK)
+  rwOffsets::Vector{Int64}    # nq + 1: the rewire candidates of sample i are rwOffsets[i] + 1 : rwOffsets[i + 1]
+  rwNode::Vector{Int32}       # 0-based node index
+  rwValue::Vector{Float64}    # the rrtLMC that node would get through the new node
+  nearestIdx::Vector{Int32}
+  nearestDist::Vector{Float64}
+  sampleUnsafe::Vector{UInt8}
+end
+
+function extendSelect(tree::HipTree, S::TS, positions::Array{Float64,2}, hyberBallRad::Float64) where {TS}
+  syncObstacles(tree, S)
+  nq = size(positions, 2)                     # d x nq, each sample contiguous
+  pidx = Vector{Int32}(undef, nq); pentry = Vector{Int64}(undef, nq); lmcNew = Vector{Float64}(undef, nq)
+  status = Vector{UInt8}(undef, nq); rwoff = Vector{Int64}(undef, nq + 1)
+  nidx = Vector{Int32}(undef, nq); ndist = Vector{Float64}(undef, nq); unsafe = Vector{UInt8}(undef, nq)
+  rwcap = 16 * nq
+  while true
+    rwnode = Vector{Int32}(undef, rwcap); rwval = Vector{Float64}(undef, rwcap)
+    rwneeded = Ref{Int64}(0); needed = Ref{Int64}(0)
+    rc = GC.@preserve positions pidx pentry lmcNew status rwoff rwnode rwval nidx ndist unsafe ccall((:rrtx_extend_select, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble}, Ptr{UInt8},
+         Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Int64, Ref{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Int64},
+         Ptr{Int32}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Int64, Ref{Int64}),
+        tree.ctx, positions, nq, hyberBallRad, S.robotRadius, C_NULL, pidx, pentry, lmcNew, status, rwoff, rwnode, rwval,
+        rwcap, rwneeded, nidx, ndist, unsafe, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, 0, needed)
+    if rc == RRTX_E_CAPACITY
+      rwcap = Int(rwneeded[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    n = Int(rwneeded[])
+    return ExtendSelection(status, pidx, lmcNew, rwoff, rwnode[1:n], rwval[1:n], nidx, ndist, unsafe)
+  end
+end
+
+# device-pointer form over the lists rrtx_extend_candidates_dev / _dubins_dev left on the device (all arguments device
+# pointers as Ptr{Cvoid}; for SimpleEdge lists pass the cost array as costOut and costIn; lmc = C_NULL: setNodeCosts' array)
+function extendSelectDev(tree::HipTree, nq::Int, offsets, idx, costOut, costIn, hitOut, hitIn, nValid, cap::Int, unsafe, lmc,
+                         parentIdx, parentEntry, lmcNew, status, rwOffsets, rwNode, rwValue, rwCap::Int, rwNeeded)
+  rrtx_check(tree, ccall((:rrtx_extend_select_dev, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int64}, Int64,
+       Ptr{UInt8}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble},
+       Int64, Ptr{Int64}),
+      tree.ctx, nq, offsets, idx, costOut, costIn, hitOut, hitIn, nValid, cap, unsafe, lmc, parentIdx, parentEntry,
+      lmcNew, status, rwOffsets, rwNode, rwValue, rwCap, rwNeeded))
+end
+
+# ---------------------------------------------------------------------------
 # addNewObstacle's edge loop (R/DRRT_Q.jl:3220-3290) against a device mirror of the planner's
 # directed edges.  registerEdges is called where the planner creates edges (makeNeighborOf,
 # makeInitialOutNeighborOf, makeParentOf); it returns the id of the first edge, ids are

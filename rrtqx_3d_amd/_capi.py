@@ -34,6 +34,13 @@ RRTX_OPT_TUNE = 11
 RRTX_OPT_SPACE_HAS_TIME = 12
 RRTX_OPT_ROOT_RULE = 13
 RRTX_OPT_LAST_PLACEMENT = 14
+RRTX_OPT_SELECT_LIST_CAP = 15
+# status[s] of rrtx_extend_select*
+RRTX_SEL_OK = 0
+RRTX_SEL_NO_PARENT = 1
+RRTX_SEL_EMPTY = 2
+RRTX_SEL_UNSAFE = 3
+RRTX_SEL_OVERFLOW = 4
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -129,6 +136,11 @@ SYMBOLS = [
     ("rrtx_extend_candidates_dev", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP,
                                              C.c_int64, _VP, _VP, _VP, _VP]),
     ("rrtx_pack_hits_dev", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    ("rrtx_extend_select_dev", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP,
+                                         _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    ("rrtx_node_cost_set", C.c_int, [_VP, C.c_int64, _VP, C.c_int64]),
+    ("rrtx_extend_select", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     C.c_int64, c_int64_p, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, c_int64_p]),
 ]
 
 _lib = None

@@ -26,10 +26,14 @@ class Context:
         if rc != _capi.RRTX_OK:
             raise RrtxError(rc, self._lib.rrtx_create_error().decode())
         self._h = h
+        self._registered = []       # arrays this object page-locked (select_out_buffers): alive until close()
 
     # ---- lifetime -------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
+            for a in getattr(self, "_registered", []):
+                self._lib.rrtx_host_unregister(self._h, a.ctypes.data)
+            self._registered = []
             self._lib.rrtx_destroy(self._h)
             self._h = None
 
@@ -351,6 +355,100 @@ class Context:
         n, (idx, cost, hout, hin) = self._two_call(cap, call)
         return dict(offsets=offsets, idx=idx[:n], cost=cost[:n], hit_out=hout[:n], hit_in=hin[:n],
                     nearest_idx=nidx, nearest_dist=ndist, sample_unsafe=unsafe)
+
+    # ---- findBestParent + rewire test on the device -------------------------------------------------
+    def node_cost_set(self, first_index: int, lmc):
+        """rrtLMC of nodes first_index .. first_index + len(lmc) - 1 in the context's own device array (+Inf for a node
+        never set); extend_select(lmc=None) reads it."""
+        v = f64(lmc, (-1,))
+        self._check(self._lib.rrtx_node_cost_set(self._h, int(first_index), _capi._ptr(v), v.shape[0]))
+
+    def select_out_buffers(self, nq: int, rw_cap: int, register: bool = False, list_cap: int = 0) -> dict:
+        """Output arrays for extend_select(..., out=...) that a caller keeps across calls.  register=True page-locks
+        them; the context keeps them alive and unregisters them in close().  list_cap > 0 adds room for the neighbour
+        lists themselves (a planner that keeps RRT^X neighbour sets)."""
+        out = dict(parent_idx=np.empty(nq, dtype=np.int32), parent_entry=np.empty(nq, dtype=np.int64),
+                   lmc_new=np.empty(nq, dtype=np.float64), status=np.empty(nq, dtype=np.uint8),
+                   rw_offsets=np.empty(nq + 1, dtype=np.int64), rw_node=np.empty(max(rw_cap, 1), dtype=np.int32),
+                   rw_value=np.empty(max(rw_cap, 1), dtype=np.float64), nearest_idx=np.empty(nq, dtype=np.int32),
+                   nearest_dist=np.empty(nq, dtype=np.float64), sample_unsafe=np.empty(nq, dtype=np.uint8))
+        if list_cap > 0:
+            out.update(offsets=np.empty(nq + 1, dtype=np.int64), idx=np.empty(list_cap, dtype=np.int32),
+                       cost=np.empty(list_cap, dtype=np.float64), hit_out=np.empty(list_cap, dtype=np.uint8),
+                       hit_in=np.empty(list_cap, dtype=np.uint8))
+        if register:
+            for a in out.values():
+                if a.nbytes:
+                    self.host_register(a)
+                    self._registered.append(a)
+        return out
+
+    def extend_select(self, q, r: float, robot_radius: float, lmc=None, rw_cap: Optional[int] = None,
+                      out: Optional[dict] = None, want_lists: bool = False, cap: Optional[int] = None):
+        """rrtx_extend_select: per sample the parent findBestParent picks, the sample's rrtLMC, a status
+        (_capi.RRTX_SEL_*) and the neighbours the rewire test of extend() would lower, as a CSR (rw_offsets, rw_node,
+        rw_value).  lmc: rrtLMC of every node, or None for the values node_cost_set left on the device.
+        out: arrays of select_out_buffers (no allocation, no growth: a count beyond their room raises
+        RRTX_E_CAPACITY); otherwise the arrays are allocated here and grown on demand.  want_lists also returns
+        the neighbour lists (offsets, idx, cost, hit_out, hit_in)."""
+        q = f64(q, (-1, self.dim))
+        nq = q.shape[0]
+        lmc_a = None if lmc is None else f64(lmc, (-1,))
+        if lmc_a is not None and lmc_a.shape[0] < self.n_nodes:
+            raise ValueError("lmc needs one entry per node")
+        fixed = out is not None
+        if fixed:
+            rw_cap = out["rw_node"].shape[0]
+            want_lists = "idx" in out
+            cap = out["idx"].shape[0] if want_lists else 0
+        else:
+            out = self.select_out_buffers(nq, 0)
+            rw_cap = max(16 * nq, 1024) if rw_cap is None else int(rw_cap)
+            cap = (max(64 * nq, 1024) if cap is None else int(cap)) if want_lists else 0
+            if want_lists:
+                out["offsets"] = np.empty(nq + 1, dtype=np.int64)
+        while True:
+            if not fixed:
+                if out["rw_node"].shape[0] < max(rw_cap, 1):
+                    out["rw_node"] = np.empty(max(rw_cap, 1), dtype=np.int32)
+                    out["rw_value"] = np.empty(max(rw_cap, 1), dtype=np.float64)
+                if want_lists and ("idx" not in out or out["idx"].shape[0] < max(cap, 1)):
+                    out.update(idx=np.empty(max(cap, 1), dtype=np.int32), cost=np.empty(max(cap, 1), dtype=np.float64),
+                               hit_out=np.empty(max(cap, 1), dtype=np.uint8), hit_in=np.empty(max(cap, 1), dtype=np.uint8))
+            rw_needed, needed = C.c_int64(), C.c_int64()
+            g = (lambda k: _capi._ptr(out[k])) if want_lists else (lambda k: None)
+            rc = self._lib.rrtx_extend_select(
+                self._h, _capi._ptr(q), nq, r, robot_radius, _capi._ptr(lmc_a), _capi._ptr(out["parent_idx"]),
+                _capi._ptr(out["parent_entry"]), _capi._ptr(out["lmc_new"]), _capi._ptr(out["status"]),
+                _capi._ptr(out["rw_offsets"]), _capi._ptr(out["rw_node"]), _capi._ptr(out["rw_value"]), rw_cap,
+                C.byref(rw_needed), _capi._ptr(out["nearest_idx"]), _capi._ptr(out["nearest_dist"]),
+                _capi._ptr(out["sample_unsafe"]), g("offsets"), g("idx"), g("cost"), g("hit_out"), g("hit_in"), cap,
+                C.byref(needed))
+            if rc != _capi.RRTX_E_CAPACITY or fixed:
+                self._check(rc)
+                break
+            rw_cap = max(rw_cap, int(rw_needed.value))
+            cap = max(cap, int(needed.value)) if want_lists else 0
+        nrw, n = int(rw_needed.value), int(needed.value)
+        res = {k: out[k] for k in ("parent_idx", "parent_entry", "lmc_new", "status", "rw_offsets", "nearest_idx",
+                                   "nearest_dist", "sample_unsafe")}
+        res.update(rw_node=out["rw_node"][:nrw], rw_value=out["rw_value"][:nrw], n_neighbors=n)
+        if want_lists:
+            res.update(offsets=out["offsets"], idx=out["idx"][:n], cost=out["cost"][:n], hit_out=out["hit_out"][:n],
+                       hit_in=out["hit_in"][:n])
+        return res
+
+    def extend_select_dev(self, nq: int, offsets_ptr: int, idx_ptr: int, cost_out_ptr: int, cost_in_ptr: int,
+                          hit_out_ptr: int, hit_in_ptr: int, n_valid_ptr: Optional[int], cap: int,
+                          unsafe_ptr: Optional[int], lmc_ptr: Optional[int], parent_idx_ptr: int, parent_entry_ptr: int,
+                          lmc_new_ptr: int, status_ptr: int, rw_offsets_ptr: int, rw_node_ptr: int, rw_value_ptr: int,
+                          rw_cap: int, rw_needed_ptr: int):
+        """rrtx_extend_select_dev over the device lists of extend_candidates_dev / extend_candidates_dubins_dev (for
+        SimpleEdge lists pass the cost array twice); lmc_ptr None selects the array node_cost_set fills."""
+        self._check(self._lib.rrtx_extend_select_dev(
+            self._h, nq, offsets_ptr, idx_ptr, cost_out_ptr, cost_in_ptr, hit_out_ptr, hit_in_ptr, n_valid_ptr, cap,
+            unsafe_ptr, lmc_ptr, parent_idx_ptr, parent_entry_ptr, lmc_new_ptr, status_ptr, rw_offsets_ptr, rw_node_ptr,
+            rw_value_ptr, rw_cap, rw_needed_ptr))
 
     def extend_candidates_dubins(self, q, r: float, robot_radius: float, r_min: float, cap: Optional[int] = None):
         """Fused extend() preamble for Edge = DubinsEdge (dim 4, theta wrapped, polygon obstacles)."""

@@ -529,8 +529,9 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
                     &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
-                    &ctx->gc.in_pos};
+                    &ctx->gc.in_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc};
   for (auto b : bufs) b->release();
+  if (ctx->node_lmc) (void)hipFree(ctx->node_lmc);
   if (ctx->ge_start) (void)hipFree(ctx->ge_start);
   if (ctx->ge_end) (void)hipFree(ctx->ge_end);
   if (ctx->ge_dist) (void)hipFree(ctx->ge_dist);
@@ -593,6 +594,7 @@ int rrtx_set_option(rrtx_ctx *ctx, int option, int64_t value) {
       ctx->bkt_mult = m;
       return RRTX_OK;
     }
+    case RRTX_OPT_SELECT_LIST_CAP: ctx->sel_list_cap = value > 0 ? value : 0; return RRTX_OK;
     default: return fail(ctx, RRTX_E_INVALID, "set_option: unknown option %d", option);
   }
 }
@@ -636,6 +638,7 @@ int rrtx_get_option(rrtx_ctx *ctx, int option, int64_t *value) {
     case RRTX_OPT_NEAREST_REC_CAP: *value = (int64_t)ctx->opt_nearest_rec_cap; return RRTX_OK;
     case RRTX_OPT_BUCKET_MULT: *value = ctx->bkt_mult; return RRTX_OK;
     case RRTX_OPT_LAST_PLACEMENT: *value = ctx->last_placement; return RRTX_OK;
+    case RRTX_OPT_SELECT_LIST_CAP: *value = ctx->sel_list_cap; return RRTX_OK;
     default: return fail(ctx, RRTX_E_INVALID, "get_option: unknown option %d", option);
   }
 }
@@ -1685,6 +1688,173 @@ int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit
   if (cap < 0 || (cap > 0 && (!hit_out || !hit_in || !n_valid_dev || !words)))
     return fail(ctx, RRTX_E_INVALID, "pack_hits: bad arguments");
   return launch_pack_hits(ctx, hit_out, hit_in, n_valid_dev, cap, words);
+}
+
+// ---- parent and rewire selection over the extend lists (kernels_select.hip) -----------------------
+int rrtx_extend_select_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
+                           const double *cost_in, const uint8_t *hit_out, const uint8_t *hit_in,
+                           const int64_t *n_valid_dev, int64_t cap, const uint8_t *sample_unsafe, const double *lmc,
+                           int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
+                           int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
+                           int64_t *rw_needed_dev) {
+  CHECK_CTX(ctx);
+  if (nq < 0 || cap < 0 || rw_cap < 0 || !offsets || !rw_offsets || !rw_needed_dev ||
+      (nq > 0 && (!parent_idx || !parent_entry || !lmc_new || !status)) ||
+      (cap > 0 && (!idx || !cost_out || !cost_in || !hit_out || !hit_in)) || (rw_cap > 0 && (!rw_node || !rw_value)))
+    return fail(ctx, RRTX_E_INVALID, "extend_select: bad arguments");
+  SelectLaunch L;
+  L.nq = nq;
+  L.offsets = offsets; L.idx = idx; L.cost_out = cost_out; L.cost_in = cost_in; L.hit_out = hit_out; L.hit_in = hit_in;
+  L.n_valid_dev = n_valid_dev; L.cap = cap;
+  L.sample_unsafe = sample_unsafe;
+  L.lmc = lmc; L.n_lmc = ctx->n_nodes;
+  if (!lmc) {
+    int rc = node_cost_ensure(ctx);
+    if (rc) return rc;
+    L.lmc = ctx->node_lmc; L.n_lmc = ctx->node_lmc_n;
+  }
+  L.parent_idx = parent_idx; L.parent_entry = parent_entry; L.lmc_new = lmc_new; L.status = status;
+  L.rw_offsets = rw_offsets; L.rw_node = rw_node; L.rw_value = rw_value; L.rw_cap = rw_cap;
+  L.rw_needed_dev = rw_needed_dev;
+  return launch_select(ctx, L);
+}
+
+int rrtx_node_cost_set(rrtx_ctx *ctx, int64_t first_index, const double *lmc, int64_t n) {
+  CHECK_CTX(ctx);
+  if (n < 0 || first_index < 0 || (n > 0 && !lmc)) return fail(ctx, RRTX_E_INVALID, "node_cost_set: bad arguments");
+  if (first_index > ctx->n_nodes || n > ctx->n_nodes - first_index)
+    return fail(ctx, RRTX_E_INVALID, "node_cost_set: nodes %lld .. %lld of %lld", (long long)first_index,
+                (long long)(first_index + n), (long long)ctx->n_nodes);
+  int rc = node_cost_ensure(ctx);
+  if (rc || n == 0) return rc;
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->node_lmc + first_index, lmc, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
+}
+
+int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, const double *lmc,
+                       int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
+                       int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap, int64_t *rw_needed,
+                       int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe, int64_t *offsets,
+                       int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed) {
+  CHECK_CTX(ctx);
+  const bool want_lists = offsets != nullptr;
+  if (nq < 0 || rw_cap < 0 || !rw_offsets || (nq > 0 && (!q || !parent_idx || !parent_entry || !lmc_new || !status)) ||
+      (rw_cap > 0 && (!rw_node || !rw_value)) ||
+      (want_lists && (cap < 0 || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))))
+    return fail(ctx, RRTX_E_INVALID, "extend_select: bad arguments");
+  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_select is the SimpleEdge (dim=3) path");
+  if (nq == 0) {
+    rw_offsets[0] = 0;
+    if (rw_needed) *rw_needed = 0;
+    if (want_lists) offsets[0] = 0;
+    if (needed) *needed = 0;
+    return RRTX_OK;
+  }
+  // ONE device block for everything that is per sample -- [entry count, rewire count | rw_offsets | parent_entry |
+  // lmc_new | nearest_dist | parent_idx | nearest_idx | status | sample_unsafe | offsets] -- so that it leaves in one
+  // transfer (without its tail, the list offsets, unless the caller wants the lists).
+  const size_t n = (size_t)nq;
+  const size_t o_rwoff = 2 * sizeof(int64_t), o_pe = o_rwoff + sizeof(int64_t) * (n + 1), o_ln = o_pe + sizeof(int64_t) * n,
+               o_nd = o_ln + sizeof(double) * n, o_pi = o_nd + sizeof(double) * n, o_ni = o_pi + sizeof(int32_t) * n,
+               o_st = o_ni + sizeof(int32_t) * n, o_un = o_st + n, o_off = (o_un + n + 7) & ~(size_t)7,
+               blk_bytes = o_off + sizeof(int64_t) * (n + 1), out_bytes = want_lists ? blk_bytes : o_off;
+  const size_t q_bytes = sizeof(double) * n * (size_t)ctx->dim, lmc_bytes = lmc ? sizeof(double) * (size_t)ctx->n_nodes : 0;
+  const size_t staged = (256u << 10) + 64;   // what d2h may take per small output array
+  int rc = arena_begin(ctx, out_bytes + q_bytes + (lmc_bytes <= (1u << 20) ? lmc_bytes : 0) + 6 * staged + 512);
+  if (rc) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
+  const double *lmc_dev;
+  int64_t n_lmc;
+  if (lmc) {
+    if ((rc = stage_in_small(ctx, ctx->ws_sel_lmc, lmc, lmc_bytes))) return rc;
+    lmc_dev = ctx->ws_sel_lmc.as<double>(); n_lmc = ctx->n_nodes;
+  } else {
+    if ((rc = node_cost_ensure(ctx))) return rc;
+    lmc_dev = ctx->node_lmc; n_lmc = ctx->node_lmc_n;
+  }
+  RRTX_HIP(ctx, ctx->ws_sel_blk.ensure(blk_bytes + 64));
+  RRTX_HIP(ctx, ctx->ws_sel_rwn.ensure(sizeof(int32_t) * (size_t)(rw_cap > 0 ? rw_cap : 1)));
+  RRTX_HIP(ctx, ctx->ws_sel_rwv.ensure(sizeof(double) * (size_t)(rw_cap > 0 ? rw_cap : 1)));
+  char *blk = ctx->ws_sel_blk.as<char>();
+  int64_t *hdr_dev = reinterpret_cast<int64_t *>(blk);
+  char *host_blk = arena_take(ctx, out_bytes);
+  if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "extend_select: staging arena");
+  // the neighbour lists stay on the device; their capacity is the context's business: sized once from what the last
+  // search produced, and when a call produces more, grown to that and the call run once more
+  int64_t lcap = ctx->sel_list_cap > 0 ? ctx->sel_list_cap
+                                       : std::max<int64_t>(ctx->last_neighbors + ctx->last_neighbors / 8, std::max<int64_t>(64 * (int64_t)nq, 1024));
+  int64_t total = 0, rw_total = 0;
+  for (int attempt = 0;; ++attempt) {
+    RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)lcap));
+    RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)lcap));
+    RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)lcap));
+    RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)lcap));
+    ctx->sel_list_cap = lcap;
+    const bool want_nearest = nearest_idx && nearest_dist;
+    rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, reinterpret_cast<int64_t *>(blk + o_off),
+                                    ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_dist.as<double>(),
+                                    ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(), lcap, hdr_dev,
+                                    want_nearest ? reinterpret_cast<int32_t *>(blk + o_ni) : nullptr,
+                                    want_nearest ? reinterpret_cast<double *>(blk + o_nd) : nullptr,
+                                    reinterpret_cast<uint8_t *>(blk + o_un));
+    if (rc) return rc;
+    SelectLaunch L;
+    L.nq = nq;
+    L.offsets = reinterpret_cast<int64_t *>(blk + o_off);
+    L.idx = ctx->ws_out_idx.as<int32_t>();
+    L.cost_out = L.cost_in = ctx->ws_out_dist.as<double>();
+    L.hit_out = ctx->ws_out_u8a.as<uint8_t>(); L.hit_in = ctx->ws_out_u8b.as<uint8_t>();
+    L.n_valid_dev = hdr_dev; L.cap = lcap;
+    L.sample_unsafe = reinterpret_cast<uint8_t *>(blk + o_un);
+    L.lmc = lmc_dev; L.n_lmc = n_lmc;
+    L.parent_idx = reinterpret_cast<int32_t *>(blk + o_pi);
+    L.parent_entry = reinterpret_cast<int64_t *>(blk + o_pe);
+    L.lmc_new = reinterpret_cast<double *>(blk + o_ln);
+    L.status = reinterpret_cast<uint8_t *>(blk + o_st);
+    L.rw_offsets = reinterpret_cast<int64_t *>(blk + o_rwoff);
+    L.rw_node = ctx->ws_sel_rwn.as<int32_t>(); L.rw_value = ctx->ws_sel_rwv.as<double>(); L.rw_cap = rw_cap;
+    L.rw_needed_dev = hdr_dev + 1;
+    if ((rc = launch_select(ctx, L))) return rc;
+    RRTX_HIP(ctx, hipMemcpyAsync(host_blk, blk, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(&total, host_blk, sizeof(int64_t));
+    ctx->last_neighbors = total;
+    if (total <= lcap) break;
+    if (attempt) return fail(ctx, RRTX_E_STATE, "extend_select: %lld neighbours after growing to %lld", (long long)total, (long long)lcap);
+    lcap = total + total / 8;
+  }
+  std::memcpy(&rw_total, host_blk + sizeof(int64_t), sizeof(int64_t));
+  std::memcpy(rw_offsets, host_blk + o_rwoff, sizeof(int64_t) * (n + 1));
+  std::memcpy(parent_entry, host_blk + o_pe, sizeof(int64_t) * n);
+  std::memcpy(lmc_new, host_blk + o_ln, sizeof(double) * n);
+  std::memcpy(parent_idx, host_blk + o_pi, sizeof(int32_t) * n);
+  std::memcpy(status, host_blk + o_st, n);
+  if (sample_unsafe) std::memcpy(sample_unsafe, host_blk + o_un, n);
+  const bool want_nearest = nearest_idx && nearest_dist;
+  if (want_nearest) {
+    std::memcpy(nearest_dist, host_blk + o_nd, sizeof(double) * n);
+    std::memcpy(nearest_idx, host_blk + o_ni, sizeof(int32_t) * n);
+  }
+  if (want_lists) std::memcpy(offsets, host_blk + o_off, sizeof(int64_t) * (n + 1));
+  if (needed) *needed = total;
+  if ((rc = check_capacity(ctx, "extend_select", "rewire entries", rw_total, rw_cap, rw_needed))) return rc;
+  if (want_lists && (rc = check_capacity(ctx, "extend_select", "neighbours", total, cap, needed))) return rc;
+  if (rw_total > 0) {
+    if ((rc = d2h(ctx, rw_value, ctx->ws_sel_rwv.p, sizeof(double) * (size_t)rw_total))) return rc;
+    if ((rc = d2h(ctx, rw_node, ctx->ws_sel_rwn.p, sizeof(int32_t) * (size_t)rw_total))) return rc;
+  }
+  if (want_lists && total > 0) {
+    if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)total))) return rc;
+    if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
+    if ((rc = d2h(ctx, hit_out, ctx->ws_out_u8a.p, (size_t)total))) return rc;
+    if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
+  }
+  if (rw_total > 0 || (want_lists && total > 0)) {
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    arena_flush(ctx);
+  }
+  return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
 }
 
 }  // extern "C"

@@ -230,6 +230,14 @@ struct rrtx_ctx {
   int64_t ge_n = 0, ge_cap = 0;
   rrtx::DevBuf ws_sweep_mark, ws_sweep_flag, ws_sweep_cnt, ws_sweep_start;
 
+  // parent / rewire selection over the extend lists (kernels_select.hip)
+  double *node_lmc = nullptr;       // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
+  int64_t node_lmc_cap = 0, node_lmc_n = 0;   // slots allocated; slots initialised (follows n_nodes)
+  rrtx::DevBuf ws_sel_cnt;          // int32 rewire entries per sample
+  rrtx::DevBuf ws_sel_blk;          // rrtx_extend_select: everything that is per sample, one block
+  rrtx::DevBuf ws_sel_rwn, ws_sel_rwv, ws_sel_lmc;   // ... its rewire lists and a caller-given rrtLMC array
+  int64_t sel_list_cap = 0;         // ... entries its neighbour lists have room for
+
   // radius -> threshold cache
   double thr_cache_r = -1.0, thr_cache_lt = 0.0, thr_cache_gt = 0.0;
 
@@ -375,6 +383,18 @@ void graph_cost_forget(rrtx_ctx *ctx);
 
 int launch_pack_hits(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit_in, const int64_t *n_valid_dev,
                      int64_t cap, uint64_t *words);
+
+// findBestParent + rewire test over the lists of the extend preamble (kernels_select.hip); device pointers
+struct SelectLaunch {
+  int nq;
+  const int64_t *offsets; const int32_t *idx; const double *cost_out, *cost_in; const uint8_t *hit_out, *hit_in;
+  const int64_t *n_valid_dev; int64_t cap;
+  const uint8_t *sample_unsafe; const double *lmc; int64_t n_lmc;
+  int32_t *parent_idx; int64_t *parent_entry; double *lmc_new; uint8_t *status;
+  int64_t *rw_offsets; int32_t *rw_node; double *rw_value; int64_t rw_cap; int64_t *rw_needed_dev;
+};
+int launch_select(rrtx_ctx *ctx, const SelectLaunch &L);
+int node_cost_ensure(rrtx_ctx *ctx);   // ctx->node_lmc covers every node (new slots +Inf)
 
 // make sure the packed obstacle tables on the device match the host truth
 int sync_spheres(rrtx_ctx *ctx, double robot_radius);

@@ -541,6 +541,39 @@ def extend_candidates(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: flo
     return out
 
 
+def extend_select(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, lmc=None):
+    """findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) for many samples at once, on
+    the device: per sample the parent, its own rrtLMC and the neighbours whose rrtLMC it would lower, as
+    dict(status, parent_idx, parent_entry, lmc_new, rw_offsets, rw_node, rw_value, nearest_idx, nearest_dist,
+    sample_unsafe); status is one of _capi.RRTX_SEL_OK / NO_PARENT / UNSAFE.  lmc: rrtLMC per node in insertion
+    order, or None for the values Context.node_cost_set left on the device (RRTNode.rrtLMC then answers for the
+    closestNode rule).  A sample with an empty ball is linked to closestNode as the reference does (:1930-1935): one
+    edge each way through calculateTrajectory / explicitEdgeCheck.  Samples of one batch do not see each other."""
+    if tree.d != 3:
+        error("extend_select is the SimpleEdge (3-D) path")
+    if S.inWarmupTime:
+        error("extend_select checks obstacles; during warm-up use extend_candidates")
+    S.bind(tree)
+    kind = _sync_obstacles(S)
+    from . import _capi
+    tree.ctx.set_option(_capi.RRTX_OPT_EXTEND_OBSTACLES, kind)
+    q = np.asarray(newPositions, dtype=np.float64).reshape(-1, 3)
+    out = tree.ctx.extend_select(q, float(hyberBallRad_), S.robotRadius, lmc=lmc)
+    for s in np.flatnonzero(out["status"] == _capi.RRTX_SEL_EMPTY):
+        near = tree.nodes[int(out["nearest_idx"][s])]
+        new = RRTNode(q[s])
+        e = newEdge(new, near)
+        calculateTrajectory(S, e)
+        near_lmc = near.rrtLMC if lmc is None else float(lmc[near.index])
+        out["status"][s] = _capi.RRTX_SEL_NO_PARENT
+        if not explicitEdgeCheck(S, e) and Inf > near_lmc + e.dist:
+            out["status"][s] = _capi.RRTX_SEL_OK
+            out["parent_idx"][s] = near.index
+            out["lmc_new"][s] = near_lmc + e.dist
+            # (the one neighbour is the parent, so the rewire test has nobody to ask)
+    return out
+
+
 # ------------------------------------------------------------ file dumps ----
 # The reference's dump writers walk the kd-tree's child pointers (R/DRRT_Q.jl:250-364); with the device
 # tree there are none, so these walk HipTree.nodes in insertion order instead.  Same rows, same number
