@@ -149,6 +149,16 @@ def lib() -> C.CDLL:
     L.orc_graph_reduce_inconsistency.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double]
     L.orc_graph_block_edge.argtypes = [C.c_void_p, C.c_int64]
     L.orc_graph_propagate_descendants.argtypes = [C.c_void_p]
+    L.orc_graph_add_edges.restype = C.c_int64
+    L.orc_graph_add_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
+    L.orc_graph_read.restype = None
+    L.orc_graph_read.argtypes = [C.c_void_p] * 4
+    L.orc_graph_block_edges.restype = None
+    L.orc_graph_block_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.orc_sweep_edges_batch.restype = C.c_int
+    L.orc_sweep_edges_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_double, C.c_double, C.c_void_p]
     L.orc_julia_range_len.restype = C.c_int64
     L.orc_julia_range_len.argtypes = [C.c_double] * 3
     L.orc_kd_insert_many.restype = None
@@ -604,6 +614,23 @@ class Graph:
     def add_edge(self, start: int, end: int, dist: float, initial: bool = False, valid_move: bool = True) -> int:
         return lib().orc_graph_add_edge(self._h, start, end, dist, 1 if initial else 0, 1 if valid_move else 0)
 
+    def add_edges(self, start, end, dist, initial: bool = False, valid_move: bool = True) -> int:
+        """add_edge for every start[i] -> end[i] with dist[i], in order, in C; returns the first id"""
+        s = np.ascontiguousarray(start, dtype=np.int32).reshape(-1)
+        e = np.ascontiguousarray(end, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(dist, dtype=np.float64).reshape(-1)
+        assert s.shape == e.shape == w.shape
+        assert s.size == 0 or (0 <= min(s.min(), e.min()) and max(s.max(), e.max()) < self.n)
+        return lib().orc_graph_add_edges(self._h, _at(s), _at(e), _at(w), s.size, 1 if initial else 0,
+                                         1 if valid_move else 0)
+
+    def _read(self, which: str) -> np.ndarray:
+        out = np.empty(self.n, dtype=np.int64 if which == "parent_edge" else np.float64)
+        args = [None, None, None]
+        args[("lmc", "tree_cost", "parent_edge").index(which)] = _at(out)
+        lib().orc_graph_read(self._h, *args)
+        return out
+
     def set_node(self, v: int, lmc: float, tree_cost: float):
         lib().orc_graph_set_node(self._h, v, lmc, tree_cost)
 
@@ -614,16 +641,13 @@ class Graph:
         lib().orc_graph_set_edge_dist(self._h, e, dist)
 
     def lmc(self):
-        L = lib()
-        return np.array([L.orc_graph_lmc(self._h, v) for v in range(self.n)])
+        return self._read("lmc")
 
     def tree_cost(self):
-        L = lib()
-        return np.array([L.orc_graph_tree_cost(self._h, v) for v in range(self.n)])
+        return self._read("tree_cost")
 
     def parent_edge(self):
-        L = lib()
-        return np.array([L.orc_graph_parent_edge(self._h, v) for v in range(self.n)], dtype=np.int64)
+        return self._read("parent_edge")
 
     def queue_length(self) -> int:
         return lib().orc_graph_queue_length(self._h)
@@ -643,6 +667,12 @@ class Graph:
     def blockEdge(self, e: int):
         """addNewObstacle's handling of one edge the new obstacle hits (R/DRRT_Q.jl:3248-3268)"""
         lib().orc_graph_block_edge(self._h, e)
+
+    def block_edges(self, ids):
+        """blockEdge for every id, in the order given, in C"""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        assert ids.size == 0 or (0 <= ids.min() and ids.max() < lib().orc_graph_n_edges(self._h))
+        lib().orc_graph_block_edges(self._h, _at(ids), ids.size)
 
     def propogateDescendants(self):
         lib().orc_graph_propagate_descendants(self._h)
@@ -953,6 +983,38 @@ def points_check_batch(obs, P, robot_radius: float, quick: bool = True, threads=
                                                                     robot_radius, int(quick), _at(unsafe, i0),
                                                                     _at(clr, i0)) or 0)
     return unsafe, clr
+
+
+EDGE_SIMPLE, EDGE_DUBINS, EDGE_DUBINS_TIME = 0, 1, 2
+
+
+def sweep_edges_batch(nodes, es, ee, in_conflict, obs, j: int, robot_radius: float, edge: int = EDGE_SIMPLE,
+                      remove: bool = False, dist=None, r_min: float = 0.0, threads=None) -> np.ndarray:
+    """The edge loop of addNewObstacle (remove: removeObstacle) over the mirror es -> ee, in C: the ids (ascending, as
+    add_new_obstacle_edges / remove_obstacle_edges return them) of the edges that start at a node with
+    in_conflict[node] set and for which explicitEdgeCheck(S, edge, obs[j]) is true; remove: that also have
+    dist == Inf and hit no other obstacle of the list in use.  obs is a PolygonSet or make_spheres()'s (array, m)
+    (SimpleEdge only); edge is EDGE_SIMPLE, EDGE_DUBINS or EDGE_DUBINS_TIME (the piecewise time column)."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+    d = nodes.shape[1]
+    es = np.ascontiguousarray(es, dtype=np.int32).reshape(-1)
+    ee = np.ascontiguousarray(ee, dtype=np.int32).reshape(-1)
+    mask = np.ascontiguousarray(in_conflict, dtype=np.uint8).reshape(-1)
+    assert es.shape == ee.shape and mask.shape == (nodes.shape[0],)
+    assert es.size == 0 or (0 <= min(es.min(), ee.min()) and max(es.max(), ee.max()) < nodes.shape[0])
+    w = None
+    if remove:
+        w = np.ascontiguousarray(dist, dtype=np.float64).reshape(-1)
+        assert w.shape == es.shape
+    sph, poly, m = _obs_args(obs)
+    if not 0 <= j < m:
+        raise IndexError(f"obstacle {j} of a list of {m}")
+    sel = np.zeros(es.size, dtype=np.uint8)
+    L = lib()
+    _run_ranges(es.size, threads, lambda e0, e1: L.orc_sweep_edges_batch(
+        _at(es), _at(ee), _at(w), e0, e1, _at(nodes), d, _at(mask), sph, poly, m, int(j), int(remove), int(edge),
+        robot_radius, r_min, _at(sel)), per_thread=4096)
+    return np.flatnonzero(sel).astype(np.int32)
 
 
 def extend_candidates_batch(trees, Q, r: float, nodes, obs, robot_radius: float, rng: dict = None,

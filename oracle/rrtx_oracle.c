@@ -1630,6 +1630,50 @@ void orc_points_check_batch(const double *p, int64_t n, int d, const orc_sphere 
   }
 }
 
+/* explicitEdgeCheck(S, edge, ob) against obstacle k of the list alone: 0 / 1, or dubins_one's negative code */
+static int sweep_check_one(const orc_sphere *sph, const orc_polygon *poly, int k, int edge_kind, const double *a,
+                           const double *b, double robot_radius, double r_min, dub_scratch *sc) {
+  if (sph) return orc_edge_check_sphere(&sph[k], a, b, robot_radius);
+  if (edge_kind == ORC_EDGE_SIMPLE) return orc_edge_check_polygon(&poly[k], a, b, robot_radius);
+  double c, w, v;
+  char wd[4];
+  int tl, h, ok;
+  int32_t fh;
+  const int rc = dubins_one(a, b, r_min, robot_radius, &poly[k], 1, edge_kind == ORC_EDGE_DUBINS_TIME, 1, 0.0, 0.0, sc,
+                            &c, &w, &v, wd, &tl, &h, &fh, &ok);
+  return rc ? rc : h;
+}
+
+int orc_sweep_edges_batch(const int32_t *es, const int32_t *ee, const double *dist, int64_t e_begin, int64_t e_end,
+                          const double *nodes, int d, const uint8_t *in_conflict, const orc_sphere *sph,
+                          const orc_polygon *poly, int m, int j, int remove, int edge_kind, double robot_radius,
+                          double r_min, uint8_t *sel) {
+  if (e_begin == e_end) return 0;
+  if (j < 0 || j >= m || e_begin < 0 || e_begin > e_end || (sph && edge_kind != ORC_EDGE_SIMPLE) ||
+      (!sph && !poly) || edge_kind < ORC_EDGE_SIMPLE || edge_kind > ORC_EDGE_DUBINS_TIME || (remove && !dist))
+    return -2;
+  dub_scratch sc = {NULL, 0};
+  if (edge_kind != ORC_EDGE_SIMPLE && dub_scratch_init(&sc)) return -3;
+  int rc = 0;
+  for (int64_t e = e_begin; e < e_end; ++e) {
+    sel[e] = 0;
+    if (!in_conflict[es[e]] || (remove && !(dist[e] == INFINITY))) continue;
+    const double *a = nodes + (int64_t)d * es[e], *b = nodes + (int64_t)d * ee[e];
+    int h = sweep_check_one(sph, poly, j, edge_kind, a, b, robot_radius, r_min, &sc);
+    if (h < 0) { rc = h; break; }
+    for (int k = 0; remove && h && k < m; ++k) {
+      if (k == j || (sph ? sph[k].unused : poly[k].unused)) continue;
+      const int o = sweep_check_one(sph, poly, k, edge_kind, a, b, robot_radius, r_min, &sc);
+      if (o < 0) { rc = o; break; }
+      if (o) h = 0;
+    }
+    if (rc) break;
+    sel[e] = (uint8_t)h;
+  }
+  free(sc.rows);
+  return rc;
+}
+
 /* ------------------------------------------------------------------------ */
 /* CPU baseline: the per-sample inner loop of extend/findBestParent          */
 /* R/rrtqx.jl:926 (kdFindNearest), R/DRRT_Q.jl:2551 (kdFindWithinRange),     */

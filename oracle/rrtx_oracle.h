@@ -201,6 +201,21 @@ void orc_edges_check_batch(const double *p0, const double *p1, int64_t n, int d,
  * orc_point_check_polygons; unsafe and clearance optional */
 void orc_points_check_batch(const double *p, int64_t n, int d, const orc_sphere *sph, const orc_polygon *poly, int m,
                             double robot_radius, int quick, uint8_t *unsafe, double *clearance);
+/* The edge loops of addNewObstacle / removeObstacle (R/DRRT.jl:3127-3290, R/DRRT_Q.jl:3195-3290) over mirrored edges
+ * e in [e_begin, e_end): es[e] -> ee[e] (node rows of d in nodes).  in_conflict: one byte per node, the caller's
+ * findPointsInConflictWithObstacle / kdFindWithinRange list.  The list is sph where non-NULL (SimpleEdge only), else
+ * poly; j is the obstacle swept.  explicitEdgeCheck(S, edge, ob) against ONE obstacle k is orc_edge_check_sphere /
+ * orc_edge_check_polygon (edge_kind ORC_EDGE_SIMPLE), or the Dubins steering and two-stage check of
+ * orc_dubins_edges_batch with a list of one (ORC_EDGE_DUBINS; ORC_EDGE_DUBINS_TIME: with time, the piecewise time
+ * column).  Add (remove = 0): sel[e] = in_conflict[es[e]] and the check against j.  Remove: also dist[e] == Inf and
+ * no hit against any other obstacle k != j of the list that is in use (!unused), one call per obstacle.  sel is
+ * indexed by e.  Returns 0, -1 where the Dubins check has no branch (moving obstacle without time), -2 bad
+ * arguments, -3 out of memory. */
+enum { ORC_EDGE_SIMPLE = 0, ORC_EDGE_DUBINS = 1, ORC_EDGE_DUBINS_TIME = 2 };
+int orc_sweep_edges_batch(const int32_t *es, const int32_t *ee, const double *dist, int64_t e_begin, int64_t e_end,
+                          const double *nodes, int d, const uint8_t *in_conflict, const orc_sphere *sph,
+                          const orc_polygon *poly, int m, int j, int remove, int edge_kind, double robot_radius,
+                          double r_min, uint8_t *sel);
 /* the shared deterministic transcendentals of include/rrtx_detmath.h, element-wise (tests compare them with
  * libm here and with the device's build of the same header bit for bit).
  * op: 0 sin(x)  1 cos(x)  2 atan2(y, x)  3 acos(x);  returns 1 in the ORC_LIBM_TRIG build, else 0 */
@@ -242,6 +257,13 @@ void orc_graph_make_parent_of(orc_graph *g, int64_t new_parent, int64_t node, in
 void orc_graph_reduce_inconsistency(orc_graph *g, int64_t goal, int64_t root, double ball, double change_thresh);
 void orc_graph_block_edge(orc_graph *g, int64_t e);
 void orc_graph_propagate_descendants(orc_graph *g);
+/* Batched forms, plain loops over the functions above: orc_graph_add_edge for es[i] -> ee[i] with dist[i], i in
+ * [0, n), in order (returns the first id); lmc / tree cost / parent edge of every node, each output optional;
+ * orc_graph_block_edge for ids[i] in the order given. */
+int64_t orc_graph_add_edges(orc_graph *g, const int32_t *es, const int32_t *ee, const double *dist, int64_t n,
+                            int initial, int valid_move);
+void orc_graph_read(const orc_graph *g, double *lmc, double *tree_cost, int64_t *parent_edge);
+void orc_graph_block_edges(orc_graph *g, const int64_t *ids, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -106,12 +106,26 @@ int64_t orc_graph_add_edge(orc_graph *G, int64_t start, int64_t end, double dist
   return e;
 }
 
+int64_t orc_graph_add_edges(orc_graph *G, const int32_t *es, const int32_t *ee, const double *dist, int64_t n,
+                            int initial, int valid_move) {
+  const int64_t first = G->m;
+  for (int64_t i = 0; i < n; ++i) orc_graph_add_edge(G, es[i], ee[i], dist[i], initial, valid_move);
+  return first;
+}
+
 void orc_graph_set_node(orc_graph *G, int64_t v, double lmc, double tree_cost) { G->lmc[v] = lmc; G->g[v] = tree_cost; }
 void orc_graph_set_move_goal(orc_graph *G, int64_t v, int flag) { G->move_goal[v] = flag ? 1 : 0; }
 void orc_graph_set_edge_dist(orc_graph *G, int64_t e, double dist) { G->ed[e] = dist; }
 double orc_graph_lmc(const orc_graph *G, int64_t v) { return G->lmc[v]; }
 double orc_graph_tree_cost(const orc_graph *G, int64_t v) { return G->g[v]; }
 int64_t orc_graph_parent_edge(const orc_graph *G, int64_t v) { return G->parent_used[v] ? G->parent_edge[v] : -1; }
+void orc_graph_read(const orc_graph *G, double *lmc, double *tree_cost, int64_t *parent_edge) {
+  for (int64_t v = 0; v < G->n; ++v) {
+    if (lmc) lmc[v] = orc_graph_lmc(G, v);
+    if (tree_cost) tree_cost[v] = orc_graph_tree_cost(G, v);
+    if (parent_edge) parent_edge[v] = orc_graph_parent_edge(G, v);
+  }
+}
 int64_t orc_graph_queue_length(const orc_graph *G) { return G->heap_last; }
 int64_t orc_graph_n_edges(const orc_graph *G) { return G->m; }
 
@@ -300,6 +314,10 @@ void orc_graph_block_edge(orc_graph *G, int64_t e) {
     G->parent_used[v] = 0;
     orc_graph_verify_in_os(G, v);
   }
+}
+
+void orc_graph_block_edges(orc_graph *G, const int64_t *ids, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) orc_graph_block_edge(G, ids[i]);
 }
 
 /* propogateDescendants, R/DRRT_Q.jl:2724-2817 (the robot's move target is the caller's business) */

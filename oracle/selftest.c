@@ -166,6 +166,59 @@ int main(void) {
     bad += orc_knearest_batch(wt, 3, qs4, NQ, 3, idx, key, kcnt) != -1;
     orc_kd_destroy(wt);
   }
+  {
+    /* batched graph forms and the sweep edge loop: every edge kind, add and remove, the argument checks */
+    enum { GN = 400, GE = 2400 };
+    static int32_t ges[GE], gee[GE];
+    static double gw[GE], glmc[GN + 1], gtc[GN + 1], n3[3 * GN], n4[4 * GN], n4t[4 * GN];
+    static int64_t gpar[GN + 1], gblk[40];
+    static uint8_t mask[GN], sel[GE];
+    for (int e = 0; e < GE; ++e) {
+      ges[e] = e % GN; gee[e] = (int32_t)((e % GN + 1 + (int)(20 * frand(&seed))) % GN);
+      gw[e] = 0.1 + frand(&seed);
+    }
+    orc_graph *gg = orc_graph_create(GN + 1);
+    bad += orc_graph_add_edges(gg, ges, gee, gw, 0, 0, 1) != 0;
+    bad += orc_graph_add_edges(gg, ges, gee, gw, GE / 2, 0, 1) != 0;
+    bad += orc_graph_add_edges(gg, ges + GE / 2, gee + GE / 2, gw + GE / 2, GE - GE / 2, 1, 1) != GE / 2;
+    for (int v = 0; v <= GN; ++v) orc_graph_set_node(gg, v, INFINITY, INFINITY);
+    orc_graph_set_node(gg, 0, 0.0, INFINITY);
+    orc_graph_verify_in_queue(gg, 0);
+    orc_graph_reduce_inconsistency(gg, GN, 0, INFINITY, 0.0);
+    orc_graph_read(gg, NULL, NULL, NULL);
+    orc_graph_read(gg, glmc, gtc, gpar);
+    for (int v = 0; v < GN; ++v) bad += glmc[v] != orc_graph_lmc(gg, v) || gpar[v] != orc_graph_parent_edge(gg, v);
+    for (int k = 0; k < 40; ++k) gblk[k] = (k % 2) && gpar[k + 1] >= 0 ? gpar[k + 1] : (int64_t)(GE * frand(&seed));
+    orc_graph_block_edges(gg, gblk, 0);
+    orc_graph_block_edges(gg, gblk, 40);
+    orc_graph_propagate_descendants(gg);
+    orc_graph_reduce_inconsistency(gg, GN, 0, INFINITY, 0.0);
+    orc_graph_read(gg, glmc, NULL, NULL);
+    orc_graph_destroy(gg);
+    for (int v = 0; v < GN; ++v) {
+      n3[3 * v] = 10 * frand(&seed); n3[3 * v + 1] = 10 * frand(&seed); n3[3 * v + 2] = 0;
+      n4[4 * v] = n3[3 * v]; n4[4 * v + 1] = n3[3 * v + 1]; n4[4 * v + 2] = 0; n4[4 * v + 3] = 6.28 * frand(&seed);
+      n4t[4 * v] = n4[4 * v]; n4t[4 * v + 1] = n4[4 * v + 1]; n4t[4 * v + 2] = 20 * frand(&seed); n4t[4 * v + 3] = n4[4 * v + 3];
+      mask[v] = (uint8_t)(frand(&seed) < 0.6);
+    }
+    for (int e = 0; e < GE; ++e) gw[e] = (e % 3) ? INFINITY : 1.0;
+    orc_polygon two[2] = {pg, pg};
+    two[1].verts = sq; two[1].cx += 0.25;
+    orc_polygon tmv[2] = {mv, mv};
+    tmv[1].unused = 1;
+    for (int rm = 0; rm < 2; ++rm) {
+      bad += orc_sweep_edges_batch(ges, gee, gw, 5, GE, n3, 3, mask, sp, NULL, 4, 1, rm, ORC_EDGE_SIMPLE, 0.5, 0, sel) != 0;
+      bad += orc_sweep_edges_batch(ges, gee, gw, 0, GE, n3, 3, mask, NULL, two, 2, 0, rm, ORC_EDGE_SIMPLE, 0.5, 0, sel) != 0;
+      bad += orc_sweep_edges_batch(ges, gee, gw, 0, 300, n4, 4, mask, NULL, two, 2, 1, rm, ORC_EDGE_DUBINS, 0.5, 1.0, sel) != 0;
+      bad += orc_sweep_edges_batch(ges, gee, gw, 0, 300, n4t, 4, mask, NULL, tmv, 2, 0, rm, ORC_EDGE_DUBINS_TIME, 0.5, 1.0,
+                                   sel) != 0;
+    }
+    bad += orc_sweep_edges_batch(ges, gee, gw, 0, 300, n4, 4, mask, NULL, tmv, 2, 0, 0, ORC_EDGE_DUBINS, 0.5, 1.0, sel) != -1;
+    bad += orc_sweep_edges_batch(ges, gee, gw, 0, 3, n3, 3, mask, sp, NULL, 4, 4, 0, ORC_EDGE_SIMPLE, 0.5, 0, sel) != -2;
+    bad += orc_sweep_edges_batch(ges, gee, gw, 0, 3, n4, 4, mask, sp, NULL, 4, 0, 0, ORC_EDGE_DUBINS, 0.5, 1.0, sel) != -2;
+    bad += orc_sweep_edges_batch(ges, gee, NULL, 0, 3, n3, 3, mask, sp, NULL, 4, 0, 1, ORC_EDGE_SIMPLE, 0.5, 0, sel) != -2;
+    bad += orc_sweep_edges_batch(ges, gee, NULL, 7, 7, n3, 3, mask, sp, NULL, 4, 0, 1, ORC_EDGE_SIMPLE, 0.5, 0, sel) != 0;
+  }
   printf(bad ? "selftest FAILED (%d)\n" : "selftest ok\n", bad);
   return bad != 0;
 }
