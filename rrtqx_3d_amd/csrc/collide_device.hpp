@@ -1,5 +1,5 @@
-// collide_device.hpp -- the exact sphere edge test as a device function, shared by
-// kernels_collide.hip (edge kernels) and kernels_sweep.hip (obstacle sweeps).
+// collide_device.hpp -- the exact sphere edge test and the 2-D segment distances as device functions, shared by
+// kernels_collide.hip (edge kernels), kernels_dubins.hip and kernels_sweep.hip (obstacle sweeps).
 #pragma once
 #include "exact_math.hpp"
 #include "rrtx_internal.hpp"
@@ -19,6 +19,57 @@ __device__ __forceinline__ bool edge_hits_sphere(double p0x, double p0y, double 
   double s = sq3(ob.cx, ob.cy, ob.cz, qx, qy, qz);
   // distS > robotRadius + radius  <=>  s >= thr ; collision unless that holds
   return !(s >= ob.thr);
+}
+
+// ---- 2-D segment arithmetic of the polygon checks (kernels_collide.hip, kernels_dubins.hip) ----
+// distanceSqrdPointToSegment, R/DRRT.jl:1060-1083
+__device__ __forceinline__ double dist_sqrd_point_to_segment(double px, double py, double ax, double ay,
+                                                             double bx, double by) {
+  double vx = px - ax, vy = py - ay;
+  double ux = bx - ax, uy = by - ay;
+  double det = vx * ux + vy * uy;
+  if (det <= 0) {
+    return vx * vx + vy * vy;
+  } else {
+    double len = ux * ux + uy * uy;
+    if (det >= len) {
+      double ex = bx - px, ey = by - py;
+      return ex * ex + ey * ey;
+    } else {
+      double cr = ux * vy - uy * vx;
+      return (cr * cr) / len;
+    }
+  }
+}
+
+// segmentDistSqrd, R/DRRT.jl:1144-1202
+__device__ double segment_dist_sqrd(double pax, double pay, double pbx, double pby, double qax, double qay,
+                                    double qbx, double qby) {
+  bool possible = true;
+  if (fabs(pbx - pax) < .000001) {
+    if ((qax >= pax && qbx >= pax) || (qax <= pax && qbx <= pax)) possible = false;
+  } else {
+    double m = (pby - pay) / (pbx - pax);
+    double diffA = (m * (qax - pax) + pay) - qay;
+    double diffB = (m * (qbx - pax) + pay) - qby;
+    if ((diffA > 0.0 && diffB > 0.0) || (diffA < 0.0 && diffB < 0.0)) possible = false;
+  }
+  if (possible) {
+    if (fabs(qbx - qax) < .000001) {
+      if ((pax >= qax && pbx >= qax) || (pax <= qax && pbx <= qax)) possible = false;
+    } else {
+      double m = (qby - qay) / (qbx - qax);
+      double diffA = (m * (pax - qax) + qay) - pay;
+      double diffB = (m * (pbx - qax) + qay) - pby;
+      if ((diffA > 0.0 && diffB > 0.0) || (diffA < 0.0 && diffB < 0.0)) possible = false;
+    }
+  }
+  if (possible) return 0.0;
+  double r = dist_sqrd_point_to_segment(pax, pay, qax, qay, qbx, qby);
+  r = jl_min(r, dist_sqrd_point_to_segment(pbx, pby, qax, qay, qbx, qby));
+  r = jl_min(r, dist_sqrd_point_to_segment(qax, qay, pax, pay, pbx, pby));
+  r = jl_min(r, dist_sqrd_point_to_segment(qbx, qby, pax, pay, pbx, pby));
+  return r;
 }
 
 // ---- polygons moving in time (kinds 6 and 7) ------------------------------------------------

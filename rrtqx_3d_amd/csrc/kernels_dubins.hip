@@ -431,50 +431,10 @@ __global__ __launch_bounds__(256) void detmath_eval_kernel(int op, const double 
   out[i] = r;
 }
 
-// polygon helpers live in kernels_collide.hip; the Dubins check needs the same
-// arithmetic, restated here to keep the translation units independent.
-__device__ __forceinline__ double dspts(double px, double py, double ax, double ay, double bx, double by) {
-  double vx = px - ax, vy = py - ay;
-  double ux = bx - ax, uy = by - ay;
-  double det = vx * ux + vy * uy;
-  if (det <= 0) return vx * vx + vy * vy;
-  double len = ux * ux + uy * uy;
-  if (det >= len) { double ex = bx - px, ey = by - py; return ex * ex + ey * ey; }
-  double cr = ux * vy - uy * vx;
-  return (cr * cr) / len;
-}
-__device__ double seg_dist_sqrd(double pax, double pay, double pbx, double pby, double qax, double qay,
-                                double qbx, double qby) {
-  bool possible = true;
-  if (fabs(pbx - pax) < .000001) {
-    if ((qax >= pax && qbx >= pax) || (qax <= pax && qbx <= pax)) possible = false;
-  } else {
-    double m = (pby - pay) / (pbx - pax);
-    double diffA = (m * (qax - pax) + pay) - qay;
-    double diffB = (m * (qbx - pax) + pay) - qby;
-    if ((diffA > 0.0 && diffB > 0.0) || (diffA < 0.0 && diffB < 0.0)) possible = false;
-  }
-  if (possible) {
-    if (fabs(qbx - qax) < .000001) {
-      if ((pax >= qax && pbx >= qax) || (pax <= qax && pbx <= qax)) possible = false;
-    } else {
-      double m = (qby - qay) / (qbx - qax);
-      double diffA = (m * (pax - qax) + qay) - pay;
-      double diffB = (m * (pbx - qax) + qay) - pby;
-      if ((diffA > 0.0 && diffB > 0.0) || (diffA < 0.0 && diffB < 0.0)) possible = false;
-    }
-  }
-  if (possible) return 0.0;
-  double r = dspts(pax, pay, qax, qay, qbx, qby);
-  r = jl_min(r, dspts(pbx, pby, qax, qay, qbx, qby));
-  r = jl_min(r, dspts(qax, qay, pax, pay, pbx, pby));
-  r = jl_min(r, dspts(qbx, qby, pax, pay, pbx, pby));
-  return r;
-}
 // explicitEdgeCheck2D (R/DRRT.jl:1523-1578) in two steps: the bounding-circle test (:1536-1539) ...
 __device__ __forceinline__ bool seg_outside_circle(double ax, double ay, double bx, double by, double robot_radius,
                                                    const double *__restrict__ meta, int j) {
-  const double dsq = dspts(meta[4 * j + 0], meta[4 * j + 1], ax, ay, bx, by);
+  const double dsq = dist_sqrd_point_to_segment(meta[4 * j + 0], meta[4 * j + 1], ax, ay, bx, by);
   const double rr = robot_radius + meta[4 * j + 2];
   return dsq > rr * rr;
 }
@@ -500,7 +460,7 @@ __device__ bool seg_hits_polygon_past_circle(double ax, double ay, double bx, do
     const double rr2 = robot_radius * robot_radius;
     for (int v = b; v < e; ++v) {
       double Bx = vxy[2 * v], By = vxy[2 * v + 1];
-      if (seg_dist_sqrd(ax, ay, bx, by, Ax, Ay, Bx, By) < rr2) return true;
+      if (segment_dist_sqrd(ax, ay, bx, by, Ax, Ay, Bx, By) < rr2) return true;
       Ax = Bx; Ay = By;
     }
   }
@@ -663,7 +623,7 @@ __device__ bool wave_dubins_collides(WaveDubinsT<TIME> &w, bool valid, const Ste
           const int j = j0 + b;
           const int vb0 = off[j], P = off[j + 1] - vb0;
           const int va = vb0 + (sg == 0 ? P - 1 : sg - 1), vb = vb0 + sg;
-          if (seg_dist_sqrd(w.chord[0][e], w.chord[1][e], w.chord[2][e], w.chord[3][e], vxy[2 * va], vxy[2 * va + 1],
+          if (segment_dist_sqrd(w.chord[0][e], w.chord[1][e], w.chord[2][e], w.chord[3][e], vxy[2 * va], vxy[2 * va + 1],
                             vxy[2 * vb], vxy[2 * vb + 1]) < rr2)
             atomicOr(&w.mask[e], 1ull << b);
         }
@@ -789,7 +749,7 @@ __device__ bool wave_dubins_collides(WaveDubinsT<TIME> &w, bool valid, const Ste
                 double Ax = vxy[2 * (ve - 1)], Ay = vxy[2 * (ve - 1) + 1];
                 for (int v = vb; v < ve; ++v) {
                   const double Bx = vxy[2 * v], By = vxy[2 * v + 1];
-                  d2min = jl_min(d2min, dspts(pc.cx, pc.cy, Ax, Ay, Bx, By));
+                  d2min = jl_min(d2min, dist_sqrd_point_to_segment(pc.cx, pc.cy, Ax, Ay, Bx, By));
                   Ax = Bx; Ay = By;
                 }
               }

@@ -525,13 +525,11 @@ int launch_nn_finish(rrtx_ctx *ctx, const FinishLaunch &f) {
   // (measured at C3, lists of ~1400: 1.0 ms in that build against 1.7 ms in the 8-waves-per-SIMD build, whose
   //  64 registers the sort network spills -- so any call whose capacity allows for lists in the hundreds takes it)
   const bool huge = f.out_cap / (f.nq > 0 ? f.nq : 1) > 512;
-  if (D == 4) {
-    if (huge) hipLaunchKernelGGL((nn_finish_kernel<4, kHugeSort>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((nn_finish_kernel<4, kBigSort>), grid, block, 0, ctx->stream, a);
-  } else {
-    if (huge) hipLaunchKernelGGL((nn_finish_kernel<3, kHugeSort>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((nn_finish_kernel<3, kBigSort>), grid, block, 0, ctx->stream, a);
-  }
+  for_dim(D, [&](auto dc) {
+    constexpr int DD = decltype(dc)::value;
+    if (huge) hipLaunchKernelGGL((nn_finish_kernel<DD, kHugeSort>), grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL((nn_finish_kernel<DD, kBigSort>), grid, block, 0, ctx->stream, a);
+  });
   RRTX_HIP(ctx, hipGetLastError());
   return RRTX_OK;
 }

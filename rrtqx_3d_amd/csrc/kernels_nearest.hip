@@ -334,16 +334,13 @@ static int launch_nn_nearest_exact(rrtx_ctx *ctx, const double *q_dev, int nq, i
   hipStream_t st = ctx->stream;
   span_begin(ctx, KF_NN_NEAREST);
   dim3 grid(qblocks, n_seg), block(256);
-  if (ctx->dim == 4)
-    hipLaunchKernelGGL(nn_nearest_partial_kernel<4>, grid, block, 0, st, ctx->nodes[0], ctx->nodes[1],
-                       ctx->nodes[2], ctx->nodes[3], n_nodes, q_dev, nq, ctx->n_wraps, ctx->wrap_dim[0],
+  for_dim(ctx->dim, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    hipLaunchKernelGGL(nn_nearest_partial_kernel<D>, grid, block, 0, st, ctx->nodes[0], ctx->nodes[1],
+                       ctx->nodes[2], ctx->nodes[D == 4 ? 3 : 2], n_nodes, q_dev, nq, ctx->n_wraps, ctx->wrap_dim[0],
                        ctx->wrap_dim[1], ctx->wrap_dim[2], ctx->wrap_period[0], ctx->wrap_period[1],
                        ctx->wrap_period[2], seg_len, pd2, pidx);
-  else
-    hipLaunchKernelGGL(nn_nearest_partial_kernel<3>, grid, block, 0, st, ctx->nodes[0], ctx->nodes[1],
-                       ctx->nodes[2], ctx->nodes[2], n_nodes, q_dev, nq, ctx->n_wraps, ctx->wrap_dim[0],
-                       ctx->wrap_dim[1], ctx->wrap_dim[2], ctx->wrap_period[0], ctx->wrap_period[1],
-                       ctx->wrap_period[2], seg_len, pd2, pidx);
+  });
   hipLaunchKernelGGL(nn_nearest_reduce_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, pd2, pidx, nq, n_seg,
                      idx_dev, dist_dev);
   span_end(ctx);
@@ -395,39 +392,21 @@ static int launch_nn_nearest_screened(rrtx_ctx *ctx, const double *q_dev, int nq
     dim3 grid((nq + 255) / 256), block(256);
     dim3 pgrid((unsigned)((n_copies_max + kQPI + 255) / 256));
     dim3 sgrid((unsigned)cblocks * (unsigned)n_seg);
-    if (D == 4) {
-      hipLaunchKernelGGL(nn_pack_kernel<4>, grid, block, 0, st, q_dev, nq, (const double *)nullptr,
-                         (const double *)nullptr, inf, nan, ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1],
-                         ctx->wrap_dim[2], ctx->wrap_period[0], ctx->wrap_period[1], ctx->wrap_period[2],
-                         ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
-                         ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec4>(), ctx->ws_copy_meta.as<int2>(), sc,
-                         (const unsigned long long *)nullptr, 1, 1, (int *)nullptr, (int2 *)nullptr, PackFused{},
+    const unsigned long long *absmax = ctx->d_absmax.as<unsigned long long>();
+    for_dim(D, [&](auto dc) {
+      constexpr int DD = decltype(dc)::value;
+      constexpr int wi = DD == 4 ? 3 : 2;
+      typename QRecT<DD>::type *copies = ctx->ws_copies.as<typename QRecT<DD>::type>();
+      typename QRecFT<DD>::type *copies_f = ctx->ws_copies_f.as<typename QRecFT<DD>::type>();
+      launch_nn_pack<DD>(ctx, q_dev, nq, nullptr, nullptr, inf, nan, sc, nullptr, 1, 1, nullptr, nullptr, PackFused{},
                          ConfirmArgs{}, QSlots{});
-      hipLaunchKernelGGL(nn_filter_prep_kernel<4>, pgrid, block, 0, st, ctx->ws_copies.as<QRec4>(), sc,
-                         ctx->d_absmax.as<unsigned long long>(), (int)n_copies_max, ctx->origin[0], ctx->origin[1],
-                         ctx->origin[2], ctx->origin[3], ctx->ws_copies_f.as<QRecF4>());
-      hipLaunchKernelGGL(nn_nearest_f32_kernel<4>, sgrid, block, 0, st, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2],
-                         ctx->nodes[3], ctx->nodes_f[0], ctx->nodes_f[1], ctx->nodes_f[2], ctx->nodes_f[3],
-                         ctx->nodes_pp, n_nodes, ctx->ws_copies.as<QRec4>(), ctx->ws_copies_f.as<QRecF4>(),
-                         ctx->ws_copy_meta.as<int2>(), ctx->d_absmax.as<unsigned long long>(), n_seg, seg_len,
+      hipLaunchKernelGGL(nn_filter_prep_kernel<DD>, pgrid, block, 0, st, copies, sc, absmax, (int)n_copies_max,
+                         ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3], copies_f);
+      hipLaunchKernelGGL(nn_nearest_f32_kernel<DD>, sgrid, block, 0, st, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2],
+                         ctx->nodes[wi], ctx->nodes_f[0], ctx->nodes_f[1], ctx->nodes_f[2], ctx->nodes_f[wi],
+                         ctx->nodes_pp, n_nodes, copies, copies_f, ctx->ws_copy_meta.as<int2>(), absmax, n_seg, seg_len,
                          ctx->ws_recs.as<HitRec>(), rec_cap, sc, best_bits, redo);
-    } else {
-      hipLaunchKernelGGL(nn_pack_kernel<3>, grid, block, 0, st, q_dev, nq, (const double *)nullptr,
-                         (const double *)nullptr, inf, nan, ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1],
-                         ctx->wrap_dim[2], ctx->wrap_period[0], ctx->wrap_period[1], ctx->wrap_period[2],
-                         ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
-                         ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec3>(), ctx->ws_copy_meta.as<int2>(), sc,
-                         (const unsigned long long *)nullptr, 1, 1, (int *)nullptr, (int2 *)nullptr, PackFused{},
-                         ConfirmArgs{}, QSlots{});
-      hipLaunchKernelGGL(nn_filter_prep_kernel<3>, pgrid, block, 0, st, ctx->ws_copies.as<QRec3>(), sc,
-                         ctx->d_absmax.as<unsigned long long>(), (int)n_copies_max, ctx->origin[0], ctx->origin[1],
-                         ctx->origin[2], ctx->origin[3], ctx->ws_copies_f.as<QRecF3>());
-      hipLaunchKernelGGL(nn_nearest_f32_kernel<3>, sgrid, block, 0, st, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2],
-                         ctx->nodes[2], ctx->nodes_f[0], ctx->nodes_f[1], ctx->nodes_f[2], ctx->nodes_f[2],
-                         ctx->nodes_pp, n_nodes, ctx->ws_copies.as<QRec3>(), ctx->ws_copies_f.as<QRecF3>(),
-                         ctx->ws_copy_meta.as<int2>(), ctx->d_absmax.as<unsigned long long>(), n_seg, seg_len,
-                         ctx->ws_recs.as<HitRec>(), rec_cap, sc, best_bits, redo);
-    }
+    });
     hipLaunchKernelGGL(nn_nearest_tie_kernel, dim3(1024), dim3(256), 0, st, ctx->ws_recs.as<HitRec>(), rec_cap, sc,
                        best_bits, best_idx);
     hipLaunchKernelGGL(nn_nearest_out_kernel, grid, block, 0, st, best_bits, best_idx, nq, idx_dev, dist_dev);
@@ -439,14 +418,11 @@ static int launch_nn_nearest_screened(rrtx_ctx *ctx, const double *q_dev, int nq
     ni.n_nodes = n_nodes;
     ni.n_chunks = (n_nodes + kSlabChunk - 1) / kSlabChunk;
     const dim3 fgrid((unsigned)(nq < 2048 ? nq : 2048));
-    if (D == 4)
-      hipLaunchKernelGGL(nn_nearest_fixup_kernel<4>, fgrid, dim3(kFixThreads), 0, st, sc, rec_cap, redo, q_dev, nq,
-                         ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2], ctx->wrap_period[0],
-                         ctx->wrap_period[1], ctx->wrap_period[2], ni, idx_dev, dist_dev);
-    else
-      hipLaunchKernelGGL(nn_nearest_fixup_kernel<3>, fgrid, dim3(kFixThreads), 0, st, sc, rec_cap, redo, q_dev, nq,
-                         ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2], ctx->wrap_period[0],
-                         ctx->wrap_period[1], ctx->wrap_period[2], ni, idx_dev, dist_dev);
+    for_dim(D, [&](auto dc) {
+      hipLaunchKernelGGL(nn_nearest_fixup_kernel<decltype(dc)::value>, fgrid, dim3(kFixThreads), 0, st, sc, rec_cap,
+                         redo, q_dev, nq, ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2],
+                         ctx->wrap_period[0], ctx->wrap_period[1], ctx->wrap_period[2], ni, idx_dev, dist_dev);
+    });
   }
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
@@ -688,8 +664,10 @@ static void knearest_exhaustive(rrtx_ctx *ctx, const double *q_dev, int n_blocks
   hipLaunchKernelGGL((nn_knearest_kernel<D, NT>), dim3(n_blocks), dim3(NT), 0, ctx->stream, ctx->nodes[0],      \
                      ctx->nodes[1], ctx->nodes[2], nw, n_nodes, q_dev, kk, stride, idx_dev, dist_dev, count_dev, \
                      qlist, n_list)
-  if (ctx->dim == 4) { if (qlist) RRTX_KNN_LAUNCH(4, 1024); else RRTX_KNN_LAUNCH(4, 256); }
-  else { if (qlist) RRTX_KNN_LAUNCH(3, 1024); else RRTX_KNN_LAUNCH(3, 256); }
+  for_dim(ctx->dim, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    if (qlist) RRTX_KNN_LAUNCH(D, 1024); else RRTX_KNN_LAUNCH(D, 256);
+  });
 #undef RRTX_KNN_LAUNCH
 }
 
@@ -772,14 +750,12 @@ int launch_nn_knearest(rrtx_ctx *ctx, const double *q_dev, int nq, int k, int32_
                           count_dev + first, nullptr, nullptr);
     } else {
       RRTX_HIP(ctx, hipMemsetAsync(n_fb, 0, sizeof(int), st));
-      if (ctx->dim == 4)
-        hipLaunchKernelGGL(nn_knearest_lists_kernel<4>, dim3(nb), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
-                           ctx->nodes[2], ctx->nodes[3], q_dev, first, off, ctx->ws_knn_idx.as<int32_t>(), kk, stride,
-                           idx_dev, dist_dev, count_dev, fb_list, n_fb);
-      else
-        hipLaunchKernelGGL(nn_knearest_lists_kernel<3>, dim3(nb), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
-                           ctx->nodes[2], ctx->nodes[2], q_dev, first, off, ctx->ws_knn_idx.as<int32_t>(), kk, stride,
-                           idx_dev, dist_dev, count_dev, fb_list, n_fb);
+      for_dim(ctx->dim, [&](auto dc) {
+        constexpr int D = decltype(dc)::value;
+        hipLaunchKernelGGL(nn_knearest_lists_kernel<D>, dim3(nb), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
+                           ctx->nodes[2], ctx->nodes[D == 4 ? 3 : 2], q_dev, first, off, ctx->ws_knn_idx.as<int32_t>(),
+                           kk, stride, idx_dev, dist_dev, count_dev, fb_list, n_fb);
+      });
       knearest_exhaustive(ctx, q_dev, nb, kk, stride, idx_dev, dist_dev, count_dev, fb_list, n_fb);
     }
     span_end(ctx);

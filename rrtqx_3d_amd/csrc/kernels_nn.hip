@@ -5,7 +5,9 @@
 // nn_device.hpp.  gfx950 only: 64-lane waves, scalar (SMEM) query stream, packed
 // fp32 screen, exact fp64 confirmation.
 //
-// Radius search pipeline (all on ctx->stream, no host sync):
+// Radius search pipeline (all on ctx->stream, no host sync).  launch_nn_radius plans the call
+// (plan_radius: route and every size, arithmetic only), sizes the workspaces (radius_workspaces), builds the
+// kernels' arguments (radius_args) and then runs one function per stage:
 //   pack    : queries -> slot table (query + ghosts), copy records, grid bucket and rank of
 //             every copy, the root rule (<= instead of <, R/kdTree_general.jl:896 vs :830),
 //             per-call state
@@ -1247,6 +1249,301 @@ __global__ void nn_scatter_kernel(const HitRec *__restrict__ recs, long long cap
 }  // namespace
 
 // ------------------------------------------------------------- launchers ----
+namespace {
+
+static_assert(kMaxQBuckets == 64 * 64 && kMaxQBuckets == 16 * 16 * 16, "g2 stops at 64, g3 at 16: n_buckets fits");
+static_assert(kTbSlack >= 0 && kEvSlack >= 0, "a drained slice holds the worst case of the next screen step");
+static_assert(kTileQFilter % kQPI == 0 && kTileQExact % kQPI == 0 && 128 % kQPI == 0, "kQPI copy records per read");
+
+struct RadiusPlan {
+  bool use_filter;      // fp32 screen + exact confirmation (RRTX_OPT_NN_FILTER); off: exact fp64 scan of every pair
+  bool use_cull;        // slab culling: on for large trees (RRTX_OPT_NN_CULL) unless the screen is off
+  bool slot_route;      // culled, no ghosts: the pack pass fills the bucket-slot table and the tile kernel places the
+                        // copies itself (three launches); with ghosts, or experiment switch 4: the place pass
+  bool fuse;            // the tile kernel carries the extend() work (sphere list): culled 3-D search without ghosts
+  bool prescatter;      // offsets + scatter launched in front of the finish kernel: very large batches, or the
+                        // previous call left many records on the overflow list
+  int nq, n_nodes, n_chunks;   // (chunks of kSlabChunk positions of the slab index)
+  int n_slots;          // copies per query: the query and its ghosts
+  size_t n_copies_max;  // nq * n_slots: what every per-copy buffer is sized by
+  long long rec_cap;    // entries the caller made room for (>= 1) = records of the overflow list
+  // copy tiles x node segments of the brute-force scans (the culled search: tiles of kTileB in bucket order)
+  int tile_q, n_tiles;  // copies per tile: a multiple of kQPI, screened <= 128 (bounds slice_cap)
+  int n_seg, seg_len;   // segment index = blockIdx % 8 class = XCD; seg_len a multiple of the chunk
+  // query buckets of the culled search (query_grid, nn_device.hpp)
+  int g2, g3;           // side of the square (x, y) grid, ~16 copies per bucket, <= 64; of the cubic grid, ~4, <= 16
+  int n_buckets;        // max(g2^2, g3^3) <= kMaxQBuckets: counters of ws_qhist in use (it holds kMaxQBuckets + 1)
+  // bucket-slot table of the slot route (QSlots, TilePlace)
+  int capb;             // slots per bucket: twice the average over the coarser grid with headroom, 8 .. 128
+  int spill_base;       // n_buckets * capb: start of the spill list (ranks >= capb)
+  int n_tab;            // n_buckets * capb + n_copies_max records in ws_qslot: room even if every copy spills
+  int bcap;             // records per query bucket: bkt_mult x the average the caller made room for, a multiple of 8
+                        // in 8 .. 2^24, at most 16 GiB of buckets in all
+  // scan launch
+  int n_parts;          // culled: workgroups sharing a tile's units (few tiles), 1 .. 64
+  unsigned scan_grid;   // workgroups: culled min(tiles * n_parts, 4096); screened min(n_tiles * n_seg,
+                        // opt_scan_blocks in eights); exact n_tiles * n_seg
+  int n_slices;         // entry slices = waves of the scan grid (exact scan: none)
+  int slice_cap;        // entries per slice.  Culled: 64 * kTileB + kTbSlack, a wave drains its slice when
+                        // wn + 64 * kTileB > slice_cap; screened: 64 * tile_q + kEvSlack, drained likewise
+};
+
+// prev_overflow: what the previous call left in the mailbox; want_extend: the caller offers the extend() work
+RadiusPlan plan_radius(const rrtx_ctx *ctx, int nq, int64_t cap, unsigned prev_overflow, bool want_extend) {
+  RadiusPlan p{};
+  const TuneBits tune = tune_bits(ctx);
+  p.nq = nq; p.n_nodes = (int)ctx->n_nodes; p.n_slots = 1 << ctx->n_wraps;
+  p.n_copies_max = (size_t)nq * p.n_slots;
+  p.rec_cap = (long long)(cap > 0 ? cap : 1);
+  p.n_chunks = (p.n_nodes + kSlabChunk - 1) / kSlabChunk;
+  p.use_filter = ctx->opt_nn_filter != 0;
+  p.use_cull = p.use_filter && (ctx->opt_nn_cull == 2 || (ctx->opt_nn_cull == 1 && p.n_nodes >= 8192));
+  p.slot_route = p.use_cull && p.n_slots == 1 && !tune.place_pass;
+  p.fuse = want_extend && p.use_cull && ctx->dim == 3 && p.n_slots == 1;
+  p.prescatter = nq > 65536 || prev_overflow > 8192u;
+
+  p.tile_q = p.use_filter ? kTileQFilter : kTileQExact;
+  if (ctx->opt_tile_q > 0) p.tile_q = (ctx->opt_tile_q + kQPI - 1) / kQPI * kQPI;
+  if (p.use_filter && p.tile_q > 128) p.tile_q = 128;   // bounds the worst case of one chunk (64 tile_q entries)
+  p.n_tiles = (int)((p.n_copies_max + p.tile_q - 1) / p.tile_q);
+
+  p.g2 = 1; p.g3 = 1; p.n_buckets = 1; p.n_parts = 1;
+  if (p.use_cull) {
+    while (p.g2 * p.g2 < (long long)(p.n_copies_max / 16) && p.g2 * p.g2 < kMaxQBuckets) p.g2 *= 2;
+    p.g3 = (int)std::lround(std::cbrt((double)p.n_copies_max / 4.0));
+    if (p.g3 < 1) p.g3 = 1;
+    if (tune.g3_side) p.g3 = tune.g3_side;
+    if (p.g3 > 16) p.g3 = 16;
+    if (tune.xy_order) p.g3 = 1;
+    p.n_buckets = std::max(p.g2 * p.g2, p.g3 * p.g3 * p.g3);
+  }
+  if (p.slot_route) {
+    const long long min_b = std::max(1ll, std::min((long long)p.g2 * p.g2, (long long)p.g3 * p.g3 * p.g3));
+    const long long avg = ((long long)p.n_copies_max + min_b - 1) / min_b;
+    p.capb = (int)std::min(128ll, std::max(8ll, (2 * avg + 8 + 3) / 4 * 4));
+    p.spill_base = p.n_buckets * p.capb;
+    p.n_tab = p.spill_base + (int)p.n_copies_max;
+  }
+
+  long long bcap = (p.rec_cap + nq - 1) / nq * ctx->bkt_mult;
+  while (bcap > 16 && bcap * nq > (1ll << 30)) bcap /= 2;   // (records of 16 bytes: 16 GiB; there are 288)
+  bcap = (bcap + 7) / 8 * 8;
+  p.bcap = (int)std::min(std::max(bcap, 8ll), 1ll << 24);
+
+  const int chunk = p.use_filter ? kChunkF : kChunk;
+  const int wg_nodes = (kScanThreads / 64) * chunk;  // nodes one workgroup covers per pass
+  const int max_seg = (p.n_nodes + wg_nodes - 1) / wg_nodes;
+  const int want_seg = ((p.use_filter ? ctx->opt_scan_items : 4096) + p.n_tiles - 1) / p.n_tiles;
+  p.n_seg = std::max(1, std::min(want_seg, max_seg));
+  if (p.n_seg >= 8) p.n_seg = p.n_seg / 8 * 8;
+  p.seg_len = round_up((p.n_nodes + p.n_seg - 1) / p.n_seg, chunk);
+  p.n_seg = (p.n_nodes + p.seg_len - 1) / p.seg_len;
+  p.scan_grid = (unsigned)p.n_tiles * (unsigned)p.n_seg;
+  if (p.use_cull) {
+    // one workgroup per (tile, part): few tiles share their chunks among parts, many are walked by a bounded grid
+    const int n_tiles_b = (int)((p.n_copies_max + kTileB - 1) / kTileB);
+    p.n_parts = std::min(64, (1024 + n_tiles_b - 1) / n_tiles_b);
+    p.scan_grid = (unsigned)std::min(4096ll, (long long)n_tiles_b * p.n_parts);   // (capped: n_parts == 1)
+    p.slice_cap = 64 * kTileB + kTbSlack;
+  } else if (p.use_filter) {              // persistent grid striding over the work
+    const unsigned pg = std::max(8u, (unsigned)ctx->opt_scan_blocks / 8u * 8u);
+    p.scan_grid = std::min(p.scan_grid, pg);
+    p.slice_cap = 64 * p.tile_q + kEvSlack;
+  }
+  if (p.use_filter) p.n_slices = (int)p.scan_grid * (kScanThreads / 64);
+  return p;
+}
+
+// Every buffer the call uses, sized by the plan; the slab index is brought up to date on the way (its kernels
+// come after the first-use memset of the scalars and before that of the bucket histogram).
+int radius_workspaces(rrtx_ctx *ctx, const RadiusPlan &p) {
+  hipStream_t st = ctx->stream;
+  const size_t nc = p.n_copies_max;
+  const size_t qrec_bytes = (ctx->dim == 4) ? sizeof(QRec4) : sizeof(QRec3);
+  RRTX_HIP(ctx, ctx->ws_slots.ensure(nc * sizeof(SlotRec)));
+  RRTX_HIP(ctx, ctx->ws_counts.ensure(((size_t)p.nq * 3 + 2) * sizeof(int)));
+  // two Scalars records used alternately: each call's pack kernel resets the other one
+  if (!ctx->ws_scalars.p) {
+    RRTX_HIP(ctx, ctx->ws_scalars.ensure(2 * sizeof(Scalars)));
+    RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_scalars.p, 0, 2 * sizeof(Scalars), st));
+  }
+  RRTX_HIP(ctx, ctx->ws_recs.ensure((size_t)p.rec_cap * sizeof(HitRec)));
+  RRTX_HIP(ctx, ctx->ws_tmp.ensure((size_t)p.rec_cap * sizeof(BktRec)));
+  if (!ctx->mailbox) {                    // host-mapped words the finish kernel reports to
+    RRTX_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->mailbox), 64, hipHostMallocMapped));
+    std::memset(ctx->mailbox, 0, 64);
+  }
+  if (!p.slot_route) {                    // (the slot route needs none of these: its copies live in the table)
+    const size_t qf_bytes = (ctx->dim == 4) ? sizeof(QRecF4) : sizeof(QRecF3);
+    RRTX_HIP(ctx, ctx->ws_copies.ensure(nc * qrec_bytes));
+    RRTX_HIP(ctx, ctx->ws_copy_meta.ensure(nc * sizeof(int2)));
+    // (kQPI records of padding: the screens read kQPI at a time)
+    if (p.use_filter) RRTX_HIP(ctx, ctx->ws_copies_f.ensure((nc + kQPI) * qf_bytes));
+    if (p.use_cull) RRTX_HIP(ctx, ctx->ws_copies_s.ensure(nc * qrec_bytes));
+    if (p.use_cull) RRTX_HIP(ctx, ctx->ws_meta_s.ensure(nc * sizeof(int2)));
+  }
+  if (p.use_cull) {
+    int rc = slab_refresh(ctx, (long long)((nc + 15) / 16));
+    if (rc) return rc;
+    if (!ctx->ws_qhist.p) {               // stays all zero between calls (the finish kernel re-zeroes it)
+      RRTX_HIP(ctx, ctx->ws_qhist.ensure(sizeof(int) * (size_t)(kMaxQBuckets + 1)));
+      RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_qhist.p, 0, sizeof(int) * (size_t)(kMaxQBuckets + 1), st));
+    }
+    RRTX_HIP(ctx, ctx->ws_cb.ensure(sizeof(int2) * nc));
+    const size_t rec_bytes = (ctx->dim == 4) ? sizeof(QSlotRec<4>) : sizeof(QSlotRec<3>);
+    if (p.slot_route) RRTX_HIP(ctx, ctx->ws_qslot.ensure((size_t)p.n_tab * rec_bytes));
+  }
+  RRTX_HIP(ctx, ctx->ws_bkt.ensure((size_t)p.nq * (size_t)p.bcap * sizeof(BktRec)));
+  RRTX_HIP(ctx, ctx->ws_confirm_args.ensure(sizeof(ConfirmArgs)));
+  if (p.use_filter) {
+    RRTX_HIP(ctx, ctx->ws_ev_a.ensure((size_t)p.n_slices * (size_t)p.slice_cap * sizeof(int2)));
+    RRTX_HIP(ctx, ctx->ws_ev_cnt.ensure((size_t)p.n_slices * sizeof(int)));
+  }
+  if (p.prescatter) RRTX_HIP(ctx, ctx->ws_bsum.ensure(sizeof(long long) * (size_t)((p.nq + 255) / 256)));
+  return RRTX_OK;
+}
+
+// What the kernels of one call are handed: pointers into the workspaces and the argument records built from them
+struct RadiusArgs {
+  Scalars *sc;            // this call's record; the pack kernel resets the other one (pf.sc_next)
+  int *count, *cursor;    // list lengths; scatter cursors (count[nq] is scratch of the pack kernel)
+  int *qhist; int2 *cbk;  // bucket histogram and (bucket, rank) per copy; null without culling
+  ConfirmArgs ca, *ca_dev;   // (ca.hs: the hit sink)
+  PackFused pf; QSlots qs; ExtendDev xd;
+};
+
+void radius_args(rrtx_ctx *ctx, const RadiusPlan &p, int flip, const ExtendFuse *ext, RadiusArgs &d) {
+  const int wi = ctx->dim == 4 ? 3 : 2;   // (3-D: the third array stands in for the fourth)
+  std::memset(&d, 0, sizeof(d));
+  d.sc = ctx->ws_scalars.as<Scalars>() + flip;
+  d.count = ctx->ws_counts.as<int>();
+  d.cursor = d.count + p.nq + 1;
+  if (p.use_cull) { d.qhist = ctx->ws_qhist.as<int>(); d.cbk = ctx->ws_cb.as<int2>(); }
+  if (p.slot_route) {
+    d.qs.capb = p.capb; d.qs.spill_base = p.spill_base;
+    d.qs.tab = ctx->ws_qslot.p; d.qs.spill_key = d.cbk; d.qs.node_absmax = ctx->d_absmax.as<unsigned long long>();
+  }
+  HitSink &hs = d.ca.hs;
+  hs.count = d.count; hs.bkt = ctx->ws_bkt.as<BktRec>(); hs.bcap = p.bcap;
+  hs.recs = ctx->ws_recs.as<HitRec>(); hs.cap = p.rec_cap; hs.sc = d.sc;
+  double *const *pd = p.use_cull ? ctx->sl_d : ctx->nodes;
+  d.ca.nx = pd[0]; d.ca.ny = pd[1]; d.ca.nz = pd[2]; d.ca.nw = pd[wi];
+  // (slot route: the tile kernel confirms against its copies in LDS and takes the owners from there)
+  d.ca.copies = p.slot_route ? nullptr : (p.use_cull ? ctx->ws_copies_s.p : ctx->ws_copies.p);
+  d.ca.meta = p.slot_route ? nullptr : (p.use_cull ? ctx->ws_meta_s.as<int2>() : ctx->ws_copy_meta.as<int2>());
+  d.ca.slots = ctx->ws_slots.as<SlotRec>(); d.ca.pos_id = p.use_cull ? ctx->sl_id : nullptr; d.ca.n_slots = p.n_slots;
+  d.ca_dev = ctx->ws_confirm_args.as<ConfirmArgs>();
+  d.pf.count = d.count; d.pf.sc_next = ctx->ws_scalars.as<Scalars>() + (flip ^ 1); d.pf.ca_dst = d.ca_dev;
+  d.pf.nx = ctx->nodes[0]; d.pf.ny = ctx->nodes[1]; d.pf.nz = ctx->nodes[2]; d.pf.nw = ctx->nodes[wi];
+  d.pf.sph = nullptr; d.pf.m_sph = -1; d.pf.root_rule = ctx->opt_root_rule;
+  d.xd.r_bound = -1.0;
+  if (p.fuse) {                           // (sphere list; the caller has synced the tables)
+    d.xd.sph = ctx->d_sph.as<SphRec>(); d.xd.stab = ctx->d_sph_sample.as<SampleSph>();
+    d.xd.reach_f = ctx->d_sph_reach_f.as<float>(); d.xd.naos = reinterpret_cast<const double4 *>(ctx->nodes_aos);
+    d.xd.ox = ctx->origin[0]; d.xd.oy = ctx->origin[1]; d.xd.oz = ctx->origin[2]; d.xd.m = ctx->sph_n_active;
+    d.xd.r_bound = (ext->r >= 0.0 && d.xd.m > 0) ? ext->r * (1.0 + 1e-12) : -1.0;
+    d.xd.sample_unsafe = ext->sample_unsafe;
+    d.pf.sph = d.xd.sph; d.pf.m_sph = d.xd.m;
+  }
+}
+
+// place (culled search off the slot route) or prep (brute-force screen): the fp32 screen records
+void radius_place_or_prep(rrtx_ctx *ctx, const RadiusPlan &p, const RadiusArgs &d) {
+  const dim3 grid((unsigned)((p.n_copies_max + kQPI + 255) / 256)), block(256);
+  const unsigned long long *absmax = ctx->d_absmax.as<unsigned long long>();
+  for_dim(ctx->dim, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    using Q = typename QRecT<D>::type;
+    using QF = typename QRecFT<D>::type;
+    if (p.use_cull)
+      hipLaunchKernelGGL(nn_place_kernel<D>, grid, block, 0, ctx->stream, ctx->ws_copies.as<Q>(),
+                         ctx->ws_copy_meta.as<int2>(), d.cbk, d.qhist, p.n_buckets, d.sc, absmax, ctx->origin[0],
+                         ctx->origin[1], ctx->origin[2], ctx->origin[3], ctx->ws_copies_s.as<Q>(),
+                         ctx->ws_meta_s.as<int2>(), ctx->ws_copies_f.as<QF>());
+    else
+      hipLaunchKernelGGL(nn_filter_prep_kernel<D>, grid, block, 0, ctx->stream, ctx->ws_copies.as<Q>(), d.sc, absmax,
+                         (int)p.n_copies_max, ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
+                         ctx->ws_copies_f.as<QF>());
+  });
+}
+
+// scan, culled: one workgroup per (tile of kTileB copies, part)
+void radius_scan_tiles(rrtx_ctx *ctx, const RadiusPlan &p, const RadiusArgs &d) {
+  TileGrid tg;
+  tg.sp = ctx->ws_slab_params.as<SlabParams>();
+  tg.cell_start = ctx->ws_slab_start.as<int>();
+  tg.n_sorted_chunks = (ctx->ws_slab_params.p && ctx->ws_slab_start.p) ? (int)(ctx->sl_n_sorted / kSlabChunk) : 0;
+  tg.kz = ctx->sl_kz > 0 ? ctx->sl_kz : 1;
+  tg.groups = (tg.kz > 1 && !tune_bits(ctx).whole_chunks) ? 1 : 0;
+  TilePlace tpl;
+  tpl.qhist = d.qhist; tpl.tab = d.qs.tab; tpl.spill_key = d.qs.spill_key;
+  tpl.n_buckets = p.n_buckets; tpl.capb = p.capb; tpl.spill_base = p.spill_base; tpl.n_tab = p.n_tab;
+  const int wi = ctx->dim == 4 ? 3 : 2;
+#define RRTX_TILE_LAUNCH(DD, EE, SS)                                                                                   \
+  hipLaunchKernelGGL((nn_tile_kernel<DD, EE, SS>), dim3(p.scan_grid), dim3(kScanThreads), 0, ctx->stream,              \
+                     ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2], ctx->sl_f[wi], ctx->sl_pp, p.n_nodes, p.n_chunks,       \
+                     reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),                                               \
+                     SS ? nullptr : ctx->ws_copies_s.as<typename QRecT<DD>::type>(),                                   \
+                     SS ? nullptr : ctx->ws_copies_f.as<typename QRecFT<DD>::type>(), d.sc, p.n_parts,                 \
+                     ctx->ws_ev_a.as<int2>(), p.slice_cap, d.ca, d.ca_dev, tg, d.xd, ctx->ws_ev_cnt.as<int>(),         \
+                     p.n_slots == 1 ? p.nq : -1, tpl)
+  for_dim(ctx->dim, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    if constexpr (D == 3) {               // (only the 3-D search carries the extend() work)
+      if (p.fuse) {
+        if (p.slot_route) RRTX_TILE_LAUNCH(3, true, true); else RRTX_TILE_LAUNCH(3, true, false);
+        return;
+      }
+    }
+    if (p.slot_route) RRTX_TILE_LAUNCH(D, false, true); else RRTX_TILE_LAUNCH(D, false, false);
+  });
+#undef RRTX_TILE_LAUNCH
+}
+
+// scan, brute force.  Screened: entries into the waves' slices, then their exact confirmation, one lane per entry;
+// exact: every (copy, node) pair in fp64
+void radius_scan_brute(rrtx_ctx *ctx, const RadiusPlan &p, const RadiusArgs &d) {
+  int2 *ev = ctx->ws_ev_a.as<int2>();
+  int *ev_cnt = ctx->ws_ev_cnt.as<int>();
+  const dim3 grid(p.scan_grid), block(kScanThreads), cgrid((unsigned)(((long long)p.n_slices * kConfirmParts + 3) / 4));
+  for_dim(ctx->dim, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    constexpr int wi = D == 4 ? 3 : 2;
+    if (p.use_filter) {
+      hipLaunchKernelGGL(nn_scan_f32_kernel<D>, grid, block, 0, ctx->stream, ctx->nodes_f[0], ctx->nodes_f[1],
+                         ctx->nodes_f[2], ctx->nodes_f[wi], ctx->nodes_pp, p.n_nodes,
+                         ctx->ws_copies_f.as<typename QRecFT<D>::type>(), p.tile_q, p.n_seg, p.seg_len, d.sc, ev, ev_cnt,
+                         p.slice_cap, d.ca_dev);
+      hipLaunchKernelGGL((nn_confirm_kernel<D, false>), cgrid, dim3(256), 0, ctx->stream, d.ca, ev, ev_cnt, p.n_slices,
+                         p.slice_cap, p.n_nodes);
+    } else {
+      hipLaunchKernelGGL(nn_scan_kernel<D>, grid, block, 0, ctx->stream, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2],
+                         ctx->nodes[wi], p.n_nodes, ctx->ws_copies.as<typename QRecT<D>::type>(),
+                         ctx->ws_copy_meta.as<int2>(), ctx->ws_slots.as<SlotRec>(), p.n_slots, p.tile_q, p.n_seg,
+                         p.seg_len, d.sc, d.ca.hs);
+    }
+  });
+}
+
+// offsets + scatter in front of the finish kernel (plan: prescatter)
+void radius_prescatter(rrtx_ctx *ctx, const RadiusPlan &p, const RadiusArgs &d, int64_t *offsets_dev,
+                       int64_t *needed_dev, int64_t cap) {
+  hipStream_t st = ctx->stream;
+  long long *bsum = ctx->ws_bsum.as<long long>();
+  const int nblk = (p.nq + 255) / 256;
+  const long long *bsum_arg = nullptr;
+  if (p.nq > 65536) {                     // large batch: per-256 sums first
+    hipLaunchKernelGGL(nn_blocksum_kernel, dim3(nblk), dim3(256), 0, st, d.count, p.nq, bsum);
+    bsum_arg = bsum;
+  }
+  hipLaunchKernelGGL(nn_offsets_kernel, dim3(nblk), dim3(256), 0, st, d.count, p.nq, bsum_arg, offsets_dev, d.cursor,
+                     needed_dev, (int *)nullptr, 0);
+  hipLaunchKernelGGL(nn_scatter_kernel, dim3(1024), dim3(256), 0, st, ctx->ws_recs.as<HitRec>(), p.rec_cap, d.sc,
+                     offsets_dev, d.cursor, p.bcap, ctx->ws_tmp.as<BktRec>(), (long long)cap);
+}
+
+}  // namespace
+
 int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr_lt, double r_scalar, int nq,
                      int64_t *offsets_dev, int32_t *idx_dev, double *dist_dev, int64_t cap,
                      int64_t *needed_dev, int32_t *owner_dev, int32_t *nearest_idx_dev,
@@ -1256,9 +1553,6 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "radius search on an empty tree");
   if (nq <= 0) return RRTX_OK;
   if (nq >= (1 << 30)) return fail(ctx, RRTX_E_INVALID, "radius search: at most 2^30 - 1 queries per call");
-  const int D = ctx->dim;
-  const int n_slots = 1 << ctx->n_wraps;
-  hipStream_t st = ctx->stream;
 
   double tlt = 0.0, tgt = 0.0;
   if (!r_dev_thr_lt) {
@@ -1270,333 +1564,64 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
     tlt = ctx->thr_cache_lt;
     tgt = ctx->thr_cache_gt;
   }
-  const size_t n_copies_max = (size_t)nq * n_slots;
-  const size_t qrec_bytes = (D == 4) ? sizeof(QRec4) : sizeof(QRec3);
-  RRTX_HIP(ctx, ctx->ws_slots.ensure(n_copies_max * sizeof(SlotRec)));
-  RRTX_HIP(ctx, ctx->ws_counts.ensure(((size_t)nq * 3 + 2) * sizeof(int)));
-  // two Scalars records used alternately: each call's pack kernel resets the other one
-  if (!ctx->ws_scalars.p) {
-    RRTX_HIP(ctx, ctx->ws_scalars.ensure(2 * sizeof(Scalars)));
-    RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_scalars.p, 0, 2 * sizeof(Scalars), st));
-  }
-  const long long rec_cap = (long long)(cap > 0 ? cap : 1);
-  RRTX_HIP(ctx, ctx->ws_recs.ensure((size_t)rec_cap * sizeof(HitRec)));
-  RRTX_HIP(ctx, ctx->ws_tmp.ensure((size_t)rec_cap * sizeof(BktRec)));
   // What the previous calls reported (host-mapped words written by the finish kernel; possibly one call
   // stale, which is fine: this only tunes, every setting gives the same lists).  Lists that outgrew
   // their buckets: wider buckets from now on; many such records: offsets + scatter as launches of their
   // own in front of the finish kernel instead of every overflowed query collecting its own records.
-  if (!ctx->mailbox) {
-    RRTX_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->mailbox), 64, hipHostMallocMapped));
-    std::memset(ctx->mailbox, 0, 64);
-  }
-  const unsigned prev_overflow = *reinterpret_cast<volatile unsigned *>(ctx->mailbox);
+  const unsigned prev_overflow = ctx->mailbox ? *reinterpret_cast<volatile unsigned *>(ctx->mailbox) : 0u;
   if (prev_overflow > 0 && ctx->bkt_mult < 16) ctx->bkt_mult *= 2;
 
-  // (the switch is committed once the pack kernel, which resets the other record, is enqueued:
-  // an error return before that leaves the pristine record for the next call)
+  const RadiusPlan p = plan_radius(ctx, nq, cap, prev_overflow, ext != nullptr);
+  int rc = radius_workspaces(ctx, p);
+  if (rc) return rc;
+  // (the switch of the Scalars records is committed once the pack kernel, which resets the other record, is
+  // enqueued: an error return before that leaves the pristine record for the next call)
   const int flip = ctx->scalars_flip ^ 1;
-  Scalars *sc = ctx->ws_scalars.as<Scalars>() + flip;
-  Scalars *sc_next = ctx->ws_scalars.as<Scalars>() + (flip ^ 1);
-  int *count = ctx->ws_counts.as<int>();
-  int *cursor = count + nq + 1;         // (count[nq] is scratch of the pack kernel)
-
-  // ---- slab culling: on for large trees unless the worst-case unit list would be huge ----
-  const int n_nodes = (int)ctx->n_nodes;
-  const bool use_filter = ctx->opt_nn_filter != 0;
-  int tile_q = use_filter ? kTileQFilter : kTileQExact;
-  if (ctx->opt_tile_q > 0) tile_q = (ctx->opt_tile_q + kQPI - 1) / kQPI * kQPI;
-  if (use_filter && tile_q > 128) tile_q = 128;   // bounds the worst case of one chunk (64 tile_q entries)
-  const int n_tiles = (int)((n_copies_max + tile_q - 1) / tile_q);
-  const int n_chunks = (n_nodes + kSlabChunk - 1) / kSlabChunk;
-  const bool use_cull = use_filter && (ctx->opt_nn_cull == 2 || (ctx->opt_nn_cull == 1 && n_nodes >= 8192));
-  ctx->last_culled = use_cull;
-  int n_buckets = 1, g2 = 1, g3 = 1;
-  int *qhist = nullptr;
-  int2 *cbk = nullptr;
-  // culled search without ghosts: the pack pass fills the bucket-slot table and the tile kernel places the
-  // copies itself (three launches); with ghosts, or experiment switch 4, the place pass puts them in order
-  const bool slot_route = use_cull && n_slots == 1 && !(ctx->opt_tune & 4);
-  ctx->last_placement = slot_route ? 2 : (use_cull ? 1 : 0);
-  QSlots qs;
-  std::memset(&qs, 0, sizeof(qs));
-  int n_tab = 0;
-  if (!slot_route) {                      // (the slot route writes neither: its copies live in the table)
-    RRTX_HIP(ctx, ctx->ws_copies.ensure(n_copies_max * qrec_bytes));
-    RRTX_HIP(ctx, ctx->ws_copy_meta.ensure(n_copies_max * sizeof(int2)));
-  }
-  if (use_cull) {
-    int rc = slab_refresh(ctx, (long long)((n_copies_max + 15) / 16));
-    if (rc) return rc;
-    // square (x, y) grid of about 16 copies per bucket, or (trees with an extent in the third coordinate,
-    // decided by the pack kernel from the node bounds) a cubic grid of about 4: query_grid, nn_device.hpp
-    while (g2 * g2 < (long long)(n_copies_max / 16) && g2 * g2 < kMaxQBuckets) g2 *= 2;
-    g3 = (int)std::lround(std::cbrt((double)n_copies_max / 4.0));
-    if (g3 < 1) g3 = 1;
-    if (g3 > 16) g3 = 16;
-    if ((ctx->opt_tune >> 16) & 0x1f) g3 = (ctx->opt_tune >> 16) & 0x1f;   // experiment switch: side of the cubic grid
-    if (g3 > 16) g3 = 16;
-    if (ctx->opt_tune & 1) g3 = 1;          // experiment switch: (x, y) order of the copies
-    n_buckets = g2 * g2 > g3 * g3 * g3 ? g2 * g2 : g3 * g3 * g3;
-    if (!ctx->ws_qhist.p) {               // stays all zero between calls (nn_offsets_kernel re-zeroes it)
-      RRTX_HIP(ctx, ctx->ws_qhist.ensure(sizeof(int) * (size_t)(kMaxQBuckets + 1)));
-      RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_qhist.p, 0, sizeof(int) * (size_t)(kMaxQBuckets + 1), st));
-    }
-    RRTX_HIP(ctx, ctx->ws_cb.ensure(sizeof(int2) * n_copies_max));
-    if (!slot_route) {
-      RRTX_HIP(ctx, ctx->ws_copies_s.ensure(n_copies_max * qrec_bytes));
-      RRTX_HIP(ctx, ctx->ws_meta_s.ensure(n_copies_max * sizeof(int2)));
-    }
-    qhist = ctx->ws_qhist.as<int>();
-    cbk = ctx->ws_cb.as<int2>();
-    if (slot_route) {
-      // slots per bucket: the average over the coarser of the two grids with headroom (the rest spills)
-      const long long min_b = std::max(1ll, std::min((long long)g2 * g2, (long long)g3 * g3 * g3));
-      const long long avg = ((long long)n_copies_max + min_b - 1) / min_b;
-      const int capb = (int)std::min(128ll, std::max(8ll, (2 * avg + 8 + 3) / 4 * 4));
-      qs.capb = capb;
-      qs.spill_base = n_buckets * capb;
-      n_tab = qs.spill_base + (int)n_copies_max;
-      const size_t rec_bytes = (D == 4) ? sizeof(QSlotRec<4>) : sizeof(QSlotRec<3>);
-      RRTX_HIP(ctx, ctx->ws_qslot.ensure((size_t)n_tab * rec_bytes));
-      qs.tab = ctx->ws_qslot.p;
-      qs.spill_key = cbk;
-      qs.node_absmax = ctx->d_absmax.as<unsigned long long>();
-    }
-  }
-  // ---- hit sink: per-query buckets (bkt_mult x the average the caller made room for, at most 16 GiB
-  //      in all -- there are 288) + overflow list ----
-  long long bcap_ll = (rec_cap + nq - 1) / nq * ctx->bkt_mult;
-  while (bcap_ll > 16 && bcap_ll * nq > (1ll << 30)) bcap_ll /= 2;
-  bcap_ll = (bcap_ll + 7) / 8 * 8;
-  if (bcap_ll < 8) bcap_ll = 8;
-  if (bcap_ll > (1ll << 24)) bcap_ll = 1ll << 24;
-  const int bcap = (int)bcap_ll;
-  RRTX_HIP(ctx, ctx->ws_bkt.ensure((size_t)nq * (size_t)bcap * sizeof(BktRec)));
-  HitSink hs;
-  hs.count = count;
-  hs.bkt = ctx->ws_bkt.as<BktRec>();
-  hs.bcap = bcap;
-  hs.pad = 0;
-  hs.recs = ctx->ws_recs.as<HitRec>();
-  hs.cap = rec_cap;
-  hs.sc = sc;
-  ConfirmArgs ca;
-  double *const *pd = use_cull ? ctx->sl_d : ctx->nodes;
-  ca.nx = pd[0]; ca.ny = pd[1]; ca.nz = pd[2]; ca.nw = pd[D == 4 ? 3 : 2];
-  // (slot route: the tile kernel confirms against its copies in LDS and takes the owners from there)
-  ca.copies = slot_route ? nullptr : (use_cull ? ctx->ws_copies_s.p : ctx->ws_copies.p);
-  ca.meta = slot_route ? nullptr : (use_cull ? ctx->ws_meta_s.as<int2>() : ctx->ws_copy_meta.as<int2>());
-  ca.slots = ctx->ws_slots.as<SlotRec>();
-  ca.pos_id = use_cull ? ctx->sl_id : nullptr;
-  ca.n_slots = n_slots;
-  ca.pad = 0;
-  ca.hs = hs;
-  RRTX_HIP(ctx, ctx->ws_confirm_args.ensure(sizeof(ConfirmArgs)));
-  ConfirmArgs *ca_dev = ctx->ws_confirm_args.as<ConfirmArgs>();
-  PackFused pf;
-  pf.count = count;
-  pf.sc_next = sc_next;
-  pf.ca_dst = ca_dev;
-  pf.nx = ctx->nodes[0]; pf.ny = ctx->nodes[1]; pf.nz = ctx->nodes[2]; pf.nw = ctx->nodes[D == 4 ? 3 : 2];
-  // fused extend() path (sphere list; the caller has synced the tables): only the culled search carries it
-  const bool fuse = ext && use_cull && D == 3 && n_slots == 1;
-  ExtendDev xd;
-  std::memset(&xd, 0, sizeof(xd));
-  xd.r_bound = -1.0;
-  pf.sph = nullptr; pf.m_sph = -1;
-  pf.root_rule = ctx->opt_root_rule;
-  if (fuse) {
-    xd.sph = ctx->d_sph.as<SphRec>();
-    xd.stab = ctx->d_sph_sample.as<SampleSph>();
-    xd.reach_f = ctx->d_sph_reach_f.as<float>();
-    xd.naos = reinterpret_cast<const double4 *>(ctx->nodes_aos);
-    xd.ox = ctx->origin[0]; xd.oy = ctx->origin[1]; xd.oz = ctx->origin[2];
-    xd.m = ctx->sph_n_active;
-    xd.r_bound = (ext->r >= 0.0 && xd.m > 0) ? ext->r * (1.0 + 1e-12) : -1.0;
-    xd.sample_unsafe = ext->sample_unsafe;
-    pf.sph = xd.sph; pf.m_sph = xd.m;
-    ext->fused = true;
-  }
-
-  const double *thr_lt_arr = r_dev_thr_lt;
-  const double *thr_gt_arr = r_dev_thr_lt ? r_dev_thr_lt + nq : nullptr;
+  RadiusArgs d;
+  radius_args(ctx, p, flip, ext, d);
+  if (p.fuse) ext->fused = true;
+  ctx->last_culled = p.use_cull;
+  ctx->last_placement = p.slot_route ? 2 : (p.use_cull ? 1 : 0);
+  ctx->last_tile_q = p.use_cull ? kTileB : p.tile_q;
+  if (p.use_cull) ctx->last_visit_slices = p.n_slices;
+  ctx->last_pairs = (int64_t)p.n_copies_max * p.n_nodes;
 
   span_begin(ctx, KF_NN_FINISH);
-  {
-    dim3 grid((nq + 255) / 256), block(256);
-    if (D == 4)
-      hipLaunchKernelGGL(nn_pack_kernel<4>, grid, block, 0, st, q_dev, nq, thr_lt_arr, thr_gt_arr, tlt, tgt,
-                         ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2],
-                         ctx->wrap_period[0], ctx->wrap_period[1], ctx->wrap_period[2],
-                         ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
-                         ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec4>(),
-                         ctx->ws_copy_meta.as<int2>(), sc, ctx->d_xrange.as<unsigned long long>(), g2, g3, qhist,
-                         cbk, pf, ca, qs);
-    else
-      hipLaunchKernelGGL(nn_pack_kernel<3>, grid, block, 0, st, q_dev, nq, thr_lt_arr, thr_gt_arr, tlt, tgt,
-                         ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2],
-                         ctx->wrap_period[0], ctx->wrap_period[1], ctx->wrap_period[2],
-                         ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
-                         ctx->ws_slots.as<SlotRec>(), ctx->ws_copies.as<QRec3>(),
-                         ctx->ws_copy_meta.as<int2>(), sc, ctx->d_xrange.as<unsigned long long>(), g2, g3, qhist,
-                         cbk, pf, ca, qs);
-  }
+  for_dim(ctx->dim, [&](auto dc) {        // pack
+    launch_nn_pack<decltype(dc)::value>(ctx, q_dev, nq, r_dev_thr_lt, r_dev_thr_lt ? r_dev_thr_lt + nq : nullptr, tlt,
+                                        tgt, d.sc, ctx->d_xrange.as<unsigned long long>(), p.g2, p.g3, d.qhist, d.cbk,
+                                        d.pf, d.ca, d.qs);
+  });
   span_end(ctx);
   ctx->scalars_flip = flip;
 
-  // ---- scan geometry: tiles of copies x node segments (segment = XCD-affine) ----
-  const int chunk = use_filter ? kChunkF : kChunk;
-  const int wg_nodes = (kScanThreads / 64) * chunk;  // nodes one workgroup covers per pass
-  int max_seg = (n_nodes + wg_nodes - 1) / wg_nodes;
-  int want_seg = ((use_filter ? ctx->opt_scan_items : 4096) + n_tiles - 1) / n_tiles;
-  int n_seg = want_seg < max_seg ? want_seg : max_seg;
-  if (n_seg < 1) n_seg = 1;
-  if (n_seg >= 8) n_seg = n_seg / 8 * 8;  // segment index == blockIdx % 8 class == XCD
-  int seg_len = round_up((n_nodes + n_seg - 1) / n_seg, chunk);
-  n_seg = (n_nodes + seg_len - 1) / seg_len;
-  ctx->last_tile_q = use_cull ? kTileB : tile_q;
-
-  if (use_filter && !slot_route) {
-    const size_t qf_bytes = (D == 4) ? sizeof(QRecF4) : sizeof(QRecF3);
-    RRTX_HIP(ctx, ctx->ws_copies_f.ensure((n_copies_max + kQPI) * qf_bytes));
+  if (p.use_filter && !p.slot_route) {
     span_begin(ctx, KF_NN_FINISH);
-    dim3 grid((unsigned)((n_copies_max + kQPI + 255) / 256)), block(256);
-    const unsigned long long *absmax = ctx->d_absmax.as<unsigned long long>();
-    if (use_cull) {
-      if (D == 4)
-        hipLaunchKernelGGL(nn_place_kernel<4>, grid, block, 0, st, ctx->ws_copies.as<QRec4>(),
-                           ctx->ws_copy_meta.as<int2>(), cbk, qhist, n_buckets, sc, absmax, ctx->origin[0],
-                           ctx->origin[1], ctx->origin[2], ctx->origin[3], ctx->ws_copies_s.as<QRec4>(),
-                           ctx->ws_meta_s.as<int2>(), ctx->ws_copies_f.as<QRecF4>());
-      else
-        hipLaunchKernelGGL(nn_place_kernel<3>, grid, block, 0, st, ctx->ws_copies.as<QRec3>(),
-                           ctx->ws_copy_meta.as<int2>(), cbk, qhist, n_buckets, sc, absmax, ctx->origin[0],
-                           ctx->origin[1], ctx->origin[2], ctx->origin[3], ctx->ws_copies_s.as<QRec3>(),
-                           ctx->ws_meta_s.as<int2>(), ctx->ws_copies_f.as<QRecF3>());
-    } else if (D == 4)
-      hipLaunchKernelGGL(nn_filter_prep_kernel<4>, grid, block, 0, st, ctx->ws_copies.as<QRec4>(), sc, absmax,
-                         (int)n_copies_max, ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
-                         ctx->ws_copies_f.as<QRecF4>());
-    else
-      hipLaunchKernelGGL(nn_filter_prep_kernel<3>, grid, block, 0, st, ctx->ws_copies.as<QRec3>(), sc, absmax,
-                         (int)n_copies_max, ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3],
-                         ctx->ws_copies_f.as<QRecF3>());
+    radius_place_or_prep(ctx, p, d);
     span_end(ctx);
   }
 
   span_begin(ctx, KF_NN_SCAN);
-  {
-    dim3 grid((unsigned)n_tiles * (unsigned)n_seg), block(kScanThreads);
-    const int wi = D == 4 ? 3 : 2;
-    if (use_cull) {
-      // one workgroup per (tile of kTileB copies, part); few tiles: several parts share a tile's chunks;
-      // many tiles: a bounded grid walks them
-      const int n_tiles_b = (int)((n_copies_max + kTileB - 1) / kTileB);
-      int n_parts = (1024 + n_tiles_b - 1) / n_tiles_b;
-      if (n_parts > 64) n_parts = 64;
-      long long nb = (long long)n_tiles_b * n_parts;
-      if (nb > 4096) nb = 4096;             // n_parts == 1 here
-      const int n_slices = (int)nb * (kScanThreads / 64);
-      const int slice_cap = 64 * kTileB + kTbSlack;
-      RRTX_HIP(ctx, ctx->ws_ev_a.ensure((size_t)n_slices * (size_t)slice_cap * sizeof(int2)));
-      RRTX_HIP(ctx, ctx->ws_ev_cnt.ensure((size_t)n_slices * sizeof(int)));
-      ctx->last_visit_slices = n_slices;
-      TileGrid tg;
-      tg.sp = ctx->ws_slab_params.as<SlabParams>();
-      tg.cell_start = ctx->ws_slab_start.as<int>();
-      tg.n_sorted_chunks = (ctx->ws_slab_params.p && ctx->ws_slab_start.p) ? (int)(ctx->sl_n_sorted / kSlabChunk) : 0;
-      tg.kz = ctx->sl_kz > 0 ? ctx->sl_kz : 1;
-      tg.groups = (tg.kz > 1 && !(ctx->opt_tune & 2)) ? 1 : 0;     // (experiment switch 2: whole chunks)
-      TilePlace tpl;
-      tpl.qhist = qhist; tpl.tab = qs.tab; tpl.spill_key = qs.spill_key;
-      tpl.n_buckets = n_buckets; tpl.capb = qs.capb; tpl.spill_base = qs.spill_base; tpl.n_tab = n_tab;
-#define RRTX_TILE_LAUNCH(DD, EE, SS)                                                                                   \
-  hipLaunchKernelGGL((nn_tile_kernel<DD, EE, SS>), dim3((unsigned)nb), block, 0, st, ctx->sl_f[0], ctx->sl_f[1],       \
-                     ctx->sl_f[2], ctx->sl_f[wi], ctx->sl_pp, n_nodes, n_chunks,                                       \
-                     reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),                                               \
-                     SS ? nullptr : ctx->ws_copies_s.as<typename QRecT<DD>::type>(),                                   \
-                     SS ? nullptr : ctx->ws_copies_f.as<typename QRecFT<DD>::type>(), sc, n_parts,                     \
-                     ctx->ws_ev_a.as<int2>(), slice_cap, ca, ca_dev, tg, xd, ctx->ws_ev_cnt.as<int>(),                 \
-                     n_slots == 1 ? nq : -1, tpl)
-      if (fuse) {
-        if (slot_route) RRTX_TILE_LAUNCH(3, true, true); else RRTX_TILE_LAUNCH(3, true, false);
-      } else if (D == 4) {
-        if (slot_route) RRTX_TILE_LAUNCH(4, false, true); else RRTX_TILE_LAUNCH(4, false, false);
-      } else {
-        if (slot_route) RRTX_TILE_LAUNCH(3, false, true); else RRTX_TILE_LAUNCH(3, false, false);
-      }
-#undef RRTX_TILE_LAUNCH
-    } else if (use_filter) {
-      // persistent grid: opt_scan_blocks workgroups (multiple of 8) striding over the work
-      unsigned pg = (unsigned)ctx->opt_scan_blocks / 8u * 8u;
-      if (pg < 8u) pg = 8u;
-      if (pg < grid.x) grid.x = pg;
-      const int n_slices = (int)grid.x * (kScanThreads / 64);
-      const int slice_cap = 64 * tile_q + kEvSlack;
-      RRTX_HIP(ctx, ctx->ws_ev_a.ensure((size_t)n_slices * (size_t)slice_cap * sizeof(int2)));
-      RRTX_HIP(ctx, ctx->ws_ev_cnt.ensure((size_t)n_slices * sizeof(int)));
-      int2 *ev = ctx->ws_ev_a.as<int2>();
-      int *ev_cnt = ctx->ws_ev_cnt.as<int>();
-      float *const *nf = ctx->nodes_f;
-      if (D == 4)
-        hipLaunchKernelGGL(nn_scan_f32_kernel<4>, grid, block, 0, st, nf[0], nf[1], nf[2], nf[wi], ctx->nodes_pp,
-                           n_nodes, ctx->ws_copies_f.as<QRecF4>(), tile_q, n_seg, seg_len, sc, ev, ev_cnt, slice_cap,
-                           ca_dev);
-      else
-        hipLaunchKernelGGL(nn_scan_f32_kernel<3>, grid, block, 0, st, nf[0], nf[1], nf[2], nf[wi], ctx->nodes_pp,
-                           n_nodes, ctx->ws_copies_f.as<QRecF3>(), tile_q, n_seg, seg_len, sc, ev, ev_cnt, slice_cap,
-                           ca_dev);
-      // exact confirmation of the queued entries: one lane per entry
-      dim3 cgrid((unsigned)(((long long)n_slices * kConfirmParts + 3) / 4));
-      if (D == 4)
-        hipLaunchKernelGGL((nn_confirm_kernel<4, false>), cgrid, dim3(256), 0, st, ca, ev, ev_cnt, n_slices, slice_cap,
-                           n_nodes);
-      else
-        hipLaunchKernelGGL((nn_confirm_kernel<3, false>), cgrid, dim3(256), 0, st, ca, ev, ev_cnt, n_slices, slice_cap,
-                           n_nodes);
-    } else if (D == 4)
-      hipLaunchKernelGGL(nn_scan_kernel<4>, grid, block, 0, st, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2],
-                         ctx->nodes[3], n_nodes, ctx->ws_copies.as<QRec4>(), ctx->ws_copy_meta.as<int2>(),
-                         ctx->ws_slots.as<SlotRec>(), n_slots, tile_q, n_seg, seg_len, sc, hs);
-    else
-      hipLaunchKernelGGL(nn_scan_kernel<3>, grid, block, 0, st, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2],
-                         ctx->nodes[2], n_nodes, ctx->ws_copies.as<QRec3>(), ctx->ws_copy_meta.as<int2>(),
-                         ctx->ws_slots.as<SlotRec>(), n_slots, tile_q, n_seg, seg_len, sc, hs);
-  }
+  if (p.use_cull) radius_scan_tiles(ctx, p, d);
+  else radius_scan_brute(ctx, p, d);
   span_end(ctx);
-  ctx->last_pairs = (int64_t)n_copies_max * n_nodes;
 
   // ---- finish: offsets, order, (extend work), one launch (kernels_finish.hip) ----
-  const bool prescatter = nq > 65536 || prev_overflow > 8192u;
   span_begin(ctx, KF_NN_FINISH);
-  if (prescatter) {
-    RRTX_HIP(ctx, ctx->ws_bsum.ensure(sizeof(long long) * (size_t)((nq + 255) / 256)));
-    long long *bsum = ctx->ws_bsum.as<long long>();
-    const int nblk = (nq + 255) / 256;
-    const long long *bsum_arg = nullptr;
-    if (nq > 65536) {                     // large batch: per-256 sums first
-      hipLaunchKernelGGL(nn_blocksum_kernel, dim3(nblk), dim3(256), 0, st, count, nq, bsum);
-      bsum_arg = bsum;
-    }
-    hipLaunchKernelGGL(nn_offsets_kernel, dim3(nblk), dim3(256), 0, st, count, nq, bsum_arg, offsets_dev, cursor,
-                       needed_dev, (int *)nullptr, 0);
-    hipLaunchKernelGGL(nn_scatter_kernel, dim3(1024), dim3(256), 0, st, ctx->ws_recs.as<HitRec>(), rec_cap, sc,
-                       offsets_dev, cursor, bcap, ctx->ws_tmp.as<BktRec>(), (long long)cap);
-  }
+  if (p.prescatter) radius_prescatter(ctx, p, d, offsets_dev, needed_dev, cap);
   {
     FinishLaunch f;
-    f.count = count; f.nq = nq; f.bcap = bcap;
-    f.bkt = hs.bkt; f.tmp = ctx->ws_tmp.p; f.ovf = ctx->ws_recs.p; f.ovf_cap = rec_cap; f.scalars = sc;
-    f.prescattered = prescatter;
+    f.count = d.count; f.nq = nq; f.bcap = p.bcap;
+    f.bkt = d.ca.hs.bkt; f.tmp = ctx->ws_tmp.p; f.ovf = ctx->ws_recs.p; f.ovf_cap = p.rec_cap; f.scalars = d.sc;
+    f.prescattered = p.prescatter;
     f.offsets = offsets_dev; f.needed = needed_dev; f.idx = idx_dev; f.dist = dist_dev; f.out_cap = (long long)cap;
     f.owner = owner_dev; f.nearest_idx = nearest_idx_dev; f.nearest_dist = nearest_dist_dev;
-    f.qhist = qhist; f.n_qhist = use_cull ? n_buckets + 1 : 0;
+    f.qhist = d.qhist; f.n_qhist = p.use_cull ? p.n_buckets + 1 : 0;
     f.mailbox = ctx->mailbox;
     f.q = q_dev;
     f.r_start = (!r_dev_thr_lt && r_scalar > 0.0) ? 2.0 * r_scalar : 1.0;
-    f.hit_out = fuse ? ext->hit_out : nullptr; f.hit_in = fuse ? ext->hit_in : nullptr;
-    int rc = launch_nn_finish(ctx, f);
+    f.hit_out = p.fuse ? ext->hit_out : nullptr; f.hit_in = p.fuse ? ext->hit_in : nullptr;
+    rc = launch_nn_finish(ctx, f);
     if (rc) return rc;
   }
   span_end(ctx);

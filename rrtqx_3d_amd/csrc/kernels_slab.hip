@@ -309,12 +309,13 @@ int slab_refresh(rrtx_ctx *ctx, long long n_tiles) {
   hipStream_t st = ctx->stream;
   // about one cell per chunk: cells of ~512 nodes, laid out as a square grid over (x, y)
   // (experiment switches, RRTX_OPT_TUNE bits 24-25: smaller cells; bits 8-15: bins of the third coordinate)
-  const int cell_nodes = kSlabChunk >> ((ctx->opt_tune >> 24) & 3);
+  const TuneBits tune = tune_bits(ctx);
+  const int cell_nodes = kSlabChunk >> tune.cell_shift;
   int side = (int)std::sqrt((double)n / (double)cell_nodes);
   if (side < 2) side = 2;
   if (side > 256) side = 256;
   const int K = side * side;
-  const int Kz = ((ctx->opt_tune >> 8) & 0xff) ? ((ctx->opt_tune >> 8) & 0xff) : kSlabKz;
+  const int Kz = tune.kz_bins ? tune.kz_bins : kSlabKz;
   const int KK = K * Kz;                  // sort keys: (cell, bin of the third coordinate)
   // Workspaces sized for the node CAPACITY, not the current count: a tree that grows towards its capacity then
   // rebuilds without a hipFree / hipMalloc pair (each a device synchronisation, occasionally milliseconds) in

@@ -342,6 +342,20 @@ __global__ void nn_pack_kernel(const double *__restrict__ q, int nq, const doubl
   if ((threadIdx.x & 63) == 0 && am != 0ull) atomicMax(&sc->q_absmax, am);
 }
 
+// The one launch of the pack kernel (a template, so only the translation units that search instantiate it).  The
+// nearest search passes thresholds inf / nan, no grid (xrange and qhist null, g2 = g3 = 1) and empty pf / ca / qs.
+template <int D>
+inline void launch_nn_pack(rrtx_ctx *ctx, const double *q, int nq, const double *thr_lt_arr, const double *thr_gt_arr,
+                           double thr_lt_s, double thr_gt_s, Scalars *sc, const unsigned long long *xrange, int g2,
+                           int g3, int *qhist, int2 *cb, const PackFused &pf, const ConfirmArgs &ca, const QSlots &qs) {
+  hipLaunchKernelGGL(nn_pack_kernel<D>, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, q, nq, thr_lt_arr,
+                     thr_gt_arr, thr_lt_s, thr_gt_s, ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2],
+                     ctx->wrap_period[0], ctx->wrap_period[1], ctx->wrap_period[2], ctx->origin[0], ctx->origin[1],
+                     ctx->origin[2], ctx->origin[3], ctx->ws_slots.as<SlotRec>(),
+                     ctx->ws_copies.as<typename QRecT<D>::type>(), ctx->ws_copy_meta.as<int2>(), sc, xrange, g2, g3,
+                     qhist, cb, pf, ca, qs);
+}
+
 // ---------------------------------------------------------------- scan ------
 // was this node already discovered by an earlier copy (slot < my slot) of the
 // same query?  (addToRangeList keeps the first discovery, R/kdTree_general.jl:765)

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rrtx.h"
@@ -274,6 +275,28 @@ struct ApiRange {
       return ::rrtx::fail((ctx), RRTX_E_DEVICE, "%s failed: %s (%s:%d)", #expr,           \
                           hipGetErrorString(_e), __FILE__, __LINE__);                     \
   } while (0)
+
+// RRTX_OPT_TUNE decoded, in the one place that shifts and masks it (experiment switches: never change a result)
+struct TuneBits {
+  bool xy_order;       // bit 0: order the query copies by (x, y) bucket only (g3 = 1)
+  bool whole_chunks;   // bit 1: the tile kernel lists whole chunks, never groups of eight positions
+  bool place_pass;     // bit 2 (value 4): the place pass orders the copies even without ghosts
+  int kz_bins;         // bits 8-15: bins of the third coordinate inside a slab cell (0: kSlabKz)
+  int g3_side;         // bits 16-20: side of the cubic grid of query buckets (0: from the batch size)
+  int cell_shift;      // bits 24-25: slab cells of kSlabChunk >> cell_shift nodes
+};
+inline TuneBits tune_bits(const rrtx_ctx *ctx) {
+  const int t = ctx->opt_tune;
+  return TuneBits{(t & 1) != 0, (t & 2) != 0, (t & 4) != 0, (t >> 8) & 0xff, (t >> 16) & 0x1f, (t >> 24) & 3};
+}
+
+// One launch site per kernel template: fn (a generic lambda) gets the dimension as std::integral_constant<int, 3>
+// or <int, 4>; combinations that are never launched are kept out with `if constexpr` at the call site.
+template <class Fn>
+inline void for_dim(int dim, Fn &&fn) {
+  if (dim == 4) fn(std::integral_constant<int, 4>{});
+  else fn(std::integral_constant<int, 3>{});
+}
 
 // profiling spans around a kernel family
 void span_begin(rrtx_ctx *ctx, int family);
