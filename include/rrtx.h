@@ -489,6 +489,42 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
                        int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe, int64_t *offsets,
                        int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
 
+/* ---- a robot's new move target ------------------------------------------------- */
+/* findNewTarget (R/DRRT_Q.jl:2901-2994) for a batch of robot poses, on the device: kdFindWithinRange around the pose,
+ * the edge pose -> neighbour steered and collision-checked for every neighbour, the neighbour with the lowest
+ * rrtLMC + edge.dist taken; without a safe one the ball doubles (kdFindMoreWithinRange) until there is one or the ball
+ * exceeds r_max (the reference's maxSearchBallRad = dist(S.lowerBounds, S.upperBounds)).  All pointers are host
+ * pointers; pose is nq x dim; r0 holds one first radius (r_stride 0) or one per pose (r_stride 1), as in rrtx_nn_radius;
+ * lmc is rrtLMC of every node (rrtx_nodes_count doubles) or NULL for the context's own array (rrtx_node_cost_set).
+ * Per pose i, independently of the others:
+ *   r = r0[i]; k = 1
+ *   loop: L = the list rrtx_nn_radius gives at r (root with <=, ghost rule), in ascending node index;
+ *         best = +Inf; for e in L: cost = edge.dist of calculateTrajectory for pose_i -> node, blocked = the hit_out byte
+ *           of rrtx_extend_candidates[_dubins] for that edge is non-zero (with time it carries !validMove too);
+ *           cand = lmc[node] + cost; adopted when !blocked and cand < best (the first of equals wins; NaN and +Inf never);
+ *         best != +Inf: status RRTX_TGT_OK, target_idx = node, edge_dist = cost, cost_to_goal = best, radius_used = r,
+ *           rounds = k; stop
+ *         r = 2 r; r > r_max: status RRTX_TGT_NOT_FOUND, target_idx = -1, edge_dist = cost_to_goal = +Inf,
+ *           radius_used = the last radius searched, rounds = k; stop
+ *         k += 1
+ * The first search is always at r0[i]: clipping it to min(max(hyperBallRad, dist(pose, oldTarget)), r_max) stays with
+ * the caller, as in the reference.  Exact, no tolerance: every output is an input value, an index, one rounded fp64
+ * addition or r0 * 2^j.  RRTX_E_INVALID unless every r0[i] is finite and positive, r_max is finite and
+ * r0[i] >= r_max * 2^-40 (the reference loops forever on r0 = 0); RRTX_E_STATE on an empty tree.
+ * The SimpleEdge form needs dim == 3 and no wraps and reads the spheres or the polygons by RRTX_OPT_EXTEND_OBSTACLES;
+ * the Dubins form needs dim == 4, honours the wraps and RRTX_OPT_SPACE_HAS_TIME and reads the polygon list.  The
+ * neighbour lists stay on the device, in the context-owned buffers of rrtx_extend_select (RRTX_OPT_SELECT_LIST_CAP: a
+ * round that produces more grows them and runs once more); per round the host reads three words. */
+#define RRTX_TGT_OK 0
+#define RRTX_TGT_NOT_FOUND 1
+int rrtx_find_new_target(rrtx_ctx *ctx, const double *pose, int nq, const double *r0, int r_stride, double r_max,
+                         double robot_radius, const double *lmc, int32_t *target_idx, double *edge_dist,
+                         double *cost_to_goal, double *radius_used, int32_t *rounds, uint8_t *status);
+int rrtx_find_new_target_dubins(rrtx_ctx *ctx, const double *pose, int nq, const double *r0, int r_stride, double r_max,
+                                double robot_radius, double r_min, const double *lmc, int32_t *target_idx,
+                                double *edge_dist, double *cost_to_goal, double *radius_used, int32_t *rounds,
+                                uint8_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -467,6 +467,63 @@ function extendSelectDev(tree::HipTree, nq::Int, offsets, idx, costOut, costIn, 
 end
 
 # ---------------------------------------------------------------------------
+# findNewTarget (R/DRRT_Q.jl:2901-2994) on the device: the search around the robot pose, the edge to every neighbour
+# steered and checked, the neighbour with the lowest rrtLMC + edge.dist taken, the ball doubling while there is none.
+# rrtLMC is read from the array setNodeCosts fills.  findNewTargets is the batch form (the agents of R/rrtqx.jl):
+# poses is d x nq, r0 one first radius per pose; it returns the per-pose results without touching any RobotData.
+const RRTX_TGT_OK = UInt8(0)
+const RRTX_TGT_NOT_FOUND = UInt8(1)
+
+struct NewTargets
+  status::Vector{UInt8}       # RRTX_TGT_*
+  targetIdx::Vector{Int32}    # 0-based node index (-1 unless RRTX_TGT_OK)
+  edgeDist::Vector{Float64}   # edge.dist of pose -> target
+  costToGoal::Vector{Float64} # rrtLMC(target) + edge.dist
+  radiusUsed::Vector{Float64}
+  rounds::Vector{Int32}
+end
+
+function findNewTargets(tree::HipTree, S::TS, poses::Array{Float64,2}, r0::Vector{Float64}, maxSearchBallRad::Float64) where {TS}
+  nq = size(poses, 2)
+  tidx = Vector{Int32}(undef, nq); edist = Vector{Float64}(undef, nq); cgoal = Vector{Float64}(undef, nq)
+  rused = Vector{Float64}(undef, nq); rounds = Vector{Int32}(undef, nq); status = Vector{UInt8}(undef, nq)
+  if tree.d == 4
+    syncPolygonObstacles(tree, S)
+    syncDubinsSpace(tree, S)
+    GC.@preserve poses r0 tidx edist cgoal rused rounds status rrtx_check(tree, ccall((:rrtx_find_new_target_dubins, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{UInt8}),
+        tree.ctx, poses, nq, r0, 1, maxSearchBallRad, S.robotRadius, S.minTurningRadius, C_NULL, tidx, edist, cgoal, rused,
+        rounds, status))
+  else
+    syncObstacles(tree, S)
+    GC.@preserve poses r0 tidx edist cgoal rused rounds status rrtx_check(tree, ccall((:rrtx_find_new_target, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{UInt8}),
+        tree.ctx, poses, nq, r0, 1, maxSearchBallRad, S.robotRadius, C_NULL, tidx, edist, cgoal, rused, rounds, status))
+  end
+  return NewTargets(status, tidx, edist, cgoal, rused, rounds)
+end
+
+function findNewTarget(S::TS, KD::HipTree{T}, R::RobotData{T}, hyberBallRad::Float64) where {T, TS}
+  R.robotEdgeUsed = false
+  R.distAlongRobotEdge = 0.0
+  R.timeAlongRobotEdge = 0.0
+  R.robotEdgeForPlottingUsed = false
+  R.distAlongRobotEdgeForPlotting = 0.0
+  R.timeAlongRobotEdgeForPlotting = 0.0
+  maxSearchBallRad = dist(S.lowerBounds, S.upperBounds)
+  searchBallRad = min(max(hyberBallRad, dist(R.robotPose, R.nextMoveTarget.position)), maxSearchBallRad)
+  out = findNewTargets(KD, S, reshape(copy(R.robotPose), KD.d, 1), [searchBallRad], maxSearchBallRad)
+  if out.status[1] != RRTX_TGT_OK
+    error("unable to find a valid move target")
+  end
+  R.nextMoveTarget = KD.nodes[out.targetIdx[1] + 1]
+  R.distanceFromNextRobotPoseToNextMoveTarget = out.edgeDist[1]
+  R.currentMoveInvalid = false
+end
+
+# ---------------------------------------------------------------------------
 # addNewObstacle's edge loop (R/DRRT_Q.jl:3220-3290) against a device mirror of the planner's
 # directed edges.  registerEdges is called where the planner creates edges (makeNeighborOf,
 # makeInitialOutNeighborOf, makeParentOf); it returns the id of the first edge, ids are

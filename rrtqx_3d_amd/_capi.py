@@ -41,6 +41,9 @@ RRTX_SEL_NO_PARENT = 1
 RRTX_SEL_EMPTY = 2
 RRTX_SEL_UNSAFE = 3
 RRTX_SEL_OVERFLOW = 4
+# status[i] of rrtx_find_new_target*
+RRTX_TGT_OK = 0
+RRTX_TGT_NOT_FOUND = 1
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -141,6 +144,10 @@ SYMBOLS = [
     ("rrtx_node_cost_set", C.c_int, [_VP, C.c_int64, _VP, C.c_int64]),
     ("rrtx_extend_select", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                      C.c_int64, c_int64_p, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, c_int64_p]),
+    ("rrtx_find_new_target", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP,
+                                       _VP, _VP]),
+    ("rrtx_find_new_target_dubins", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_double, C.c_double, C.c_double, _VP, _VP,
+                                              _VP, _VP, _VP, _VP, _VP]),
 ]
 
 _lib = None

@@ -450,6 +450,41 @@ class Context:
             unsafe_ptr, lmc_ptr, parent_idx_ptr, parent_entry_ptr, lmc_new_ptr, status_ptr, rw_offsets_ptr, rw_node_ptr,
             rw_value_ptr, rw_cap, rw_needed_ptr))
 
+    # ---- findNewTarget on the device ----------------------------------------------------------------
+    def _find_new_target(self, pose, r0, r_max: float, robot_radius: float, lmc, r_min):
+        pose = f64(pose, (-1, self.dim))
+        nq = pose.shape[0]
+        r = f64(r0, (-1,))
+        if r.shape[0] not in (1, nq):
+            raise ValueError("r0 must be a scalar or have one entry per pose")
+        stride = 0 if r.shape[0] == 1 else 1
+        lmc_a = None if lmc is None else f64(lmc, (-1,))
+        if lmc_a is not None and lmc_a.shape[0] < self.n_nodes:
+            raise ValueError("lmc needs one entry per node")
+        out = dict(target_idx=np.empty(nq, dtype=np.int32), edge_dist=np.empty(nq, dtype=np.float64),
+                   cost_to_goal=np.empty(nq, dtype=np.float64), radius_used=np.empty(nq, dtype=np.float64),
+                   rounds=np.empty(nq, dtype=np.int32), status=np.empty(nq, dtype=np.uint8))
+        tail = [_capi._ptr(lmc_a)] + [_capi._ptr(out[k]) for k in ("target_idx", "edge_dist", "cost_to_goal", "radius_used",
+                                                                    "rounds", "status")]
+        head = [self._h, _capi._ptr(pose), nq, _capi._ptr(r), stride, float(r_max), float(robot_radius)]
+        if r_min is None:
+            self._check(self._lib.rrtx_find_new_target(*head, *tail))
+        else:
+            self._check(self._lib.rrtx_find_new_target_dubins(*head, float(r_min), *tail))
+        return out
+
+    def find_new_target(self, pose, r0, r_max: float, robot_radius: float, lmc=None) -> dict:
+        """rrtx_find_new_target (SimpleEdge, dim 3): per pose the neighbour with the lowest rrtLMC + edge.dist over the
+        safe edges pose -> neighbour, the ball doubling from r0 (a scalar or one radius per pose) until one exists or it
+        exceeds r_max.  dict(target_idx, edge_dist, cost_to_goal, radius_used, rounds, status); status is
+        _capi.RRTX_TGT_OK or RRTX_TGT_NOT_FOUND.  lmc: rrtLMC of every node, or None for what node_cost_set left on the
+        device."""
+        return self._find_new_target(pose, r0, r_max, robot_radius, lmc, None)
+
+    def find_new_target_dubins(self, pose, r0, r_max: float, robot_radius: float, r_min: float, lmc=None) -> dict:
+        """rrtx_find_new_target_dubins (dim 4, [x y t theta], polygon list; wraps and a space with time as set)."""
+        return self._find_new_target(pose, r0, r_max, robot_radius, lmc, r_min)
+
     def extend_candidates_dubins(self, q, r: float, robot_radius: float, r_min: float, cap: Optional[int] = None):
         """Fused extend() preamble for Edge = DubinsEdge (dim 4, theta wrapped, polygon obstacles)."""
         q = f64(q, (-1, 4))

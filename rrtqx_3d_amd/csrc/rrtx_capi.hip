@@ -529,7 +529,8 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
                     &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
-                    &ctx->gc.in_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc};
+                    &ctx->gc.in_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
+                    &ctx->ws_tgt_blk[0], &ctx->ws_tgt_blk[1], &ctx->ws_tgt_res};
   for (auto b : bufs) b->release();
   if (ctx->node_lmc) (void)hipFree(ctx->node_lmc);
   if (ctx->ge_start) (void)hipFree(ctx->ge_start);
@@ -1855,6 +1856,162 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
     arena_flush(ctx);
   }
   return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
+}
+
+// ---- findNewTarget over a batch of poses (kernels_target.hip) ---------------------------------------
+namespace {
+int find_new_target(rrtx_ctx *ctx, const char *fn, bool dubins, const double *pose, int nq, const double *r0, int r_stride,
+                    double r_max, double robot_radius, double r_min, const double *lmc, int32_t *target_idx,
+                    double *edge_dist, double *cost_to_goal, double *radius_used, int32_t *rounds, uint8_t *status) {
+  if (nq < 0 || (r_stride != 0 && r_stride != 1) ||
+      (nq > 0 && (!pose || !r0 || !target_idx || !edge_dist || !cost_to_goal || !radius_used || !rounds || !status)))
+    return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
+  if (dubins) {
+    if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "%s needs a dim=4 [x y t theta] context", fn);
+  } else if (ctx->dim != 3 || ctx->n_wraps != 0) {
+    return fail(ctx, RRTX_E_STATE, "%s is the SimpleEdge path: dim=3 without wrapped dimensions", fn);
+  }
+  if (!std::isfinite(r_max)) return fail(ctx, RRTX_E_INVALID, "%s: r_max must be finite", fn);
+  for (int i = 0; i < (r_stride ? nq : std::min(nq, 1)); ++i)
+    if (!std::isfinite(r0[i]) || !(r0[i] > 0.0) || !(r0[i] >= r_max * 0x1p-40))
+      return fail(ctx, RRTX_E_INVALID, "%s: r0[%d] = %g is not a finite positive radius of at least r_max / 2^40", fn, i, r0[i]);
+  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "%s on an empty tree", fn);
+  if (nq == 0) return RRTX_OK;
+
+  // One query block per round side, [pose | radius | thr_lt, thr_gt | slot], so that the first round's goes up in one
+  // transfer; one result block [cost_to_goal | edge_dist | radius_used | target_idx | rounds | status] that leaves in
+  // one transfer, followed by the rounds' own words [pending | header].
+  const size_t n = (size_t)nq, dim = (size_t)ctx->dim;
+  const size_t o_rad = sizeof(double) * n * dim, o_thr = o_rad + sizeof(double) * n, o_slot = o_thr + 2 * sizeof(double) * n,
+               blk_bytes = o_slot + sizeof(int32_t) * n;
+  const size_t o_ed = sizeof(double) * n, o_ru = 2 * o_ed, o_ti = 3 * o_ed, o_rd = o_ti + sizeof(int32_t) * n,
+               o_st = o_rd + sizeof(int32_t) * n, res_bytes = o_st + n, o_pend = (res_bytes + 7) & ~(size_t)7,
+               o_hdr = (o_pend + sizeof(int32_t) * n + 7) & ~(size_t)7, dev_bytes = o_hdr + 3 * sizeof(int64_t);
+  const size_t lmc_bytes = lmc ? sizeof(double) * (size_t)ctx->n_nodes : 0;
+  int rc = arena_begin(ctx, blk_bytes + res_bytes + (lmc_bytes <= (1u << 20) ? lmc_bytes : 0) + 1024);
+  if (rc) return rc;
+  RRTX_HIP(ctx, ctx->ws_tgt_blk[0].ensure(blk_bytes));
+  RRTX_HIP(ctx, ctx->ws_tgt_blk[1].ensure(blk_bytes));
+  RRTX_HIP(ctx, ctx->ws_tgt_res.ensure(dev_bytes));
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(sizeof(int64_t) * (n + 2)));
+  char *up = arena_take(ctx, blk_bytes);
+  char *host_res = arena_take(ctx, res_bytes);
+  int64_t *host_hdr = reinterpret_cast<int64_t *>(arena_take(ctx, 3 * sizeof(int64_t)));
+  if (!up || !host_res || !host_hdr) return fail(ctx, RRTX_E_NOMEM, "%s: staging arena", fn);
+  {
+    std::memcpy(up, pose, o_rad);
+    double *rad = reinterpret_cast<double *>(up + o_rad), *thr = reinterpret_cast<double *>(up + o_thr);
+    int32_t *slot = reinterpret_cast<int32_t *>(up + o_slot);
+    double last_r = std::nan(""), lt = 0, gt = 0;
+    for (int i = 0; i < nq; ++i) {
+      const double r = r0[r_stride ? i : 0];
+      if (!(r == last_r)) { last_r = r; lt = thr_first_ge(r); gt = thr_first_gt(r); }
+      rad[i] = r; thr[i] = lt; thr[n + i] = gt; slot[i] = i;
+    }
+    RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_tgt_blk[0].p, up, blk_bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  const double *lmc_dev;
+  int64_t n_lmc;
+  if (lmc) {
+    if ((rc = stage_in_small(ctx, ctx->ws_sel_lmc, lmc, lmc_bytes))) return rc;
+    lmc_dev = ctx->ws_sel_lmc.as<double>(); n_lmc = ctx->n_nodes;
+  } else {
+    if ((rc = node_cost_ensure(ctx))) return rc;
+    lmc_dev = ctx->node_lmc; n_lmc = ctx->node_lmc_n;
+  }
+  char *res = ctx->ws_tgt_res.as<char>();
+  int64_t *hdr_dev = reinterpret_cast<int64_t *>(res + o_hdr);
+  // the neighbour lists stay on the device, in the buffers and with the capacity rule of rrtx_extend_select: sized from
+  // what the last search produced, and a round that produces more grows them and runs once more
+  int64_t lcap = ctx->sel_list_cap > 0 ? ctx->sel_list_cap
+                                       : std::max<int64_t>(ctx->last_neighbors + ctx->last_neighbors / 8, std::max<int64_t>(64 * (int64_t)nq, 1024));
+  int n_act = nq, side = 0;
+  for (int round = 1; n_act > 0; ++round, side ^= 1) {
+    if (round > 64) return fail(ctx, RRTX_E_STATE, "%s: %d poses still searching after 64 rounds", fn, n_act);
+    char *cur = ctx->ws_tgt_blk[side].as<char>(), *nxt = ctx->ws_tgt_blk[side ^ 1].as<char>();
+    const double *q_dev = reinterpret_cast<const double *>(cur);
+    for (int attempt = 0;; ++attempt) {
+      RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)lcap));
+      RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (dubins ? 3 : 1) * (size_t)lcap));   // key, cost_out, cost_in
+      RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)lcap));
+      RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)lcap));
+      RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)lcap));
+      ctx->sel_list_cap = lcap;
+      int64_t *off_dev = ctx->ws_out_off.as<int64_t>();
+      int32_t *idx_dev = ctx->ws_out_idx.as<int32_t>(), *owner_dev = ctx->ws_owner.as<int32_t>();
+      double *key_dev = ctx->ws_out_dist.as<double>();
+      uint8_t *ho_dev = ctx->ws_out_u8a.as<uint8_t>(), *hi_dev = ctx->ws_out_u8b.as<uint8_t>();
+      const double *cost_dev = key_dev;
+      rc = launch_nn_radius(ctx, q_dev, reinterpret_cast<const double *>(cur + o_thr), 0.0, n_act, off_dev, idx_dev, key_dev,
+                            lcap, hdr_dev, owner_dev);
+      if (rc) return rc;
+      if (dubins) {
+        cost_dev = key_dev + lcap;
+        rc = launch_candidate_dubins(ctx, q_dev, n_act, off_dev, idx_dev, owner_dev, lcap, r_min, robot_radius,
+                                     key_dev + lcap, key_dev + 2 * lcap, nullptr, nullptr, ho_dev, hi_dev);
+      } else if (ctx->opt_extend_polygons) {
+        rc = launch_candidate_edges_polygons(ctx, q_dev, n_act, off_dev, idx_dev, owner_dev, lcap, robot_radius, ho_dev,
+                                             hi_dev, nullptr, -1.0);
+      } else {      // (r < 0: the radii differ from pose to pose, every sphere is looked at)
+        rc = launch_candidate_edges(ctx, q_dev, n_act, off_dev, idx_dev, owner_dev, lcap, robot_radius, ho_dev, hi_dev, -1.0,
+                                    nullptr);
+      }
+      if (rc) return rc;
+      TargetRound T;
+      T.n_act = n_act; T.nq = nq; T.round = round; T.dim = ctx->dim; T.r_max = r_max;
+      T.offsets = off_dev; T.idx = idx_dev; T.cost = cost_dev; T.hit_out = ho_dev;
+      T.n_valid = hdr_dev; T.cap = (long long)lcap;
+      T.lmc = lmc_dev; T.n_lmc = (long long)n_lmc;
+      T.q = q_dev; T.rad = reinterpret_cast<const double *>(cur + o_rad); T.slot = reinterpret_cast<const int32_t *>(cur + o_slot);
+      T.pending = reinterpret_cast<int32_t *>(res + o_pend);
+      T.cost_to_goal = reinterpret_cast<double *>(res); T.edge_dist = reinterpret_cast<double *>(res + o_ed);
+      T.radius_used = reinterpret_cast<double *>(res + o_ru); T.target_idx = reinterpret_cast<int32_t *>(res + o_ti);
+      T.rounds = reinterpret_cast<int32_t *>(res + o_rd); T.status = reinterpret_cast<uint8_t *>(res + o_st);
+      T.q_next = reinterpret_cast<double *>(nxt); T.rad_next = reinterpret_cast<double *>(nxt + o_rad);
+      T.thr_next = reinterpret_cast<double *>(nxt + o_thr); T.slot_next = reinterpret_cast<int32_t *>(nxt + o_slot);
+      T.hdr = hdr_dev;
+      if ((rc = launch_target_round(ctx, T))) return rc;
+      RRTX_HIP(ctx, hipMemcpyAsync(host_hdr, hdr_dev, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+      RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      const int64_t total = host_hdr[0];
+      ctx->last_neighbors = total;
+      if (total <= lcap) break;
+      if (attempt) return fail(ctx, RRTX_E_STATE, "%s: %lld neighbours after growing to %lld", fn, (long long)total, (long long)lcap);
+      lcap = total + total / 8;
+    }
+    if (host_hdr[1] < 0 || host_hdr[1] > n_act) return fail(ctx, RRTX_E_STATE, "%s: round %d left %lld of %d poses", fn, round, (long long)host_hdr[1], n_act);
+    n_act = (int)host_hdr[1];
+    // twice the radius is eight times the ball: make room for what the poses that go on will find (at most every node each)
+    const int64_t guess = std::min<int64_t>(host_hdr[2] * 8, (int64_t)n_act * ctx->n_nodes);
+    if (guess > lcap) lcap = guess + guess / 8;
+  }
+  RRTX_HIP(ctx, hipMemcpyAsync(host_res, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(cost_to_goal, host_res, sizeof(double) * n);
+  std::memcpy(edge_dist, host_res + o_ed, sizeof(double) * n);
+  std::memcpy(radius_used, host_res + o_ru, sizeof(double) * n);
+  std::memcpy(target_idx, host_res + o_ti, sizeof(int32_t) * n);
+  std::memcpy(rounds, host_res + o_rd, sizeof(int32_t) * n);
+  std::memcpy(status, host_res + o_st, n);
+  return RRTX_OK;
+}
+}  // namespace
+
+int rrtx_find_new_target(rrtx_ctx *ctx, const double *pose, int nq, const double *r0, int r_stride, double r_max,
+                         double robot_radius, const double *lmc, int32_t *target_idx, double *edge_dist,
+                         double *cost_to_goal, double *radius_used, int32_t *rounds, uint8_t *status) {
+  CHECK_CTX(ctx);
+  return find_new_target(ctx, "find_new_target", false, pose, nq, r0, r_stride, r_max, robot_radius, 0.0, lmc, target_idx,
+                         edge_dist, cost_to_goal, radius_used, rounds, status);
+}
+
+int rrtx_find_new_target_dubins(rrtx_ctx *ctx, const double *pose, int nq, const double *r0, int r_stride, double r_max,
+                                double robot_radius, double r_min, const double *lmc, int32_t *target_idx,
+                                double *edge_dist, double *cost_to_goal, double *radius_used, int32_t *rounds,
+                                uint8_t *status) {
+  CHECK_CTX(ctx);
+  return find_new_target(ctx, "find_new_target_dubins", true, pose, nq, r0, r_stride, r_max, robot_radius, r_min, lmc,
+                         target_idx, edge_dist, cost_to_goal, radius_used, rounds, status);
 }
 
 }  // extern "C"

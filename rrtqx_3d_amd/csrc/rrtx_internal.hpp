@@ -239,6 +239,10 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_sel_rwn, ws_sel_rwv, ws_sel_lmc;   // ... its rewire lists and a caller-given rrtLMC array
   int64_t sel_list_cap = 0;         // ... entries its neighbour lists have room for
 
+  // move-target selection (kernels_target.hip): the two query blocks the rounds alternate between, each
+  // [pose | radius | thr_lt, thr_gt | slot] of the poses still searching, and [results | pending | header]
+  rrtx::DevBuf ws_tgt_blk[2], ws_tgt_res;
+
   // radius -> threshold cache
   double thr_cache_r = -1.0, thr_cache_lt = 0.0, thr_cache_gt = 0.0;
 
@@ -417,6 +421,24 @@ struct SelectLaunch {
   int64_t *rw_offsets; int32_t *rw_node; double *rw_value; int64_t rw_cap; int64_t *rw_needed_dev;
 };
 int launch_select(rrtx_ctx *ctx, const SelectLaunch &L);
+
+// findNewTarget, one round (kernels_target.hip): the first minimum of lmc[node] + cost over the unblocked entries of
+// every pose still searching, then the poses without one move on to the next round's query block with twice the radius
+// (or leave as NOT_FOUND beyond r_max).  Device pointers; also the argument record of the two kernels.
+struct TargetRound {
+  int n_act, nq, round, dim;        // poses of this round; poses of the call; 1-based round; doubles per pose
+  double r_max;
+  const int64_t *offsets;           // CSR of the round over its n_act poses
+  const int32_t *idx; const double *cost; const uint8_t *hit_out;
+  const int64_t *n_valid; long long cap;      // entries the search produced; entries the list arrays hold
+  const double *lmc; long long n_lmc;
+  const double *q, *rad; const int32_t *slot; // this round's block: pose, radius, index of the pose in the call
+  int32_t *pending;                 // n_act: -1 resolved, else the length of the list that gave no target
+  double *cost_to_goal, *edge_dist, *radius_used; int32_t *target_idx, *rounds; uint8_t *status;   // nq each
+  double *q_next, *rad_next, *thr_next; int32_t *slot_next;   // next round's block (thr_gt follows n_next thr_lt)
+  int64_t *hdr;                     // [1] poses of the next round (-1: this round overflowed), [2] entries they had
+};
+int launch_target_round(rrtx_ctx *ctx, const TargetRound &T);
 int node_cost_ensure(rrtx_ctx *ctx);   // ctx->node_lmc covers every node (new slots +Inf)
 
 // make sure the packed obstacle tables on the device match the host truth

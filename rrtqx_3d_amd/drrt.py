@@ -22,6 +22,8 @@ implementation behind these names: without the HIP library / a GPU they raise.
     explicitEdgeCheck(S, edge[, ob]),            same names (+ batched plural forms)
       explicitPointCheck, explicitNodeCheck
       (R/DRRT_Q.jl:1520-1595, 1775-1826)
+    findNewTarget(S, KD, R, hyberBallRad)        same name, RobotData (one robot or a batch)
+      (R/DRRT_Q.jl:2901-2994)
 """
 from __future__ import annotations
 
@@ -571,6 +573,63 @@ def extend_select(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, 
             out["parent_idx"][s] = near.index
             out["lmc_new"][s] = near_lmc + e.dist
             # (the one neighbour is the parent, so the rewire test has nobody to ask)
+    return out
+
+
+class RobotData:
+    """The fields of RobotData{T} that findNewTarget reads and writes (R/DRRT_data_structures.jl)."""
+
+    def __init__(self, robotPose, nextMoveTarget: Optional[RRTNode] = None):
+        self.robotPose = np.asarray(robotPose, dtype=np.float64).reshape(-1)
+        self.nextMoveTarget = nextMoveTarget
+        self.distanceFromNextRobotPoseToNextMoveTarget = 0.0
+        self.currentMoveInvalid = True
+        self.robotEdgeUsed = False
+        self.distAlongRobotEdge = 0.0
+        self.timeAlongRobotEdge = 0.0
+
+
+def findNewTarget(S: CSpace, KD: HipTree, R, hyberBallRad_: float, lmc=None):
+    """findNewTarget(S, KD, R, hyberBallRad) (R/DRRT_Q.jl:2901-2994) on the device: the first ball is
+    min(max(hyberBallRad, dist(R.robotPose, R.nextMoveTarget.position)), maxSearchBallRad) with maxSearchBallRad =
+    dist(S.lowerBounds, S.upperBounds); every neighbour's edge from the pose is steered and checked, the one with the
+    lowest rrtLMC + edge.dist becomes R.nextMoveTarget (with R.distanceFromNextRobotPoseToNextMoveTarget = edge.dist and
+    R.currentMoveInvalid = false); the ball doubles while there is none and error("unable to find a valid move target")
+    is raised once it exceeds maxSearchBallRad.  R is one RobotData or a sequence of them (the agents of R/rrtqx.jl, one
+    batch on the device; the robots before the one that raises have been updated).  lmc: rrtLMC per node in insertion
+    order, or None for the values Context.node_cost_set left on the device.  The edge type is the tree's: SimpleEdge for
+    d = 3, DubinsEdge (S.minTurningRadius, S.spaceHasTime) for d = 4; dist is KD.distanceFunction when given, else the
+    Euclidean distance."""
+    robots = [R] if isinstance(R, RobotData) else list(R)
+    if S.inWarmupTime:
+        error("findNewTarget checks obstacles: not during warm-up")
+    S.bind(KD)
+    kind = _sync_obstacles(S)
+    from . import _capi
+    dist = KD.distanceFunction or (lambda a, b: math.sqrt(sum((float(x) - float(y)) ** 2 for x, y in zip(a, b))))
+    maxSearchBallRad = float(dist(S.lowerBounds, S.upperBounds))
+    r0 = []
+    for rb in robots:
+        rb.robotEdgeUsed = False
+        rb.distAlongRobotEdge = 0.0
+        rb.timeAlongRobotEdge = 0.0
+        searchBallRad = float(hyberBallRad_)
+        if rb.nextMoveTarget is not None:
+            searchBallRad = max(searchBallRad, float(dist(rb.robotPose, rb.nextMoveTarget.position.reshape(-1))))
+        r0.append(min(searchBallRad, maxSearchBallRad))
+    pose = np.array([rb.robotPose for rb in robots], dtype=np.float64).reshape(-1, KD.d)
+    if KD.d == 3:
+        KD.ctx.set_option(_capi.RRTX_OPT_EXTEND_OBSTACLES, kind)
+        out = KD.ctx.find_new_target(pose, r0, maxSearchBallRad, S.robotRadius, lmc=lmc)
+    else:
+        KD.ctx.set_space_has_time(bool(S.spaceHasTime))
+        out = KD.ctx.find_new_target_dubins(pose, r0, maxSearchBallRad, S.robotRadius, S.minTurningRadius, lmc=lmc)
+    for i, rb in enumerate(robots):
+        if out["status"][i] != _capi.RRTX_TGT_OK:
+            error("unable to find a valid move target")
+        rb.nextMoveTarget = KD.nodes[int(out["target_idx"][i])]
+        rb.distanceFromNextRobotPoseToNextMoveTarget = float(out["edge_dist"][i])
+        rb.currentMoveInvalid = False
     return out
 
 
