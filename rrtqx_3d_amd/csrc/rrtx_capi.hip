@@ -432,6 +432,116 @@ static int stage_in_small(rrtx_ctx *ctx, DevBuf &buf, const void *host, size_t b
   return RRTX_OK;
 }
 
+// ---- packed blocks: what a batched call holds per sample, in one allocation so that it moves in one transfer ----
+// A block is described once, as an ordered list of typed fields (the structs below).  The description gives the byte
+// size of the transfer and every field's address under any base: the device block or its copy in the pinned arena.
+template <class T>
+struct Field {
+  size_t off, count;
+  T *in(void *base) const { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
+  size_t bytes() const { return sizeof(T) * count; }
+  void to(T *dst, void *base) const { std::memcpy(dst, in(base), bytes()); }
+};
+// `n` elements of T appended to a block of `bytes` bytes, at T's own alignment unless one is given
+template <class T>
+Field<T> take(size_t &bytes, size_t n, size_t align = alignof(T)) {
+  bytes = (bytes + align - 1) & ~(align - 1);
+  const Field<T> f{bytes, n};
+  bytes += f.bytes();
+  return f;
+}
+// (a block is made from its sample count alone, B{n}: the fields are then initialised in the order they are declared,
+// which is the layout, and `bytes` grows with them to the size of the block)
+struct CandidatesBlock {            // rrtx_extend_candidates
+  size_t n, bytes = 0;
+  Field<int64_t> offsets = take<int64_t>(bytes, n + 1), count = take<int64_t>(bytes, 1);
+  Field<double> nearest_dist = take<double>(bytes, n);
+  Field<int32_t> nearest_idx = take<int32_t>(bytes, n);
+  Field<uint8_t> sample_unsafe = take<uint8_t>(bytes, n);
+};
+struct SelectBlock {                // rrtx_extend_select
+  size_t n, bytes = 0;
+  Field<int64_t> counts = take<int64_t>(bytes, 2);              // list entries, rewire entries
+  Field<int64_t> rw_offsets = take<int64_t>(bytes, n + 1), parent_entry = take<int64_t>(bytes, n);
+  Field<double> lmc_new = take<double>(bytes, n), nearest_dist = take<double>(bytes, n);
+  Field<int32_t> parent_idx = take<int32_t>(bytes, n), nearest_idx = take<int32_t>(bytes, n);
+  Field<uint8_t> status = take<uint8_t>(bytes, n), sample_unsafe = take<uint8_t>(bytes, n);
+  Field<int64_t> offsets = take<int64_t>(bytes, n + 1, 8);      // the tail: leaves only if the caller wants the lists
+  size_t bytes_without_lists = offsets.off;
+};
+struct TargetQueryBlock {           // find_new_target: the poses still searching, one block per round side
+  size_t n, dim, bytes = 0;
+  Field<double> pose = take<double>(bytes, n * dim), rad = take<double>(bytes, n);
+  Field<double> thr = take<double>(bytes, 2 * n);               // thr_lt of every pose, then thr_gt
+  Field<int32_t> slot = take<int32_t>(bytes, n);
+};
+struct TargetResultBlock {          // find_new_target: what leaves at the end, then the rounds' own words
+  size_t n, bytes = 0;
+  Field<double> cost_to_goal = take<double>(bytes, n), edge_dist = take<double>(bytes, n), radius_used = take<double>(bytes, n);
+  Field<int32_t> target_idx = take<int32_t>(bytes, n), rounds = take<int32_t>(bytes, n);
+  Field<uint8_t> status = take<uint8_t>(bytes, n);
+  size_t result_bytes = bytes;
+  Field<int32_t> pending = take<int32_t>(bytes, n, 8);
+  Field<int64_t> hdr = take<int64_t>(bytes, 3, 8);              // TargetRound::hdr
+};
+
+// thr_first_ge / thr_first_gt of per-query radii r[i * r_stride] (a run of equal radii is worked out once)
+void fill_thresholds(const double *r, int r_stride, int nq, double *lt, double *gt) {
+  double last_r = std::nan(""), l = 0, g = 0;
+  for (int i = 0; i < nq; ++i) {
+    const double ri = r[(size_t)i * r_stride];
+    if (!(ri == last_r)) { last_r = ri; l = thr_first_ge(ri); g = thr_first_gt(ri); }
+    lt[i] = l; gt[i] = g;
+  }
+}
+
+// rrtLMC of a call: the caller's host array staged into ws_sel_lmc, or (null) the context's own array as
+// rrtx_node_cost_set left it.  Call after arena_begin, which has reserved lmc_arena_need for it (what stage_in_small
+// takes from the arena for an array of that size).
+struct Lmc { const double *dev; int64_t n; };
+size_t lmc_arena_need(const rrtx_ctx *ctx, const double *lmc_host) {
+  const size_t bytes = lmc_host ? sizeof(double) * (size_t)ctx->n_nodes : 0;
+  return bytes <= (1u << 20) ? bytes : 0;
+}
+int resolve_lmc(rrtx_ctx *ctx, const double *lmc_host, Lmc *lmc) {
+  int rc = lmc_host ? stage_in_small(ctx, ctx->ws_sel_lmc, lmc_host, sizeof(double) * (size_t)ctx->n_nodes) : node_cost_ensure(ctx);
+  *lmc = lmc_host ? Lmc{ctx->ws_sel_lmc.as<double>(), ctx->n_nodes} : Lmc{ctx->node_lmc, ctx->node_lmc_n};
+  return rc;
+}
+
+// The neighbour lists of rrtx_extend_select and find_new_target stay on the device, in ws_out_idx / _dist / _u8a / _u8b
+// (and ws_owner).  Their capacity is the context's business: sized once from what the last search produced, and when an
+// attempt produces more, grown to that with an eighth of headroom and the attempt made once more.  `attempt` enqueues
+// the search and what follows it over lists of L.cap entries; the `bytes` at `dev`, which begin with the int64 count of
+// entries the search produced, are then read back into the arena at `host`.
+struct NeighbourLists { int32_t *idx, *owner; double *key; uint8_t *hit_out, *hit_in; int64_t cap; };
+template <class Attempt>
+int with_neighbour_lists(rrtx_ctx *ctx, const char *fn, int nq, int64_t at_least, int key_arrays, bool want_owner, void *host,
+                         const void *dev, size_t bytes, Attempt attempt) {
+  int64_t cap = ctx->sel_list_cap > 0 ? ctx->sel_list_cap
+                                      : std::max<int64_t>(ctx->last_neighbors + ctx->last_neighbors / 8, std::max<int64_t>(64 * (int64_t)nq, 1024));
+  cap = std::max(cap, at_least);
+  for (int again = 0;; ++again) {
+    RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)cap));
+    RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)key_arrays * (size_t)cap));   // Dubins: key, cost_out, cost_in
+    RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)cap));
+    RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)cap));
+    if (want_owner) RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)cap));
+    ctx->sel_list_cap = cap;
+    const NeighbourLists L = {ctx->ws_out_idx.as<int32_t>(), ctx->ws_owner.as<int32_t>(), ctx->ws_out_dist.as<double>(),
+                              ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(), cap};
+    int rc = attempt(L);
+    if (rc) return rc;
+    RRTX_HIP(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t total = *static_cast<const int64_t *>(host);
+    ctx->last_neighbors = total;
+    if (total <= cap) return RRTX_OK;
+    if (again) return fail(ctx, RRTX_E_STATE, "%s: %lld neighbours after growing to %lld", fn, (long long)total, (long long)cap);
+    cap = total + total / 8;
+  }
+}
+
 std::string g_create_err;
 std::mutex g_create_mu;
 
@@ -916,11 +1026,7 @@ int rrtx_nn_radius(rrtx_ctx *ctx, const double *q, const double *r, int r_stride
   const double *thr_dev = nullptr;
   if (r_stride == 1) {
     std::vector<double> thr(2 * (size_t)nq);
-    double last_r = std::nan(""), lt = 0, gt = 0;
-    for (int i = 0; i < nq; ++i) {
-      if (!(r[i] == last_r)) { last_r = r[i]; lt = thr_first_ge(r[i]); gt = thr_first_gt(r[i]); }
-      thr[i] = lt; thr[(size_t)nq + i] = gt;
-    }
+    fill_thresholds(r, 1, nq, thr.data(), thr.data() + nq);
     RRTX_HIP(ctx, stage_in(ctx, ctx->ws_thr, thr.data(), sizeof(double) * thr.size()));
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // thr goes out of scope
     thr_dev = ctx->ws_thr.as<double>();
@@ -1534,41 +1640,35 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
   int rc = extend_candidates_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
   if (rc) return rc;
   if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
-  // ONE small device block for everything that is per sample -- [offsets (nq + 1) | count | nearest_dist (nq) |
-  // nearest_idx (nq) | sample_unsafe (nq)] -- so that it leaves in one transfer; the per-entry arrays follow once the
-  // count is known.  Small transfers go through the context's pinned arena, large ones straight to the caller.
+  // Everything that is per sample sits in ONE small device block (CandidatesBlock), so that it leaves in one transfer;
+  // the per-entry arrays follow once the count is known.  Small transfers go through the context's pinned arena, large
+  // ones straight to the caller.
   const int64_t dcap = cap > 0 ? cap : 1;
-  const size_t o_cnt = sizeof(int64_t) * ((size_t)nq + 1), o_nd = o_cnt + sizeof(int64_t), o_ni = o_nd + sizeof(double) * (size_t)nq,
-               o_un = o_ni + sizeof(int32_t) * (size_t)nq, small_bytes = o_un + (size_t)nq;
-  rc = arena_begin(ctx, small_bytes + sizeof(double) * (size_t)nq * ctx->dim + 256);
+  const CandidatesBlock B{(size_t)nq};
+  rc = arena_begin(ctx, B.bytes + sizeof(double) * (size_t)nq * ctx->dim + 256);
   if (rc) return rc;
   rc = stage_in_small(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim);
   if (rc) return rc;
-  RRTX_HIP(ctx, ctx->ws_out_off.ensure(small_bytes + 64));
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(B.bytes + 64));
   RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)dcap));
   RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)dcap));
   RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)dcap));
   RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)dcap));
   char *blk = ctx->ws_out_off.as<char>();
-  int64_t *off_dev = reinterpret_cast<int64_t *>(blk);
-  int64_t *needed_dev = off_dev + nq + 1;
-  double *nd_dev = reinterpret_cast<double *>(blk + o_nd);
-  int32_t *ni_dev = reinterpret_cast<int32_t *>(blk + o_ni);
-  uint8_t *unsafe_dev = reinterpret_cast<uint8_t *>(blk + o_un);
   const bool want_nearest = nearest_idx && nearest_dist;
-  rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, off_dev,
+  rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, B.offsets.in(blk),
                                   ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_dist.as<double>(),
-                                  ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(), cap, needed_dev,
-                                  want_nearest ? ni_dev : nullptr, want_nearest ? nd_dev : nullptr,
-                                  sample_unsafe ? unsafe_dev : nullptr);
+                                  ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(), cap, B.count.in(blk),
+                                  want_nearest ? B.nearest_idx.in(blk) : nullptr,
+                                  want_nearest ? B.nearest_dist.in(blk) : nullptr,
+                                  sample_unsafe ? B.sample_unsafe.in(blk) : nullptr);
   if (rc) return rc;
-  char *host_blk = arena_take(ctx, small_bytes);
+  char *host_blk = arena_take(ctx, B.bytes);
   if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "extend_candidates: staging arena");
-  RRTX_HIP(ctx, hipMemcpyAsync(host_blk, blk, small_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, hipMemcpyAsync(host_blk, blk, B.bytes, hipMemcpyDeviceToHost, ctx->stream));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  int64_t total = 0;
-  std::memcpy(offsets, host_blk, o_cnt);
-  std::memcpy(&total, host_blk + o_cnt, sizeof(int64_t));
+  B.offsets.to(offsets, host_blk);
+  const int64_t total = *B.count.in(host_blk);
   ctx->last_neighbors = total;
   if ((rc = check_capacity(ctx, "extend_candidates", "neighbours", total, cap, needed))) return rc;
   if (total > 0) {
@@ -1578,10 +1678,10 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
     if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
   }
   // (the per-sample results are copied out of the arena while the per-entry transfers are in flight)
-  if (sample_unsafe) std::memcpy(sample_unsafe, host_blk + o_un, (size_t)nq);
+  if (sample_unsafe) B.sample_unsafe.to(sample_unsafe, host_blk);
   if (want_nearest) {
-    std::memcpy(nearest_dist, host_blk + o_nd, sizeof(double) * (size_t)nq);
-    std::memcpy(nearest_idx, host_blk + o_ni, sizeof(int32_t) * (size_t)nq);
+    B.nearest_dist.to(nearest_dist, host_blk);
+    B.nearest_idx.to(nearest_idx, host_blk);
   }
   if (total > 0) {
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1692,6 +1792,21 @@ int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit
 }
 
 // ---- parent and rewire selection over the extend lists (kernels_select.hip) -----------------------
+// (the selection over lists on the device, rrtLMC a device array or null for the context's own: shared by the _dev entry
+// point and rrtx_extend_select, which runs it inside its own call)
+static int select_over_lists(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
+                             const double *cost_in, const uint8_t *hit_out, const uint8_t *hit_in,
+                             const int64_t *n_valid_dev, int64_t cap, const uint8_t *sample_unsafe, Lmc lmc,
+                             int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
+                             int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
+                             int64_t *rw_needed_dev) {
+  int rc = lmc.dev ? RRTX_OK : resolve_lmc(ctx, nullptr, &lmc);
+  if (rc) return rc;
+  return launch_select(ctx, SelectLaunch{nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, n_valid_dev, cap,
+                                         sample_unsafe, lmc.dev, lmc.n, parent_idx, parent_entry, lmc_new, status, rw_offsets,
+                                         rw_node, rw_value, rw_cap, rw_needed_dev});
+}
+
 int rrtx_extend_select_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
                            const double *cost_in, const uint8_t *hit_out, const uint8_t *hit_in,
                            const int64_t *n_valid_dev, int64_t cap, const uint8_t *sample_unsafe, const double *lmc,
@@ -1703,21 +1818,8 @@ int rrtx_extend_select_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const 
       (nq > 0 && (!parent_idx || !parent_entry || !lmc_new || !status)) ||
       (cap > 0 && (!idx || !cost_out || !cost_in || !hit_out || !hit_in)) || (rw_cap > 0 && (!rw_node || !rw_value)))
     return fail(ctx, RRTX_E_INVALID, "extend_select: bad arguments");
-  SelectLaunch L;
-  L.nq = nq;
-  L.offsets = offsets; L.idx = idx; L.cost_out = cost_out; L.cost_in = cost_in; L.hit_out = hit_out; L.hit_in = hit_in;
-  L.n_valid_dev = n_valid_dev; L.cap = cap;
-  L.sample_unsafe = sample_unsafe;
-  L.lmc = lmc; L.n_lmc = ctx->n_nodes;
-  if (!lmc) {
-    int rc = node_cost_ensure(ctx);
-    if (rc) return rc;
-    L.lmc = ctx->node_lmc; L.n_lmc = ctx->node_lmc_n;
-  }
-  L.parent_idx = parent_idx; L.parent_entry = parent_entry; L.lmc_new = lmc_new; L.status = status;
-  L.rw_offsets = rw_offsets; L.rw_node = rw_node; L.rw_value = rw_value; L.rw_cap = rw_cap;
-  L.rw_needed_dev = rw_needed_dev;
-  return launch_select(ctx, L);
+  return select_over_lists(ctx, nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, n_valid_dev, cap, sample_unsafe,
+                           Lmc{lmc, ctx->n_nodes}, parent_idx, parent_entry, lmc_new, status, rw_offsets, rw_node, rw_value, rw_cap, rw_needed_dev);
 }
 
 int rrtx_node_cost_set(rrtx_ctx *ctx, int64_t first_index, const double *lmc, int64_t n) {
@@ -1752,92 +1854,49 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
     if (needed) *needed = 0;
     return RRTX_OK;
   }
-  // ONE device block for everything that is per sample -- [entry count, rewire count | rw_offsets | parent_entry |
-  // lmc_new | nearest_dist | parent_idx | nearest_idx | status | sample_unsafe | offsets] -- so that it leaves in one
-  // transfer (without its tail, the list offsets, unless the caller wants the lists).
+  // Everything that is per sample sits in ONE device block (SelectBlock), so that it leaves in one transfer: without
+  // its tail, the list offsets, unless the caller wants the lists.
   const size_t n = (size_t)nq;
-  const size_t o_rwoff = 2 * sizeof(int64_t), o_pe = o_rwoff + sizeof(int64_t) * (n + 1), o_ln = o_pe + sizeof(int64_t) * n,
-               o_nd = o_ln + sizeof(double) * n, o_pi = o_nd + sizeof(double) * n, o_ni = o_pi + sizeof(int32_t) * n,
-               o_st = o_ni + sizeof(int32_t) * n, o_un = o_st + n, o_off = (o_un + n + 7) & ~(size_t)7,
-               blk_bytes = o_off + sizeof(int64_t) * (n + 1), out_bytes = want_lists ? blk_bytes : o_off;
-  const size_t q_bytes = sizeof(double) * n * (size_t)ctx->dim, lmc_bytes = lmc ? sizeof(double) * (size_t)ctx->n_nodes : 0;
+  const SelectBlock B{n};
+  const size_t out_bytes = want_lists ? B.bytes : B.bytes_without_lists;
+  const size_t q_bytes = sizeof(double) * n * (size_t)ctx->dim;
   const size_t staged = (256u << 10) + 64;   // what d2h may take per small output array
-  int rc = arena_begin(ctx, out_bytes + q_bytes + (lmc_bytes <= (1u << 20) ? lmc_bytes : 0) + 6 * staged + 512);
+  int rc = arena_begin(ctx, out_bytes + q_bytes + lmc_arena_need(ctx, lmc) + 6 * staged + 512);
   if (rc) return rc;
   if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
-  const double *lmc_dev;
-  int64_t n_lmc;
-  if (lmc) {
-    if ((rc = stage_in_small(ctx, ctx->ws_sel_lmc, lmc, lmc_bytes))) return rc;
-    lmc_dev = ctx->ws_sel_lmc.as<double>(); n_lmc = ctx->n_nodes;
-  } else {
-    if ((rc = node_cost_ensure(ctx))) return rc;
-    lmc_dev = ctx->node_lmc; n_lmc = ctx->node_lmc_n;
-  }
-  RRTX_HIP(ctx, ctx->ws_sel_blk.ensure(blk_bytes + 64));
+  Lmc lmc_dev;
+  if ((rc = resolve_lmc(ctx, lmc, &lmc_dev))) return rc;
+  RRTX_HIP(ctx, ctx->ws_sel_blk.ensure(B.bytes + 64));
   RRTX_HIP(ctx, ctx->ws_sel_rwn.ensure(sizeof(int32_t) * (size_t)(rw_cap > 0 ? rw_cap : 1)));
   RRTX_HIP(ctx, ctx->ws_sel_rwv.ensure(sizeof(double) * (size_t)(rw_cap > 0 ? rw_cap : 1)));
   char *blk = ctx->ws_sel_blk.as<char>();
-  int64_t *hdr_dev = reinterpret_cast<int64_t *>(blk);
   char *host_blk = arena_take(ctx, out_bytes);
   if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "extend_select: staging arena");
-  // the neighbour lists stay on the device; their capacity is the context's business: sized once from what the last
-  // search produced, and when a call produces more, grown to that and the call run once more
-  int64_t lcap = ctx->sel_list_cap > 0 ? ctx->sel_list_cap
-                                       : std::max<int64_t>(ctx->last_neighbors + ctx->last_neighbors / 8, std::max<int64_t>(64 * (int64_t)nq, 1024));
-  int64_t total = 0, rw_total = 0;
-  for (int attempt = 0;; ++attempt) {
-    RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)lcap));
-    RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)lcap));
-    RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)lcap));
-    RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)lcap));
-    ctx->sel_list_cap = lcap;
-    const bool want_nearest = nearest_idx && nearest_dist;
-    rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, reinterpret_cast<int64_t *>(blk + o_off),
-                                    ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_dist.as<double>(),
-                                    ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(), lcap, hdr_dev,
-                                    want_nearest ? reinterpret_cast<int32_t *>(blk + o_ni) : nullptr,
-                                    want_nearest ? reinterpret_cast<double *>(blk + o_nd) : nullptr,
-                                    reinterpret_cast<uint8_t *>(blk + o_un));
-    if (rc) return rc;
-    SelectLaunch L;
-    L.nq = nq;
-    L.offsets = reinterpret_cast<int64_t *>(blk + o_off);
-    L.idx = ctx->ws_out_idx.as<int32_t>();
-    L.cost_out = L.cost_in = ctx->ws_out_dist.as<double>();
-    L.hit_out = ctx->ws_out_u8a.as<uint8_t>(); L.hit_in = ctx->ws_out_u8b.as<uint8_t>();
-    L.n_valid_dev = hdr_dev; L.cap = lcap;
-    L.sample_unsafe = reinterpret_cast<uint8_t *>(blk + o_un);
-    L.lmc = lmc_dev; L.n_lmc = n_lmc;
-    L.parent_idx = reinterpret_cast<int32_t *>(blk + o_pi);
-    L.parent_entry = reinterpret_cast<int64_t *>(blk + o_pe);
-    L.lmc_new = reinterpret_cast<double *>(blk + o_ln);
-    L.status = reinterpret_cast<uint8_t *>(blk + o_st);
-    L.rw_offsets = reinterpret_cast<int64_t *>(blk + o_rwoff);
-    L.rw_node = ctx->ws_sel_rwn.as<int32_t>(); L.rw_value = ctx->ws_sel_rwv.as<double>(); L.rw_cap = rw_cap;
-    L.rw_needed_dev = hdr_dev + 1;
-    if ((rc = launch_select(ctx, L))) return rc;
-    RRTX_HIP(ctx, hipMemcpyAsync(host_blk, blk, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(&total, host_blk, sizeof(int64_t));
-    ctx->last_neighbors = total;
-    if (total <= lcap) break;
-    if (attempt) return fail(ctx, RRTX_E_STATE, "extend_select: %lld neighbours after growing to %lld", (long long)total, (long long)lcap);
-    lcap = total + total / 8;
-  }
-  std::memcpy(&rw_total, host_blk + sizeof(int64_t), sizeof(int64_t));
-  std::memcpy(rw_offsets, host_blk + o_rwoff, sizeof(int64_t) * (n + 1));
-  std::memcpy(parent_entry, host_blk + o_pe, sizeof(int64_t) * n);
-  std::memcpy(lmc_new, host_blk + o_ln, sizeof(double) * n);
-  std::memcpy(parent_idx, host_blk + o_pi, sizeof(int32_t) * n);
-  std::memcpy(status, host_blk + o_st, n);
-  if (sample_unsafe) std::memcpy(sample_unsafe, host_blk + o_un, n);
   const bool want_nearest = nearest_idx && nearest_dist;
+  rc = with_neighbour_lists(ctx, "extend_select", nq, 0, 1, false, host_blk, blk, out_bytes, [&](const NeighbourLists &L) {
+    int rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, B.offsets.in(blk), L.idx, L.key,
+                                        L.hit_out, L.hit_in, L.cap, B.counts.in(blk),
+                                        want_nearest ? B.nearest_idx.in(blk) : nullptr,
+                                        want_nearest ? B.nearest_dist.in(blk) : nullptr, B.sample_unsafe.in(blk));
+    if (rc) return rc;
+    return select_over_lists(ctx, nq, B.offsets.in(blk), L.idx, L.key, L.key, L.hit_out, L.hit_in, B.counts.in(blk), L.cap,
+                             B.sample_unsafe.in(blk), lmc_dev, B.parent_idx.in(blk), B.parent_entry.in(blk),
+                             B.lmc_new.in(blk), B.status.in(blk), B.rw_offsets.in(blk), ctx->ws_sel_rwn.as<int32_t>(),
+                             ctx->ws_sel_rwv.as<double>(), rw_cap, B.counts.in(blk) + 1);
+  });
+  if (rc) return rc;
+  const int64_t total = B.counts.in(host_blk)[0], rw_total = B.counts.in(host_blk)[1];
+  B.rw_offsets.to(rw_offsets, host_blk);
+  B.parent_entry.to(parent_entry, host_blk);
+  B.lmc_new.to(lmc_new, host_blk);
+  B.parent_idx.to(parent_idx, host_blk);
+  B.status.to(status, host_blk);
+  if (sample_unsafe) B.sample_unsafe.to(sample_unsafe, host_blk);
   if (want_nearest) {
-    std::memcpy(nearest_dist, host_blk + o_nd, sizeof(double) * n);
-    std::memcpy(nearest_idx, host_blk + o_ni, sizeof(int32_t) * n);
+    B.nearest_dist.to(nearest_dist, host_blk);
+    B.nearest_idx.to(nearest_idx, host_blk);
   }
-  if (want_lists) std::memcpy(offsets, host_blk + o_off, sizeof(int64_t) * (n + 1));
+  if (want_lists) B.offsets.to(offsets, host_blk);
   if (needed) *needed = total;
   if ((rc = check_capacity(ctx, "extend_select", "rewire entries", rw_total, rw_cap, rw_needed))) return rc;
   if (want_lists && (rc = check_capacity(ctx, "extend_select", "neighbours", total, cap, needed))) return rc;
@@ -1878,121 +1937,77 @@ int find_new_target(rrtx_ctx *ctx, const char *fn, bool dubins, const double *po
   if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "%s on an empty tree", fn);
   if (nq == 0) return RRTX_OK;
 
-  // One query block per round side, [pose | radius | thr_lt, thr_gt | slot], so that the first round's goes up in one
-  // transfer; one result block [cost_to_goal | edge_dist | radius_used | target_idx | rounds | status] that leaves in
-  // one transfer, followed by the rounds' own words [pending | header].
-  const size_t n = (size_t)nq, dim = (size_t)ctx->dim;
-  const size_t o_rad = sizeof(double) * n * dim, o_thr = o_rad + sizeof(double) * n, o_slot = o_thr + 2 * sizeof(double) * n,
-               blk_bytes = o_slot + sizeof(int32_t) * n;
-  const size_t o_ed = sizeof(double) * n, o_ru = 2 * o_ed, o_ti = 3 * o_ed, o_rd = o_ti + sizeof(int32_t) * n,
-               o_st = o_rd + sizeof(int32_t) * n, res_bytes = o_st + n, o_pend = (res_bytes + 7) & ~(size_t)7,
-               o_hdr = (o_pend + sizeof(int32_t) * n + 7) & ~(size_t)7, dev_bytes = o_hdr + 3 * sizeof(int64_t);
-  const size_t lmc_bytes = lmc ? sizeof(double) * (size_t)ctx->n_nodes : 0;
-  int rc = arena_begin(ctx, blk_bytes + res_bytes + (lmc_bytes <= (1u << 20) ? lmc_bytes : 0) + 1024);
+  // One query block per round side (TargetQueryBlock), so that the first round's goes up in one transfer; one result
+  // block (TargetResultBlock) whose results leave in one transfer at the end.
+  const size_t n = (size_t)nq;
+  const TargetQueryBlock Q{n, (size_t)ctx->dim};
+  const TargetResultBlock R{n};
+  int rc = arena_begin(ctx, Q.bytes + R.result_bytes + lmc_arena_need(ctx, lmc) + 1024);
   if (rc) return rc;
-  RRTX_HIP(ctx, ctx->ws_tgt_blk[0].ensure(blk_bytes));
-  RRTX_HIP(ctx, ctx->ws_tgt_blk[1].ensure(blk_bytes));
-  RRTX_HIP(ctx, ctx->ws_tgt_res.ensure(dev_bytes));
+  RRTX_HIP(ctx, ctx->ws_tgt_blk[0].ensure(Q.bytes));
+  RRTX_HIP(ctx, ctx->ws_tgt_blk[1].ensure(Q.bytes));
+  RRTX_HIP(ctx, ctx->ws_tgt_res.ensure(R.bytes));
   RRTX_HIP(ctx, ctx->ws_out_off.ensure(sizeof(int64_t) * (n + 2)));
-  char *up = arena_take(ctx, blk_bytes);
-  char *host_res = arena_take(ctx, res_bytes);
-  int64_t *host_hdr = reinterpret_cast<int64_t *>(arena_take(ctx, 3 * sizeof(int64_t)));
+  char *up = arena_take(ctx, Q.bytes);
+  char *host_res = arena_take(ctx, R.result_bytes);
+  int64_t *host_hdr = reinterpret_cast<int64_t *>(arena_take(ctx, R.hdr.bytes()));
   if (!up || !host_res || !host_hdr) return fail(ctx, RRTX_E_NOMEM, "%s: staging arena", fn);
-  {
-    std::memcpy(up, pose, o_rad);
-    double *rad = reinterpret_cast<double *>(up + o_rad), *thr = reinterpret_cast<double *>(up + o_thr);
-    int32_t *slot = reinterpret_cast<int32_t *>(up + o_slot);
-    double last_r = std::nan(""), lt = 0, gt = 0;
-    for (int i = 0; i < nq; ++i) {
-      const double r = r0[r_stride ? i : 0];
-      if (!(r == last_r)) { last_r = r; lt = thr_first_ge(r); gt = thr_first_gt(r); }
-      rad[i] = r; thr[i] = lt; thr[n + i] = gt; slot[i] = i;
-    }
-    RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_tgt_blk[0].p, up, blk_bytes, hipMemcpyHostToDevice, ctx->stream));
-  }
-  const double *lmc_dev;
-  int64_t n_lmc;
-  if (lmc) {
-    if ((rc = stage_in_small(ctx, ctx->ws_sel_lmc, lmc, lmc_bytes))) return rc;
-    lmc_dev = ctx->ws_sel_lmc.as<double>(); n_lmc = ctx->n_nodes;
-  } else {
-    if ((rc = node_cost_ensure(ctx))) return rc;
-    lmc_dev = ctx->node_lmc; n_lmc = ctx->node_lmc_n;
-  }
+  std::memcpy(Q.pose.in(up), pose, Q.pose.bytes());
+  for (int i = 0; i < nq; ++i) { Q.rad.in(up)[i] = r0[r_stride ? i : 0]; Q.slot.in(up)[i] = i; }
+  fill_thresholds(r0, r_stride, nq, Q.thr.in(up), Q.thr.in(up) + n);
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_tgt_blk[0].p, up, Q.bytes, hipMemcpyHostToDevice, ctx->stream));
+  Lmc lmc_dev;
+  if ((rc = resolve_lmc(ctx, lmc, &lmc_dev))) return rc;
   char *res = ctx->ws_tgt_res.as<char>();
-  int64_t *hdr_dev = reinterpret_cast<int64_t *>(res + o_hdr);
-  // the neighbour lists stay on the device, in the buffers and with the capacity rule of rrtx_extend_select: sized from
-  // what the last search produced, and a round that produces more grows them and runs once more
-  int64_t lcap = ctx->sel_list_cap > 0 ? ctx->sel_list_cap
-                                       : std::max<int64_t>(ctx->last_neighbors + ctx->last_neighbors / 8, std::max<int64_t>(64 * (int64_t)nq, 1024));
+  int64_t *hdr_dev = R.hdr.in(res), *off_dev = ctx->ws_out_off.as<int64_t>();
   int n_act = nq, side = 0;
+  int64_t room = 0;          // entries the coming round asks for beyond what the lists hold
   for (int round = 1; n_act > 0; ++round, side ^= 1) {
     if (round > 64) return fail(ctx, RRTX_E_STATE, "%s: %d poses still searching after 64 rounds", fn, n_act);
     char *cur = ctx->ws_tgt_blk[side].as<char>(), *nxt = ctx->ws_tgt_blk[side ^ 1].as<char>();
-    const double *q_dev = reinterpret_cast<const double *>(cur);
-    for (int attempt = 0;; ++attempt) {
-      RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)lcap));
-      RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (dubins ? 3 : 1) * (size_t)lcap));   // key, cost_out, cost_in
-      RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)lcap));
-      RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)lcap));
-      RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)lcap));
-      ctx->sel_list_cap = lcap;
-      int64_t *off_dev = ctx->ws_out_off.as<int64_t>();
-      int32_t *idx_dev = ctx->ws_out_idx.as<int32_t>(), *owner_dev = ctx->ws_owner.as<int32_t>();
-      double *key_dev = ctx->ws_out_dist.as<double>();
-      uint8_t *ho_dev = ctx->ws_out_u8a.as<uint8_t>(), *hi_dev = ctx->ws_out_u8b.as<uint8_t>();
-      const double *cost_dev = key_dev;
-      rc = launch_nn_radius(ctx, q_dev, reinterpret_cast<const double *>(cur + o_thr), 0.0, n_act, off_dev, idx_dev, key_dev,
-                            lcap, hdr_dev, owner_dev);
+    const double *q_dev = Q.pose.in(cur);
+    rc = with_neighbour_lists(ctx, fn, nq, room, dubins ? 3 : 1, true, host_hdr, hdr_dev, R.hdr.bytes(), [&](const NeighbourLists &L) {
+      int rc = launch_nn_radius(ctx, q_dev, Q.thr.in(cur), 0.0, n_act, off_dev, L.idx, L.key, L.cap, hdr_dev, L.owner);
       if (rc) return rc;
-      if (dubins) {
-        cost_dev = key_dev + lcap;
-        rc = launch_candidate_dubins(ctx, q_dev, n_act, off_dev, idx_dev, owner_dev, lcap, r_min, robot_radius,
-                                     key_dev + lcap, key_dev + 2 * lcap, nullptr, nullptr, ho_dev, hi_dev);
+      if (dubins) {      // (cost_out, cost_in follow the keys)
+        rc = launch_candidate_dubins(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, r_min, robot_radius, L.key + L.cap,
+                                     L.key + 2 * L.cap, nullptr, nullptr, L.hit_out, L.hit_in);
       } else if (ctx->opt_extend_polygons) {
-        rc = launch_candidate_edges_polygons(ctx, q_dev, n_act, off_dev, idx_dev, owner_dev, lcap, robot_radius, ho_dev,
-                                             hi_dev, nullptr, -1.0);
+        rc = launch_candidate_edges_polygons(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, robot_radius, L.hit_out,
+                                             L.hit_in, nullptr, -1.0);
       } else {      // (r < 0: the radii differ from pose to pose, every sphere is looked at)
-        rc = launch_candidate_edges(ctx, q_dev, n_act, off_dev, idx_dev, owner_dev, lcap, robot_radius, ho_dev, hi_dev, -1.0,
-                                    nullptr);
+        rc = launch_candidate_edges(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, robot_radius, L.hit_out, L.hit_in,
+                                    -1.0, nullptr);
       }
       if (rc) return rc;
       TargetRound T;
       T.n_act = n_act; T.nq = nq; T.round = round; T.dim = ctx->dim; T.r_max = r_max;
-      T.offsets = off_dev; T.idx = idx_dev; T.cost = cost_dev; T.hit_out = ho_dev;
-      T.n_valid = hdr_dev; T.cap = (long long)lcap;
-      T.lmc = lmc_dev; T.n_lmc = (long long)n_lmc;
-      T.q = q_dev; T.rad = reinterpret_cast<const double *>(cur + o_rad); T.slot = reinterpret_cast<const int32_t *>(cur + o_slot);
-      T.pending = reinterpret_cast<int32_t *>(res + o_pend);
-      T.cost_to_goal = reinterpret_cast<double *>(res); T.edge_dist = reinterpret_cast<double *>(res + o_ed);
-      T.radius_used = reinterpret_cast<double *>(res + o_ru); T.target_idx = reinterpret_cast<int32_t *>(res + o_ti);
-      T.rounds = reinterpret_cast<int32_t *>(res + o_rd); T.status = reinterpret_cast<uint8_t *>(res + o_st);
-      T.q_next = reinterpret_cast<double *>(nxt); T.rad_next = reinterpret_cast<double *>(nxt + o_rad);
-      T.thr_next = reinterpret_cast<double *>(nxt + o_thr); T.slot_next = reinterpret_cast<int32_t *>(nxt + o_slot);
+      T.offsets = off_dev; T.idx = L.idx; T.cost = dubins ? L.key + L.cap : L.key; T.hit_out = L.hit_out;
+      T.n_valid = hdr_dev; T.cap = (long long)L.cap;
+      T.lmc = lmc_dev.dev; T.n_lmc = (long long)lmc_dev.n;
+      T.q = q_dev; T.rad = Q.rad.in(cur); T.slot = Q.slot.in(cur);
+      T.pending = R.pending.in(res);
+      T.cost_to_goal = R.cost_to_goal.in(res); T.edge_dist = R.edge_dist.in(res); T.radius_used = R.radius_used.in(res);
+      T.target_idx = R.target_idx.in(res); T.rounds = R.rounds.in(res); T.status = R.status.in(res);
+      T.q_next = Q.pose.in(nxt); T.rad_next = Q.rad.in(nxt); T.thr_next = Q.thr.in(nxt); T.slot_next = Q.slot.in(nxt);
       T.hdr = hdr_dev;
-      if ((rc = launch_target_round(ctx, T))) return rc;
-      RRTX_HIP(ctx, hipMemcpyAsync(host_hdr, hdr_dev, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-      RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      const int64_t total = host_hdr[0];
-      ctx->last_neighbors = total;
-      if (total <= lcap) break;
-      if (attempt) return fail(ctx, RRTX_E_STATE, "%s: %lld neighbours after growing to %lld", fn, (long long)total, (long long)lcap);
-      lcap = total + total / 8;
-    }
+      return launch_target_round(ctx, T);
+    });
+    if (rc) return rc;
     if (host_hdr[1] < 0 || host_hdr[1] > n_act) return fail(ctx, RRTX_E_STATE, "%s: round %d left %lld of %d poses", fn, round, (long long)host_hdr[1], n_act);
     n_act = (int)host_hdr[1];
     // twice the radius is eight times the ball: make room for what the poses that go on will find (at most every node each)
     const int64_t guess = std::min<int64_t>(host_hdr[2] * 8, (int64_t)n_act * ctx->n_nodes);
-    if (guess > lcap) lcap = guess + guess / 8;
+    room = guess > ctx->sel_list_cap ? guess + guess / 8 : 0;
   }
-  RRTX_HIP(ctx, hipMemcpyAsync(host_res, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, hipMemcpyAsync(host_res, res, R.result_bytes, hipMemcpyDeviceToHost, ctx->stream));
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(cost_to_goal, host_res, sizeof(double) * n);
-  std::memcpy(edge_dist, host_res + o_ed, sizeof(double) * n);
-  std::memcpy(radius_used, host_res + o_ru, sizeof(double) * n);
-  std::memcpy(target_idx, host_res + o_ti, sizeof(int32_t) * n);
-  std::memcpy(rounds, host_res + o_rd, sizeof(int32_t) * n);
-  std::memcpy(status, host_res + o_st, n);
+  R.cost_to_goal.to(cost_to_goal, host_res);
+  R.edge_dist.to(edge_dist, host_res);
+  R.radius_used.to(radius_used, host_res);
+  R.target_idx.to(target_idx, host_res);
+  R.rounds.to(rounds, host_res);
+  R.status.to(status, host_res);
   return RRTX_OK;
 }
 }  // namespace

@@ -235,12 +235,13 @@ struct rrtx_ctx {
   double *node_lmc = nullptr;       // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
   int64_t node_lmc_cap = 0, node_lmc_n = 0;   // slots allocated; slots initialised (follows n_nodes)
   rrtx::DevBuf ws_sel_cnt;          // int32 rewire entries per sample
-  rrtx::DevBuf ws_sel_blk;          // rrtx_extend_select: everything that is per sample, one block
+  rrtx::DevBuf ws_sel_blk;          // rrtx_extend_select: everything that is per sample, one block (SelectBlock, rrtx_capi.hip)
   rrtx::DevBuf ws_sel_rwn, ws_sel_rwv, ws_sel_lmc;   // ... its rewire lists and a caller-given rrtLMC array
   int64_t sel_list_cap = 0;         // ... entries its neighbour lists have room for
 
   // move-target selection (kernels_target.hip): the two query blocks the rounds alternate between, each
   // [pose | radius | thr_lt, thr_gt | slot] of the poses still searching, and [results | pending | header]
+  // (TargetQueryBlock and TargetResultBlock in rrtx_capi.hip describe them)
   rrtx::DevBuf ws_tgt_blk[2], ws_tgt_res;
 
   // radius -> threshold cache
