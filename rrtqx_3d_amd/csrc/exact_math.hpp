@@ -54,7 +54,66 @@ __device__ __forceinline__ double jl_clamp01(double v) {
 
 // correctly rounded fp64 sqrt / divide: hipcc's default lowering is IEEE for
 // f64 (checked on hardware by tests/test_gpu_parity.py::test_device_sqrt_div)
-__device__ __forceinline__ double sqrt_rn(double x) { return __builtin_sqrt(x); }
+__host__ __device__ __forceinline__ double sqrt_rn(double x) { return __builtin_sqrt(x); }
+
+// ---- exact thresholds on squared distances (host and device: one definition) ----
+// sqrt is monotone non-decreasing under round-to-nearest, so {s : sqrt(s) >= r} is an upper set of the non-negative
+// doubles; its least element is found by a few one-ulp steps around r * r (bisection over the bit pattern as fallback).
+// The bit patterns of the non-negative doubles order like their values, so a step is +-1 on the pattern and the
+// function needs no nextafter.
+__host__ __device__ __forceinline__ double bits_to_double(unsigned long long b) {
+  double d;
+  __builtin_memcpy(&d, &b, sizeof d);
+  return d;
+}
+__host__ __device__ __forceinline__ unsigned long long double_to_bits(double d) {
+  unsigned long long b;
+  __builtin_memcpy(&b, &d, sizeof b);
+  return b;
+}
+
+// first s in [0, +inf] for which pred holds, pred monotone (false ... false true ... true) over that range; NaN when
+// it never holds
+template <class Pred>
+__host__ __device__ inline double first_true(double guess, Pred pred) {
+  constexpr unsigned long long kInf = 0x7ff0000000000000ull;
+  double s = guess > 0.0 ? guess : 0.0;               // (NaN, negative and -0.0 guesses start at +0.0)
+  for (int it = 0; it < 16; ++it) {
+    const unsigned long long b = double_to_bits(s);
+    if (pred(s)) {
+      if (b == 0ull) return 0.0;
+      const double p = bits_to_double(b - 1ull);      // the next double towards zero
+      if (!pred(p)) return s;
+      s = p;
+    } else {
+      if (b == kInf) return __builtin_nan("");        // s == +inf and pred false: never true
+      const double n = bits_to_double(b + 1ull);      // the next double towards +inf
+      if (pred(n)) return n;
+      s = n;
+    }
+  }
+  unsigned long long lo = 0ull, hi = kInf;            // 0 .. +inf
+  if (pred(0.0)) return 0.0;
+  if (!pred(bits_to_double(hi))) return __builtin_nan("");
+  while (hi - lo > 1ull) {
+    const unsigned long long mid = lo + (hi - lo) / 2ull;
+    if (pred(bits_to_double(mid))) hi = mid; else lo = mid;
+  }
+  return bits_to_double(hi);
+}
+
+//   sq_first_ge(r): smallest s >= 0 with sqrt(s) >= r   (sqrt(s) <  r  <=>  s <  sq_first_ge(r))
+//   sq_first_gt(r): smallest s >= 0 with sqrt(s) >  r   (sqrt(s) <= r  <=>  s <  sq_first_gt(r))
+__host__ __device__ inline double sq_first_ge(double r) {
+  if (r != r) return __builtin_nan("");    // sqrt(s) < NaN is never true
+  if (r <= 0.0) return 0.0;                // sqrt(s) >= r for every s >= 0
+  return first_true(r * r, [r](double s) { return sqrt_rn(s) >= r; });
+}
+__host__ __device__ inline double sq_first_gt(double r) {
+  if (r != r) return 0.0;                  // sqrt(s) <= NaN never true: s < 0 never
+  if (r < 0.0) return 0.0;
+  return first_true(r * r, [r](double s) { return sqrt_rn(s) > r; });
+}
 
 // Order-preserving map double -> uint64 (for atomicMin / atomicMax on coordinates) and back.
 // An empty minimum is ~0 and an empty maximum is 0; both decode to NaN, which fails every

@@ -27,6 +27,7 @@
 // reference's result depend on the order of its heap pops; that variant stays on the host.  gfx950 only.
 #include "exact_math.hpp"
 #include "rrtx_internal.hpp"
+#include "wave_device.hpp"
 
 namespace rrtx {
 
@@ -97,37 +98,10 @@ __global__ __launch_bounds__(256) void csr_tile_sum_kernel(const int *__restrict
   const int base = blockIdx.x * kScanTile;
   int local = 0;
   for (int k = threadIdx.x; k < kScanTile; k += 256) local += (base + k < n) ? cnt[base + k] : 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off);
+  local = wave_sum(local);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = local;
   __syncthreads();
   if (threadIdx.x == 0) tile_sum[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// exclusive scan of the tile sums by one workgroup of 1024 (in place); out[n] = total
-__global__ __launch_bounds__(1024) void csr_scan_tiles_kernel(int *__restrict__ v, int n) {
-  __shared__ int wsum[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int per = (n + 1023) / 1024;
-  const int b = min(t * per, n), e = min(b + per, n);
-  int local = 0;
-  for (int i = b; i < e; ++i) local += v[i];
-  int x = local;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(x, off);
-    if (lane >= off) x += o;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  int prefix = x - local;
-  for (int w = 0; w < wave; ++w) prefix += wsum[w];
-  for (int i = b; i < e; ++i) {
-    const int c = v[i];
-    v[i] = prefix;
-    prefix += c;
-  }
-  if (t == 1023) v[n] = prefix;
 }
 
 // start = exclusive scan of cnt (tile offset + scan inside the tile, 8 consecutive counts per lane); cursor = start
@@ -142,12 +116,7 @@ __global__ __launch_bounds__(256) void csr_tile_scan_kernel(const int *__restric
     c[k] = (base + k < n) ? cnt[base + k] : 0;
     local += c[k];
   }
-  int x = local;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(x, off);
-    if (lane >= off) x += o;
-  }
+  const int x = wave_incl_scan(local, lane);
   if (lane == 63) wsum[wave] = x;
   __syncthreads();
   int prefix = tile_off[blockIdx.x] + x - local;
@@ -285,12 +254,7 @@ __global__ __launch_bounds__(256) void graph_pass_kernel(const int *__restrict__
       b0 = in_start[i];
       deg = in_start[i + 1] - b0;
     }
-    int v = deg;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(v, off);
-      if (lane >= off) v += o;
-    }
+    int v = wave_incl_scan(deg, lane);
     if (lane == 63) wsum[wave] = v;
     sb0[t] = b0;
     sdu[t] = du;
@@ -388,7 +352,7 @@ int build_in_csr(rrtx_ctx *ctx, int n, long long ne) {
   RRTX_HIP(ctx, hipMemsetAsync(gc.in_cnt.p, 0, sizeof(int) * (size_t)(n + 1), st));
   if (ne > 0) hipLaunchKernelGGL(csr_count_kernel, grid_for(ne), dim3(256), 0, st, ctx->ge_end, ne, gc.in_cnt.as<int>());
   hipLaunchKernelGGL(csr_tile_sum_kernel, dim3(n_tiles), dim3(256), 0, st, gc.in_cnt.as<int>(), n, gc.in_tiles.as<int>());
-  hipLaunchKernelGGL(csr_scan_tiles_kernel, dim3(1), dim3(1024), 0, st, gc.in_tiles.as<int>(), n_tiles);
+  launch_excl_scan(st, gc.in_tiles.as<int>(), gc.in_tiles.as<int>(), n_tiles);      // (in place)
   hipLaunchKernelGGL(csr_tile_scan_kernel, dim3(n_tiles), dim3(256), 0, st, gc.in_cnt.as<int>(), n, gc.in_tiles.as<int>(), n_tiles,
                      gc.in_start.as<int>(), gc.in_cursor.as<int>());
   if (ne > 0)

@@ -42,54 +42,6 @@ __global__ void slab_rank_kernel(const double *__restrict__ nx, const double *__
   sr[i] = make_int2(b, atomicAdd(&hist[b], 1));
 }
 
-// exclusive scan of n ints by one workgroup of 1024; out[n] = total
-// exclusive prefix sum of n counters by ONE workgroup, 4096 at a time: every thread takes four neighbouring counters (one
-// 16-byte load, the wave reads 1 KB in a row), the waves' sums meet in LDS, the running total carries over.  (Round 2 gave
-// every thread a contiguous stretch of n / 1024 counters: 64 cache lines per load instruction and two dependent loads per
-// counter -- 22 us for the 15 000 counters of a 500 k-node index, a quarter of a rebuild.)
-__global__ __launch_bounds__(1024) void excl_scan_kernel(const int *__restrict__ in, int *__restrict__ out, int n) {
-  __shared__ int wsum[2][16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int carry = 0, flip = 0;
-  for (int base = 0; base < n; base += 4096, flip ^= 1) {
-    const int i = base + 4 * t;
-    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    if (i + 3 < n) {
-      const int4 v4 = *reinterpret_cast<const int4 *>(in + i);       // (in is 256-byte aligned, i a multiple of four)
-      c0 = v4.x; c1 = v4.y; c2 = v4.z; c3 = v4.w;
-    } else {
-      if (i < n) c0 = in[i];
-      if (i + 1 < n) c1 = in[i + 1];
-      if (i + 2 < n) c2 = in[i + 2];
-    }
-    const int local = c0 + c1 + c2 + c3;
-    int v = local;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(v, off);
-      if (lane >= off) v += o;
-    }
-    if (lane == 63) wsum[flip][wave] = v;
-    __syncthreads();                      // (two sets of sums: the next round's writes cannot overtake this round's reads)
-    int prefix = carry + v - local, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const int x = wsum[flip][w];
-      if (w < wave) prefix += x;
-      total += x;
-    }
-    if (i + 3 < n) {
-      *reinterpret_cast<int4 *>(out + i) = make_int4(prefix, prefix + c0, prefix + c0 + c1, prefix + c0 + c1 + c2);
-    } else {
-      if (i < n) out[i] = prefix;
-      if (i + 1 < n) out[i + 1] = prefix + c0;
-      if (i + 2 < n) out[i + 2] = prefix + c0 + c1;
-    }
-    carry += total;
-  }
-  if (t == 0) out[n] = carry;
-}
-
 // Rebuild, last two steps.  (Round 2 scattered every node's ten values to its place -- ten partial-line writes to
 // random addresses per node, 33 us for 400 k nodes -- and read them back in a separate launch for the chunks' extents, 11
 // us.)  Now only the node's index goes to its place (4 bytes), and a second kernel walks the places in order, fetches
@@ -185,12 +137,7 @@ __global__ __launch_bounds__(256) void run_place_kernel(
       const int c0 = k < K ? hist[k] : 0, c1 = k + 1 < K ? hist[k + 1] : 0, c2 = k + 2 < K ? hist[k + 2] : 0,
                 c3 = k + 3 < K ? hist[k + 3] : 0;
       const int local = c0 + c1 + c2 + c3;
-      int v = local;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(v, off);
-        if (lane >= off) v += o;
-      }
+      const int v = wave_incl_scan(local, lane);
       if (lane == 63) wsum[wave] = v;
       __syncthreads();
       int prefix = carry + v - local, total = 0;
@@ -340,7 +287,7 @@ int slab_refresh(rrtx_ctx *ctx, long long n_tiles) {
                      ctx->d_xrange.as<unsigned long long>(), side, side, Kz, sp, hist);
   hipLaunchKernelGGL(slab_rank_kernel, dim3(nb), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2], (int)n, sp,
                      hist, sr);
-  hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(1024), 0, st, hist, start, KK);
+  launch_excl_scan(st, hist, start, KK);
   hipLaunchKernelGGL(slab_sid_kernel, dim3(nb), dim3(256), 0, st, (int)n, sr, start, ctx->sl_id);
   hipLaunchKernelGGL(slab_gather_kernel, dim3(n_chunks), dim3(kSlabChunk), 0, st, (int)n, ctx->sl_id,
                      reinterpret_cast<const double4 *>(ctx->nodes_aos), ctx->origin[0], ctx->origin[1], ctx->origin[2],

@@ -4,6 +4,7 @@
 // that starts at such a node, explicitEdgeCheck(S, edge, ob) against that one obstacle.
 // Returns the ids of the colliding edges in ascending order.  gfx950 only.
 #include "collide_device.hpp"
+#include "wave_device.hpp"
 
 namespace rrtx {
 
@@ -40,39 +41,8 @@ __global__ __launch_bounds__(kSweepBlock) void sweep_edges_kernel(
     }
     flag[e] = hit ? 1 : 0;
   }
-  const unsigned long long m = __ballot(hit);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int w = 0; w < kSweepBlock / 64; ++w) c += wcnt[w];
-    block_count[blockIdx.x] = c;
-  }
-}
-
-// exclusive scan of the block counts by one workgroup of 1024; out[n] = total
-__global__ __launch_bounds__(1024) void sweep_scan_kernel(const int *__restrict__ in, long long *__restrict__ out, int n) {
-  __shared__ long long wsum[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int per = (n + 1023) / 1024;
-  const int b = min(t * per, n), e = min(b + per, n);
-  long long local = 0;
-  for (int i = b; i < e; ++i) local += in[i];
-  long long v = local;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long o = __shfl_up(v, off);
-    if (lane >= off) v += o;
-  }
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  long long prefix = v - local;
-  for (int w = 0; w < wave; ++w) prefix += wsum[w];
-  for (int i = b; i < e; ++i) {
-    out[i] = prefix;
-    prefix += in[i];
-  }
-  if (t == 1023) out[n] = prefix;
+  block_votes<kSweepBlock>(hit, wcnt);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = block_votes_total<kSweepBlock>(wcnt);
 }
 
 // ---- polygon / Dubins space (R/DRRT.jl:3048-3290) ----
@@ -110,14 +80,8 @@ __global__ __launch_bounds__(kSweepBlock) void sweep_select_kernel(const int32_t
     sel = (unsigned)a < (unsigned)n_nodes && mark[a] != 0 && (!blocked_only || e_dist[e] == __builtin_inf());
     flag[e] = sel ? 1 : 0;
   }
-  const unsigned long long m = __ballot(sel);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int w = 0; w < kSweepBlock / 64; ++w) c += wcnt[w];
-    block_count[blockIdx.x] = c;
-  }
+  block_votes<kSweepBlock>(sel, wcnt);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = block_votes_total<kSweepBlock>(wcnt);
 }
 
 // flag[k] = hit[k] and none of the "other obstacle" results (may be null); per-block counts
@@ -131,14 +95,8 @@ __global__ __launch_bounds__(kSweepBlock) void sweep_combine_kernel(const uint8_
     f = hit[k] != 0 && !(o1 && o1[k] != 0) && !(o2 && o2[k] != 0);
     flag[k] = f ? 1 : 0;
   }
-  const unsigned long long m = __ballot(f);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int w = 0; w < kSweepBlock / 64; ++w) c += wcnt[w];
-    block_count[blockIdx.x] = c;
-  }
+  block_votes<kSweepBlock>(f, wcnt);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = block_votes_total<kSweepBlock>(wcnt);
 }
 
 // start / end rows (dim doubles each) of the mirrored edges ids[k]
@@ -162,13 +120,9 @@ __global__ __launch_bounds__(kSweepBlock) void sweep_write_kernel(const uint8_t 
   __shared__ int wcnt[kSweepBlock / 64];
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool hit = e < ne && flag[e] != 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(hit);
-  if (lane == 0) wcnt[wave] = __popcll(m);
-  __syncthreads();
+  const unsigned long long m = block_votes<kSweepBlock>(hit, wcnt);
   if (!hit) return;
-  long long pos = block_start[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) pos += wcnt[w];
+  const long long pos = block_start[blockIdx.x] + block_votes_before(wcnt, threadIdx.x >> 6) + __popcll(m & lanes_below(threadIdx.x & 63));
   if (pos < cap) out[pos] = ids ? ids[e] : (int32_t)e;
 }
 
@@ -193,8 +147,7 @@ int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, 
                        ctx->ws_sweep_mark.as<uint8_t>(), ctx->nodes_aos, ob, active, ctx->ws_sweep_flag.as<uint8_t>(),
                        ctx->ws_sweep_cnt.as<int>());
   }
-  hipLaunchKernelGGL(sweep_scan_kernel, dim3(1), dim3(1024), 0, st, ctx->ws_sweep_cnt.as<int>(),
-                     ctx->ws_sweep_start.as<long long>(), nb);
+  launch_excl_scan(st, ctx->ws_sweep_cnt.as<int>(), ctx->ws_sweep_start.as<long long>(), nb);
   if (nb > 0 && cap > 0) {
     hipLaunchKernelGGL(sweep_write_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ws_sweep_flag.as<uint8_t>(), ne,
                        ctx->ws_sweep_start.as<long long>(), out_dev, (long long)cap);
@@ -221,8 +174,7 @@ int launch_sweep_mark_multi(rrtx_ctx *ctx, const void *queries_host, int nqs) {
 // positions with flag != 0 -> out (ids[position] when ids is given), ascending; *total_dev = their number
 static int compact_flags(rrtx_ctx *ctx, long long n, const int32_t *ids_dev, int32_t *out_dev, long long cap, long long **total_dev) {
   const int nb = (int)((n + kSweepBlock - 1) / kSweepBlock);
-  hipLaunchKernelGGL(sweep_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->ws_sweep_cnt.as<int>(),
-                     ctx->ws_sweep_start.as<long long>(), nb);
+  launch_excl_scan(ctx->stream, ctx->ws_sweep_cnt.as<int>(), ctx->ws_sweep_start.as<long long>(), nb);
   if (nb > 0 && cap > 0)
     hipLaunchKernelGGL(sweep_write_kernel, dim3(nb), dim3(kSweepBlock), 0, ctx->stream, ctx->ws_sweep_flag.as<uint8_t>(), n,
                        ctx->ws_sweep_start.as<long long>(), out_dev, cap, ids_dev);

@@ -6,6 +6,7 @@
 #include "collide_device.hpp"
 #include "exact_math.hpp"
 #include "rrtx_internal.hpp"
+#include "wave_device.hpp"
 
 namespace rrtx {
 namespace {

@@ -53,52 +53,9 @@ ApiRange::~ApiRange() {
   if (active) (void)g_roctx_pop();
 }
 
-// ---- exact thresholds on squared distances ------------------------------------
-// sqrt is monotone non-decreasing under round-to-nearest, so {s : sqrt(s) >= r}
-// is an upper set of the non-negative doubles; its least element is found by a
-// few nextafter steps around r*r (bisection over the bit pattern as fallback).
-namespace {
-template <class Pred>
-double first_true(double guess, Pred pred) {
-  // pred is monotone (false ... false true ... true) over s in [0, +inf]
-  if (!(guess >= 0.0)) guess = 0.0;
-  double s = guess;
-  for (int it = 0; it < 16; ++it) {
-    if (pred(s)) {
-      if (s == 0.0) return 0.0;
-      double p = std::nextafter(s, -INFINITY);
-      if (!pred(p)) return s;
-      s = p;
-    } else {
-      double n = std::nextafter(s, INFINITY);
-      if (n == s) return std::nan("");  // s == +inf and pred false: never true
-      if (pred(n)) return n;
-      s = n;
-    }
-  }
-  // bisection on the IEEE bit pattern (monotone for non-negative doubles)
-  uint64_t lo = 0, hi = 0x7ff0000000000000ull;  // 0 .. +inf
-  auto val = [](uint64_t b) { double d; std::memcpy(&d, &b, 8); return d; };
-  if (pred(val(lo))) return 0.0;
-  if (!pred(val(hi))) return std::nan("");
-  while (hi - lo > 1) {
-    uint64_t mid = lo + (hi - lo) / 2;
-    if (pred(val(mid))) hi = mid; else lo = mid;
-  }
-  return val(hi);
-}
-}  // namespace
-
-double thr_first_ge(double r) {
-  if (std::isnan(r)) return std::nan("");  // sqrt(s) < NaN is never true
-  if (r <= 0.0) return 0.0;                // sqrt(s) >= r for every s >= 0
-  return first_true(r * r, [r](double s) { return std::sqrt(s) >= r; });
-}
-double thr_first_gt(double r) {
-  if (std::isnan(r)) return 0.0;           // sqrt(s) <= NaN never true: s < 0 never
-  if (r < 0.0) return 0.0;
-  return first_true(r * r, [r](double s) { return std::sqrt(s) > r; });
-}
+// ---- exact thresholds on squared distances (exact_math.hpp) -------------------
+double thr_first_ge(double r) { return sq_first_ge(r); }
+double thr_first_gt(double r) { return sq_first_gt(r); }
 
 // first s with !((sqrt(s) - robotRadius) - radius < 0): explicitPointCheck's per-sphere test
 // (R/DRRT_Q.jl:1555-1570) as a threshold on the squared distance, "collision <=> s < thr".

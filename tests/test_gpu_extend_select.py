@@ -236,6 +236,89 @@ def test_device_form_edge_cases():
         assert len(e["status"]) == 0 and e["rw_offsets"].tolist() == [0] and len(e["rw_node"]) == 0
 
 
+# ---- synthetic device lists: the shared scan and the list walk at their edges ------------------------------------------
+SYN_LENGTHS = np.array([0, 1, 7, 8, 9, 63, 64, 65, 300])
+# the share of each length; the mean list length (7.0, 14.4, 27.5, 57.4) decides the lanes per sample: 8, 16, 32, 64
+SYN_WEIGHTS = {8: [.25, .25, .2, .15, .12, .01, .01, .005, .005], 16: [.1, .1, .25, .25, .2, .03, .03, .03, .01],
+               32: [.1, .1, .2, .2, .15, .08, .07, .07, .03], 64: [1 / 9] * 9}
+SYN_NODES = 64
+
+
+def _synthetic_lists(rng, nq, group):
+    cnt = rng.choice(SYN_LENGTHS, nq, p=SYN_WEIGHTS[group])
+    off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    n = int(off[-1])
+    idx = rng.integers(0, SYN_NODES, n).astype(np.int32)
+    cost = rng.integers(0, 12, n) / 4.0                            # quarter integers: exact ties in lmc + cost
+    ho = (rng.random(n) < 0.2).astype(np.uint8) * rng.choice(np.array([1, 2, 3], dtype=np.uint8), n)
+    hi = (rng.random(n) < 0.2).astype(np.uint8) * rng.choice(np.array([1, 2, 3], dtype=np.uint8), n)
+    uns = (rng.random(nq) < 0.05).astype(np.uint8)
+    lmc = rng.integers(0, 40, SYN_NODES) / 4.0
+    lmc[rng.random(SYN_NODES) < 0.15] = math.inf
+    lmc[[5, 41]] = math.nan
+    lmc[0] = 0.0
+    return dict(offsets=off, idx=idx, cost=cost, hit_out=ho, hit_in=hi, sample_unsafe=uns), lmc
+
+
+@pytest.mark.parametrize("nq", [0, 1, 3, 4, 5, 4095, 4096, 4097, 8193])
+def test_synthetic_lists_across_scan_rounds(nq):
+    """rrtx_extend_select_dev on lists written by the test over a tree of 64 nodes: sample counts around the scan's four
+    counters per thread and its 4096-counter rounds, list lengths around every group size (empty and over-long lists in
+    every group), exact ties, +Inf and NaN costs.  All eight outputs against select_numpy, exactly; then with rw_cap
+    below rw_needed (the prefix is written, nothing beyond it, rw_needed is the full count) and with rw_offsets at an
+    address that is only 8-byte aligned (the scan's one-by-one stores)."""
+    torch = pytest.importorskip("torch")
+    rng = np.random.default_rng(1000 + nq)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    groups = set()
+    with Context(3) as ctx:
+        ctx.nodes_append(np.random.default_rng(1).uniform(-5, 5, (SYN_NODES, 3)))
+        for group in (8, 16, 32, 64):
+            lists, lmc = _synthetic_lists(rng, nq, group)
+            n = int(lists["offsets"][-1])
+            ref = _reference(lists, lmc)
+            mean = n // max(nq, 1)
+            groups.add(min(g for g in (8, 16, 32, 64) if g >= mean or g == 64))
+            if nq >= 4095:
+                assert {SEL_OK, SEL_EMPTY, SEL_UNSAFE, SEL_NO_PARENT} == set(ref["status"].tolist())
+                assert tie_samples(lists["offsets"], lists["idx"], lists["cost"], lists["hit_out"], lmc) >= 64
+                assert len(ref["rw_node"]) > nq // 4
+            d = _Dev(torch, nq, n + 3, max(len(ref["rw_node"]), 1))
+            d.off[:nq + 1] = up(lists["offsets"])
+            if n:
+                d.idx[:n], d.cost[:n] = up(lists["idx"]), up(lists["cost"])
+                d.ho[:n], d.hi[:n] = up(lists["hit_out"]), up(lists["hit_in"])
+            if nq:
+                d.un[:nq] = up(lists["sample_unsafe"])
+            d.need.fill_(n)
+            d_lmc = up(lmc)
+            got = d.select(ctx, d_lmc.data_ptr())
+            assert got["rw_needed"] == len(ref["rw_node"]), (nq, group)
+            got["rw_offsets"] = got["rw_offsets"][:nq + 1]
+            _assert_same(got, ref, (nq, group))
+            # rw_cap below rw_needed
+            need = len(ref["rw_node"])
+            if need >= 2:
+                small_cap = need // 2
+                d.rwn.fill_(-7); d.rwv.fill_(-7.0); d.rwo.fill_(-7); d.rwneed.fill_(-7)
+                small = d.select(ctx, d_lmc.data_ptr(), rw_cap=small_cap)
+                assert small["rw_needed"] == need and np.array_equal(small["rw_offsets"][:nq + 1], ref["rw_offsets"])
+                rwn, rwv = d.rwn.cpu().numpy(), d.rwv.cpu().numpy()
+                assert np.array_equal(rwn[:small_cap], ref["rw_node"][:small_cap]) and (rwn[small_cap:] == -7).all()
+                assert np.array_equal(rwv[:small_cap], ref["rw_value"][:small_cap]) and (rwv[small_cap:] == -7.0).all()
+            # rw_offsets one int64 past an aligned address
+            odd = torch.full((nq + 2,), -7, dtype=torch.int64, device="cuda:0")
+            ctx.extend_select_dev(nq, d.off.data_ptr(), d.idx.data_ptr(), d.cost.data_ptr(), d.cost.data_ptr(), d.ho.data_ptr(),
+                                  d.hi.data_ptr(), d.need.data_ptr(), d.cap, d.un.data_ptr(), d_lmc.data_ptr(), d.pi.data_ptr(),
+                                  d.pe.data_ptr(), d.ln.data_ptr(), d.st.data_ptr(), odd.data_ptr() + 8, d.rwn.data_ptr(),
+                                  d.rwv.data_ptr(), d.rw_cap, d.rwneed.data_ptr())
+            ctx.sync()
+            odd = odd.cpu().numpy()
+            assert odd[0] == -7 and np.array_equal(odd[1:], ref["rw_offsets"]), (nq, group, "unaligned rw_offsets")
+    if nq >= 4095:
+        assert groups == {8, 16, 32, 64}, groups
+
+
 # ---- the fused host-pointer call ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("obstacles", ["spheres", "polygons"])
 @pytest.mark.parametrize("registered", [False, True])

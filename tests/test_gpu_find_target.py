@@ -177,6 +177,33 @@ def test_not_found_and_limits(oracle):
         assert err.value.code == _capi.RRTX_E_STATE
 
 
+def test_1025_poses_that_all_need_a_second_round(oracle):
+    """The poses that go on are compacted by ONE workgroup of 1024: 1025 of them take two passes of its loop, in every
+    round.  First with orphans only within r0 of every pose (all go on after round 1, most find a target later),
+    then with every node an orphan (all 1025 go on in every round and end NOT_FOUND)."""
+    O = oracle
+    n, nq = 6000, 1025
+    pts = synth.nodes(n, 3)
+    sph = synth.spheres(16)
+    scene = Scene("spheres", pts, O.make_spheres(sph), RR)
+    ts = scene.tree_set(O)
+    poses = synth.queries(nq, 3, seed=10)
+    r0 = np.full(nq, 5.0)
+    lmc = np.random.default_rng(6).uniform(0.0, 50.0, n)
+    lmc[O.range_batch(ts, poses, r0, nearest=False)["idx"]] = math.inf
+    ref = find_target_batch(O, scene, ts, poses, r0, 60.0, lmc)
+    print("rounds", np.bincount(ref["rounds"]), "ok", (ref["status"] == TGT_OK).sum())
+    assert (ref["rounds"] >= 2).all() and (ref["status"] == TGT_OK).sum() > nq // 2
+    inf = np.full(n, math.inf)
+    ref_inf = find_target_batch(O, scene, ts, poses, r0, 60.0, inf)
+    assert (ref_inf["status"] == TGT_NOT_FOUND).all() and (ref_inf["rounds"] == 4).all()
+    with Context(3) as ctx:
+        ctx.nodes_append(pts)
+        ctx.spheres_set(sph)
+        _assert_same(ctx.find_new_target(poses, r0, 60.0, RR, lmc=lmc), ref, "second round")
+        _assert_same(ctx.find_new_target(poses, r0, 60.0, RR, lmc=inf), ref_inf, "all orphans")
+
+
 # ---- Dubins ----------------------------------------------------------------------------------------------------------
 def _lmc_second_round(O, ts, n, poses, r0, seed):
     """Every second pose has only orphans within 0.99 r0: it needs the second round."""

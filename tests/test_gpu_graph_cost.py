@@ -111,6 +111,37 @@ def test_cost_to_root_matches_reduce_inconsistency(oracle, n, r):
         assert none is None and np.array_equal(lmc3, lmc2)
 
 
+@pytest.mark.parametrize("n", [2048 * 1 - 1, 2048 * 1 + 1, 2048 * 5 - 1, 2048 * 5 + 1])
+def test_lattices_with_a_ragged_last_tile(oracle, n):
+    """The in-edge CSR is built from per-tile sums (2048 nodes a tile) that ONE workgroup scans in place: with
+    2048 k +- 1 nodes the number of tiles (1, 2, 5, 6) is no multiple of the four counters a thread takes and the last
+    tile is ragged.  rrtLMC bit for bit against the graph oracle, parent edges where one edge attains the minimum.
+    (More than 4096 tiles -- a second round of that scan -- needs 8.4 M nodes and is not built here: it is the same
+    instantiation of the scan kernel, int and in place, that the slab rebuild runs and that
+    test_gpu_extend_select.py::test_synthetic_lists_across_scan_rounds takes across rounds in its 64-bit form.)"""
+    W = 64
+    rng = np.random.default_rng(n)
+    i = np.arange(n)
+    pts = np.stack([(i % W).astype(np.float64), (i // W).astype(np.float64), rng.uniform(0.0, 0.25, n)], axis=1)
+    right = i[(i % W != W - 1) & (i + 1 < n)]
+    down = i[i + W < n]
+    a = np.concatenate([right, down])
+    b = np.concatenate([right + 1, down + W])
+    s, e = np.concatenate([a, b]).astype(np.int32), np.concatenate([b, a]).astype(np.int32)
+    w = _edge_dist(pts, s, e)
+    root = n - 1                                           # in the ragged tile
+    with Context(3) as ctx:
+        ctx.nodes_append(pts)
+        ctx.graph_edges_append(s, e)
+        lmc, par, passes = ctx.graph_cost_to_root(root)
+        want, want_par = _oracle_solve(oracle, n, s, e, w, root)
+        assert np.array_equal(lmc, want)
+        assert lmc[root] == 0.0 and np.isfinite(lmc).all() and passes >= n // W
+        att = _check_parents(lmc, par, s, e, w, root)
+        single = np.bincount(s[att], minlength=n) == 1
+        assert np.array_equal(par[single], want_par[single])
+
+
 def test_costs_set_by_the_host_and_orphans(oracle):
     # costs that are not distances (Dubins lengths, costs with time), a part of the graph cut off from the root
     rng = np.random.default_rng(3)

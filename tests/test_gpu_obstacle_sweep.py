@@ -68,6 +68,35 @@ def test_obstacle_sweep_matches_oracle(oracle, n):
         assert ctx.n_graph_edges == 0 and len(ctx.obstacle_sweep(3, 30.0, RR)) == 0
 
 
+@pytest.mark.parametrize("ne", [4096 * 1024 + 1, 1024 * 5 + 3])
+def test_sweep_over_a_mirror_that_crosses_a_scan_round(oracle, ne):
+    """The ids come from a scan of one count per block of 1024 edges: 4097 counts are one more than a round of the scan
+    takes (4096), 6 counts are no multiple of the four a thread takes.  The mirror repeats the edges of a small graph;
+    ids against the oracle's sweep_edges_batch, exactly."""
+    rng = np.random.default_rng(7)
+    n = 300
+    pts = rng.uniform(-30, 30, (n, 3))
+    base = 9973                                            # (a prime: the repeats do not line up with the blocks)
+    bs, be = rng.integers(0, n, base), rng.integers(0, n, base)
+    es, ee = np.resize(bs, ne).astype(np.int32), np.resize(be, ne).astype(np.int32)
+    sph = np.array([[2.0, -1.0, 3.0, 16.0]])
+    search = RR + DELTA + sph[0, 3]
+    tree = oracle.KDTree(3)
+    tree.insert_many(pts)
+    near = np.zeros(n, dtype=np.uint8)
+    near[tree.within_range(search, sph[0, :3])[0]] = 1
+    want = oracle.sweep_edges_batch(pts, es, ee, near, oracle.make_spheres(sph), 0, RR)
+    assert 0.01 * ne <= len(want) <= 0.5 * ne, (len(want), ne)     # neither empty nor full, judged on the oracle alone
+    with Context(3) as ctx:
+        ctx.nodes_append(pts)
+        ctx.spheres_set(sph)
+        assert ctx.graph_edges_append(es, ee) == 0 and ctx.n_graph_edges == ne
+        got = ctx.obstacle_sweep(0, search, RR, cap=len(want) + 5)
+        assert len(got) == len(want) and np.array_equal(got, want)
+        short = ctx.obstacle_sweep(0, search, RR, cap=16)              # the two-call path over the same scan
+        assert np.array_equal(short, want)
+
+
 def test_obstacle_sweep_through_the_mirror_names(oracle):
     rng = np.random.default_rng(5)
     KD = drrt.KDTree(3)

@@ -3,8 +3,8 @@
 rrtx_graph_edges_set_dist) and the cost propagation (rrtx_graph_cost_to_root, rrtx_graph_cost_update).
 
 Sizes are chosen so that the device paths which only switch on at full size run: more than 2^20 mirrored edges
-(several blocks per lane in sweep_scan_kernel), a sweep with more than 2^21 candidates (later chunks of the Dubins
-check through edge ids), more than 2^21 nodes (several tiles per lane in csr_scan_tiles_kernel), appended edges on both
+(more than one 4096-counter round of the block-count scan), a sweep with more than 2^21 candidates (later chunks of the Dubins
+check through edge ids), more than 2^21 nodes (1024 tiles of 2048 nodes in the tile-sum scan), appended edges on both
 sides of the in-edge CSR rebuild threshold, and nodes appended past the last solve's buffers.
 
 Every comparison is exact: edge ids with np.array_equal, rrtLMC bit for bit.  Parent edges are held to the lowest
@@ -27,9 +27,9 @@ pytestmark = pytest.mark.gpu
 INF = float("inf")
 RR, DELTA = 0.5, 8.0
 TAIL_BASE = 262144                 # graph_cost_impl rebuilds the in-edge CSR inside an update once tail > this + E0 / 8
-SCAN_BLOCKS = 1024 * 1024          # sweep_scan_kernel: one lane per block of 1024 edges up to this many edges
+SCAN_BLOCKS = 1024 * 1024          # (one lane of the former block-count scan per block of 1024 edges up to this many edges)
 DUB_CHUNK = 1 << 21                # launch_dubins_edges_idx / the steering kernel: edges per chunk
-SCAN_TILES = 1024 * 2048           # csr_scan_tiles_kernel: one lane per tile of 2048 nodes up to this many nodes
+SCAN_TILES = 1024 * 2048           # (one lane of the former tile-sum scan per tile of 2048 nodes up to this many nodes)
 
 
 def _report(step, **kv):
