@@ -264,6 +264,25 @@ int64_t rrtx_graph_edges_count(rrtx_ctx *ctx);
 int rrtx_graph_edges_clear(rrtx_ctx *ctx);
 int rrtx_obstacle_sweep(rrtx_ctx *ctx, int obstacle, double search_range, double robot_radius, int32_t *edge_ids,
                         int64_t cap, int64_t *needed);
+/* rrtx_obstacle_sweep for k sphere obstacles in one pass over the mirror: the edge loops of a burst of addNewObstacle
+ * calls (R/DRRT_Q.jl:3195-3290 each) -- the obstacles another agent injects in one main-loop iteration, or every
+ * active obstacle re-added when the kino-distance grows.  obstacles[j] is a list position of rrtx_spheres_set,
+ * search_range[j] its range (= robotRadius + delta + radius).  CSR output: row j, edge_ids[offsets[j] .. offsets[j+1]),
+ * is exactly what rrtx_obstacle_sweep(ctx, obstacles[j], search_range[j], robot_radius, ...) returns -- the same ids,
+ * ascending; the thresholds of every obstacle are the ones that call computes.  Rows come in the order of
+ * `obstacles`; an edge that collides with several obstacles is in each of their rows; an obstacle that is not in use
+ * gives an empty row (R/DRRT_Q.jl:1777); a position listed twice gives two equal rows.
+ *   0 <= k <= 65536; k == 0 is RRTX_OK with offsets[0] = 0.  A position outside the sphere list is RRTX_E_INVALID and
+ *   nothing runs.  An empty tree and dim != 3 are RRTX_E_STATE, as in the single call; an empty mirror gives empty rows.
+ *   Two-call capacity pattern: with more than cap ids in all rows together the call returns RRTX_E_CAPACITY with
+ *   *needed set and offsets valid.
+ *   block != 0: after a call that returns RRTX_OK every returned edge is blocked in the mirror, on the device, exactly
+ *   as rrtx_graph_edges_block over the union of the rows leaves it (dist = Inf, marked as touched for the next
+ *   rrtx_graph_cost_update); the ids do not travel down and up again for it.  A call that does not return RRTX_OK
+ *   blocks nothing.  Blocking never changes what this or a later sweep returns: the sphere sweep does not read dist. */
+int rrtx_obstacle_sweep_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range /* k */,
+                              double robot_radius, int block, int64_t *offsets /* k + 1 */, int32_t *edge_ids,
+                              int64_t cap, int64_t *needed);
 /* The obstacle sweeps of the POLYGON list -- the 2-D Euclidean and the Dubins space, with or without time
  * (legacy planner, R/DRRT.jl:3048-3290; BASELINE config 5's "dynamic discoverable obstacles" run these).  The edge
  * type is the context's: dim = 3 SimpleEdge, dim = 4 DubinsEdge (r_min = S.minTurningRadius; with

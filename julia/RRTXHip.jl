@@ -568,6 +568,43 @@ function obstacleSweep(tree::HipTree, S::TS, ob::SphereObstacle) where {TS}
   end
 end
 
+# The same for a burst of sphere obstacles -- the ones multirrtqx injects for the other agents in one iteration, or every
+# obstacle re-added when the kino-distance grows -- in ONE pass over the registered edges (rrtx_obstacle_sweep_batch):
+# one id vector per obstacle, in the order given, each exactly what obstacleSweep(tree, S, ob) returns.  block = true
+# also sets dist = Inf for every returned edge in the device mirror (blockEdges over all of them, without the ids
+# travelling back); the caller still sets edge.dist = Inf on its own edge objects.
+function obstacleSweepBatch(tree::HipTree, S::TS, obs::Vector{SphereObstacle}, block::Bool = false) where {TS}
+  syncObstacles(tree, S)
+  k = length(obs)
+  which = fill(Int32(-1), k)                  # list positions (0-based)
+  ptr = S.obstacles.front
+  for i = 1:S.obstacles.length
+    for j = 1:k
+      if ptr.data === obs[j]
+        which[j] = i - 1
+      end
+    end
+    ptr = ptr.child
+  end
+  all(which .>= 0) || error("obstacle is not in CSpace.obstacles")
+  range = Float64[S.robotRadius + S.delta + ob.radius for ob in obs]
+  offsets = Vector{Int64}(undef, k + 1)
+  cap = 4096
+  while true
+    ids = Vector{Int32}(undef, cap)
+    needed = Ref{Int64}(0)
+    rc = GC.@preserve which range offsets ids ccall((:rrtx_obstacle_sweep_batch, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Cdouble}, Cdouble, Cint, Ptr{Int64}, Ptr{Int32}, Int64, Ref{Int64}),
+        tree.ctx, which, k, range, S.robotRadius, block ? 1 : 0, offsets, ids, cap, needed)
+    if rc == RRTX_E_CAPACITY
+      cap = Int(needed[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    return [ids[Int(offsets[j]) + 1:Int(offsets[j + 1])] for j = 1:k]
+  end
+end
+
 # The same for the POLYGON list (legacy planner, R/DRRT.jl:3048-3290; BASELINE config 5's discoverable / moving
 # obstacles): findPointsInConflictWithObstacle(::Obstacle) -- Euclidean query, the Dubins one ([x y 0.0 pi], range +
 # pi), one query per path segment for kinds 6 / 7 -- and the edge loop of addNewObstacle (remove = false) or

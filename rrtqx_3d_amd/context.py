@@ -612,6 +612,28 @@ class Context:
         n, ids = self._two_call(cap, call)
         return ids[:n]
 
+    def obstacle_sweep_batch(self, obstacles, search_range, robot_radius: float, block: bool = False,
+                             cap: Optional[int] = None):
+        """obstacle_sweep for a burst of sphere obstacles in one pass over the mirror (rrtx_obstacle_sweep_batch):
+        returns (offsets, edge_ids), row j = edge_ids[offsets[j]:offsets[j + 1]] being exactly
+        obstacle_sweep(obstacles[j], search_range[j], robot_radius); rows in the order given.  search_range: one range
+        per obstacle (a scalar serves all).  block=True also blocks every returned edge in the mirror, on the device
+        (what graph_edges_block over the union of the rows does)."""
+        obs = np.ascontiguousarray(obstacles, dtype=np.int32).reshape(-1)
+        k = obs.shape[0]
+        rng = np.ascontiguousarray(np.broadcast_to(np.asarray(search_range, dtype=np.float64), (k,)))
+        if cap is None:
+            cap = 4096
+
+        def call(cap, needed):
+            off = np.zeros(k + 1, dtype=np.int64)
+            ids = np.empty(max(cap, 1), dtype=np.int32)
+            return self._lib.rrtx_obstacle_sweep_batch(self._h, _capi._ptr(obs), k, _capi._ptr(rng), robot_radius,
+                                                       1 if block else 0, _capi._ptr(off), _capi._ptr(ids), cap,
+                                                       needed), (off, ids)
+        n, (off, ids) = self._two_call(cap, call)
+        return off, ids[:n]
+
     def obstacle_sweep_polygon(self, obstacle: int, robot_radius: float, delta: float, r_min: float = 0.0,
                                remove: bool = False, cap: Optional[int] = None):
         """The edge loops of addNewObstacle / removeObstacle for the polygon list (R/DRRT.jl:3048-3290): ids

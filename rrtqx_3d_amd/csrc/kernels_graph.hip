@@ -387,6 +387,16 @@ int launch_graph_block(rrtx_ctx *ctx, const int32_t *ids_host, long long n) {
   return RRTX_OK;
 }
 
+// the same for ids a kernel left on the device (the batched sweep's rows; an id may repeat): nothing travels, no sync
+int launch_graph_block_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n) {
+  if (n <= 0) return RRTX_OK;
+  hipLaunchKernelGGL(graph_block_kernel, grid_for(n), dim3(256), 0, ctx->stream, ids_dev, n, ctx->ge_dist, ctx->ge_dirty,
+                     ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne, ctx->gc.in_w.as<double>());
+  RRTX_HIP(ctx, hipGetLastError());
+  ctx->gc.touched_old = true;
+  return RRTX_OK;
+}
+
 // edge costs [first, first + n) were overwritten on the stream (rrtx_graph_edges_set_dist)
 int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n) {
   if (n <= 0) return RRTX_OK;

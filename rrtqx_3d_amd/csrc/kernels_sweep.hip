@@ -126,6 +126,110 @@ __global__ __launch_bounds__(kSweepBlock) void sweep_write_kernel(const uint8_t 
   if (pos < cap) out[pos] = ids ? ids[e] : (int32_t)e;
 }
 
+// ---- the batched sweep (rrtx_obstacle_sweep_batch): up to 64 obstacles a pass over the nodes and over the mirror ----
+constexpr int kSweepGroup = 64;      // obstacles per pass: one bit each of a 64-bit word
+
+// word[i] bit b = node i is in range of obstacle b of the group and that obstacle is in use (sweep_mark_kernel's test)
+__global__ void sweep_mark_words_kernel(const double *__restrict__ nx, const double *__restrict__ ny,
+                                        const double *__restrict__ nz, int n, const SweepObs *__restrict__ tab, int kg,
+                                        unsigned long long *__restrict__ word) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x = nx[i], y = ny[i], z = nz[i];
+  unsigned long long w = 0ull;
+  for (int b = 0; b < kg; ++b) {
+    const SweepObs o = tab[b];                                   // (uniform: scalar loads)
+    const double s = sq3(o.ob.cx, o.ob.cy, o.ob.cz, x, y, z);
+    if (((s < o.thr_lt) || (i == 0 && s < o.thr_gt)) && o.active) w |= 1ull << b;
+  }
+  word[i] = w;
+}
+
+// One block of kSweepBlock mirrored edges against the group.  An edge whose start node has an empty word is done after
+// that read; any other loads its endpoints, forms its length once and runs edge_hits_sphere for every set bit.  The edges
+// with a hit leave (id, hit word) in the block's own stretch of seg_id / seg_word, ascending (rank of the thread among
+// the block's hits); blk_n[block] = how many, cnt[b * nb + block] = how many of them hit obstacle b.
+__global__ __launch_bounds__(kSweepBlock) void sweep_edges_words_kernel(
+    const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end, long long ne, int n_nodes,
+    const unsigned long long *__restrict__ word, const double *__restrict__ naos, const SweepObs *__restrict__ tab, int kg,
+    int nb, int32_t *__restrict__ seg_id, unsigned long long *__restrict__ seg_word, int *__restrict__ blk_n,
+    int *__restrict__ cnt) {
+  __shared__ int wcnt[kSweepBlock / 64];
+  __shared__ unsigned long long lw[kSweepBlock];
+  const int t = threadIdx.x;
+  const long long e = (long long)blockIdx.x * blockDim.x + t;
+  unsigned long long hits = 0ull;
+  if (e < ne) {
+    const int a = e_start[e];
+    unsigned long long w = (unsigned)a < (unsigned)n_nodes ? word[a] : 0ull;
+    if (w != 0ull) {
+      const int b = e_end[e];
+      if ((unsigned)b < (unsigned)n_nodes) {
+        const double4 p0 = reinterpret_cast<const double4 *>(naos)[a];
+        const double4 p1 = reinterpret_cast<const double4 *>(naos)[b];
+        const double len = sqrt_rn(sq3(p0.x, p0.y, p0.z, p1.x, p1.y, p1.z));
+        const double bx = p1.x - p0.x, by = p1.y - p0.y, bz = p1.z - p0.z;
+        while (w != 0ull) {
+          const int j = __ffsll((long long)w) - 1;               // (j < kg: the mark kernel sets no other bit)
+          w &= w - 1ull;
+          if (edge_hits_sphere(p0.x, p0.y, p0.z, bx, by, bz, len, tab[j].ob)) hits |= 1ull << j;
+        }
+      }
+    }
+  }
+  const bool any = hits != 0ull;
+  const unsigned long long m = block_votes<kSweepBlock>(any, wcnt);
+  const int total = block_votes_total<kSweepBlock>(wcnt);
+  if (t == 0) blk_n[blockIdx.x] = total;
+  if (total == 0) {                                              // (the whole block takes this branch or none of it)
+    if (t < kg) cnt[(size_t)t * nb + blockIdx.x] = 0;
+    return;
+  }
+  if (any) {
+    const int r = block_votes_before(wcnt, t >> 6) + __popcll(m & lanes_below(t & 63));
+    const size_t at = (size_t)blockIdx.x * kSweepBlock + r;
+    seg_id[at] = (int32_t)e;
+    seg_word[at] = hits;
+    lw[r] = hits;
+  }
+  __syncthreads();
+  if (t < kg) {
+    int c = 0;
+    for (int r = 0; r < total; ++r) c += (int)((lw[r] >> t) & 1ull);
+    cnt[(size_t)t * nb + blockIdx.x] = c;
+  }
+}
+
+// The rows of one group out of the blocks' lists: pos = exclusive scan of cnt (obstacle-major, so pos[b * nb + block] is
+// where block's ids of obstacle b start inside the group and pos[b * nb] where row b starts), *base = ids of the groups
+// before this one.  One workgroup of 64 per block of edges, thread b walks the block's list for obstacle b: blocks
+// ascend with the scan, ids ascend inside a list.  Block 0 also writes the group's offsets and the next group's base.
+__global__ __launch_bounds__(kSweepGroup) void sweep_rows_write_kernel(
+    const int32_t *__restrict__ seg_id, const unsigned long long *__restrict__ seg_word, const int *__restrict__ blk_n,
+    const long long *__restrict__ pos, int nb, int kg, const long long *__restrict__ base, long long *__restrict__ base_next,
+    int64_t *__restrict__ offsets, int32_t *__restrict__ out, long long cap) {
+  const int t = threadIdx.x;
+  const long long b0 = *base;
+  if (blockIdx.x == 0) {
+    if (t < kg) offsets[t] = b0 + pos[(size_t)t * nb];
+    if (t == 0) {
+      const long long end = b0 + pos[(size_t)kg * nb];
+      offsets[kg] = end;
+      *base_next = end;
+    }
+  }
+  const int m = blk_n[blockIdx.x];
+  if (m == 0 || t >= kg) return;
+  long long p = b0 + pos[(size_t)t * nb + blockIdx.x];
+  const size_t at = (size_t)blockIdx.x * kSweepBlock;
+  for (int r = 0; r < m; ++r) {
+    if ((seg_word[at + r] >> t) & 1ull) {
+      if (p < cap) out[p] = seg_id[at + r];
+      ++p;
+    }
+  }
+}
+
 }  // namespace
 
 // device side of rrtx_obstacle_sweep; needed_dev[0] = colliding edges, needed_dev[1] = block count scratch
@@ -155,6 +259,49 @@ int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, 
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
   *total_dev = ctx->ws_sweep_start.as<long long>() + nb;
+  return RRTX_OK;
+}
+
+// device side of rrtx_obstacle_sweep_batch (the mirror is not empty): groups of kSweepGroup obstacles in list order,
+// each one mark pass over the nodes, one pass over the mirror, one scan of its (obstacle, block) counts and the write
+// of its rows; a group's rows follow the rows of the group before it (ws_swb_base[g] = ids before group g)
+int launch_obstacle_sweep_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev) {
+  const int n = (int)ctx->n_nodes;
+  const long long ne = ctx->ge_n;
+  const int nb = (int)((ne + kSweepBlock - 1) / kSweepBlock);
+  const int ng = (k + kSweepGroup - 1) / kSweepGroup;
+  const int kg_max = std::min(k, kSweepGroup);        // (edge ids are int32: kg_max * nb < 2^27 counts, an int for the scan)
+  RRTX_HIP(ctx, ctx->ws_swb_tab.ensure(sizeof(SweepObs) * (size_t)k));
+  RRTX_HIP(ctx, ctx->ws_swb_word.ensure(sizeof(unsigned long long) * (size_t)n));
+  RRTX_HIP(ctx, ctx->ws_swb_seg_id.ensure(sizeof(int32_t) * (size_t)nb * kSweepBlock));
+  RRTX_HIP(ctx, ctx->ws_swb_seg_word.ensure(sizeof(unsigned long long) * (size_t)nb * kSweepBlock));
+  RRTX_HIP(ctx, ctx->ws_swb_blk_n.ensure(sizeof(int) * (size_t)nb));
+  RRTX_HIP(ctx, ctx->ws_swb_cnt.ensure(sizeof(int) * ((size_t)kg_max * nb + 1)));
+  RRTX_HIP(ctx, ctx->ws_swb_pos.ensure(sizeof(long long) * ((size_t)kg_max * nb + 2)));
+  RRTX_HIP(ctx, ctx->ws_swb_base.ensure(sizeof(long long) * (size_t)(ng + 1)));
+  RRTX_HIP(ctx, ctx->ws_swb_off.ensure(sizeof(int64_t) * (size_t)(k + 1)));
+  hipStream_t st = ctx->stream;
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_swb_tab.p, ctx->swb_tab_host.data(), sizeof(SweepObs) * (size_t)k, hipMemcpyHostToDevice, st));
+  RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_swb_base.p, 0, sizeof(long long), st));
+  span_begin(ctx, KF_EDGES);
+  for (int g = 0; g < ng; ++g) {
+    const int kg = std::min(kSweepGroup, k - g * kSweepGroup);
+    const SweepObs *tab = ctx->ws_swb_tab.as<SweepObs>() + (size_t)g * kSweepGroup;
+    hipLaunchKernelGGL(sweep_mark_words_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
+                       ctx->nodes[2], n, tab, kg, ctx->ws_swb_word.as<unsigned long long>());
+    hipLaunchKernelGGL(sweep_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ctx->ge_end, ne, n,
+                       ctx->ws_swb_word.as<unsigned long long>(), ctx->nodes_aos, tab, kg, nb, ctx->ws_swb_seg_id.as<int32_t>(),
+                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(), ctx->ws_swb_cnt.as<int>());
+    launch_excl_scan(st, ctx->ws_swb_cnt.as<int>(), ctx->ws_swb_pos.as<long long>(), kg * nb);
+    hipLaunchKernelGGL(sweep_rows_write_kernel, dim3(nb), dim3(kSweepGroup), 0, st, ctx->ws_swb_seg_id.as<int32_t>(),
+                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(),
+                       ctx->ws_swb_pos.as<long long>(), nb, kg, ctx->ws_swb_base.as<long long>() + g,
+                       ctx->ws_swb_base.as<long long>() + g + 1, ctx->ws_swb_off.as<int64_t>() + (size_t)g * kSweepGroup, out_dev,
+                       (long long)cap);
+  }
+  span_end(ctx);
+  RRTX_HIP(ctx, hipGetLastError());
+  *total_dev = ctx->ws_swb_base.as<long long>() + ng;
   return RRTX_OK;
 }
 

@@ -41,6 +41,11 @@ struct alignas(16) HitRec { int32_t owner; int32_t idx; double d2; };
 // distance (hit <=> !(s >= thr), thr = first s with sqrt(s) > robotRadius+radius).
 struct alignas(32) SphRec { double cx, cy, cz, thr; };
 
+// One obstacle of a batched sweep (rrtx_obstacle_sweep_batch) as its two kernels read it: the SphRec of the edge test
+// (its centre is also the centre of the range query), the two thresholds of the range query on the squared distance
+// (node in range <=> s < thr_lt, the root: s < thr_gt) and whether the obstacle is in use.
+struct alignas(64) SweepObs { SphRec ob; double thr_lt, thr_gt; int32_t active, pad0; double pad1; };
+
 // host-side mirror of exact_math.hpp's ChunkExt (this header is also read by plain C++)
 struct ChunkExtHost { unsigned long long xlo, xhi, ylo, yhi; };
 
@@ -230,6 +235,10 @@ struct rrtx_ctx {
   rrtx::GraphCost gc;               // cost propagation state (kernels_graph.hip)
   int64_t ge_n = 0, ge_cap = 0;
   rrtx::DevBuf ws_sweep_mark, ws_sweep_flag, ws_sweep_cnt, ws_sweep_start;
+  // the batched sweep: obstacle table, in-range word per node, per-block lists of (edge id, hit word), counts per
+  // (obstacle, block) and their scan, first CSR position of every group of 64 obstacles, the offsets
+  rrtx::DevBuf ws_swb_tab, ws_swb_word, ws_swb_seg_id, ws_swb_seg_word, ws_swb_blk_n, ws_swb_cnt, ws_swb_pos, ws_swb_base, ws_swb_off;
+  std::vector<rrtx::SweepObs> swb_tab_host;   // what ws_swb_tab is copied from (lives until the call's sync)
 
   // parent / rewire selection over the extend lists (kernels_select.hip)
   double *node_lmc = nullptr;       // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
@@ -403,9 +412,14 @@ int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const 
 int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, double thr_gt, const SphRec &ob,
                           int active, int32_t *out_dev, int64_t cap, long long **total_dev);
 
+// device side of rrtx_obstacle_sweep_batch over ctx->swb_tab_host (k obstacles): row j of the CSR in ws_swb_off (k + 1
+// offsets) / out_dev (at most cap ids) is obstacle j's sweep; *total_dev = the number of ids of all rows
+int launch_obstacle_sweep_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev);
+
 int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n);
 int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n);
 int launch_graph_block(rrtx_ctx *ctx, const int32_t *ids_host, long long n);
+int launch_graph_block_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n);   // ids already on the device, in [0, ge_n)
 int launch_graph_cost(rrtx_ctx *ctx, int root, bool update, double *lmc_dev, int32_t *parent_dev, int *passes_out);
 void graph_cost_forget(rrtx_ctx *ctx);
 

@@ -746,6 +746,22 @@ def obstacleSweep(S: CSpace, KD: HipTree, ob, remove: bool = False) -> np.ndarra
     return KD.ctx.obstacle_sweep(_list_position(S, ob), S.robotRadius + S.delta + ob.radius, S.robotRadius)
 
 
+def obstacleSweepBatch(S: CSpace, KD: HipTree, obs: Sequence[SphereObstacle], block: bool = False) -> List[np.ndarray]:
+    """obstacleSweep for a burst of SphereObstacles of S.obstacles -- the ones multirrtqx injects for the other agents
+    in one iteration, or every obstacle re-added when the kino-distance grows -- in one pass over the registered edges:
+    one id array per obstacle, in the order given, each what obstacleSweep(S, KD, ob) returns.  block=True is
+    blockEdges over all of them as well, without the ids travelling back."""
+    S.bind(KD)
+    _sync_obstacles(S)
+    if any(isinstance(ob, Obstacle) for ob in obs):
+        error("obstacleSweepBatch takes sphere obstacles; polygons go through obstacleSweep one at a time")
+    if S.spaceHasTime or S.spaceHasTheta:
+        error("this type of obstacle not coded for this type of space")
+    off, ids = KD.ctx.obstacle_sweep_batch([_list_position(S, ob) for ob in obs],
+                                           [S.robotRadius + S.delta + ob.radius for ob in obs], S.robotRadius, block=block)
+    return [ids[off[j]:off[j + 1]] for j in range(len(obs))]
+
+
 def syncEdgeCosts(KD: HipTree, first_id: int, edges: Sequence[SimpleEdge]):
     """edge.dist of registered edges first_id, first_id + 1, ... (registerEdges gives every edge the
     SimpleEdge cost of its two nodes; Dubins costs and costs in a space with time are sent with this)."""
