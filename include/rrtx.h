@@ -144,6 +144,23 @@ int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out);
  *   sizes them itself (from what the last calls produced; a call that produces more grows them and runs once more);
  *   reading tells what it settled on, setting forces a starting value (testing). */
 #define RRTX_OPT_SELECT_LIST_CAP 15
+/*   RRTX_OPT_DUBINS_TIME_COLUMN (default RRTX_TIME_COLUMN_PIECEWISE; any value but the two below is RRTX_E_INVALID):
+ *   how the time column of a Dubins edge's stored polyline is formed in a dim = 4 context with
+ *   RRTX_OPT_SPACE_HAS_TIME (without it the option has no effect).  Let rows 0 .. P-1 be the stored rows before the
+ *   last one is overwritten with the end node, st the start node's time and vel = Wdist / (st - end time).
+ *     RRTX_TIME_COLUMN_PIECEWISE: the distance walked at row k of a piece is (distance at the piece's first row) +
+ *       k x (the piece's first chord), the three junctions measured once.  Differs from the reference by rounding.
+ *     RRTX_TIME_COLUMN_RUNNING_SUM: the reference's own column (R/DRRT_DubinsEdge_functions.jl:689-695):
+ *       cum_0 = 0, cum_i = fl(cum_{i-1} + len(row_{i-1}, row_i)) for i = 1 .. P-2, strictly left to right, with
+ *       len = sqrt((dx * dx) + (dy * dy)) unfused and correctly rounded; t_i = st - cum_i / vel.
+ *   In both forms row 0 carries st and row P-1 is the end node's (x, y, t).  Costs, words, velocities, validMove, row
+ *   counts and the (x, y) of every row do not depend on the option.  Every consumer of the stamps follows it:
+ *   rrtx_dubins_trajectory, rrtx_dubins_edges_check, rrtx_dubins_edges_check_obstacle,
+ *   rrtx_extend_candidates_dubins(_dev), rrtx_find_new_target_dubins and the Dubins branch of
+ *   rrtx_obstacle_sweep_polygon.  This one DOES select behaviour (in the last bits of the stamps). */
+#define RRTX_OPT_DUBINS_TIME_COLUMN 16
+#define RRTX_TIME_COLUMN_PIECEWISE 0
+#define RRTX_TIME_COLUMN_RUNNING_SUM 1
 int rrtx_set_option(rrtx_ctx *ctx, int option, int64_t value);
 /* The value an option currently has (as rrtx_set_option normalised it): callers that size buffers by an
  * option -- the row width of rrtx_dubins_trajectory -- read it here instead of keeping a shadow copy. */

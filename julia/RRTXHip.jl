@@ -18,6 +18,11 @@ const LIBRRTX = get(ENV, "RRTX_HIP_LIB", "librrtx_hip.so")
 
 const RRTX_OK = Cint(0)
 const RRTX_E_CAPACITY = Cint(-2)
+# RRTX_OPT_DUBINS_TIME_COLUMN and its values (include/rrtx.h): how the time column of a Dubins edge's trajectory is
+# formed in a space with time -- the kernels' piecewise form (default) or the reference's running sum
+const RRTX_OPT_DUBINS_TIME_COLUMN = Cint(16)
+const RRTX_TIME_COLUMN_PIECEWISE = Int64(0)
+const RRTX_TIME_COLUMN_RUNNING_SUM = Int64(1)
 
 mutable struct HipTree{T}
   d::Int                       # fields the planner reads (R/rrtqx.jl:382, R/DRRT_Q.jl:2624,2631)
@@ -676,6 +681,13 @@ function syncDubinsSpace(tree::HipTree, S::TS) where {TS}
   rrtx_check(tree, ccall((:rrtx_set_option, LIBRRTX), Cint, (Ptr{Cvoid}, Cint, Int64), tree.ctx, 12, S.spaceHasTime ? 1 : 0))
   rrtx_check(tree, ccall((:rrtx_set_dubins_velocity, LIBRRTX), Cint, (Ptr{Cvoid}, Cdouble, Cdouble),
       tree.ctx, S.dubinsMinVelocity, S.dubinsMaxVelocity))
+end
+
+# RRTX_TIME_COLUMN_RUNNING_SUM: every time stamp the Dubins entry points form or test is the reference's own running
+# sum (R/DRRT_DubinsEdge_functions.jl:689-695), bit for bit; RRTX_TIME_COLUMN_PIECEWISE (default) the faster form.
+function setDubinsTimeColumn(tree::HipTree, value::Integer)
+  rrtx_check(tree, ccall((:rrtx_set_option, LIBRRTX), Cint, (Ptr{Cvoid}, Cint, Int64), tree.ctx,
+      RRTX_OPT_DUBINS_TIME_COLUMN, Int64(value)))
 end
 
 # calculateTrajectory(S, ::DubinsEdge) (R/DRRT_DubinsEdge_functions.jl:329-709): dubinsType, Wdist, dist,

@@ -35,6 +35,10 @@ RRTX_OPT_SPACE_HAS_TIME = 12
 RRTX_OPT_ROOT_RULE = 13
 RRTX_OPT_LAST_PLACEMENT = 14
 RRTX_OPT_SELECT_LIST_CAP = 15
+RRTX_OPT_DUBINS_TIME_COLUMN = 16
+# values of RRTX_OPT_DUBINS_TIME_COLUMN
+RRTX_TIME_COLUMN_PIECEWISE = 0
+RRTX_TIME_COLUMN_RUNNING_SUM = 1
 # status[s] of rrtx_extend_select*
 RRTX_SEL_OK = 0
 RRTX_SEL_NO_PARENT = 1

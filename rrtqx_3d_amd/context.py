@@ -96,6 +96,11 @@ class Context:
         """CSpace.spaceHasTime as the CONTEXT holds it (no shadow copy: buffers are sized from this)."""
         return self.get_option(_capi.RRTX_OPT_SPACE_HAS_TIME) != 0
 
+    @property
+    def dubins_time_column(self) -> int:
+        """RRTX_OPT_DUBINS_TIME_COLUMN as the context holds it: _capi.RRTX_TIME_COLUMN_PIECEWISE or _RUNNING_SUM."""
+        return self.get_option(_capi.RRTX_OPT_DUBINS_TIME_COLUMN)
+
     def stats(self) -> Stats:
         s = Stats()
         self._check(self._lib.rrtx_stats(self._h, C.byref(s)))
@@ -242,6 +247,11 @@ class Context:
     def set_space_has_time(self, has_time: bool):
         """CSpace.spaceHasTime for the Dubins entry points (dim = 4: [x y t theta])."""
         self.set_option(_capi.RRTX_OPT_SPACE_HAS_TIME, 1 if has_time else 0)
+
+    def set_dubins_time_column(self, value: int):
+        """How the time column of a Dubins edge's polyline is formed in a space with time: RRTX_TIME_COLUMN_PIECEWISE
+        (default) or RRTX_TIME_COLUMN_RUNNING_SUM, the reference's own sum (include/rrtx.h); anything else raises."""
+        self.set_option(_capi.RRTX_OPT_DUBINS_TIME_COLUMN, int(value))
 
     def set_dubins_velocity(self, v_min: float, v_max: float):
         """S.dubinsMinVelocity / S.dubinsMaxVelocity (validMove in a space with time)."""

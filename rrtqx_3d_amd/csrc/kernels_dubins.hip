@@ -367,6 +367,67 @@ __device__ __forceinline__ void polyline_point_t(const Piece *pc, const TimeInfo
   else t = ti.st - (ti.cum[pi] + (double)k * ti.chord[pi]) / ti.vel;
 }
 
+// ---- the reference's own time column (RRTX_OPT_DUBINS_TIME_COLUMN = RRTX_TIME_COLUMN_RUNNING_SUM) ----------------
+// cum_0 = 0, cum_i = fl(cum_{i-1} + len(row_{i-1}, row_i)) strictly left to right over the rows piece_point gives,
+// t_i = st - cum_i / vel (:689-695).  ONE definition of the step and of the stamp: the checkpoint walk, the check
+// kernel's pieces and the trajectory kernel all go through it.
+struct RunningSum {
+  double cum, lx, ly;      // distance walked at the last row taken, and that row
+  __device__ __forceinline__ void start(double cum0, double x0, double y0) { cum = cum0; lx = x0; ly = y0; }
+  __device__ __forceinline__ void step(double x, double y) { cum = cum + seg_len2(lx, ly, x, y); lx = x; ly = y; }
+  __device__ __forceinline__ double stamp(double st, double vel) const { return st - cum / vel; }
+};
+
+// The additions are sequential, up to 190 per edge; the rows and the chords are not.  One lane per edge walks the rows
+// ONCE (dubins_time_ckpt_kernel, right after the steering launch) and leaves cum at every kCkptRows-th row -- the
+// very doubles the fold passes through -- so that a piece of the check kernel folds at most kCkptRows - 1 chords
+// forward from the checkpoint at or below its first row.  A polyline is three arcs of < 2 pi at 0.1 rad or two and a
+// line: at most 190 rows, kCkptMax checkpoints; rows past the last checkpoint (none today) fold from it.
+constexpr int kCkptRows = 16;
+constexpr int kCkptMax = 12;
+
+struct TimeInfoRS {
+  double st, et, vel;
+  double gx, gy;
+  const double *ck;        // the edge's kCkptMax checkpoints: ck[c] = cum at row c * kCkptRows (ck[0] = 0)
+  int P;
+};
+
+__device__ __forceinline__ TimeInfoRS time_info_rs(const Steer &st, const double *__restrict__ s,
+                                                   const double *__restrict__ g, const double *ck) {
+  TimeInfoRS ti;
+  ti.st = s[2]; ti.et = g[2];
+  ti.vel = st.cost / (s[2] - g[2]);
+  ti.gx = g[0]; ti.gy = g[1];
+  ti.ck = ck;
+  ti.P = st.pc[0].len + st.pc[1].len + st.pc[2].len;
+  return ti;
+}
+
+__device__ __forceinline__ void polyline_point(const Piece *pc, int row, double r_min, double &x, double &y);
+
+// rows `row - 1` and `row` (1 <= row <= P - 1) of the stored polyline with their time stamps: the piece the edge
+// check hands to explicitEdgeCheck2D
+__device__ __forceinline__ void polyline_piece_rs(const Piece *pc, const TimeInfoRS &ti, int row, double r_min, double &px,
+                                                  double &py, double &pt, double &x, double &y, double &t) {
+  const int r0 = row - 1;
+  int c = r0 / kCkptRows;
+  c = c < kCkptMax ? c : kCkptMax - 1;
+  RunningSum rs;
+  polyline_point(pc, c * kCkptRows, r_min, x, y);
+  rs.start(ti.ck[c], x, y);
+  for (int i = c * kCkptRows + 1; i <= r0; ++i) {
+    polyline_point(pc, i, r_min, x, y);
+    rs.step(x, y);
+  }
+  px = rs.lx; py = rs.ly;
+  pt = (r0 == 0) ? ti.st : rs.stamp(ti.st, ti.vel);
+  if (row == ti.P - 1) { x = ti.gx; y = ti.gy; t = ti.et; return; }
+  polyline_point(pc, row, r_min, x, y);
+  rs.step(x, y);
+  t = rs.stamp(ti.st, ti.vel);
+}
+
 // edge.dist with S.spaceHasTime: sqrt(bestDist^2 + (start time - end time)^2), Inf stays Inf (:661-667)
 __device__ __forceinline__ double dist_with_time(double best, double st, double et) {
   if (best == __builtin_inf()) return best;
@@ -494,7 +555,11 @@ __device__ unsigned long long g_dub_clk[8];
 #define RRTX_DUB_ACC(acc, a, b) do { } while (0)
 #endif
 
-template <bool TIME>
+template <bool RSUM> struct TimeInfoOf { using type = TimeInfo; };
+template <> struct TimeInfoOf<true> { using type = TimeInfoRS; };
+
+// RSUM (with TIME): the pieces' time stamps are the reference's running sum, folded from the edge's checkpoints
+template <bool TIME, bool RSUM = false>
 struct WaveDubinsT {
   Piece pc[64][3];
   unsigned long long mask[64];
@@ -510,7 +575,7 @@ struct WaveDubinsT {
   int pstart[65];
   int pqn;
   unsigned char done[64];
-  TimeInfo ti[TIME ? 64 : 1];
+  typename TimeInfoOf<RSUM>::type ti[TIME ? 64 : 1];
 };
 
 __device__ __forceinline__ void polyline_point(const Piece *pc, int row, double r_min, double &x, double &y) {
@@ -520,10 +585,11 @@ __device__ __forceinline__ void polyline_point(const Piece *pc, int row, double 
   piece_point(pc[pi], row, r_min, x, y);
 }
 
-template <bool TIME>
-__device__ bool wave_dubins_collides(WaveDubinsT<TIME> &w, bool valid, const Steer &st, const double *__restrict__ sp,
+template <bool TIME, bool RSUM = false>
+__device__ bool wave_dubins_collides(WaveDubinsT<TIME, RSUM> &w, bool valid, const Steer &st, const double *__restrict__ sp,
                                      const double *__restrict__ gp, double r_min, double robot_radius,
-                                     const PolyTab &tab) {
+                                     const PolyTab &tab, const double *ck = nullptr) {
+  static_assert(TIME || !RSUM, "a running-sum time column needs a space with time");
   const double *__restrict__ meta = tab.meta;
   const int32_t *__restrict__ off = tab.off;
   const double *__restrict__ vxy = tab.vxy;
@@ -531,7 +597,8 @@ __device__ bool wave_dubins_collides(WaveDubinsT<TIME> &w, bool valid, const Ste
   const double sx = sp[0], sy = sp[1], gx = gp[0], gy = gp[1];
   const int lane = threadIdx.x & 63;
   w.pc[lane][0] = st.pc[0]; w.pc[lane][1] = st.pc[1]; w.pc[lane][2] = st.pc[2];
-  if constexpr (TIME) w.ti[lane] = time_info(st, sp, gp, r_min);
+  if constexpr (RSUM) w.ti[lane] = time_info_rs(st, sp, gp, ck);
+  else if constexpr (TIME) w.ti[lane] = time_info(st, sp, gp, r_min);
   w.done[lane] = 0;
   const int rows = st.pc[0].len + st.pc[1].len + st.pc[2].len;
   for (int j0 = 0; j0 < m; j0 += 64) {
@@ -826,7 +893,16 @@ __device__ bool wave_dubins_collides(WaveDubinsT<TIME> &w, bool valid, const Ste
       const int ee = (int)(ent & 63u), row = (int)((ent >> 6) & 255u), j = j0 + (int)(ent >> 14);
       if (w.done[ee]) return;
       double px, py, x, y, pt = 0.0, t = 0.0;
-      if constexpr (TIME) {
+      if constexpr (RSUM) {
+        // (a static obstacle never reads the stamps: only a piece that meets a moving one pays for the fold)
+        if (meta[4 * j + 3] >= 6.0) {
+          polyline_piece_rs(w.pc[ee], w.ti[ee], row, r_min, px, py, pt, x, y, t);
+        } else {
+          polyline_point(w.pc[ee], row - 1, r_min, px, py);
+          polyline_point(w.pc[ee], row, r_min, x, y);
+          if (row == w.ti[ee].P - 1) { x = w.ti[ee].gx; y = w.ti[ee].gy; }
+        }
+      } else if constexpr (TIME) {
         polyline_point_t(w.pc[ee], w.ti[ee], row - 1, r_min, px, py, pt);
         polyline_point_t(w.pc[ee], w.ti[ee], row, r_min, x, y, t);
       } else {
@@ -1113,18 +1189,47 @@ __global__ __launch_bounds__(256) void dubins_steer_rec_kernel(const EdgeSrc src
   }
 }
 
+// The running-sum checkpoints of the steered edges [base, base + count) (see RunningSum): one lane per edge walks the
+// rows of its record once, left to right, and stores cum at rows 0, kCkptRows, 2 kCkptRows, ... <= P - 2 at
+// ckpt[kCkptMax * k + c].  Launched between the steering and the check launch of a chunk, in a space with time only.
+__global__ __launch_bounds__(256) void dubins_time_ckpt_kernel(const EdgeSrc src, long long base, long long count, long long n,
+                                                               double r_min, const double *__restrict__ rec,
+                                                               double *__restrict__ ckpt) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  double s[4], g[4];
+  if (!load_edge(src, base + k, n, s, g)) return;     // (no such edge: its record may never have been written)
+  Steer st;
+  load_rec(rec + kRecDoubles * k, st);
+  const int P = st.pc[0].len + st.pc[1].len + st.pc[2].len;
+  double *__restrict__ ck = ckpt + kCkptMax * k;
+  ck[0] = 0.0;
+  RunningSum rs;
+  int row = 0;
+  for (int pi = 0; pi < 3; ++pi)
+    for (int j = 0; j < st.pc[pi].len && row <= P - 2; ++j, ++row) {
+      double x, y;
+      piece_point(st.pc[pi], j, r_min, x, y);
+      if (row == 0) { rs.start(0.0, x, y); continue; }
+      rs.step(x, y);
+      if (row % kCkptRows == 0 && row / kCkptRows < kCkptMax) ck[row / kCkptRows] = rs.cum;
+    }
+}
+
 // explicitEdgeCheck(S, ::DubinsEdge, ob) over the polygon list (:750-774) for the steered edges of a chunk:
 // stage 1 = straight chord with radius robotRadius + 2*minTurningRadius, stage 2 = every stored polyline piece
 // with robotRadius.  TIME: the pieces carry time; for the candidate edges of extend() (mode 1) bit 1 of the hit
 // byte says !validMove (findBestParent blocks an edge on explicitEdgeCheck || !validMove, R/DRRT_Q.jl:1960).
 // spread: a wave takes every n_waves-th edge of the chunk instead of 64 neighbours -- edges that arrive grouped
 // by their sample cost what the sample's surroundings make them cost, and all waves should get the same mix.
-template <bool TIME>
+// RSUM (with TIME): the pieces' stamps are the reference's running sum, folded from ckpt (dubins_time_ckpt_kernel).
+template <bool TIME, bool RSUM = false>
 __global__ __launch_bounds__(256, TIME ? 2 : 3) void dubins_check_rec_kernel(
     const EdgeSrc src, long long base, long long count, long long n, int spread, double r_min, double robot_radius,
-    double vmin, double vmax, const PolyTab tab, const double *__restrict__ rec, uint8_t *__restrict__ hit) {
-  __shared__ WaveDubinsT<TIME> wd[4];
-  WaveDubinsT<TIME> &w = wd[threadIdx.x >> 6];
+    double vmin, double vmax, const PolyTab tab, const double *__restrict__ rec, uint8_t *__restrict__ hit,
+    const double *__restrict__ ckpt) {
+  __shared__ WaveDubinsT<TIME, RSUM> wd[4];
+  WaveDubinsT<TIME, RSUM> &w = wd[threadIdx.x >> 6];
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long k = t;
   if (spread) {
@@ -1141,7 +1246,9 @@ __global__ __launch_bounds__(256, TIME ? 2 : 3) void dubins_check_rec_kernel(
   RRTX_DUB_ADD(6, 0ull, 1ull);
   int bad_move = 0;
   if (TIME && src.mode == 1 && valid && !valid_move_time(s[2], g[2], st.cost / (s[2] - g[2]), vmin, vmax)) bad_move = 2;
-  const bool h = wave_dubins_collides<TIME>(w, valid, st, s, g, r_min, robot_radius, tab);
+  bool h;
+  if constexpr (RSUM) h = wave_dubins_collides<TIME, RSUM>(w, valid, st, s, g, r_min, robot_radius, tab, ckpt + kCkptMax * (valid ? k : 0));
+  else h = wave_dubins_collides<TIME>(w, valid, st, s, g, r_min, robot_radius, tab);
   if (valid) hit[base + k] = (uint8_t)((h ? 1 : 0) | bad_move);
 }
 
@@ -1176,6 +1283,35 @@ __global__ __launch_bounds__(256) void dubins_trajectory_kernel(const double *__
       double x, y;
       piece_point(st.pc[pi], k, r_min, x, y);
       if (row < cap_rows) { traj[2 * row] = x; traj[2 * row + 1] = y; }
+    }
+}
+
+// The same rows in a space with time with the reference's running-sum time column: one lane per edge, one walk.
+__global__ __launch_bounds__(256) void dubins_trajectory_rs_kernel(const double *__restrict__ s, const double *__restrict__ g,
+                                                                   long long ne, double r_min,
+                                                                   const int64_t *__restrict__ traj_off,
+                                                                   double *__restrict__ traj, long long cap_rows,
+                                                                   int32_t *__restrict__ traj_len) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ne) return;
+  Steer st;
+  dubins_steer<true>(s + 4 * i, g + 4 * i, r_min, st);
+  const int P = st.pc[0].len + st.pc[1].len + st.pc[2].len;
+  if (traj_len) traj_len[i] = P;
+  if (!traj) return;
+  long long row = traj_off[i];
+  const double t0 = s[4 * i + 2], t1 = g[4 * i + 2];
+  const double vel = st.cost / (t0 - t1);
+  RunningSum rs;
+  int k = 0;
+  for (int pi = 0; pi < 3; ++pi)
+    for (int j = 0; j < st.pc[pi].len; ++j, ++k, ++row) {
+      double x, y, t;
+      piece_point(st.pc[pi], j, r_min, x, y);
+      if (k == 0) { rs.start(0.0, x, y); t = t0; }
+      else if (k == P - 1) { x = g[4 * i]; y = g[4 * i + 1]; t = t1; }
+      else { rs.step(x, y); t = rs.stamp(t0, vel); }
+      if (row < cap_rows) { traj[3 * row] = x; traj[3 * row + 1] = y; traj[3 * row + 2] = t; }
     }
 }
 
@@ -1224,6 +1360,13 @@ static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int 
   double *rec = ctx->ws_dub_rec.as<double>();
   double *rec2 = both ? rec + kRecDoubles * (size_t)chunk : nullptr;
   const int has_time = ctx->opt_space_has_time ? 1 : 0;
+  // the running-sum time column: only a moving obstacle ever reads a piece's stamps
+  const bool rsum = check && has_time && ctx->opt_dubins_time_column == RRTX_TIME_COLUMN_RUNNING_SUM && ctx->poly_has_moving;
+  double *ckpt = nullptr;
+  if (rsum) {
+    RRTX_HIP(ctx, ctx->ws_dub_ckpt.ensure(sizeof(double) * kCkptMax * (size_t)chunk));
+    ckpt = ctx->ws_dub_ckpt.as<double>();
+  }
   EdgeSrc rsrc = src;
   rsrc.dir = 1;
   for (long long base = 0; base < n; base += chunk) {
@@ -1238,13 +1381,21 @@ static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int 
       const EdgeSrc &cs = d ? rsrc : src;
       const double *rc_ = d ? rec2 : rec;
       uint8_t *h = d ? hit2 : hit;
+      if (rsum) {                 // (one checkpoint buffer: the two directions of a chunk take turns, in stream order)
+        span_begin(ctx, KF_DUBINS_STEER);
+        hipLaunchKernelGGL(dubins_time_ckpt_kernel, grid, block, 0, ctx->stream, cs, base, count, n, r_min, rc_, ckpt);
+        span_end(ctx);
+      }
       span_begin(ctx, KF_DUBINS);
-      if (has_time)
+      if (rsum)
+        hipLaunchKernelGGL((dubins_check_rec_kernel<true, true>), grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
+                           robot_radius, ctx->dubins_vmin, ctx->dubins_vmax, tab, rc_, h, ckpt);
+      else if (has_time)
         hipLaunchKernelGGL(dubins_check_rec_kernel<true>, grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
-                           robot_radius, ctx->dubins_vmin, ctx->dubins_vmax, tab, rc_, h);
+                           robot_radius, ctx->dubins_vmin, ctx->dubins_vmax, tab, rc_, h, ckpt);
       else
         hipLaunchKernelGGL(dubins_check_rec_kernel<false>, grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
-                           robot_radius, ctx->dubins_vmin, ctx->dubins_vmax, tab, rc_, h);
+                           robot_radius, ctx->dubins_vmin, ctx->dubins_vmax, tab, rc_, h, ckpt);
       span_end(ctx);
     }
   }
@@ -1290,7 +1441,11 @@ int launch_dubins_trajectory(rrtx_ctx *ctx, const double *s_dev, const double *g
   if (ne <= 0) return RRTX_OK;
   if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "Dubins steering needs a dim=4 [x y t theta] context");
   span_begin(ctx, KF_DUBINS);
-  hipLaunchKernelGGL(dubins_trajectory_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
+  if (ctx->opt_space_has_time && ctx->opt_dubins_time_column == RRTX_TIME_COLUMN_RUNNING_SUM)
+    hipLaunchKernelGGL(dubins_trajectory_rs_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
+                       s_dev, g_dev, (long long)ne, r_min, traj_off_dev, traj_dev, (long long)cap_rows, traj_len_dev);
+  else
+    hipLaunchKernelGGL(dubins_trajectory_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream,
                      s_dev, g_dev, (long long)ne, r_min, ctx->opt_space_has_time ? 1 : 0, traj_off_dev, traj_dev,
                      (long long)cap_rows, traj_len_dev);
   span_end(ctx);

@@ -587,7 +587,7 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->d_poly_orig, &ctx->d_poly_bbox, &ctx->d_poly_ytab, &ctx->d_poly_pbox, &ctx->d_poly_grid_start, &ctx->d_poly_grid_items, &ctx->d_poly_path_off, &ctx->d_poly_path, &ctx->ws_knn_off, &ctx->ws_knn_idx,
                     &ctx->ws_knn_dist, &ctx->ws_knn_misc, &ctx->ws_q, &ctx->ws_q2, &ctx->ws_slots, &ctx->ws_copies,
                     &ctx->ws_copy_meta, &ctx->ws_copies_f, &ctx->ws_recs, &ctx->ws_counts, &ctx->ws_bsum, &ctx->ws_scalars, &ctx->ws_scalars_nn, &ctx->ws_tmp,
-                    &ctx->ws_owner, &ctx->ws_dub_rec, &ctx->ws_out_off, &ctx->ws_out_idx, &ctx->ws_out_dist, &ctx->ws_out_u8a,
+                    &ctx->ws_owner, &ctx->ws_dub_rec, &ctx->ws_dub_ckpt, &ctx->ws_out_off, &ctx->ws_out_idx, &ctx->ws_out_dist, &ctx->ws_out_u8a,
                     &ctx->ws_out_u8b, &ctx->ws_out_i32, &ctx->ws_out_f64, &ctx->ws_partial, &ctx->ws_thr, &ctx->ws_mask, &ctx->ws_i32a, &ctx->ws_i32b,
                     &ctx->ws_slab_hist, &ctx->ws_slab_start, &ctx->ws_slab_sr, &ctx->ws_slab_params, &ctx->ws_run_hist, &ctx->ws_run_sr,
                     &ctx->ws_copies_s,
@@ -657,6 +657,12 @@ int rrtx_set_option(rrtx_ctx *ctx, int option, int64_t value) {
       if (value != 0 && ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "a space with time is [x y t theta]: dim = 4");
       ctx->opt_space_has_time = value != 0;
       return RRTX_OK;
+    case RRTX_OPT_DUBINS_TIME_COLUMN:
+      if (value != RRTX_TIME_COLUMN_PIECEWISE && value != RRTX_TIME_COLUMN_RUNNING_SUM)
+        return fail(ctx, RRTX_E_INVALID, "set_option: RRTX_OPT_DUBINS_TIME_COLUMN is 0 (piecewise) or 1 (running sum), not %lld",
+                    (long long)value);
+      ctx->opt_dubins_time_column = (int)value;
+      return RRTX_OK;
     case RRTX_OPT_NEAREST_REC_CAP: ctx->opt_nearest_rec_cap = value > 0 ? (long long)value : 0; return RRTX_OK;
     case RRTX_OPT_BUCKET_MULT: {
       int m = 2;
@@ -705,6 +711,7 @@ int rrtx_get_option(rrtx_ctx *ctx, int option, int64_t *value) {
     case RRTX_OPT_TUNE: *value = ctx->opt_tune; return RRTX_OK;
     case RRTX_OPT_ROOT_RULE: *value = ctx->opt_root_rule ? 1 : 0; return RRTX_OK;
     case RRTX_OPT_SPACE_HAS_TIME: *value = ctx->opt_space_has_time ? 1 : 0; return RRTX_OK;
+    case RRTX_OPT_DUBINS_TIME_COLUMN: *value = ctx->opt_dubins_time_column; return RRTX_OK;
     case RRTX_OPT_NEAREST_REC_CAP: *value = (int64_t)ctx->opt_nearest_rec_cap; return RRTX_OK;
     case RRTX_OPT_BUCKET_MULT: *value = ctx->bkt_mult; return RRTX_OK;
     case RRTX_OPT_LAST_PLACEMENT: *value = ctx->last_placement; return RRTX_OK;

@@ -142,6 +142,7 @@ struct rrtx_ctx {
   int opt_nn_cull = 1;              // 0 off, 1 auto (trees of >= 8192 nodes), 2 always
   long long opt_nearest_rec_cap = 0; // testing: candidate record capacity of the screened nearest scan (0 = default)
   int opt_space_has_time = 0;       // CSpace.spaceHasTime for the Dubins entry points ([x y t theta], R/DRRT_data_structures.jl:330)
+  int opt_dubins_time_column = 0;   // RRTX_OPT_DUBINS_TIME_COLUMN: 0 the kernels' piecewise form, 1 the reference's running sum
   double dubins_vmin = 0.0, dubins_vmax = 1e300;   // S.dubinsMinVelocity / dubinsMaxVelocity (validMove)
   int opt_root_rule = 1;            // 0: node 0 is not the tree's root (this context holds a later node range)
   int opt_tune = 0;                 // experiment switches (RRTX_OPT_TUNE), never change a result
@@ -220,6 +221,7 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_tmp;      // list entries that did not fit their bucket, in CSR position
   rrtx::DevBuf ws_owner;    // int32 owner query of every CSR entry (extend_candidates)
   rrtx::DevBuf ws_dub_rec;  // 128-byte records of the steered Dubins edges of one chunk (kernels_dubins.hip)
+  rrtx::DevBuf ws_dub_ckpt; // running-sum checkpoints of those edges, 12 doubles each (RRTX_OPT_DUBINS_TIME_COLUMN = 1)
   rrtx::DevBuf ws_out_off, ws_out_idx, ws_out_dist, ws_out_u8a, ws_out_u8b, ws_out_i32, ws_out_f64;
   rrtx::DevBuf ws_partial;  // nearest partials
   rrtx::DevBuf ws_thr;      // per-query thresholds

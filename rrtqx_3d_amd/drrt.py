@@ -326,6 +326,7 @@ class CSpace:
         self.goal = np.asarray(G, dtype=np.float64)
         self.spaceHasTime = False
         self.spaceHasTheta = False
+        self.dubinsTimeColumn = 0      # RRTX_OPT_DUBINS_TIME_COLUMN: 0 piecewise, 1 the reference's running sum
         self.robotRadius = 0.0
         self.delta = 0.0
         self.minTurningRadius = 0.0
@@ -339,6 +340,8 @@ class CSpace:
         if self._ctx is not tree.ctx:
             self._ctx = tree.ctx
             self._sig = None
+        if self._ctx.dim == 4 and self._ctx.dubins_time_column != int(self.dubinsTimeColumn):
+            self._ctx.set_dubins_time_column(int(self.dubinsTimeColumn))
         return self
 
     @property
