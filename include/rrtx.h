@@ -300,6 +300,35 @@ int rrtx_obstacle_sweep(rrtx_ctx *ctx, int obstacle, double search_range, double
 int rrtx_obstacle_sweep_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range /* k */,
                               double robot_radius, int block, int64_t *offsets /* k + 1 */, int32_t *edge_ids,
                               int64_t cap, int64_t *needed);
+/* The leaving half: the edge loops of a burst of CORRECTED removeObstacle calls (R/DRRT_Q.jl:3295-3362 each) in one pass
+ * over the mirror -- the expired spheres of one main-loop iteration.  The reference marks the obstacle unused before its
+ * edge loop (R/DRRT_Q.jl:3302) and an unused obstacle collides with nothing (R/DRRT_Q.jl:1777), so as written that loop
+ * never frees an edge; this call is what the loop means.  The call says which obstacles leave, the list's flags say
+ * which stay: with L the set of positions in `obstacles`, sphere i STAYS when active[i] (as last given to
+ * rrtx_spheres_set / rrtx_obstacle_update) and i is not in L.  CSR output as in rrtx_obstacle_sweep_batch: row j,
+ * edge_ids[offsets[j] .. offsets[j+1]), holds in ascending order the ids e for which all of
+ *   1. dist[e] == +Inf in the mirror when the call starts (the edge is blocked);
+ *   2. the start node of e is within search_range[j] (= robotRadius + delta + radius) of the centre of sphere
+ *      obstacles[j] -- the thresholds of rrtx_obstacle_sweep, the root taken with <=;
+ *   3. explicitEdgeCheck(S, e, sphere obstacles[j]) with the sphere inflated by robot_radius.  THE FLAG OF obstacles[j]
+ *      ITSELF IS NOT READ: a caller that follows the reference's order (mark unused at :3302, then loop) and one that
+ *      clears the flag afterwards get the same rows;
+ *   4. explicitEdgeCheck(S, e, sphere i) holds for no sphere i that stays
+ * hold.  An edge is in the row of every leaving obstacle it satisfies 1-3 for; test 4 is the same for every row; every
+ * row sees the mirror as it stood at entry; a position listed twice gives two equal rows.  The time-window condition
+ * of :3326-3337 (startTime <= timeElapsed <= startTime + lifeSpan of the others) is folded into the flags by the
+ * caller, as for rrtx_obstacle_sweep_polygon mode 1.
+ *   0 <= k <= 65536; k == 0 is RRTX_OK with offsets[0] = 0.  A position outside the sphere list is RRTX_E_INVALID and
+ *   nothing runs.  An empty tree and dim != 3 are RRTX_E_STATE; an empty mirror gives empty rows.  Two-call capacity
+ *   pattern: with more than cap ids in all rows together the call returns RRTX_E_CAPACITY with *needed set and
+ *   offsets valid.
+ *   unblock != 0: after a call that returns RRTX_OK every returned edge is left, on the device, exactly as
+ *   rrtx_graph_edges_unblock over the union of the rows leaves it (dist = distOriginal, R/DRRT_Q.jl:3342, marked as
+ *   touched for the next rrtx_graph_cost_update); the ids do not travel down and up again for it.  A call that does
+ *   not return RRTX_OK unblocks nothing. */
+int rrtx_obstacle_release_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range /* k */,
+                                double robot_radius, int unblock, int64_t *offsets /* k + 1 */, int32_t *edge_ids,
+                                int64_t cap, int64_t *needed);
 /* The obstacle sweeps of the POLYGON list -- the 2-D Euclidean and the Dubins space, with or without time
  * (legacy planner, R/DRRT.jl:3048-3290; BASELINE config 5's "dynamic discoverable obstacles" run these).  The edge
  * type is the context's: dim = 3 SimpleEdge, dim = 4 DubinsEdge (r_min = S.minTurningRadius; with
@@ -340,9 +369,17 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
  * root) left on the device: nodes and edges appended since then, costs changed with set_dist / block.  This is
  * the replanning step: edges whose cost was touched and that were parent edges orphan their subtrees
  * (propogateDescendants, R/DRRT_Q.jl:2760-2817), orphans restart at Inf, and only the region that changes is
- * relaxed again.  Without a previous solve for this root it is rrtx_graph_cost_to_root. */
+ * relaxed again.  Without a previous solve for this root it is rrtx_graph_cost_to_root.
+ * The mirror also keeps edge.distOriginal: the SimpleEdge cost written by rrtx_graph_edges_append, replaced by every
+ * value rrtx_graph_edges_set_dist writes -- Inf included: a caller that blocks through set_dist has replaced the
+ * original.  rrtx_graph_edges_block and the `block` of rrtx_obstacle_sweep_batch leave it alone.
+ * rrtx_graph_edges_unblock is the counterpart of rrtx_graph_edges_block, removeObstacle's `edge.dist =
+ * edge.distOriginal` (R/DRRT_Q.jl:3342): dist = distOriginal for every id, marked as touched for the next
+ * rrtx_graph_cost_update.  An id outside the mirror is RRTX_E_INVALID and nothing is written; an id that is not
+ * blocked is rewritten with its own value; n == 0 is RRTX_OK. */
 int rrtx_graph_edges_set_dist(rrtx_ctx *ctx, int64_t first_id, const double *dist, int64_t n);
 int rrtx_graph_edges_block(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n);
+int rrtx_graph_edges_unblock(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n);
 int rrtx_graph_cost_to_root(rrtx_ctx *ctx, int root_idx, double *lmc /* n_nodes */, int32_t *parent_edge /* n_nodes */,
                             int32_t *passes);
 int rrtx_graph_cost_update(rrtx_ctx *ctx, int root_idx, double *lmc /* n_nodes */, int32_t *parent_edge /* n_nodes */,

@@ -610,6 +610,45 @@ function obstacleSweepBatch(tree::HipTree, S::TS, obs::Vector{SphereObstacle}, b
   end
 end
 
+# The leaving half: the edge loops of removeObstacle (R/DRRT_Q.jl:3295-3362) for a burst of sphere obstacles that expire
+# in one iteration, in ONE pass over the registered edges (rrtx_obstacle_release_batch) and as the loop is meant -- the
+# reference marks ob unused first (:3302) and then frees nothing.  One id vector per obstacle, in the order given: the
+# registered edges that are blocked, start within robotRadius + delta + ob.radius of ob, collide with it and with no
+# obstacle that is in use and not in obs.  obstacleUnused of the obstacles in obs is not read.  unblock = true also
+# sets dist = distOriginal for every returned edge in the device mirror (unblockEdges over all of them, without the ids
+# travelling back); the caller still resets edge.dist on its own edge objects.
+function obstacleReleaseBatch(tree::HipTree, S::TS, obs::Vector{SphereObstacle}, unblock::Bool = false) where {TS}
+  syncObstacles(tree, S)
+  k = length(obs)
+  which = fill(Int32(-1), k)                  # list positions (0-based)
+  ptr = S.obstacles.front
+  for i = 1:S.obstacles.length
+    for j = 1:k
+      if ptr.data === obs[j]
+        which[j] = i - 1
+      end
+    end
+    ptr = ptr.child
+  end
+  all(which .>= 0) || error("obstacle is not in CSpace.obstacles")
+  range = Float64[S.robotRadius + S.delta + ob.radius for ob in obs]
+  offsets = Vector{Int64}(undef, k + 1)
+  cap = 4096
+  while true
+    ids = Vector{Int32}(undef, cap)
+    needed = Ref{Int64}(0)
+    rc = GC.@preserve which range offsets ids ccall((:rrtx_obstacle_release_batch, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Cdouble}, Cdouble, Cint, Ptr{Int64}, Ptr{Int32}, Int64, Ref{Int64}),
+        tree.ctx, which, k, range, S.robotRadius, unblock ? 1 : 0, offsets, ids, cap, needed)
+    if rc == RRTX_E_CAPACITY
+      cap = Int(needed[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    return [ids[Int(offsets[j]) + 1:Int(offsets[j + 1])] for j = 1:k]
+  end
+end
+
 # The same for the POLYGON list (legacy planner, R/DRRT.jl:3048-3290; BASELINE config 5's discoverable / moving
 # obstacles): findPointsInConflictWithObstacle(::Obstacle) -- Euclidean query, the Dubins one ([x y 0.0 pi], range +
 # pi), one query per path segment for kinds 6 / 7 -- and the edge loop of addNewObstacle (remove = false) or
@@ -654,6 +693,12 @@ end
 # addNewObstacle's `edge.dist = Inf` (R/DRRT_Q.jl:3249) for the ids obstacleSweep returned
 function blockEdges(tree::HipTree, ids::Vector{Int32})
   GC.@preserve ids rrtx_check(tree, ccall((:rrtx_graph_edges_block, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Ptr{Int32}, Int64), tree.ctx, ids, length(ids)))
+end
+
+# removeObstacle's `edge.dist = edge.distOriginal` (R/DRRT_Q.jl:3342) for the ids obstacleReleaseBatch returned
+function unblockEdges(tree::HipTree, ids::Vector{Int32})
+  GC.@preserve ids rrtx_check(tree, ccall((:rrtx_graph_edges_unblock, LIBRRTX), Cint,
       (Ptr{Cvoid}, Ptr{Int32}, Int64), tree.ctx, ids, length(ids)))
 end
 

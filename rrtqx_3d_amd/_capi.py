@@ -113,11 +113,13 @@ SYMBOLS = [
     ("rrtx_graph_edges_clear", C.c_int, [_VP]),
     ("rrtx_obstacle_sweep", C.c_int, [_VP, C.c_int, C.c_double, C.c_double, _VP, C.c_int64, c_int64_p]),
     ("rrtx_obstacle_sweep_batch", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_double, C.c_int, _VP, _VP, C.c_int64, c_int64_p]),
+    ("rrtx_obstacle_release_batch", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_double, C.c_int, _VP, _VP, C.c_int64, c_int64_p]),
     ("rrtx_points_check", C.c_int, [_VP, C.c_int, _VP, C.c_int64, C.c_double, C.c_int, _VP, _VP]),
     ("rrtx_simple_steer", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP]),
     ("rrtx_dubins_steer", C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_double, _VP, _VP]),
     ("rrtx_graph_edges_set_dist", C.c_int, [_VP, C.c_int64, _VP, C.c_int64]),
     ("rrtx_graph_edges_block", C.c_int, [_VP, _VP, C.c_int64]),
+    ("rrtx_graph_edges_unblock", C.c_int, [_VP, _VP, C.c_int64]),
     ("rrtx_graph_cost_to_root", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("rrtx_graph_cost_to_root_dev", C.c_int, [_VP, C.c_int, _VP, _VP]),
     ("rrtx_graph_cost_update", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),

@@ -594,6 +594,12 @@ class Context:
         ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
         self._check(self._lib.rrtx_graph_edges_block(self._h, _capi._ptr(ids), ids.shape[0]))
 
+    def graph_edges_unblock(self, edge_ids):
+        """removeObstacle's `edge.dist = edge.distOriginal` for the ids a release returned: the cost append / set_dist
+        wrote last comes back (an id that is not blocked keeps its value)"""
+        ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
+        self._check(self._lib.rrtx_graph_edges_unblock(self._h, _capi._ptr(ids), ids.shape[0]))
+
     def graph_cost_to_root(self, root_idx: int, want_parent: bool = True, update: bool = False):
         """rrtLMC of every node at the fixed point of rewire / reduceInconsistency (changeThresh = 0) over the
         edge mirror, and the id of each node's parent edge (-1: root or orphan).  Returns (lmc, parent_edge, passes).
@@ -641,6 +647,29 @@ class Context:
             return self._lib.rrtx_obstacle_sweep_batch(self._h, _capi._ptr(obs), k, _capi._ptr(rng), robot_radius,
                                                        1 if block else 0, _capi._ptr(off), _capi._ptr(ids), cap,
                                                        needed), (off, ids)
+        n, (off, ids) = self._two_call(cap, call)
+        return off, ids[:n]
+
+    def obstacle_release_batch(self, obstacles, search_range, robot_radius: float, unblock: bool = False,
+                               cap: Optional[int] = None):
+        """The edge loops of a burst of corrected removeObstacle calls in one pass over the mirror
+        (rrtx_obstacle_release_batch): returns (offsets, edge_ids), row j = the blocked edges that start within
+        search_range[j] of sphere obstacles[j], collide with it (its own flag is not read) and with no sphere that is
+        in use and not among `obstacles`; rows in the order given.  search_range: one range per obstacle (a scalar
+        serves all).  unblock=True also gives every returned edge its original cost back in the mirror, on the device
+        (what graph_edges_unblock over the union of the rows does)."""
+        obs = np.ascontiguousarray(obstacles, dtype=np.int32).reshape(-1)
+        k = obs.shape[0]
+        rng = np.ascontiguousarray(np.broadcast_to(np.asarray(search_range, dtype=np.float64), (k,)))
+        if cap is None:
+            cap = 4096
+
+        def call(cap, needed):
+            off = np.zeros(k + 1, dtype=np.int64)
+            ids = np.empty(max(cap, 1), dtype=np.int32)
+            return self._lib.rrtx_obstacle_release_batch(self._h, _capi._ptr(obs), k, _capi._ptr(rng), robot_radius,
+                                                         1 if unblock else 0, _capi._ptr(off), _capi._ptr(ids), cap,
+                                                         needed), (off, ids)
         n, (off, ids) = self._two_call(cap, call)
         return off, ids[:n]
 

@@ -53,15 +53,17 @@ __device__ __forceinline__ bool relax(unsigned long long *lmc, int *stamp, int v
   return false;
 }
 
-// SimpleEdge cost of mirrored edges [first, first + n): edge.dist = dist(start, end) over all coordinates
-// (calculateTrajectory, R/DRRT_SimpleEdge_functions.jl:177-181)
+// SimpleEdge cost of mirrored edges [first, first + n): edge.dist = edge.distOriginal = dist(start, end) over all
+// coordinates (calculateTrajectory, R/DRRT_SimpleEdge_functions.jl:177-181)
 __global__ void graph_edge_dist_kernel(const int32_t *__restrict__ es, const int32_t *__restrict__ ee, long long first,
                                        long long n, int dim, const double4 *__restrict__ naos, double *__restrict__ dist,
-                                       uint8_t *__restrict__ dirty) {
+                                       double *__restrict__ dist0, uint8_t *__restrict__ dirty) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double4 a = naos[es[first + i]], b = naos[ee[first + i]];
-  dist[first + i] = sqrt_rn(dim == 4 ? sq4(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w) : sq3(a.x, a.y, a.z, b.x, b.y, b.z));
+  const double w = sqrt_rn(dim == 4 ? sq4(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w) : sq3(a.x, a.y, a.z, b.x, b.y, b.z));
+  dist[first + i] = w;
+  dist0[first + i] = w;
   dirty[first + i] = 0;
 }
 
@@ -76,13 +78,31 @@ __global__ void graph_block_kernel(const int32_t *__restrict__ ids, long long n,
   if (e < in_ne) in_w[in_pos[e]] = __builtin_inf();
 }
 
-// costs of edges [first, first + n) were overwritten: mark them, refresh the copies the CSR holds
-__global__ void graph_touch_kernel(long long first, long long n, const double *__restrict__ dist, uint8_t *__restrict__ dirty,
-                                   const int32_t *__restrict__ in_pos, long long in_ne, double *__restrict__ in_w) {
+// edge.dist = edge.distOriginal (removeObstacle, R/DRRT_Q.jl:3342) for the edges ids[i] (in [0, ge_n); an id may
+// repeat: every copy writes the same values): graph_block_kernel's three writes with dist0[e] in place of Inf
+__global__ void graph_unblock_kernel(const int32_t *__restrict__ ids, long long n, double *__restrict__ dist,
+                                     const double *__restrict__ dist0, uint8_t *__restrict__ dirty,
+                                     const int32_t *__restrict__ in_pos, long long in_ne, double *__restrict__ in_w) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t e = ids[i];
+  const double w = dist0[e];
+  dist[e] = w;
+  dirty[e] = 1;
+  if (e < in_ne) in_w[in_pos[e]] = w;
+}
+
+// costs of edges [first, first + n) were overwritten: they are the edges' original costs from now on; mark them,
+// refresh the copies the CSR holds
+__global__ void graph_touch_kernel(long long first, long long n, const double *__restrict__ dist, double *__restrict__ dist0,
+                                   uint8_t *__restrict__ dirty, const int32_t *__restrict__ in_pos, long long in_ne,
+                                   double *__restrict__ in_w) {
   const long long e = first + (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= first + n) return;
+  const double w = dist[e];
+  dist0[e] = w;
   dirty[e] = 1;
-  if (e < in_ne) in_w[in_pos[e]] = dist[e];
+  if (e < in_ne) in_w[in_pos[e]] = w;
 }
 
 // ---- CSR of in-edges ------------------------------------------------------------------------------------------
@@ -369,7 +389,7 @@ int build_in_csr(rrtx_ctx *ctx, int n, long long ne) {
 int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n) {
   if (n <= 0) return RRTX_OK;
   hipLaunchKernelGGL(graph_edge_dist_kernel, grid_for(n), dim3(256), 0, ctx->stream, ctx->ge_start, ctx->ge_end, first, n,
-                     ctx->dim, reinterpret_cast<const double4 *>(ctx->nodes_aos), ctx->ge_dist, ctx->ge_dirty);
+                     ctx->dim, reinterpret_cast<const double4 *>(ctx->nodes_aos), ctx->ge_dist, ctx->ge_dist0, ctx->ge_dirty);
   RRTX_HIP(ctx, hipGetLastError());
   return RRTX_OK;
 }
@@ -397,11 +417,32 @@ int launch_graph_block_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n) {
   return RRTX_OK;
 }
 
+// ids (host, validated by the caller): dist = dist0
+int launch_graph_unblock(rrtx_ctx *ctx, const int32_t *ids_host, long long n) {
+  if (n <= 0) return RRTX_OK;
+  RRTX_HIP(ctx, ctx->gc.ids.ensure(sizeof(int32_t) * (size_t)n));
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->gc.ids.p, ids_host, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  const int rc = launch_graph_unblock_dev(ctx, ctx->gc.ids.as<int32_t>(), n);
+  if (rc) return rc;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));      // ids_host is the caller's
+  return RRTX_OK;
+}
+
+// the same for ids a kernel left on the device (the batched release's rows; an id may repeat): nothing travels, no sync
+int launch_graph_unblock_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n) {
+  if (n <= 0) return RRTX_OK;
+  hipLaunchKernelGGL(graph_unblock_kernel, grid_for(n), dim3(256), 0, ctx->stream, ids_dev, n, ctx->ge_dist, ctx->ge_dist0,
+                     ctx->ge_dirty, ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne, ctx->gc.in_w.as<double>());
+  RRTX_HIP(ctx, hipGetLastError());
+  ctx->gc.touched_old = true;
+  return RRTX_OK;
+}
+
 // edge costs [first, first + n) were overwritten on the stream (rrtx_graph_edges_set_dist)
 int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n) {
   if (n <= 0) return RRTX_OK;
-  hipLaunchKernelGGL(graph_touch_kernel, grid_for(n), dim3(256), 0, ctx->stream, first, n, ctx->ge_dist, ctx->ge_dirty,
-                     ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne, ctx->gc.in_w.as<double>());
+  hipLaunchKernelGGL(graph_touch_kernel, grid_for(n), dim3(256), 0, ctx->stream, first, n, ctx->ge_dist, ctx->ge_dist0,
+                     ctx->ge_dirty, ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne, ctx->gc.in_w.as<double>());
   RRTX_HIP(ctx, hipGetLastError());
   ctx->gc.touched_old = true;
   return RRTX_OK;

@@ -230,6 +230,81 @@ __global__ __launch_bounds__(kSweepGroup) void sweep_rows_write_kernel(
   }
 }
 
+// ---- the batched release (rrtx_obstacle_release_batch): the edge loops of a burst of removeObstacle calls ----
+// One block of kSweepBlock mirrored edges against a group of leaving obstacles.  An edge that is not blocked
+// (dist != Inf: almost every edge) is done after that one coalesced read; a blocked one takes
+// sweep_edges_words_kernel's path to its hit word.  Then the test against the spheres that stay (sph / stay / na:
+// the packed in-use records of the edge checks and one byte each, 0 = it leaves with this call), dealt across the
+// wave: the lanes with a hit word are taken in turn, the edge is broadcast, the 64 lanes hold it against 64 spheres
+// at a time and ballot; an edge some staying sphere hits loses its hit word.  Only after that the block forms its
+// list and the per-obstacle counts, exactly as sweep_edges_words_kernel leaves them for sweep_rows_write_kernel.
+__global__ __launch_bounds__(kSweepBlock) void release_edges_words_kernel(
+    const double *__restrict__ e_dist, const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end, long long ne,
+    int n_nodes, const unsigned long long *__restrict__ word, const double *__restrict__ naos,
+    const SweepObs *__restrict__ tab, int kg, int nb, const SphRec *__restrict__ sph, const uint8_t *__restrict__ stay, int na,
+    int32_t *__restrict__ seg_id, unsigned long long *__restrict__ seg_word, int *__restrict__ blk_n, int *__restrict__ cnt) {
+  __shared__ int wcnt[kSweepBlock / 64];
+  __shared__ unsigned long long lw[kSweepBlock];
+  const int t = threadIdx.x, lane = t & 63;
+  const long long e = (long long)blockIdx.x * blockDim.x + t;
+  unsigned long long hits = 0ull;
+  double ax = 0.0, ay = 0.0, az = 0.0, bx = 0.0, by = 0.0, bz = 0.0, len = 0.0;
+  if (e < ne && e_dist[e] == __builtin_inf()) {
+    const int a = e_start[e];
+    unsigned long long w = (unsigned)a < (unsigned)n_nodes ? word[a] : 0ull;
+    if (w != 0ull) {
+      const int b = e_end[e];
+      if ((unsigned)b < (unsigned)n_nodes) {
+        const double4 p0 = reinterpret_cast<const double4 *>(naos)[a];
+        const double4 p1 = reinterpret_cast<const double4 *>(naos)[b];
+        len = sqrt_rn(sq3(p0.x, p0.y, p0.z, p1.x, p1.y, p1.z));
+        ax = p0.x; ay = p0.y; az = p0.z;
+        bx = p1.x - p0.x; by = p1.y - p0.y; bz = p1.z - p0.z;
+        while (w != 0ull) {
+          const int j = __ffsll((long long)w) - 1;               // (j < kg: the mark kernel sets no other bit)
+          w &= w - 1ull;
+          if (edge_hits_sphere(ax, ay, az, bx, by, bz, len, tab[j].ob)) hits |= 1ull << j;
+        }
+      }
+    }
+  }
+  unsigned long long todo = __ballot(hits != 0ull);              // (wave-uniform: the loops below do not diverge)
+  while (todo != 0ull) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1ull;
+    const double sx = __shfl(ax, src), sy = __shfl(ay, src), sz = __shfl(az, src);
+    const double tx = __shfl(bx, src), ty = __shfl(by, src), tz = __shfl(bz, src), sl = __shfl(len, src);
+    bool kept = false;
+    for (int base = 0; base < na && !kept; base += 64) {
+      const int j = base + lane;
+      const bool h = j < na && stay[j] != 0 && edge_hits_sphere(sx, sy, sz, tx, ty, tz, sl, sph[j]);
+      kept = __ballot(h) != 0ull;
+    }
+    if (kept && lane == src) hits = 0ull;
+  }
+  const bool any = hits != 0ull;
+  const unsigned long long m = block_votes<kSweepBlock>(any, wcnt);
+  const int total = block_votes_total<kSweepBlock>(wcnt);
+  if (t == 0) blk_n[blockIdx.x] = total;
+  if (total == 0) {                                              // (the whole block takes this branch or none of it)
+    if (t < kg) cnt[(size_t)t * nb + blockIdx.x] = 0;
+    return;
+  }
+  if (any) {
+    const int r = block_votes_before(wcnt, t >> 6) + __popcll(m & lanes_below(lane));
+    const size_t at = (size_t)blockIdx.x * kSweepBlock + r;
+    seg_id[at] = (int32_t)e;
+    seg_word[at] = hits;
+    lw[r] = hits;
+  }
+  __syncthreads();
+  if (t < kg) {
+    int c = 0;
+    for (int r = 0; r < total; ++r) c += (int)((lw[r] >> t) & 1ull);
+    cnt[(size_t)t * nb + blockIdx.x] = c;
+  }
+}
+
 }  // namespace
 
 // device side of rrtx_obstacle_sweep; needed_dev[0] = colliding edges, needed_dev[1] = block count scratch
@@ -291,6 +366,54 @@ int launch_obstacle_sweep_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t 
                        ctx->nodes[2], n, tab, kg, ctx->ws_swb_word.as<unsigned long long>());
     hipLaunchKernelGGL(sweep_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ctx->ge_end, ne, n,
                        ctx->ws_swb_word.as<unsigned long long>(), ctx->nodes_aos, tab, kg, nb, ctx->ws_swb_seg_id.as<int32_t>(),
+                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(), ctx->ws_swb_cnt.as<int>());
+    launch_excl_scan(st, ctx->ws_swb_cnt.as<int>(), ctx->ws_swb_pos.as<long long>(), kg * nb);
+    hipLaunchKernelGGL(sweep_rows_write_kernel, dim3(nb), dim3(kSweepGroup), 0, st, ctx->ws_swb_seg_id.as<int32_t>(),
+                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(),
+                       ctx->ws_swb_pos.as<long long>(), nb, kg, ctx->ws_swb_base.as<long long>() + g,
+                       ctx->ws_swb_base.as<long long>() + g + 1, ctx->ws_swb_off.as<int64_t>() + (size_t)g * kSweepGroup, out_dev,
+                       (long long)cap);
+  }
+  span_end(ctx);
+  RRTX_HIP(ctx, hipGetLastError());
+  *total_dev = ctx->ws_swb_base.as<long long>() + ng;
+  return RRTX_OK;
+}
+
+// device side of rrtx_obstacle_release_batch (the mirror is not empty): launch_obstacle_sweep_batch's groups, buffers and
+// steps with release_edges_words_kernel as the pass over the mirror.  No group writes the mirror, so every row sees it
+// as it stood at entry; the caller unblocks the rows afterwards.
+int launch_obstacle_release_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev) {
+  const int n = (int)ctx->n_nodes;
+  const long long ne = ctx->ge_n;
+  const int nb = (int)((ne + kSweepBlock - 1) / kSweepBlock);
+  const int ng = (k + kSweepGroup - 1) / kSweepGroup;
+  const int kg_max = std::min(k, kSweepGroup);
+  const int na = ctx->sph_n_active;
+  if ((size_t)na != ctx->rel_stay_host.size()) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch: stay mask of %zu for %d spheres in use", ctx->rel_stay_host.size(), na);
+  RRTX_HIP(ctx, ctx->ws_swb_tab.ensure(sizeof(SweepObs) * (size_t)k));
+  RRTX_HIP(ctx, ctx->ws_rel_stay.ensure((size_t)(na > 0 ? na : 1)));
+  RRTX_HIP(ctx, ctx->ws_swb_word.ensure(sizeof(unsigned long long) * (size_t)n));
+  RRTX_HIP(ctx, ctx->ws_swb_seg_id.ensure(sizeof(int32_t) * (size_t)nb * kSweepBlock));
+  RRTX_HIP(ctx, ctx->ws_swb_seg_word.ensure(sizeof(unsigned long long) * (size_t)nb * kSweepBlock));
+  RRTX_HIP(ctx, ctx->ws_swb_blk_n.ensure(sizeof(int) * (size_t)nb));
+  RRTX_HIP(ctx, ctx->ws_swb_cnt.ensure(sizeof(int) * ((size_t)kg_max * nb + 1)));
+  RRTX_HIP(ctx, ctx->ws_swb_pos.ensure(sizeof(long long) * ((size_t)kg_max * nb + 2)));
+  RRTX_HIP(ctx, ctx->ws_swb_base.ensure(sizeof(long long) * (size_t)(ng + 1)));
+  RRTX_HIP(ctx, ctx->ws_swb_off.ensure(sizeof(int64_t) * (size_t)(k + 1)));
+  hipStream_t st = ctx->stream;
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_swb_tab.p, ctx->swb_tab_host.data(), sizeof(SweepObs) * (size_t)k, hipMemcpyHostToDevice, st));
+  if (na > 0) RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_rel_stay.p, ctx->rel_stay_host.data(), (size_t)na, hipMemcpyHostToDevice, st));
+  RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_swb_base.p, 0, sizeof(long long), st));
+  span_begin(ctx, KF_EDGES);
+  for (int g = 0; g < ng; ++g) {
+    const int kg = std::min(kSweepGroup, k - g * kSweepGroup);
+    const SweepObs *tab = ctx->ws_swb_tab.as<SweepObs>() + (size_t)g * kSweepGroup;
+    hipLaunchKernelGGL(sweep_mark_words_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
+                       ctx->nodes[2], n, tab, kg, ctx->ws_swb_word.as<unsigned long long>());
+    hipLaunchKernelGGL(release_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_dist, ctx->ge_start, ctx->ge_end,
+                       ne, n, ctx->ws_swb_word.as<unsigned long long>(), ctx->nodes_aos, tab, kg, nb, ctx->d_sph.as<SphRec>(),
+                       ctx->ws_rel_stay.as<uint8_t>(), na, ctx->ws_swb_seg_id.as<int32_t>(),
                        ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(), ctx->ws_swb_cnt.as<int>());
     launch_excl_scan(st, ctx->ws_swb_cnt.as<int>(), ctx->ws_swb_pos.as<long long>(), kg * nb);
     hipLaunchKernelGGL(sweep_rows_write_kernel, dim3(nb), dim3(kSweepGroup), 0, st, ctx->ws_swb_seg_id.as<int32_t>(),

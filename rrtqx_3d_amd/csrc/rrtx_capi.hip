@@ -595,7 +595,7 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_ev_a, &ctx->ws_ev_cnt, &ctx->ws_confirm_args, &ctx->ws_sph_lists, &ctx->ws_poly_lists, &ctx->d_sph_sample,
                     &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
                     &ctx->ws_swb_tab, &ctx->ws_swb_word, &ctx->ws_swb_seg_id, &ctx->ws_swb_seg_word, &ctx->ws_swb_blk_n, &ctx->ws_swb_cnt,
-                    &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off,
+                    &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off, &ctx->ws_rel_stay,
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
                     &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
                     &ctx->gc.in_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
@@ -605,6 +605,7 @@ int rrtx_destroy(rrtx_ctx *ctx) {
   if (ctx->ge_start) (void)hipFree(ctx->ge_start);
   if (ctx->ge_end) (void)hipFree(ctx->ge_end);
   if (ctx->ge_dist) (void)hipFree(ctx->ge_dist);
+  if (ctx->ge_dist0) (void)hipFree(ctx->ge_dist0);
   if (ctx->ge_dirty) (void)hipFree(ctx->ge_dirty);
   if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
   if (ctx->h_arena) (void)hipHostFree(ctx->h_arena);
@@ -1109,6 +1110,7 @@ int rrtx_graph_edges_append(rrtx_ctx *ctx, const int32_t *start_idx, const int32
     if ((rc = regrow(ctx, ctx->ge_start, nc, ctx->ge_n))) return rc;
     if ((rc = regrow(ctx, ctx->ge_end, nc, ctx->ge_n))) return rc;
     if ((rc = regrow(ctx, ctx->ge_dist, nc, ctx->ge_n))) return rc;
+    if ((rc = regrow(ctx, ctx->ge_dist0, nc, ctx->ge_n))) return rc;
     if ((rc = regrow(ctx, ctx->ge_dirty, nc, ctx->ge_n))) return rc;
     ctx->ge_cap = nc;
   }
@@ -1141,6 +1143,14 @@ int rrtx_graph_edges_block(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
   for (int64_t i = 0; i < n; ++i)
     if (edge_ids[i] < 0 || edge_ids[i] >= ctx->ge_n) return fail(ctx, RRTX_E_INVALID, "graph_edges_block: edge id %d out of range", edge_ids[i]);
   return launch_graph_block(ctx, edge_ids, n);
+}
+
+int rrtx_graph_edges_unblock(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
+  CHECK_CTX(ctx);
+  if (n < 0 || (n > 0 && !edge_ids)) return fail(ctx, RRTX_E_INVALID, "graph_edges_unblock: bad arguments");
+  for (int64_t i = 0; i < n; ++i)
+    if (edge_ids[i] < 0 || edge_ids[i] >= ctx->ge_n) return fail(ctx, RRTX_E_INVALID, "graph_edges_unblock: edge id %d out of range", edge_ids[i]);
+  return launch_graph_unblock(ctx, edge_ids, n);
 }
 
 namespace {
@@ -1417,6 +1427,62 @@ int rrtx_obstacle_sweep_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, co
     RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
     // addNewObstacle's dist = Inf for every id of every row, where the rows are
     if (block && (rc = launch_graph_block_dev(ctx, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return RRTX_OK;
+}
+
+int rrtx_obstacle_release_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range,
+                                double robot_radius, int unblock, int64_t *offsets, int32_t *edge_ids, int64_t cap,
+                                int64_t *needed) {
+  CHECK_CTX(ctx);
+  const int m = (int)ctx->sph_active.size();
+  if (k < 0 || k > 65536 || !offsets || (k > 0 && (!obstacles || !search_range)) || cap < 0 || (cap > 0 && !edge_ids))
+    return fail(ctx, RRTX_E_INVALID, "obstacle_release_batch: bad arguments");
+  for (int j = 0; j < k; ++j)
+    if (obstacles[j] < 0 || obstacles[j] >= m)
+      return fail(ctx, RRTX_E_INVALID, "obstacle_release_batch: obstacle %d (entry %d) out of range (%d spheres)", obstacles[j], j, m);
+  if (needed) *needed = 0;
+  if (k == 0) { offsets[0] = 0; return RRTX_OK; }
+  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch on an empty tree");
+  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch is the SimpleEdge (dim=3) path");
+  if (ctx->ge_n == 0) { std::fill(offsets, offsets + k + 1, (int64_t)0); return RRTX_OK; }
+  // the table of the batched sweep, every leaving obstacle taken as in use whatever its flag says (the reference
+  // marks it unused before its loop, R/DRRT_Q.jl:3302)
+  ctx->swb_tab_host.resize((size_t)k);
+  for (int j = 0; j < k; ++j) {
+    const double *c = &ctx->sph[4 * (size_t)obstacles[j]];
+    SweepObs &o = ctx->swb_tab_host[(size_t)j];
+    o.ob.cx = c[0]; o.ob.cy = c[1]; o.ob.cz = c[2];
+    o.ob.thr = thr_first_gt(robot_radius + c[3]);
+    o.thr_lt = thr_first_ge(search_range[j]);
+    o.thr_gt = thr_first_gt(search_range[j]);
+    o.active = 1;
+    o.pad0 = 0; o.pad1 = 0.0;
+  }
+  // the staying spheres: the packed in-use records of the edge checks, less the positions that leave
+  int rc = sync_spheres(ctx, robot_radius);
+  if (rc) return rc;
+  {
+    std::vector<uint8_t> leaves((size_t)m, 0);
+    for (int j = 0; j < k; ++j) leaves[(size_t)obstacles[j]] = 1;
+    const std::vector<int32_t> pos = active_positions(ctx->sph_active);
+    ctx->rel_stay_host.assign(pos.size(), 0);
+    for (size_t a = 0; a < pos.size(); ++a) ctx->rel_stay_host[a] = leaves[(size_t)pos[a]] ? 0 : 1;
+  }
+  const int64_t dcap = cap > 0 ? cap : 1;
+  RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)dcap));
+  long long *total_dev = nullptr;
+  rc = launch_obstacle_release_batch(ctx, k, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev);
+  if (rc) return rc;
+  RRTX_HIP(ctx, copy_out(ctx, offsets, ctx->ws_swb_off.p, sizeof(int64_t) * (size_t)(k + 1)));
+  int64_t total = 0;
+  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));
+  if ((rc = check_capacity(ctx, "obstacle_release_batch", "freed edges", total, cap, needed))) return rc;
+  if (total > 0) {
+    RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
+    // removeObstacle's dist = distOriginal for every id of every row, where the rows are
+    if (unblock && (rc = launch_graph_unblock_dev(ctx, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return RRTX_OK;

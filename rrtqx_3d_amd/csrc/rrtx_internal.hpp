@@ -233,6 +233,7 @@ struct rrtx_ctx {
   // device mirror of the planner's directed edges (obstacle sweeps, kernels_sweep.hip)
   int32_t *ge_start = nullptr, *ge_end = nullptr;
   double *ge_dist = nullptr;        // edge.dist of every mirrored edge (Inf = blocked); SimpleEdge cost by default
+  double *ge_dist0 = nullptr;       // edge.distOriginal: what append / set_dist wrote last (block leaves it alone)
   uint8_t *ge_dirty = nullptr;      // edge cost touched since the last cost solve (set_dist / block)
   rrtx::GraphCost gc;               // cost propagation state (kernels_graph.hip)
   int64_t ge_n = 0, ge_cap = 0;
@@ -241,6 +242,9 @@ struct rrtx_ctx {
   // (obstacle, block) and their scan, first CSR position of every group of 64 obstacles, the offsets
   rrtx::DevBuf ws_swb_tab, ws_swb_word, ws_swb_seg_id, ws_swb_seg_word, ws_swb_blk_n, ws_swb_cnt, ws_swb_pos, ws_swb_base, ws_swb_off;
   std::vector<rrtx::SweepObs> swb_tab_host;   // what ws_swb_tab is copied from (lives until the call's sync)
+  // the batched release: one byte per packed active sphere, 1 = it stays (is not among the call's leaving obstacles)
+  rrtx::DevBuf ws_rel_stay;
+  std::vector<uint8_t> rel_stay_host;         // what ws_rel_stay is copied from (lives until the call's sync)
 
   // parent / rewire selection over the extend lists (kernels_select.hip)
   double *node_lmc = nullptr;       // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
@@ -418,10 +422,17 @@ int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, 
 // offsets) / out_dev (at most cap ids) is obstacle j's sweep; *total_dev = the number of ids of all rows
 int launch_obstacle_sweep_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev);
 
+// device side of rrtx_obstacle_release_batch over ctx->swb_tab_host (k leaving obstacles, every one marked in use) and
+// ctx->rel_stay_host (sync_spheres has run for the call's robot radius): the same outputs, row j = the blocked edges
+// obstacle j hits and no staying sphere does
+int launch_obstacle_release_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev);
+
 int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n);
 int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n);
 int launch_graph_block(rrtx_ctx *ctx, const int32_t *ids_host, long long n);
 int launch_graph_block_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n);   // ids already on the device, in [0, ge_n)
+int launch_graph_unblock(rrtx_ctx *ctx, const int32_t *ids_host, long long n);
+int launch_graph_unblock_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n); // ids already on the device, in [0, ge_n)
 int launch_graph_cost(rrtx_ctx *ctx, int root, bool update, double *lmc_dev, int32_t *parent_dev, int *passes_out);
 void graph_cost_forget(rrtx_ctx *ctx);
 

@@ -765,6 +765,25 @@ def obstacleSweepBatch(S: CSpace, KD: HipTree, obs: Sequence[SphereObstacle], bl
     return [ids[off[j]:off[j + 1]] for j in range(len(obs))]
 
 
+def obstacleReleaseBatch(S: CSpace, KD: HipTree, obs: Sequence[SphereObstacle], unblock: bool = False) -> List[np.ndarray]:
+    """The edge loops of removeObstacle (R/DRRT_Q.jl:3295-3362) for a burst of SphereObstacles of S.obstacles that
+    expire in one iteration, as the loop is meant (the reference marks ob unused first, :3302, and then frees nothing):
+    one id array per obstacle, in the order given -- the registered edges that are blocked, start within robotRadius +
+    delta + ob.radius of ob, collide with it and with no obstacle that is in use and not in `obs`.  obstacleUnused of
+    the obstacles in `obs` is not read, so it may be set before or after the call.  unblock=True is unblockEdges over
+    all of them as well, without the ids travelling back."""
+    S.bind(KD)
+    _sync_obstacles(S)
+    if any(isinstance(ob, Obstacle) for ob in obs):
+        error("obstacleReleaseBatch takes sphere obstacles; polygons go through obstacleSweep(remove=True) one at a time")
+    if S.spaceHasTime or S.spaceHasTheta:
+        error("this type of obstacle not coded for this type of space")
+    off, ids = KD.ctx.obstacle_release_batch([_list_position(S, ob) for ob in obs],
+                                             [S.robotRadius + S.delta + ob.radius for ob in obs], S.robotRadius,
+                                             unblock=unblock)
+    return [ids[off[j]:off[j + 1]] for j in range(len(obs))]
+
+
 def syncEdgeCosts(KD: HipTree, first_id: int, edges: Sequence[SimpleEdge]):
     """edge.dist of registered edges first_id, first_id + 1, ... (registerEdges gives every edge the
     SimpleEdge cost of its two nodes; Dubins costs and costs in a space with time are sent with this)."""
@@ -774,6 +793,11 @@ def syncEdgeCosts(KD: HipTree, first_id: int, edges: Sequence[SimpleEdge]):
 def blockEdges(KD: HipTree, ids):
     """addNewObstacle's `edge.dist = Inf` (R/DRRT_Q.jl:3249) for the ids obstacleSweep returned."""
     KD.ctx.graph_edges_block(ids)
+
+
+def unblockEdges(KD: HipTree, ids):
+    """removeObstacle's `edge.dist = edge.distOriginal` (R/DRRT_Q.jl:3342) for the ids obstacleReleaseBatch returned."""
+    KD.ctx.graph_edges_unblock(ids)
 
 
 def costToRoot(KD: HipTree, root: RRTNode) -> Tuple[np.ndarray, np.ndarray]:
