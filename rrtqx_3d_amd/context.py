@@ -615,6 +615,15 @@ class Context:
     def graph_cost_update(self, root_idx: int, want_parent: bool = True):
         return self.graph_cost_to_root(root_idx, want_parent, update=True)
 
+    def graph_cost_to_root_dev(self, root_idx: int, lmc_ptr: int, parent_edge_ptr: Optional[int] = None):
+        """rrtx_graph_cost_to_root_dev: rrtLMC (n_nodes doubles) and parent edges (n_nodes int32, or None) into device
+        buffers, on the context's stream"""
+        self._check(self._lib.rrtx_graph_cost_to_root_dev(self._h, int(root_idx), lmc_ptr, parent_edge_ptr))
+
+    def graph_cost_update_dev(self, root_idx: int, lmc_ptr: int, parent_edge_ptr: Optional[int] = None):
+        """rrtx_graph_cost_update_dev: graph_cost_to_root_dev continuing from the previous solve"""
+        self._check(self._lib.rrtx_graph_cost_update_dev(self._h, int(root_idx), lmc_ptr, parent_edge_ptr))
+
     def obstacle_sweep(self, obstacle: int, search_range: float, robot_radius: float, cap: Optional[int] = None):
         """addNewObstacle's edge loop: ids (ascending) of the registered edges that start within
         search_range of sphere `obstacle` and collide with it."""

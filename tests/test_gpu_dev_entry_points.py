@@ -350,3 +350,89 @@ def test_extend_dev_polygons_without_the_sample_flags(moving):
         for a, b in zip(res[0], res[1]):
             assert np.array_equal(a, b)
         assert 0 < res[0][2].sum() < len(res[0][2])
+
+
+def _solve_dev(torch, ctx, root, update, want_parent=True):
+    """rrtx_graph_cost_to_root_dev / _update_dev into torch buffers (parent_edge_dev = NULL without want_parent)"""
+    n = ctx.n_nodes
+    d_lmc = torch.full((n,), -1.0, dtype=torch.float64, device="cuda:0")
+    d_par = torch.full((n,), -7, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    fn = ctx.graph_cost_update_dev if update else ctx.graph_cost_to_root_dev
+    fn(root, d_lmc.data_ptr(), d_par.data_ptr() if want_parent else None)
+    ctx.sync()
+    return d_lmc.cpu().numpy(), d_par.cpu().numpy()
+
+
+def test_graph_cost_dev_forms_on_the_three_node_graph():
+    """The graph of test_cost_to_root_edges_of_the_domain: 1 -> 0 (5), 2 -> 1 (12), a self loop at the root."""
+    torch = pytest.importorskip("torch")
+    from rrtqx_3d_amd import _capi
+    inf = float("inf")
+    with Context(3) as ctx:
+        d_one = torch.zeros(1, dtype=torch.float64, device="cuda:0")
+        with pytest.raises(_capi.RrtxError):
+            ctx.graph_cost_to_root_dev(0, d_one.data_ptr())                 # empty tree
+        ctx.nodes_append(np.array([[0.0, 0, 0], [3.0, 4.0, 0], [3.0, 4.0, 12.0]]))
+        lmc, par = _solve_dev(torch, ctx, 1, False)                         # no edges at all
+        assert lmc.tolist() == [inf, 0.0, inf] and par.tolist() == [-1, -1, -1]
+        ctx.graph_edges_append([1, 2, 0], [0, 1, 0])
+        lmc, par = _solve_dev(torch, ctx, 0, False)
+        assert lmc.tolist() == [0.0, 5.0, 17.0] and par.tolist() == [-1, 0, 1]
+        lmc_h, par_h, _ = ctx.graph_cost_to_root(0)
+        assert np.array_equal(lmc_h, lmc) and np.array_equal(par_h, par)
+        ctx.graph_edges_set_dist(1, [float("nan")])                         # a NaN cost never relaxes
+        lmc, par = _solve_dev(torch, ctx, 0, True)
+        assert lmc.tolist() == [0.0, 5.0, inf] and par.tolist() == [-1, 0, -1]
+        lmc, par = _solve_dev(torch, ctx, 0, True, want_parent=False)       # parent_edge_dev = NULL: nothing written there
+        assert lmc.tolist() == [0.0, 5.0, inf] and par.tolist() == [-7, -7, -7]
+        ctx.graph_edges_set_dist(1, [12.0])
+        lmc, par = _solve_dev(torch, ctx, 0, True)
+        assert lmc.tolist() == [0.0, 5.0, 17.0] and par.tolist() == [-1, 0, 1]
+        for bad in (-1, 3):
+            with pytest.raises(_capi.RrtxError):
+                ctx.graph_cost_to_root_dev(bad, d_one.data_ptr())
+            with pytest.raises(_capi.RrtxError):
+                ctx.graph_cost_update_dev(bad, d_one.data_ptr())
+        with pytest.raises(_capi.RrtxError):
+            ctx.graph_cost_update_dev(0, None)                              # lmc_dev = NULL
+        lmc, par = _solve_dev(torch, ctx, 0, True)                          # the refused calls changed nothing
+        assert lmc.tolist() == [0.0, 5.0, 17.0] and par.tolist() == [-1, 0, 1]
+
+
+def test_graph_cost_dev_forms_match_host_forms_on_a_geometric_graph(oracle):
+    """2000 nodes, both directed edges between nodes closer than 4.5: a full solve, an update after blocking parent
+    edges, one after unblocking half of them and re-pricing, each in the device-pointer form on one context and in the
+    host form on another; bit for bit, with and without the parent array."""
+    torch = pytest.importorskip("torch")
+    from test_gpu_graph_cost import _geometric_graph
+    rng = np.random.default_rng(2000)
+    n, root = 2000, 17
+    pts = rng.uniform(-20, 20, (n, 3))
+    s, e = _geometric_graph(oracle, pts, 4.5)
+    with Context(3) as host, Context(3) as dctx:
+        for c in (host, dctx):
+            c.nodes_append(pts)
+            c.graph_edges_append(s, e)
+        lmc_h, par_h, _ = host.graph_cost_to_root(root)
+        lmc_d, par_d = _solve_dev(torch, dctx, root, False)
+        assert np.isfinite(lmc_h).sum() > n // 2
+        assert np.array_equal(lmc_d, lmc_h) and np.array_equal(par_d, par_h)
+        victims = rng.choice(np.nonzero(par_h >= 0)[0], 100, replace=False)
+        blocked = np.unique(par_h[victims]).astype(np.int32)
+        for c in (host, dctx):
+            c.graph_edges_block(blocked)
+        lmc_h1, par_h1, _ = host.graph_cost_update(root)
+        lmc_d1, par_d1 = _solve_dev(torch, dctx, root, True)
+        assert not np.array_equal(lmc_h1, lmc_h)
+        assert np.array_equal(lmc_d1, lmc_h1) and np.array_equal(par_d1, par_h1)
+        w = rng.uniform(0.5, 5.0, 300)
+        for c in (host, dctx):
+            c.graph_edges_unblock(blocked[::2])
+            c.graph_edges_set_dist(1000, w)
+        lmc_h2, par_h2, _ = host.graph_cost_update(root)
+        lmc_d2, par_d2 = _solve_dev(torch, dctx, root, True, want_parent=False)
+        assert not np.array_equal(lmc_h2, lmc_h1)
+        assert np.array_equal(lmc_d2, lmc_h2) and (par_d2 == -7).all()
+        lmc_d3, par_d3 = _solve_dev(torch, dctx, root, False)               # the full solve of the same state
+        assert np.array_equal(lmc_d3, lmc_h2) and np.array_equal(par_d3, par_h2)
