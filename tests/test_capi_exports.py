@@ -32,6 +32,17 @@ def test_binding_table_matches_header(hip_lib):
     assert bound == declared_symbols()
 
 
+def test_option_numbers_match_header():
+    """every RRTX_OPT_* the header defines has the same number in the binding, and the binding names no other"""
+    text = open(os.path.join(ROOT, "include", "rrtx.h")).read()
+    defines = re.findall(r"^#define\s+(RRTX_OPT_[A-Z0-9_]+)\s+\(?(-?\d+)\)?(?:\s|$)", text, flags=re.M)
+    header = {name: int(val) for name, val in defines}
+    assert len(header) == len(defines)                                 # no name defined twice
+    assert sorted(header.values()) == list(range(1, 17)), header      # 1 .. 16, each once
+    bound = {name: getattr(_capi, name) for name in dir(_capi) if name.startswith("RRTX_OPT_")}
+    assert bound == header
+
+
 def test_signatures_are_plain_c(hip_lib):
     # no torch / C++ types may appear in the boundary
     text = open(os.path.join(ROOT, "include", "rrtx.h")).read()
