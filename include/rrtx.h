@@ -384,6 +384,34 @@ int rrtx_graph_cost_to_root(rrtx_ctx *ctx, int root_idx, double *lmc /* n_nodes 
                             int32_t *passes);
 int rrtx_graph_cost_update(rrtx_ctx *ctx, int root_idx, double *lmc /* n_nodes */, int32_t *parent_edge /* n_nodes */,
                            int32_t *passes);
+/* rrtx_graph_cost_update that reports the nodes it changed instead of every node: what propogateDescendants /
+ * reduceInconsistency (R/DRRT_Q.jl:2647-2817) hand their caller -- the new orphans, the nodes whose rrtLMC moved, the
+ * nodes with another parent edge.  The solve is exactly that of rrtx_graph_cost_update(ctx, root_idx, ...): the same
+ * resume rule, fixed point, parent rule (lowest edge id that attains the minimum) and failure behaviour (a failing
+ * solve forgets the previous solve); it leaves the solver state rrtx_graph_cost_update would leave, so the two calls
+ * mix freely.
+ *   Baseline: the context remembers what this call last reported -- a root and, per node, the 64-bit pattern of its
+ *     rrtLMC and its parent edge.  A node beyond the remembered count, or every node when the remembered root is not
+ *     root_idx, counts as reported +Inf / -1 (rrtx_node_cost_set's convention for a node never set).
+ *   Output: the nodes v whose rrtLMC (compared as a bit pattern) or parent edge differs from the baseline, ascending:
+ *     node[i] = v, lmc[i] = its rrtLMC (+Inf: an orphan), parent_edge[i] = its parent edge id (-1: the root or an
+ *     orphan; parent_edge may be NULL, changes are judged on both fields all the same).  The first call for a root
+ *     returns every node that reaches the root and the root itself (lmc 0 against +Inf); a call after which nothing
+ *     differs returns *needed = 0.
+ *   Capacity, two-call pattern: more than cap changed nodes is RRTX_E_CAPACITY with *needed set, the baseline NOT
+ *     advanced and the three arrays unspecified; the next call with room returns the same list (its solve has nothing
+ *     new to do).  cap == 0 with NULL arrays counts only.  RRTX_OK advances the baseline to the solver's state of all
+ *     n_nodes nodes.
+ *   store != 0: whenever the solve itself succeeded (RRTX_OK or RRTX_E_CAPACITY) the context's own rrtLMC array --
+ *     the one rrtx_node_cost_set writes and lmc == NULL reads in rrtx_extend_select / rrtx_find_new_target -- holds the
+ *     solver's value of every node 0 .. n_nodes-1, copied on the device bit for bit over whatever was there.
+ *     store == 0 leaves that array alone.
+ *   Errors: RRTX_E_INVALID for cap < 0, cap > 0 with node or lmc NULL, needed NULL, a root outside the tree; what
+ *     rrtx_graph_cost_update refuses is refused alike (RRTX_E_STATE on an empty tree).  A failing call keeps the
+ *     baseline: what the caller was told still stands.  rrtx_graph_edges_clear forgets the baseline (the remembered
+ *     edge ids die with the mirror). */
+int rrtx_graph_cost_update_delta(rrtx_ctx *ctx, int root_idx, int store, int32_t *node, double *lmc, int32_t *parent_edge,
+                                 int64_t cap, int64_t *needed, int32_t *passes);
 /* explicitPointCheck (R/DRRT_Q.jl:1520-1556; quick=0: explicitPointCheck3D,
  * :1558-1590).  unsafe[i] in {0,1}; clearance[i] = the returned certificate
  * (0.0 when unsafe); clearance may be NULL when only the flag is wanted (the

@@ -715,6 +715,31 @@ function costToRoot(tree::HipTree, root)
   return lmc, parent
 end
 
+# costToRoot's update (rrtx_graph_cost_update) reported as the nodes it changed since the last call for this root:
+# what propogateDescendants / reduceInconsistency (R/DRRT_Q.jl:2647-2817) touched.  Returns (node, lmc, parent):
+# 0-based node indices (ascending), their rrtLMC (Inf: a new orphan), the registered id of their parent edge (-1: root /
+# orphan).  store = true leaves rrtLMC of every node in the context's own device array (setNodeCosts' array).
+function costUpdateDelta(tree::HipTree, root, store::Bool = false)
+  cap = 4096
+  while true
+    node = Vector{Int32}(undef, cap)
+    lmc = Vector{Float64}(undef, cap)
+    parent = Vector{Int32}(undef, cap)
+    needed = Ref{Int64}(0)
+    passes = Ref{Int32}(0)
+    rc = GC.@preserve node lmc parent ccall((:rrtx_graph_cost_update_delta, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}, Int64, Ref{Int64}, Ref{Int32}),
+        tree.ctx, tree.indexOf[root], store ? 1 : 0, node, lmc, parent, cap, needed, passes)
+    if rc == RRTX_E_CAPACITY
+      cap = Int(needed[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    n = Int(needed[])
+    return node[1:n], lmc[1:n], parent[1:n]
+  end
+end
+
 
 # ---------------------------------------------------------------------------
 # Edge = DubinsEdge (R/DRRT_DubinsEdge.jl, R/DRRT_DubinsEdge_functions.jl; README's per-edge-type

@@ -615,6 +615,27 @@ class Context:
     def graph_cost_update(self, root_idx: int, want_parent: bool = True):
         return self.graph_cost_to_root(root_idx, want_parent, update=True)
 
+    def graph_cost_update_delta(self, root_idx: int, store: bool = False, cap: Optional[int] = None):
+        """rrtx_graph_cost_update_delta: graph_cost_update's solve, reported as the nodes whose rrtLMC (bit pattern) or
+        parent edge differs from what this call last reported for the root (a node never reported counts as +Inf / -1).
+        Returns (node, lmc, parent_edge, passes), nodes ascending; lmc +Inf and parent_edge -1 for a new orphan.
+        store=True also leaves the solver's rrtLMC of every node in the context's own device array, the one
+        node_cost_set writes and extend_select / find_new_target read with lmc=None.  cap: room offered to the first
+        attempt; the buffers grow and the call is made once more when more nodes changed."""
+        if cap is None:
+            cap = 4096
+        passes = C.c_int32()
+
+        def call(cap, needed):
+            node = np.empty(max(cap, 1), dtype=np.int32)
+            lmc = np.empty(max(cap, 1), dtype=np.float64)
+            par = np.empty(max(cap, 1), dtype=np.int32)
+            return self._lib.rrtx_graph_cost_update_delta(self._h, int(root_idx), 1 if store else 0, _capi._ptr(node),
+                                                          _capi._ptr(lmc), _capi._ptr(par), cap, needed,
+                                                          C.byref(passes)), (node, lmc, par)
+        n, (node, lmc, par) = self._two_call(cap, call)
+        return node[:n], lmc[:n], par[:n], passes.value
+
     def graph_cost_to_root_dev(self, root_idx: int, lmc_ptr: int, parent_edge_ptr: Optional[int] = None):
         """rrtx_graph_cost_to_root_dev: rrtLMC (n_nodes doubles) and parent edges (n_nodes int32, or None) into device
         buffers, on the context's stream"""

@@ -333,6 +333,83 @@ __global__ void graph_out_kernel(NodeState s, int n, double *__restrict__ lmc_ou
   if (parent_out) parent_out[i] = s.parent[i] == kNoParent ? -1 : s.parent[i];
 }
 
+// ---- the nodes a solve changed (rrtx_graph_cost_update_delta) ---------------------------------------------------
+// The caller of propogateDescendants / reduceInconsistency (R/DRRT_Q.jl:2647-2817) learns which nodes they touched;
+// here that set is the nodes whose (rrtLMC bit pattern, parent edge) differ from what the last delta call reported
+// (base_lmc / base_par, parent edges in their public form: -1 = none; known == 0: nothing reported for this root).
+// Two kernels over workgroups of kDeltaBlock nodes with the one-workgroup scan of their counts between them: the first
+// counts the differing nodes of every workgroup, the second ranks them again and writes node v's record at
+// pos[workgroup] + rank.  Ranks follow the node index, so the records are ascending and the same from run to run; no
+// atomics.  Nothing is written at or beyond cap.
+constexpr int kDeltaBlock = 256;     // nodes per workgroup of the two kernels (tests/test_gpu_cost_delta.py: W)
+
+struct DeltaBase {
+  const unsigned long long *lmc;
+  const int32_t *par;
+  int known;
+};
+
+__device__ __forceinline__ bool delta_differs(const NodeState &s, const DeltaBase &b, int i, unsigned long long &l, int32_t &p) {
+  l = s.lmc[i];
+  const int32_t raw = s.parent[i];
+  p = raw == kNoParent ? -1 : raw;
+  const unsigned long long bl = b.known ? b.lmc[i] : kInfBits;
+  const int32_t bp = b.known ? b.par[i] : -1;
+  return l != bl || p != bp;
+}
+
+// counts per workgroup; store_to (may be null): the context's rrtLMC array takes every node's value on the way
+__global__ __launch_bounds__(kDeltaBlock) void graph_delta_count_kernel(NodeState s, int n, DeltaBase b, double *__restrict__ store_to,
+                                                                        int *__restrict__ cnt) {
+  __shared__ int wcnt[kDeltaBlock / 64];
+  const int i = blockIdx.x * kDeltaBlock + threadIdx.x;
+  bool d = false;
+  if (i < n) {
+    unsigned long long l;
+    int32_t p;
+    d = delta_differs(s, b, i, l, p);
+    if (store_to) store_to[i] = __longlong_as_double((long long)l);
+  }
+  block_votes<kDeltaBlock>(d, wcnt);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = block_votes_total<kDeltaBlock>(wcnt);
+}
+
+__global__ __launch_bounds__(kDeltaBlock) void graph_delta_write_kernel(NodeState s, int n, DeltaBase b, const int64_t *__restrict__ pos,
+                                                                        long long cap, int32_t *__restrict__ node,
+                                                                        double *__restrict__ lmc, int32_t *__restrict__ par) {
+  __shared__ int wcnt[kDeltaBlock / 64];
+  const int i = blockIdx.x * kDeltaBlock + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool d = false;
+  unsigned long long l = kInfBits;
+  int32_t p = -1;
+  if (i < n) d = delta_differs(s, b, i, l, p);
+  const unsigned long long votes = block_votes<kDeltaBlock>(d, wcnt);
+  if (!d) return;
+  const long long at = (long long)pos[blockIdx.x] + block_votes_before(wcnt, wave) + __popcll(votes & lanes_below(lane));
+  if (at >= cap) return;
+  node[at] = i;
+  lmc[at] = __longlong_as_double((long long)l);
+  par[at] = p;
+}
+
+// what was reported = the solver's state, for nodes [0, n): 12 bytes a node
+__global__ void graph_delta_advance_kernel(NodeState s, int n, unsigned long long *__restrict__ base_lmc, int32_t *__restrict__ base_par) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  base_lmc[i] = s.lmc[i];
+  const int32_t raw = s.parent[i];
+  base_par[i] = raw == kNoParent ? -1 : raw;
+}
+
+// nodes [first, first + m) have never been reported: +Inf / -1
+__global__ void graph_delta_unreported_kernel(long long first, long long m, unsigned long long *__restrict__ base_lmc,
+                                              int32_t *__restrict__ base_par) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  base_lmc[first + i] = kInfBits;
+  base_par[first + i] = -1;
+}
+
 // grow a buffer whose first keep bytes must survive
 hipError_t ensure_keep(DevBuf &b, size_t need, size_t keep, hipStream_t st) {
   if (need <= b.bytes) return hipSuccess;
@@ -448,7 +525,7 @@ int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n) {
   return RRTX_OK;
 }
 
-// lmc_dev: n_nodes doubles, parent_dev: n_nodes int32 (may be null).  update = continue from the previous solve when
+// lmc_dev: n_nodes doubles (null: the state stays on the device only), parent_dev: n_nodes int32 (may be null).  update = continue from the previous solve when
 // there is one for this root.
 static int graph_cost_impl(rrtx_ctx *ctx, int root, bool update, double *lmc_dev, int32_t *parent_dev, int *passes_out);
 
@@ -569,7 +646,7 @@ static int graph_cost_impl(rrtx_ctx *ctx, int root, bool update, double *lmc_dev
   if (ne > 0)
     hipLaunchKernelGGL(graph_parent_kernel, grid_for(ne), dim3(256), 0, st, ctx->ge_start, ctx->ge_end, ctx->ge_dist, ne, root, s,
                        flags + kFlagZeroCost);
-  hipLaunchKernelGGL(graph_out_kernel, grid_for(n), dim3(256), 0, st, s, n, lmc_dev, parent_dev);
+  if (lmc_dev) hipLaunchKernelGGL(graph_out_kernel, grid_for(n), dim3(256), 0, st, s, n, lmc_dev, parent_dev);   // (the delta call reads the state itself)
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
   if (!resume || gc.touched_old) {
@@ -591,6 +668,66 @@ void graph_cost_forget(rrtx_ctx *ctx) {
   ctx->gc.in_ne = 0;
   ctx->gc.in_nn = 0;
   ctx->gc.touched_old = false;
+}
+
+// rrtx_graph_cost_update_delta, device side: the solve of launch_graph_cost(update), then the records of the nodes that
+// differ from the baseline into node_dev / lmc_dev / par_dev (room for cap each, cap >= 0; at least one slot allocated)
+// and their number into *total_dev.  store: ctx->node_lmc takes the solver's value of every node.  The baseline stays
+// as it is: launch_graph_delta_advance moves it once the caller knows that the records fit.
+int launch_graph_delta(rrtx_ctx *ctx, int root, bool store, int32_t *node_dev, double *lmc_dev, int32_t *par_dev, long long cap,
+                       int64_t **total_dev, int *passes_out) {
+  int rc = launch_graph_cost(ctx, root, true, nullptr, nullptr, passes_out);
+  if (rc) return rc;
+  GraphCost &gc = ctx->gc;
+  const int n = (int)ctx->n_nodes;
+  hipStream_t st = ctx->stream;
+  // the baseline grows with the tree; nodes it has not seen yet read as never reported
+  const size_t keep = (size_t)gc.rep_nodes;
+  RRTX_HIP(ctx, ensure_keep(gc.rep_lmc, sizeof(unsigned long long) * (size_t)n, sizeof(unsigned long long) * keep, st));
+  RRTX_HIP(ctx, ensure_keep(gc.rep_parent, sizeof(int32_t) * (size_t)n, sizeof(int32_t) * keep, st));
+  if (n > gc.rep_nodes) {
+    const long long m = n - gc.rep_nodes;
+    hipLaunchKernelGGL(graph_delta_unreported_kernel, grid_for(m), dim3(256), 0, st, (long long)gc.rep_nodes, m,
+                       gc.rep_lmc.as<unsigned long long>(), gc.rep_parent.as<int32_t>());
+    gc.rep_nodes = n;
+  }
+  double *store_to = nullptr;
+  if (store) {
+    if ((rc = node_cost_ensure(ctx))) return rc;
+    store_to = ctx->node_lmc;
+  }
+  const int nb = (n + kDeltaBlock - 1) / kDeltaBlock;
+  RRTX_HIP(ctx, gc.delta_cnt.ensure(sizeof(int) * (size_t)nb));
+  RRTX_HIP(ctx, gc.delta_pos.ensure(sizeof(int64_t) * (size_t)(nb + 2)));      // nb + 1 offsets, then the total once more
+  const NodeState s{gc.lmc.as<unsigned long long>(), gc.parent.as<int32_t>(), gc.stamp.as<int>()};
+  const DeltaBase b{gc.rep_lmc.as<unsigned long long>(), gc.rep_parent.as<int32_t>(), gc.rep_root == root ? 1 : 0};
+  int64_t *pos = gc.delta_pos.as<int64_t>();
+  span_begin(ctx, KF_EDGES);
+  hipLaunchKernelGGL(graph_delta_count_kernel, dim3(nb), dim3(kDeltaBlock), 0, st, s, n, b, store_to, gc.delta_cnt.as<int>());
+  launch_excl_scan(st, gc.delta_cnt.as<int>(), pos, nb, pos + nb + 1);
+  hipLaunchKernelGGL(graph_delta_write_kernel, dim3(nb), dim3(kDeltaBlock), 0, st, s, n, b, pos, cap, node_dev, lmc_dev, par_dev);
+  span_end(ctx);
+  RRTX_HIP(ctx, hipGetLastError());
+  *total_dev = pos + nb + 1;
+  return RRTX_OK;
+}
+
+// the records of the last launch_graph_delta reached the caller: they, and everything unchanged, are what was reported
+int launch_graph_delta_advance(rrtx_ctx *ctx, int root) {
+  GraphCost &gc = ctx->gc;
+  const int n = (int)ctx->n_nodes;
+  const NodeState s{gc.lmc.as<unsigned long long>(), gc.parent.as<int32_t>(), gc.stamp.as<int>()};
+  hipLaunchKernelGGL(graph_delta_advance_kernel, grid_for(n), dim3(256), 0, ctx->stream, s, n, gc.rep_lmc.as<unsigned long long>(),
+                     gc.rep_parent.as<int32_t>());
+  RRTX_HIP(ctx, hipGetLastError());
+  gc.rep_root = root;
+  return RRTX_OK;
+}
+
+// the edge ids the baseline remembers are gone (rrtx_graph_edges_clear)
+void graph_delta_forget(rrtx_ctx *ctx) {
+  ctx->gc.rep_root = -1;
+  ctx->gc.rep_nodes = 0;
 }
 
 }  // namespace rrtx

@@ -598,7 +598,7 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off, &ctx->ws_rel_stay,
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
                     &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
-                    &ctx->gc.in_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
+                    &ctx->gc.in_pos, &ctx->gc.rep_lmc, &ctx->gc.rep_parent, &ctx->gc.delta_cnt, &ctx->gc.delta_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
                     &ctx->ws_tgt_blk[0], &ctx->ws_tgt_blk[1], &ctx->ws_tgt_res};
   for (auto b : bufs) b->release();
   if (ctx->node_lmc) (void)hipFree(ctx->node_lmc);
@@ -1088,6 +1088,7 @@ int rrtx_graph_edges_clear(rrtx_ctx *ctx) {
   CHECK_CTX(ctx);
   ctx->ge_n = 0;
   graph_cost_forget(ctx);
+  graph_delta_forget(ctx);
   return RRTX_OK;
 }
 
@@ -1201,6 +1202,40 @@ int rrtx_graph_cost_to_root_dev(rrtx_ctx *ctx, int root_idx, double *lmc_dev, in
 int rrtx_graph_cost_update_dev(rrtx_ctx *ctx, int root_idx, double *lmc_dev, int32_t *parent_edge_dev) {
   CHECK_CTX(ctx);
   return graph_cost_dev(ctx, "graph_cost_update", root_idx, true, lmc_dev, parent_edge_dev);
+}
+
+int rrtx_graph_cost_update_delta(rrtx_ctx *ctx, int root_idx, int store, int32_t *node, double *lmc, int32_t *parent_edge,
+                                 int64_t cap, int64_t *needed, int32_t *passes) {
+  CHECK_CTX(ctx);
+  if (cap < 0 || (cap > 0 && (!node || !lmc)) || !needed)
+    return fail(ctx, RRTX_E_INVALID, "graph_cost_update_delta: bad arguments");
+  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "graph_cost_update_delta on an empty tree");
+  if (root_idx < 0 || root_idx >= ctx->n_nodes)
+    return fail(ctx, RRTX_E_INVALID, "graph_cost_update_delta: root %d out of range", root_idx);
+  *needed = 0;
+  const size_t dcap = cap > 0 ? (size_t)cap : 1;
+  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * dcap));
+  RRTX_HIP(ctx, ctx->ws_out_f64.ensure(sizeof(double) * dcap));
+  RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * dcap));
+  int rc = arena_begin(ctx, 16 * (size_t)std::min<int64_t>(cap, ctx->n_nodes) + 256);
+  if (rc) return rc;
+  int np = 0;
+  int64_t *total_dev = nullptr;
+  rc = launch_graph_delta(ctx, root_idx, store != 0, ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_f64.as<double>(),
+                          ctx->ws_out_i32.as<int32_t>(), (long long)cap, &total_dev, &np);
+  if (rc) return rc;
+  if (passes) *passes = np;
+  int64_t total = 0;
+  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));      // the call's one synchronisation before the records leave
+  if ((rc = check_capacity(ctx, "graph_cost_update_delta", "changed nodes", total, cap, needed))) return rc;
+  // the records fit: they go to the caller, and the baseline moves to the solver's state
+  if ((rc = d2h(ctx, node, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
+  if ((rc = d2h(ctx, lmc, ctx->ws_out_f64.p, sizeof(double) * (size_t)total))) return rc;
+  if (parent_edge && (rc = d2h(ctx, parent_edge, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total))) return rc;
+  if ((rc = launch_graph_delta_advance(ctx, root_idx))) return rc;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  arena_flush(ctx);
+  return RRTX_OK;
 }
 
 // ---- obstacle sweeps of the polygon / Dubins space (R/DRRT.jl:3048-3290) ----------------------------------------

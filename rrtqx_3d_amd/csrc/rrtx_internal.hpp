@@ -75,6 +75,11 @@ struct GraphCost {
   int solved_root = -1;
   int64_t solved_nodes = 0, solved_edges = 0;
   bool touched_old = false;                         // set_dist / block since the last solve
+  // what rrtx_graph_cost_update_delta last reported: per node the bit pattern of rrtLMC and the parent edge (-1: none)
+  DevBuf rep_lmc, rep_parent;
+  int rep_root = -1;                                // -1: nothing reported
+  int64_t rep_nodes = 0;                            // nodes the two arrays are initialised for (beyond: +Inf / -1)
+  DevBuf delta_cnt, delta_pos;                      // differing nodes per workgroup, their exclusive scan
 };
 
 enum KernelFamily { KF_NN_SCAN = 0, KF_NN_FINISH, KF_NN_NEAREST, KF_EDGES, KF_POINTS, KF_DUBINS, KF_DUBINS_STEER, KF_COUNT };
@@ -435,6 +440,10 @@ int launch_graph_unblock(rrtx_ctx *ctx, const int32_t *ids_host, long long n);
 int launch_graph_unblock_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n); // ids already on the device, in [0, ge_n)
 int launch_graph_cost(rrtx_ctx *ctx, int root, bool update, double *lmc_dev, int32_t *parent_dev, int *passes_out);
 void graph_cost_forget(rrtx_ctx *ctx);
+int launch_graph_delta(rrtx_ctx *ctx, int root, bool store, int32_t *node_dev, double *lmc_dev, int32_t *par_dev, long long cap,
+                       int64_t **total_dev, int *passes_out);
+int launch_graph_delta_advance(rrtx_ctx *ctx, int root);
+void graph_delta_forget(rrtx_ctx *ctx);
 
 int launch_pack_hits(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit_in, const int64_t *n_valid_dev,
                      int64_t cap, uint64_t *words);

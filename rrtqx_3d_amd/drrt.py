@@ -806,3 +806,13 @@ def costToRoot(KD: HipTree, root: RRTNode) -> Tuple[np.ndarray, np.ndarray]:
     insertion order, registered id of each node's rrtParentEdge or -1 for the root and for orphans)."""
     lmc, parent, _ = KD.ctx.graph_cost_to_root(root.index)
     return lmc, parent
+
+
+def costUpdateDelta(KD: HipTree, root: RRTNode, store: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The nodes propogateDescendants + reduceInconsistency (R/DRRT_Q.jl:2647-2817) changed since the last call for
+    this root (rrtx_graph_cost_update_delta): (node indices in insertion order, ascending; their rrtLMC, Inf for a new
+    orphan; the registered id of their rrtParentEdge, -1 for the root and for orphans).  The first call for a root
+    returns every node that reaches it.  store=True leaves rrtLMC of every node on the device for extend_select /
+    findNewTarget with lmc=None."""
+    node, lmc, parent, _ = KD.ctx.graph_cost_update_delta(root.index, store=store)
+    return node, lmc, parent
