@@ -591,14 +591,16 @@ class Context:
 
     def graph_edges_block(self, edge_ids):
         """addNewObstacle's `edge.dist = Inf` for the ids an obstacle sweep returned"""
-        ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
-        self._check(self._lib.rrtx_graph_edges_block(self._h, _capi._ptr(ids), ids.shape[0]))
+        self._edge_ids_call(self._lib.rrtx_graph_edges_block, edge_ids)
 
     def graph_edges_unblock(self, edge_ids):
         """removeObstacle's `edge.dist = edge.distOriginal` for the ids a release returned: the cost append / set_dist
         wrote last comes back (an id that is not blocked keeps its value)"""
+        self._edge_ids_call(self._lib.rrtx_graph_edges_unblock, edge_ids)
+
+    def _edge_ids_call(self, fn, edge_ids):
         ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
-        self._check(self._lib.rrtx_graph_edges_unblock(self._h, _capi._ptr(ids), ids.shape[0]))
+        self._check(fn(self._h, _capi._ptr(ids), ids.shape[0]))
 
     def graph_cost_to_root(self, root_idx: int, want_parent: bool = True, update: bool = False):
         """rrtLMC of every node at the fixed point of rewire / reduceInconsistency (changeThresh = 0) over the
@@ -665,20 +667,7 @@ class Context:
         obstacle_sweep(obstacles[j], search_range[j], robot_radius); rows in the order given.  search_range: one range
         per obstacle (a scalar serves all).  block=True also blocks every returned edge in the mirror, on the device
         (what graph_edges_block over the union of the rows does)."""
-        obs = np.ascontiguousarray(obstacles, dtype=np.int32).reshape(-1)
-        k = obs.shape[0]
-        rng = np.ascontiguousarray(np.broadcast_to(np.asarray(search_range, dtype=np.float64), (k,)))
-        if cap is None:
-            cap = 4096
-
-        def call(cap, needed):
-            off = np.zeros(k + 1, dtype=np.int64)
-            ids = np.empty(max(cap, 1), dtype=np.int32)
-            return self._lib.rrtx_obstacle_sweep_batch(self._h, _capi._ptr(obs), k, _capi._ptr(rng), robot_radius,
-                                                       1 if block else 0, _capi._ptr(off), _capi._ptr(ids), cap,
-                                                       needed), (off, ids)
-        n, (off, ids) = self._two_call(cap, call)
-        return off, ids[:n]
+        return self._sphere_burst(self._lib.rrtx_obstacle_sweep_batch, obstacles, search_range, robot_radius, block, cap)
 
     def obstacle_release_batch(self, obstacles, search_range, robot_radius: float, unblock: bool = False,
                                cap: Optional[int] = None):
@@ -688,6 +677,9 @@ class Context:
         in use and not among `obstacles`; rows in the order given.  search_range: one range per obstacle (a scalar
         serves all).  unblock=True also gives every returned edge its original cost back in the mirror, on the device
         (what graph_edges_unblock over the union of the rows does)."""
+        return self._sphere_burst(self._lib.rrtx_obstacle_release_batch, obstacles, search_range, robot_radius, unblock, cap)
+
+    def _sphere_burst(self, fn, obstacles, search_range, robot_radius, apply, cap):
         obs = np.ascontiguousarray(obstacles, dtype=np.int32).reshape(-1)
         k = obs.shape[0]
         rng = np.ascontiguousarray(np.broadcast_to(np.asarray(search_range, dtype=np.float64), (k,)))
@@ -697,9 +689,8 @@ class Context:
         def call(cap, needed):
             off = np.zeros(k + 1, dtype=np.int64)
             ids = np.empty(max(cap, 1), dtype=np.int32)
-            return self._lib.rrtx_obstacle_release_batch(self._h, _capi._ptr(obs), k, _capi._ptr(rng), robot_radius,
-                                                         1 if unblock else 0, _capi._ptr(off), _capi._ptr(ids), cap,
-                                                         needed), (off, ids)
+            return fn(self._h, _capi._ptr(obs), k, _capi._ptr(rng), robot_radius, 1 if apply else 0, _capi._ptr(off),
+                      _capi._ptr(ids), cap, needed), (off, ids)
         n, (off, ids) = self._two_call(cap, call)
         return off, ids[:n]
 

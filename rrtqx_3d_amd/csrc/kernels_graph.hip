@@ -67,26 +67,15 @@ __global__ void graph_edge_dist_kernel(const int32_t *__restrict__ es, const int
   dirty[first + i] = 0;
 }
 
+// edge.dist = Inf (addNewObstacle; dist0 null) or edge.distOriginal (removeObstacle, R/DRRT_Q.jl:3342; dist0 given) for
+// the edges ids[i] (in [0, ge_n); an id may repeat: every copy writes the same values)
 __global__ void graph_block_kernel(const int32_t *__restrict__ ids, long long n, double *__restrict__ dist,
-                                   uint8_t *__restrict__ dirty, const int32_t *__restrict__ in_pos, long long in_ne,
-                                   double *__restrict__ in_w) {
+                                   const double *__restrict__ dist0, uint8_t *__restrict__ dirty,
+                                   const int32_t *__restrict__ in_pos, long long in_ne, double *__restrict__ in_w) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int32_t e = ids[i];
-  dist[e] = __builtin_inf();
-  dirty[e] = 1;
-  if (e < in_ne) in_w[in_pos[e]] = __builtin_inf();
-}
-
-// edge.dist = edge.distOriginal (removeObstacle, R/DRRT_Q.jl:3342) for the edges ids[i] (in [0, ge_n); an id may
-// repeat: every copy writes the same values): graph_block_kernel's three writes with dist0[e] in place of Inf
-__global__ void graph_unblock_kernel(const int32_t *__restrict__ ids, long long n, double *__restrict__ dist,
-                                     const double *__restrict__ dist0, uint8_t *__restrict__ dirty,
-                                     const int32_t *__restrict__ in_pos, long long in_ne, double *__restrict__ in_w) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int32_t e = ids[i];
-  const double w = dist0[e];
+  const double w = dist0 ? dist0[e] : __builtin_inf();
   dist[e] = w;
   dirty[e] = 1;
   if (e < in_ne) in_w[in_pos[e]] = w;
@@ -471,47 +460,26 @@ int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n) {
   return RRTX_OK;
 }
 
-// ids (host, validated by the caller): dist = Inf
-int launch_graph_block(rrtx_ctx *ctx, const int32_t *ids_host, long long n) {
+// ids on the device (the rows of a sphere burst, or staged below; an id may repeat): dist = Inf, restore: dist = dist0.
+// Nothing travels, no sync.
+int launch_graph_block_dev(rrtx_ctx *ctx, bool restore, const int32_t *ids_dev, long long n) {
   if (n <= 0) return RRTX_OK;
-  RRTX_HIP(ctx, ctx->gc.ids.ensure(sizeof(int32_t) * (size_t)n));
-  RRTX_HIP(ctx, hipMemcpyAsync(ctx->gc.ids.p, ids_host, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(graph_block_kernel, grid_for(n), dim3(256), 0, ctx->stream, ctx->gc.ids.as<int32_t>(), n, ctx->ge_dist,
-                     ctx->ge_dirty, ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne, ctx->gc.in_w.as<double>());
-  RRTX_HIP(ctx, hipGetLastError());
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));      // ids_host is the caller's
-  ctx->gc.touched_old = true;
-  return RRTX_OK;
-}
-
-// the same for ids a kernel left on the device (the batched sweep's rows; an id may repeat): nothing travels, no sync
-int launch_graph_block_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n) {
-  if (n <= 0) return RRTX_OK;
-  hipLaunchKernelGGL(graph_block_kernel, grid_for(n), dim3(256), 0, ctx->stream, ids_dev, n, ctx->ge_dist, ctx->ge_dirty,
-                     ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne, ctx->gc.in_w.as<double>());
+  hipLaunchKernelGGL(graph_block_kernel, grid_for(n), dim3(256), 0, ctx->stream, ids_dev, n, ctx->ge_dist,
+                     restore ? ctx->ge_dist0 : nullptr, ctx->ge_dirty, ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne,
+                     ctx->gc.in_w.as<double>());
   RRTX_HIP(ctx, hipGetLastError());
   ctx->gc.touched_old = true;
   return RRTX_OK;
 }
 
-// ids (host, validated by the caller): dist = dist0
-int launch_graph_unblock(rrtx_ctx *ctx, const int32_t *ids_host, long long n) {
+// the same for ids of the host (validated by the caller)
+int launch_graph_block(rrtx_ctx *ctx, bool restore, const int32_t *ids_host, long long n) {
   if (n <= 0) return RRTX_OK;
   RRTX_HIP(ctx, ctx->gc.ids.ensure(sizeof(int32_t) * (size_t)n));
   RRTX_HIP(ctx, hipMemcpyAsync(ctx->gc.ids.p, ids_host, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = launch_graph_unblock_dev(ctx, ctx->gc.ids.as<int32_t>(), n);
+  const int rc = launch_graph_block_dev(ctx, restore, ctx->gc.ids.as<int32_t>(), n);
   if (rc) return rc;
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));      // ids_host is the caller's
-  return RRTX_OK;
-}
-
-// the same for ids a kernel left on the device (the batched release's rows; an id may repeat): nothing travels, no sync
-int launch_graph_unblock_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n) {
-  if (n <= 0) return RRTX_OK;
-  hipLaunchKernelGGL(graph_unblock_kernel, grid_for(n), dim3(256), 0, ctx->stream, ids_dev, n, ctx->ge_dist, ctx->ge_dist0,
-                     ctx->ge_dirty, ctx->gc.in_pos.as<int32_t>(), (long long)ctx->gc.in_ne, ctx->gc.in_w.as<double>());
-  RRTX_HIP(ctx, hipGetLastError());
-  ctx->gc.touched_old = true;
   return RRTX_OK;
 }
 

@@ -50,8 +50,6 @@ __global__ __launch_bounds__(kSweepBlock) void sweep_edges_kernel(
 // accumulated with kdFindMoreWithinRange), each with its ghosts in wrapped dimensions: a node is in the list when
 // ANY of them finds it -- dist < range, the root with <= for the un-wrapped query points (kdTree_general.jl:896,
 // 934) and < for the ghosts.  thr_root is the root's threshold (= thr_lt where the root gets no <=).
-struct SweepQuery { double x, y, z, w, thr_lt, thr_root; };
-
 __global__ void sweep_mark_multi_kernel(const double *__restrict__ nx, const double *__restrict__ ny,
                                         const double *__restrict__ nz, const double *__restrict__ nw, int n, int dim,
                                         const SweepQuery *__restrict__ qs, int nqs, uint8_t *__restrict__ mark) {
@@ -145,38 +143,44 @@ __global__ void sweep_mark_words_kernel(const double *__restrict__ nx, const dou
   word[i] = w;
 }
 
-// One block of kSweepBlock mirrored edges against the group.  An edge whose start node has an empty word is done after
-// that read; any other loads its endpoints, forms its length once and runs edge_hits_sphere for every set bit.  The edges
-// with a hit leave (id, hit word) in the block's own stretch of seg_id / seg_word, ascending (rank of the thread among
-// the block's hits); blk_n[block] = how many, cnt[b * nb + block] = how many of them hit obstacle b.
-__global__ __launch_bounds__(kSweepBlock) void sweep_edges_words_kernel(
-    const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end, long long ne, int n_nodes,
-    const unsigned long long *__restrict__ word, const double *__restrict__ naos, const SweepObs *__restrict__ tab, int kg,
-    int nb, int32_t *__restrict__ seg_id, unsigned long long *__restrict__ seg_word, int *__restrict__ blk_n,
-    int *__restrict__ cnt) {
-  __shared__ int wcnt[kSweepBlock / 64];
-  __shared__ unsigned long long lw[kSweepBlock];
-  const int t = threadIdx.x;
-  const long long e = (long long)blockIdx.x * blockDim.x + t;
+// The head of the two passes over the mirror: the hit word of edge e (< ne) against the group.  An edge whose start node
+// has an empty word is done after that read; any other loads its endpoints, forms its length once and runs
+// edge_hits_sphere for every set bit.  seg = the edge as edge_hits_sphere takes it (untouched where no test ran).
+struct EdgeSeg { double ax, ay, az, bx, by, bz, len; };
+
+__device__ __forceinline__ unsigned long long edge_hit_word(const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end,
+                                                            long long e, int n_nodes, const unsigned long long *__restrict__ word,
+                                                            const double *__restrict__ naos, const SweepObs *__restrict__ tab,
+                                                            EdgeSeg &seg) {
   unsigned long long hits = 0ull;
-  if (e < ne) {
-    const int a = e_start[e];
-    unsigned long long w = (unsigned)a < (unsigned)n_nodes ? word[a] : 0ull;
-    if (w != 0ull) {
-      const int b = e_end[e];
-      if ((unsigned)b < (unsigned)n_nodes) {
-        const double4 p0 = reinterpret_cast<const double4 *>(naos)[a];
-        const double4 p1 = reinterpret_cast<const double4 *>(naos)[b];
-        const double len = sqrt_rn(sq3(p0.x, p0.y, p0.z, p1.x, p1.y, p1.z));
-        const double bx = p1.x - p0.x, by = p1.y - p0.y, bz = p1.z - p0.z;
-        while (w != 0ull) {
-          const int j = __ffsll((long long)w) - 1;               // (j < kg: the mark kernel sets no other bit)
-          w &= w - 1ull;
-          if (edge_hits_sphere(p0.x, p0.y, p0.z, bx, by, bz, len, tab[j].ob)) hits |= 1ull << j;
-        }
+  const int a = e_start[e];
+  unsigned long long w = (unsigned)a < (unsigned)n_nodes ? word[a] : 0ull;
+  if (w != 0ull) {
+    const int b = e_end[e];
+    if ((unsigned)b < (unsigned)n_nodes) {
+      const double4 p0 = reinterpret_cast<const double4 *>(naos)[a];
+      const double4 p1 = reinterpret_cast<const double4 *>(naos)[b];
+      seg.len = sqrt_rn(sq3(p0.x, p0.y, p0.z, p1.x, p1.y, p1.z));
+      seg.ax = p0.x; seg.ay = p0.y; seg.az = p0.z;
+      seg.bx = p1.x - p0.x; seg.by = p1.y - p0.y; seg.bz = p1.z - p0.z;
+      while (w != 0ull) {
+        const int j = __ffsll((long long)w) - 1;                 // (j < kg: the mark kernel sets no other bit)
+        w &= w - 1ull;
+        if (edge_hits_sphere(seg.ax, seg.ay, seg.az, seg.bx, seg.by, seg.bz, seg.len, tab[j].ob)) hits |= 1ull << j;
       }
     }
   }
+  return hits;
+}
+
+// The tail of the two passes: the edges with a hit word leave (id, hit word) in the block's own stretch of seg_id /
+// seg_word, ascending (rank of the thread among the block's hits); blk_n[block] = how many, cnt[b * nb + block] = how
+// many of them hit obstacle b.  wcnt / lw: the block's LDS (kSweepBlock / 64 ints, kSweepBlock words).
+__device__ __forceinline__ void block_list_write(unsigned long long hits, long long e, int kg, int nb, int *wcnt,
+                                                 unsigned long long *lw, int32_t *__restrict__ seg_id,
+                                                 unsigned long long *__restrict__ seg_word, int *__restrict__ blk_n,
+                                                 int *__restrict__ cnt) {
+  const int t = threadIdx.x;
   const bool any = hits != 0ull;
   const unsigned long long m = block_votes<kSweepBlock>(any, wcnt);
   const int total = block_votes_total<kSweepBlock>(wcnt);
@@ -198,6 +202,20 @@ __global__ __launch_bounds__(kSweepBlock) void sweep_edges_words_kernel(
     for (int r = 0; r < total; ++r) c += (int)((lw[r] >> t) & 1ull);
     cnt[(size_t)t * nb + blockIdx.x] = c;
   }
+}
+
+// One block of kSweepBlock mirrored edges against the group: head, then tail.
+__global__ __launch_bounds__(kSweepBlock) void sweep_edges_words_kernel(
+    const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end, long long ne, int n_nodes,
+    const unsigned long long *__restrict__ word, const double *__restrict__ naos, const SweepObs *__restrict__ tab, int kg,
+    int nb, int32_t *__restrict__ seg_id, unsigned long long *__restrict__ seg_word, int *__restrict__ blk_n,
+    int *__restrict__ cnt) {
+  __shared__ int wcnt[kSweepBlock / 64];
+  __shared__ unsigned long long lw[kSweepBlock];
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  EdgeSeg seg;
+  const unsigned long long hits = e < ne ? edge_hit_word(e_start, e_end, e, n_nodes, word, naos, tab, seg) : 0ull;
+  block_list_write(hits, e, kg, nb, wcnt, lw, seg_id, seg_word, blk_n, cnt);
 }
 
 // The rows of one group out of the blocks' lists: pos = exclusive scan of cnt (obstacle-major, so pos[b * nb + block] is
@@ -232,12 +250,11 @@ __global__ __launch_bounds__(kSweepGroup) void sweep_rows_write_kernel(
 
 // ---- the batched release (rrtx_obstacle_release_batch): the edge loops of a burst of removeObstacle calls ----
 // One block of kSweepBlock mirrored edges against a group of leaving obstacles.  An edge that is not blocked
-// (dist != Inf: almost every edge) is done after that one coalesced read; a blocked one takes
-// sweep_edges_words_kernel's path to its hit word.  Then the test against the spheres that stay (sph / stay / na:
-// the packed in-use records of the edge checks and one byte each, 0 = it leaves with this call), dealt across the
-// wave: the lanes with a hit word are taken in turn, the edge is broadcast, the 64 lanes hold it against 64 spheres
-// at a time and ballot; an edge some staying sphere hits loses its hit word.  Only after that the block forms its
-// list and the per-obstacle counts, exactly as sweep_edges_words_kernel leaves them for sweep_rows_write_kernel.
+// (dist != Inf: almost every edge) is done after that one coalesced read; a blocked one takes the head to its hit
+// word.  Then the test against the spheres that stay (sph / stay / na: the packed in-use records of the edge checks
+// and one byte each, 0 = it leaves with this call), dealt across the wave: the lanes with a hit word are taken in
+// turn, the edge is broadcast, the 64 lanes hold it against 64 spheres at a time and ballot; an edge some staying
+// sphere hits loses its hit word.  Only after that the tail, so sweep_rows_write_kernel finds what the sweep leaves it.
 __global__ __launch_bounds__(kSweepBlock) void release_edges_words_kernel(
     const double *__restrict__ e_dist, const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end, long long ne,
     int n_nodes, const unsigned long long *__restrict__ word, const double *__restrict__ naos,
@@ -245,35 +262,17 @@ __global__ __launch_bounds__(kSweepBlock) void release_edges_words_kernel(
     int32_t *__restrict__ seg_id, unsigned long long *__restrict__ seg_word, int *__restrict__ blk_n, int *__restrict__ cnt) {
   __shared__ int wcnt[kSweepBlock / 64];
   __shared__ unsigned long long lw[kSweepBlock];
-  const int t = threadIdx.x, lane = t & 63;
-  const long long e = (long long)blockIdx.x * blockDim.x + t;
+  const int lane = threadIdx.x & 63;
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  EdgeSeg seg = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   unsigned long long hits = 0ull;
-  double ax = 0.0, ay = 0.0, az = 0.0, bx = 0.0, by = 0.0, bz = 0.0, len = 0.0;
-  if (e < ne && e_dist[e] == __builtin_inf()) {
-    const int a = e_start[e];
-    unsigned long long w = (unsigned)a < (unsigned)n_nodes ? word[a] : 0ull;
-    if (w != 0ull) {
-      const int b = e_end[e];
-      if ((unsigned)b < (unsigned)n_nodes) {
-        const double4 p0 = reinterpret_cast<const double4 *>(naos)[a];
-        const double4 p1 = reinterpret_cast<const double4 *>(naos)[b];
-        len = sqrt_rn(sq3(p0.x, p0.y, p0.z, p1.x, p1.y, p1.z));
-        ax = p0.x; ay = p0.y; az = p0.z;
-        bx = p1.x - p0.x; by = p1.y - p0.y; bz = p1.z - p0.z;
-        while (w != 0ull) {
-          const int j = __ffsll((long long)w) - 1;               // (j < kg: the mark kernel sets no other bit)
-          w &= w - 1ull;
-          if (edge_hits_sphere(ax, ay, az, bx, by, bz, len, tab[j].ob)) hits |= 1ull << j;
-        }
-      }
-    }
-  }
+  if (e < ne && e_dist[e] == __builtin_inf()) hits = edge_hit_word(e_start, e_end, e, n_nodes, word, naos, tab, seg);
   unsigned long long todo = __ballot(hits != 0ull);              // (wave-uniform: the loops below do not diverge)
   while (todo != 0ull) {
     const int src = __ffsll((long long)todo) - 1;
     todo &= todo - 1ull;
-    const double sx = __shfl(ax, src), sy = __shfl(ay, src), sz = __shfl(az, src);
-    const double tx = __shfl(bx, src), ty = __shfl(by, src), tz = __shfl(bz, src), sl = __shfl(len, src);
+    const double sx = __shfl(seg.ax, src), sy = __shfl(seg.ay, src), sz = __shfl(seg.az, src);
+    const double tx = __shfl(seg.bx, src), ty = __shfl(seg.by, src), tz = __shfl(seg.bz, src), sl = __shfl(seg.len, src);
     bool kept = false;
     for (int base = 0; base < na && !kept; base += 64) {
       const int j = base + lane;
@@ -282,27 +281,7 @@ __global__ __launch_bounds__(kSweepBlock) void release_edges_words_kernel(
     }
     if (kept && lane == src) hits = 0ull;
   }
-  const bool any = hits != 0ull;
-  const unsigned long long m = block_votes<kSweepBlock>(any, wcnt);
-  const int total = block_votes_total<kSweepBlock>(wcnt);
-  if (t == 0) blk_n[blockIdx.x] = total;
-  if (total == 0) {                                              // (the whole block takes this branch or none of it)
-    if (t < kg) cnt[(size_t)t * nb + blockIdx.x] = 0;
-    return;
-  }
-  if (any) {
-    const int r = block_votes_before(wcnt, t >> 6) + __popcll(m & lanes_below(lane));
-    const size_t at = (size_t)blockIdx.x * kSweepBlock + r;
-    seg_id[at] = (int32_t)e;
-    seg_word[at] = hits;
-    lw[r] = hits;
-  }
-  __syncthreads();
-  if (t < kg) {
-    int c = 0;
-    for (int r = 0; r < total; ++r) c += (int)((lw[r] >> t) & 1ull);
-    cnt[(size_t)t * nb + blockIdx.x] = c;
-  }
+  block_list_write(hits, e, kg, nb, wcnt, lw, seg_id, seg_word, blk_n, cnt);
 }
 
 }  // namespace
@@ -337,62 +316,21 @@ int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, 
   return RRTX_OK;
 }
 
-// device side of rrtx_obstacle_sweep_batch (the mirror is not empty): groups of kSweepGroup obstacles in list order,
-// each one mark pass over the nodes, one pass over the mirror, one scan of its (obstacle, block) counts and the write
-// of its rows; a group's rows follow the rows of the group before it (ws_swb_base[g] = ids before group g)
-int launch_obstacle_sweep_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev) {
+// device side of rrtx_obstacle_sweep_batch and rrtx_obstacle_release_batch (the mirror is not empty): groups of
+// kSweepGroup obstacles in list order, each one mark pass over the nodes, one pass over the mirror, one scan of its
+// (obstacle, block) counts and the write of its rows; a group's rows follow the rows of the group before it
+// (ws_swb_base[g] = ids before group g).  release: release_edges_words_kernel is the pass over the mirror.  No group
+// writes the mirror, so every row sees it as it stood at entry; the caller blocks / unblocks the rows afterwards.
+int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, int64_t cap, long long **total_dev) {
   const int n = (int)ctx->n_nodes;
   const long long ne = ctx->ge_n;
   const int nb = (int)((ne + kSweepBlock - 1) / kSweepBlock);
   const int ng = (k + kSweepGroup - 1) / kSweepGroup;
   const int kg_max = std::min(k, kSweepGroup);        // (edge ids are int32: kg_max * nb < 2^27 counts, an int for the scan)
+  const int na = release ? ctx->sph_n_active : 0;
+  if (release && (size_t)na != ctx->rel_stay_host.size()) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch: stay mask of %zu for %d spheres in use", ctx->rel_stay_host.size(), na);
   RRTX_HIP(ctx, ctx->ws_swb_tab.ensure(sizeof(SweepObs) * (size_t)k));
-  RRTX_HIP(ctx, ctx->ws_swb_word.ensure(sizeof(unsigned long long) * (size_t)n));
-  RRTX_HIP(ctx, ctx->ws_swb_seg_id.ensure(sizeof(int32_t) * (size_t)nb * kSweepBlock));
-  RRTX_HIP(ctx, ctx->ws_swb_seg_word.ensure(sizeof(unsigned long long) * (size_t)nb * kSweepBlock));
-  RRTX_HIP(ctx, ctx->ws_swb_blk_n.ensure(sizeof(int) * (size_t)nb));
-  RRTX_HIP(ctx, ctx->ws_swb_cnt.ensure(sizeof(int) * ((size_t)kg_max * nb + 1)));
-  RRTX_HIP(ctx, ctx->ws_swb_pos.ensure(sizeof(long long) * ((size_t)kg_max * nb + 2)));
-  RRTX_HIP(ctx, ctx->ws_swb_base.ensure(sizeof(long long) * (size_t)(ng + 1)));
-  RRTX_HIP(ctx, ctx->ws_swb_off.ensure(sizeof(int64_t) * (size_t)(k + 1)));
-  hipStream_t st = ctx->stream;
-  RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_swb_tab.p, ctx->swb_tab_host.data(), sizeof(SweepObs) * (size_t)k, hipMemcpyHostToDevice, st));
-  RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_swb_base.p, 0, sizeof(long long), st));
-  span_begin(ctx, KF_EDGES);
-  for (int g = 0; g < ng; ++g) {
-    const int kg = std::min(kSweepGroup, k - g * kSweepGroup);
-    const SweepObs *tab = ctx->ws_swb_tab.as<SweepObs>() + (size_t)g * kSweepGroup;
-    hipLaunchKernelGGL(sweep_mark_words_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
-                       ctx->nodes[2], n, tab, kg, ctx->ws_swb_word.as<unsigned long long>());
-    hipLaunchKernelGGL(sweep_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ctx->ge_end, ne, n,
-                       ctx->ws_swb_word.as<unsigned long long>(), ctx->nodes_aos, tab, kg, nb, ctx->ws_swb_seg_id.as<int32_t>(),
-                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(), ctx->ws_swb_cnt.as<int>());
-    launch_excl_scan(st, ctx->ws_swb_cnt.as<int>(), ctx->ws_swb_pos.as<long long>(), kg * nb);
-    hipLaunchKernelGGL(sweep_rows_write_kernel, dim3(nb), dim3(kSweepGroup), 0, st, ctx->ws_swb_seg_id.as<int32_t>(),
-                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(),
-                       ctx->ws_swb_pos.as<long long>(), nb, kg, ctx->ws_swb_base.as<long long>() + g,
-                       ctx->ws_swb_base.as<long long>() + g + 1, ctx->ws_swb_off.as<int64_t>() + (size_t)g * kSweepGroup, out_dev,
-                       (long long)cap);
-  }
-  span_end(ctx);
-  RRTX_HIP(ctx, hipGetLastError());
-  *total_dev = ctx->ws_swb_base.as<long long>() + ng;
-  return RRTX_OK;
-}
-
-// device side of rrtx_obstacle_release_batch (the mirror is not empty): launch_obstacle_sweep_batch's groups, buffers and
-// steps with release_edges_words_kernel as the pass over the mirror.  No group writes the mirror, so every row sees it
-// as it stood at entry; the caller unblocks the rows afterwards.
-int launch_obstacle_release_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev) {
-  const int n = (int)ctx->n_nodes;
-  const long long ne = ctx->ge_n;
-  const int nb = (int)((ne + kSweepBlock - 1) / kSweepBlock);
-  const int ng = (k + kSweepGroup - 1) / kSweepGroup;
-  const int kg_max = std::min(k, kSweepGroup);
-  const int na = ctx->sph_n_active;
-  if ((size_t)na != ctx->rel_stay_host.size()) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch: stay mask of %zu for %d spheres in use", ctx->rel_stay_host.size(), na);
-  RRTX_HIP(ctx, ctx->ws_swb_tab.ensure(sizeof(SweepObs) * (size_t)k));
-  RRTX_HIP(ctx, ctx->ws_rel_stay.ensure((size_t)(na > 0 ? na : 1)));
+  if (release) RRTX_HIP(ctx, ctx->ws_rel_stay.ensure((size_t)(na > 0 ? na : 1)));
   RRTX_HIP(ctx, ctx->ws_swb_word.ensure(sizeof(unsigned long long) * (size_t)n));
   RRTX_HIP(ctx, ctx->ws_swb_seg_id.ensure(sizeof(int32_t) * (size_t)nb * kSweepBlock));
   RRTX_HIP(ctx, ctx->ws_swb_seg_word.ensure(sizeof(unsigned long long) * (size_t)nb * kSweepBlock));
@@ -405,31 +343,35 @@ int launch_obstacle_release_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_
   RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_swb_tab.p, ctx->swb_tab_host.data(), sizeof(SweepObs) * (size_t)k, hipMemcpyHostToDevice, st));
   if (na > 0) RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_rel_stay.p, ctx->rel_stay_host.data(), (size_t)na, hipMemcpyHostToDevice, st));
   RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_swb_base.p, 0, sizeof(long long), st));
+  unsigned long long *word = ctx->ws_swb_word.as<unsigned long long>(), *seg_word = ctx->ws_swb_seg_word.as<unsigned long long>();
+  int32_t *seg_id = ctx->ws_swb_seg_id.as<int32_t>();
+  int *blk_n = ctx->ws_swb_blk_n.as<int>(), *cnt = ctx->ws_swb_cnt.as<int>();
+  long long *pos = ctx->ws_swb_pos.as<long long>(), *base = ctx->ws_swb_base.as<long long>();
   span_begin(ctx, KF_EDGES);
   for (int g = 0; g < ng; ++g) {
     const int kg = std::min(kSweepGroup, k - g * kSweepGroup);
     const SweepObs *tab = ctx->ws_swb_tab.as<SweepObs>() + (size_t)g * kSweepGroup;
     hipLaunchKernelGGL(sweep_mark_words_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
-                       ctx->nodes[2], n, tab, kg, ctx->ws_swb_word.as<unsigned long long>());
-    hipLaunchKernelGGL(release_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_dist, ctx->ge_start, ctx->ge_end,
-                       ne, n, ctx->ws_swb_word.as<unsigned long long>(), ctx->nodes_aos, tab, kg, nb, ctx->d_sph.as<SphRec>(),
-                       ctx->ws_rel_stay.as<uint8_t>(), na, ctx->ws_swb_seg_id.as<int32_t>(),
-                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(), ctx->ws_swb_cnt.as<int>());
-    launch_excl_scan(st, ctx->ws_swb_cnt.as<int>(), ctx->ws_swb_pos.as<long long>(), kg * nb);
-    hipLaunchKernelGGL(sweep_rows_write_kernel, dim3(nb), dim3(kSweepGroup), 0, st, ctx->ws_swb_seg_id.as<int32_t>(),
-                       ctx->ws_swb_seg_word.as<unsigned long long>(), ctx->ws_swb_blk_n.as<int>(),
-                       ctx->ws_swb_pos.as<long long>(), nb, kg, ctx->ws_swb_base.as<long long>() + g,
-                       ctx->ws_swb_base.as<long long>() + g + 1, ctx->ws_swb_off.as<int64_t>() + (size_t)g * kSweepGroup, out_dev,
-                       (long long)cap);
+                       ctx->nodes[2], n, tab, kg, word);
+    if (release)
+      hipLaunchKernelGGL(release_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_dist, ctx->ge_start, ctx->ge_end,
+                         ne, n, word, ctx->nodes_aos, tab, kg, nb, ctx->d_sph.as<SphRec>(), ctx->ws_rel_stay.as<uint8_t>(), na,
+                         seg_id, seg_word, blk_n, cnt);
+    else
+      hipLaunchKernelGGL(sweep_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ctx->ge_end, ne, n, word,
+                         ctx->nodes_aos, tab, kg, nb, seg_id, seg_word, blk_n, cnt);
+    launch_excl_scan(st, cnt, pos, kg * nb);
+    hipLaunchKernelGGL(sweep_rows_write_kernel, dim3(nb), dim3(kSweepGroup), 0, st, seg_id, seg_word, blk_n, pos, nb, kg, base + g,
+                       base + g + 1, ctx->ws_swb_off.as<int64_t>() + (size_t)g * kSweepGroup, out_dev, (long long)cap);
   }
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
-  *total_dev = ctx->ws_swb_base.as<long long>() + ng;
+  *total_dev = base + ng;
   return RRTX_OK;
 }
 
 // ---- the polygon / Dubins sweep: compaction steps shared by rrtx_obstacle_sweep_polygon (rrtx_capi.hip) ----
-int launch_sweep_mark_multi(rrtx_ctx *ctx, const void *queries_host, int nqs) {
+int launch_sweep_mark_multi(rrtx_ctx *ctx, const SweepQuery *queries_host, int nqs) {
   const int n = (int)ctx->n_nodes;
   RRTX_HIP(ctx, ctx->ws_sweep_mark.ensure((size_t)n));
   RRTX_HIP(ctx, ctx->ws_mask.ensure(sizeof(SweepQuery) * (size_t)nqs));

@@ -1138,20 +1138,21 @@ int rrtx_graph_edges_set_dist(rrtx_ctx *ctx, int64_t first_id, const double *dis
   return RRTX_OK;
 }
 
+static int graph_edges_block_host(rrtx_ctx *ctx, const char *fn, bool restore, const int32_t *edge_ids, int64_t n) {
+  if (n < 0 || (n > 0 && !edge_ids)) return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
+  for (int64_t i = 0; i < n; ++i)
+    if (edge_ids[i] < 0 || edge_ids[i] >= ctx->ge_n) return fail(ctx, RRTX_E_INVALID, "%s: edge id %d out of range", fn, edge_ids[i]);
+  return launch_graph_block(ctx, restore, edge_ids, n);
+}
+
 int rrtx_graph_edges_block(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
   CHECK_CTX(ctx);
-  if (n < 0 || (n > 0 && !edge_ids)) return fail(ctx, RRTX_E_INVALID, "graph_edges_block: bad arguments");
-  for (int64_t i = 0; i < n; ++i)
-    if (edge_ids[i] < 0 || edge_ids[i] >= ctx->ge_n) return fail(ctx, RRTX_E_INVALID, "graph_edges_block: edge id %d out of range", edge_ids[i]);
-  return launch_graph_block(ctx, edge_ids, n);
+  return graph_edges_block_host(ctx, "graph_edges_block", false, edge_ids, n);
 }
 
 int rrtx_graph_edges_unblock(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
   CHECK_CTX(ctx);
-  if (n < 0 || (n > 0 && !edge_ids)) return fail(ctx, RRTX_E_INVALID, "graph_edges_unblock: bad arguments");
-  for (int64_t i = 0; i < n; ++i)
-    if (edge_ids[i] < 0 || edge_ids[i] >= ctx->ge_n) return fail(ctx, RRTX_E_INVALID, "graph_edges_unblock: edge id %d out of range", edge_ids[i]);
-  return launch_graph_unblock(ctx, edge_ids, n);
+  return graph_edges_block_host(ctx, "graph_edges_unblock", true, edge_ids, n);
 }
 
 namespace {
@@ -1240,13 +1241,11 @@ int rrtx_graph_cost_update_delta(rrtx_ctx *ctx, int root_idx, int store, int32_t
 
 // ---- obstacle sweeps of the polygon / Dubins space (R/DRRT.jl:3048-3290) ----------------------------------------
 namespace {
-struct SweepQ { double x, y, z, w, thr_lt, thr_root; };    // layout of kernels_sweep.hip's SweepQuery
-
 // one query of findPointsInConflictWithObstacle: the point itself (the root is taken with <=) and its ghosts in the
 // wrapped dimensions, in getNextGhostPoint's order and under its skip rule (R/ghostPoint.jl:60-111)
-void push_query_with_ghosts(rrtx_ctx *ctx, const double q[4], double range, std::vector<SweepQ> &out) {
+void push_query_with_ghosts(rrtx_ctx *ctx, const double q[4], double range, std::vector<SweepQuery> &out) {
   const double tlt = rrtx::thr_first_ge(range), tgt = rrtx::thr_first_gt(range);
-  SweepQ o = {q[0], q[1], q[2], q[3], tlt, ctx->opt_root_rule ? tgt : tlt};
+  SweepQuery o = {q[0], q[1], q[2], q[3], tlt, ctx->opt_root_rule ? tgt : tlt};
   out.push_back(o);
   const int nw = ctx->n_wraps;
   for (int k = 1; k < (1 << nw); ++k) {
@@ -1262,9 +1261,32 @@ void push_query_with_ghosts(rrtx_ctx *ctx, const double q[4], double range, std:
     double s = 0.0;                          // KDdist(closestUnwrappedPoint, ghost)^2, left fold over the d coordinates
     for (int d = 0; d < ctx->dim; ++d) { const double t = c[d] - g[d]; s = (d == 0) ? t * t : s + t * t; }
     if (s >= tgt) continue;                  // > bestDist: this ghost is not searched (:104)
-    SweepQ gq = {g[0], g[1], g[2], g[3], tlt, tlt};
+    SweepQuery gq = {g[0], g[1], g[2], g[3], tlt, tlt};
     out.push_back(gq);
   }
+}
+
+// the tail of a sweep entry point: read the count, refuse it above cap, queue the copy of the ids.  The caller
+// synchronises (only when *total > 0: nothing is queued otherwise).
+int sweep_ids_out(rrtx_ctx *ctx, const char *fn, const char *noun, const long long *total_dev, int32_t *edge_ids, int64_t cap,
+                  int64_t *needed, int64_t *total) {
+  RRTX_HIP(ctx, read_count(ctx, total_dev, total));
+  const int rc = check_capacity(ctx, fn, noun, *total, cap, needed);
+  if (rc) return rc;
+  if (*total > 0) RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)*total));
+  return RRTX_OK;
+}
+
+// sphere c = (x, y, z, radius) as a sweep's kernels read it: the SphRec of the edge test, the two thresholds of the range
+SweepObs sweep_obs(const double *c, double robot_radius, double range, bool active) {
+  SweepObs o;
+  o.ob.cx = c[0]; o.ob.cy = c[1]; o.ob.cz = c[2];
+  o.ob.thr = thr_first_gt(robot_radius + c[3]);
+  o.thr_lt = thr_first_ge(range);
+  o.thr_gt = thr_first_gt(range);
+  o.active = active ? 1 : 0;
+  o.pad0 = 0; o.pad1 = 0.0;
+  return o;
 }
 }  // namespace
 
@@ -1280,7 +1302,7 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
   const double cx = ctx->poly_cr[3 * (size_t)obstacle], cy = ctx->poly_cr[3 * (size_t)obstacle + 1],
                rad = ctx->poly_cr[3 * (size_t)obstacle + 2];
   // ---- findPointsInConflictWithObstacle (R/DRRT.jl:3048-3125) ----
-  std::vector<SweepQ> qs;
+  std::vector<SweepQuery> qs;
   if (kind >= 1 && kind <= 5) {
     if (has_time) return fail(ctx, RRTX_E_STATE, "this type of obstacle not coded for this type of space (a static obstacle in a "
                               "space with time, R/DRRT.jl:3067)");
@@ -1364,12 +1386,8 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
   span_end(ctx);
   if (rc) return rc;
   int64_t total = 0;
-  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));
-  if ((rc = check_capacity(ctx, "obstacle_sweep_polygon", "edges", total, cap, needed))) return rc;
-  if (total > 0) {
-    RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if ((rc = sweep_ids_out(ctx, "obstacle_sweep_polygon", "edges", total_dev, edge_ids, cap, needed, &total))) return rc;
+  if (total > 0) RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
 
@@ -1403,102 +1421,44 @@ int rrtx_obstacle_sweep(rrtx_ctx *ctx, int obstacle, double search_range, double
   if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "obstacle_sweep on an empty tree");
   if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "obstacle_sweep is the SimpleEdge (dim=3) path");
   const double *c = &ctx->sph[4 * (size_t)obstacle];
-  SphRec ob;
-  ob.cx = c[0]; ob.cy = c[1]; ob.cz = c[2];
-  ob.thr = thr_first_gt(robot_radius + c[3]);
+  const SweepObs o = sweep_obs(c, robot_radius, search_range, ctx->sph_active[obstacle] != 0);
   const int64_t dcap = cap > 0 ? cap : 1;
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)dcap));
   long long *total_dev = nullptr;
-  int rc = launch_obstacle_sweep(ctx, c, thr_first_ge(search_range), thr_first_gt(search_range), ob,
-                                 ctx->sph_active[obstacle] ? 1 : 0, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev);
+  int rc = launch_obstacle_sweep(ctx, c, o.thr_lt, o.thr_gt, o.ob, o.active, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev);
   if (rc) return rc;
   int64_t total = 0;
-  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));
-  if ((rc = check_capacity(ctx, "obstacle_sweep", "colliding edges", total, cap, needed))) return rc;
-  if (total > 0) {
-    RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if ((rc = sweep_ids_out(ctx, "obstacle_sweep", "colliding edges", total_dev, edge_ids, cap, needed, &total))) return rc;
+  if (total > 0) RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
 
-int rrtx_obstacle_sweep_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range,
-                              double robot_radius, int block, int64_t *offsets, int32_t *edge_ids, int64_t cap,
-                              int64_t *needed) {
-  CHECK_CTX(ctx);
+// rrtx_obstacle_sweep_batch (fn, release = false; apply: block the rows) and rrtx_obstacle_release_batch (release = true;
+// apply: unblock them)
+static int sphere_burst_host(rrtx_ctx *ctx, const char *fn, bool release, const int32_t *obstacles, int k,
+                             const double *search_range, double robot_radius, int apply, int64_t *offsets, int32_t *edge_ids,
+                             int64_t cap, int64_t *needed) {
   const int m = (int)ctx->sph_active.size();
   if (k < 0 || k > 65536 || !offsets || (k > 0 && (!obstacles || !search_range)) || cap < 0 || (cap > 0 && !edge_ids))
-    return fail(ctx, RRTX_E_INVALID, "obstacle_sweep_batch: bad arguments");
+    return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
   for (int j = 0; j < k; ++j)
     if (obstacles[j] < 0 || obstacles[j] >= m)
-      return fail(ctx, RRTX_E_INVALID, "obstacle_sweep_batch: obstacle %d (entry %d) out of range (%d spheres)", obstacles[j], j, m);
+      return fail(ctx, RRTX_E_INVALID, "%s: obstacle %d (entry %d) out of range (%d spheres)", fn, obstacles[j], j, m);
   if (needed) *needed = 0;
   if (k == 0) { offsets[0] = 0; return RRTX_OK; }
-  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "obstacle_sweep_batch on an empty tree");
-  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "obstacle_sweep_batch is the SimpleEdge (dim=3) path");
+  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "%s on an empty tree", fn);
+  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "%s is the SimpleEdge (dim=3) path", fn);
   if (ctx->ge_n == 0) { std::fill(offsets, offsets + k + 1, (int64_t)0); return RRTX_OK; }
-  // per obstacle what rrtx_obstacle_sweep hands its launcher: centre, SphRec, the two thresholds of the range, in use
+  // per obstacle what rrtx_obstacle_sweep hands its launcher; a leaving obstacle is taken as in use whatever its flag
+  // says (the reference marks it unused before its loop, R/DRRT_Q.jl:3302)
   ctx->swb_tab_host.resize((size_t)k);
-  for (int j = 0; j < k; ++j) {
-    const double *c = &ctx->sph[4 * (size_t)obstacles[j]];
-    SweepObs &o = ctx->swb_tab_host[(size_t)j];
-    o.ob.cx = c[0]; o.ob.cy = c[1]; o.ob.cz = c[2];
-    o.ob.thr = thr_first_gt(robot_radius + c[3]);
-    o.thr_lt = thr_first_ge(search_range[j]);
-    o.thr_gt = thr_first_gt(search_range[j]);
-    o.active = ctx->sph_active[obstacles[j]] ? 1 : 0;
-    o.pad0 = 0; o.pad1 = 0.0;
-  }
-  const int64_t dcap = cap > 0 ? cap : 1;
-  RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)dcap));
-  long long *total_dev = nullptr;
-  int rc = launch_obstacle_sweep_batch(ctx, k, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev);
-  if (rc) return rc;
-  RRTX_HIP(ctx, copy_out(ctx, offsets, ctx->ws_swb_off.p, sizeof(int64_t) * (size_t)(k + 1)));
-  int64_t total = 0;
-  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));
-  if ((rc = check_capacity(ctx, "obstacle_sweep_batch", "colliding edges", total, cap, needed))) return rc;
-  if (total > 0) {
-    RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
-    // addNewObstacle's dist = Inf for every id of every row, where the rows are
-    if (block && (rc = launch_graph_block_dev(ctx, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return RRTX_OK;
-}
-
-int rrtx_obstacle_release_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range,
-                                double robot_radius, int unblock, int64_t *offsets, int32_t *edge_ids, int64_t cap,
-                                int64_t *needed) {
-  CHECK_CTX(ctx);
-  const int m = (int)ctx->sph_active.size();
-  if (k < 0 || k > 65536 || !offsets || (k > 0 && (!obstacles || !search_range)) || cap < 0 || (cap > 0 && !edge_ids))
-    return fail(ctx, RRTX_E_INVALID, "obstacle_release_batch: bad arguments");
   for (int j = 0; j < k; ++j)
-    if (obstacles[j] < 0 || obstacles[j] >= m)
-      return fail(ctx, RRTX_E_INVALID, "obstacle_release_batch: obstacle %d (entry %d) out of range (%d spheres)", obstacles[j], j, m);
-  if (needed) *needed = 0;
-  if (k == 0) { offsets[0] = 0; return RRTX_OK; }
-  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch on an empty tree");
-  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch is the SimpleEdge (dim=3) path");
-  if (ctx->ge_n == 0) { std::fill(offsets, offsets + k + 1, (int64_t)0); return RRTX_OK; }
-  // the table of the batched sweep, every leaving obstacle taken as in use whatever its flag says (the reference
-  // marks it unused before its loop, R/DRRT_Q.jl:3302)
-  ctx->swb_tab_host.resize((size_t)k);
-  for (int j = 0; j < k; ++j) {
-    const double *c = &ctx->sph[4 * (size_t)obstacles[j]];
-    SweepObs &o = ctx->swb_tab_host[(size_t)j];
-    o.ob.cx = c[0]; o.ob.cy = c[1]; o.ob.cz = c[2];
-    o.ob.thr = thr_first_gt(robot_radius + c[3]);
-    o.thr_lt = thr_first_ge(search_range[j]);
-    o.thr_gt = thr_first_gt(search_range[j]);
-    o.active = 1;
-    o.pad0 = 0; o.pad1 = 0.0;
-  }
-  // the staying spheres: the packed in-use records of the edge checks, less the positions that leave
-  int rc = sync_spheres(ctx, robot_radius);
-  if (rc) return rc;
-  {
+    ctx->swb_tab_host[(size_t)j] = sweep_obs(&ctx->sph[4 * (size_t)obstacles[j]], robot_radius, search_range[j],
+                                             release || ctx->sph_active[obstacles[j]]);
+  int rc;
+  if (release) {
+    // the staying spheres: the packed in-use records of the edge checks, less the positions that leave
+    if ((rc = sync_spheres(ctx, robot_radius))) return rc;
     std::vector<uint8_t> leaves((size_t)m, 0);
     for (int j = 0; j < k; ++j) leaves[(size_t)obstacles[j]] = 1;
     const std::vector<int32_t> pos = active_positions(ctx->sph_active);
@@ -1508,19 +1468,30 @@ int rrtx_obstacle_release_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, 
   const int64_t dcap = cap > 0 ? cap : 1;
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)dcap));
   long long *total_dev = nullptr;
-  rc = launch_obstacle_release_batch(ctx, k, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev);
-  if (rc) return rc;
+  if ((rc = launch_sphere_burst(ctx, k, release, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev))) return rc;
   RRTX_HIP(ctx, copy_out(ctx, offsets, ctx->ws_swb_off.p, sizeof(int64_t) * (size_t)(k + 1)));
   int64_t total = 0;
-  RRTX_HIP(ctx, read_count(ctx, total_dev, &total));
-  if ((rc = check_capacity(ctx, "obstacle_release_batch", "freed edges", total, cap, needed))) return rc;
+  if ((rc = sweep_ids_out(ctx, fn, release ? "freed edges" : "colliding edges", total_dev, edge_ids, cap, needed, &total))) return rc;
   if (total > 0) {
-    RRTX_HIP(ctx, copy_out(ctx, edge_ids, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total));
-    // removeObstacle's dist = distOriginal for every id of every row, where the rows are
-    if (unblock && (rc = launch_graph_unblock_dev(ctx, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
+    // addNewObstacle's dist = Inf / removeObstacle's dist = distOriginal for every id of every row, where the rows are
+    if (apply && (rc = launch_graph_block_dev(ctx, release, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return RRTX_OK;
+}
+
+int rrtx_obstacle_sweep_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range,
+                              double robot_radius, int block, int64_t *offsets, int32_t *edge_ids, int64_t cap,
+                              int64_t *needed) {
+  CHECK_CTX(ctx);
+  return sphere_burst_host(ctx, "obstacle_sweep_batch", false, obstacles, k, search_range, robot_radius, block, offsets, edge_ids, cap, needed);
+}
+
+int rrtx_obstacle_release_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, const double *search_range,
+                                double robot_radius, int unblock, int64_t *offsets, int32_t *edge_ids, int64_t cap,
+                                int64_t *needed) {
+  CHECK_CTX(ctx);
+  return sphere_burst_host(ctx, "obstacle_release_batch", true, obstacles, k, search_range, robot_radius, unblock, offsets, edge_ids, cap, needed);
 }
 
 static int points_check_args(rrtx_ctx *ctx, int kind, const double *p, int64_t np, const uint8_t *unsafe) {

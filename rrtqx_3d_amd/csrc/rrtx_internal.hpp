@@ -46,6 +46,10 @@ struct alignas(32) SphRec { double cx, cy, cz, thr; };
 // (node in range <=> s < thr_lt, the root: s < thr_gt) and whether the obstacle is in use.
 struct alignas(64) SweepObs { SphRec ob; double thr_lt, thr_gt; int32_t active, pad0; double pad1; };
 
+// One range query of the polygon / Dubins sweep as sweep_mark_multi_kernel reads it (kernels_sweep.hip): node in range
+// <=> s < thr_lt, the root: s < thr_root
+struct SweepQuery { double x, y, z, w, thr_lt, thr_root; };
+
 // host-side mirror of exact_math.hpp's ChunkExt (this header is also read by plain C++)
 struct ChunkExtHost { unsigned long long xlo, xhi, ylo, yhi; };
 
@@ -392,7 +396,7 @@ int launch_dubins_edges_check(rrtx_ctx *ctx, const double *s_dev, const double *
                               uint8_t *hit_dev, int32_t *traj_len_dev, int pb = -1, int pe = -1);
 int launch_dubins_edges_idx(rrtx_ctx *ctx, const int32_t *ids_dev, int64_t n, double r_min, double robot_radius, int pb,
                             int pe, uint8_t *hit_dev);
-int launch_sweep_mark_multi(rrtx_ctx *ctx, const void *queries_host, int nqs);
+int launch_sweep_mark_multi(rrtx_ctx *ctx, const SweepQuery *queries_host, int nqs);
 int launch_sweep_select(rrtx_ctx *ctx, int blocked_only, int32_t *out_dev, long long cap, long long **total_dev);
 int launch_sweep_finish(rrtx_ctx *ctx, const int32_t *ids_dev, long long n, const uint8_t *hit, const uint8_t *o1,
                         const uint8_t *o2, int32_t *out_dev, long long cap, long long **total_dev);
@@ -423,21 +427,17 @@ int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const 
 int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, double thr_gt, const SphRec &ob,
                           int active, int32_t *out_dev, int64_t cap, long long **total_dev);
 
-// device side of rrtx_obstacle_sweep_batch over ctx->swb_tab_host (k obstacles): row j of the CSR in ws_swb_off (k + 1
-// offsets) / out_dev (at most cap ids) is obstacle j's sweep; *total_dev = the number of ids of all rows
-int launch_obstacle_sweep_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev);
-
-// device side of rrtx_obstacle_release_batch over ctx->swb_tab_host (k leaving obstacles, every one marked in use) and
-// ctx->rel_stay_host (sync_spheres has run for the call's robot radius): the same outputs, row j = the blocked edges
-// obstacle j hits and no staying sphere does
-int launch_obstacle_release_batch(rrtx_ctx *ctx, int k, int32_t *out_dev, int64_t cap, long long **total_dev);
+// device side of rrtx_obstacle_sweep_batch / rrtx_obstacle_release_batch over ctx->swb_tab_host (k obstacles).  Both
+// modes leave a CSR in ws_swb_off (k + 1 offsets) / out_dev (at most cap ids) and *total_dev = the ids of all rows.
+// Sweep: row j = obstacle j's sweep.  release (every obstacle of the table marked in use, ctx->rel_stay_host filled,
+// sync_spheres has run for the call's robot radius): row j = the blocked edges obstacle j hits and no staying sphere does.
+int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, int64_t cap, long long **total_dev);
 
 int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n);
 int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n);
-int launch_graph_block(rrtx_ctx *ctx, const int32_t *ids_host, long long n);
-int launch_graph_block_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n);   // ids already on the device, in [0, ge_n)
-int launch_graph_unblock(rrtx_ctx *ctx, const int32_t *ids_host, long long n);
-int launch_graph_unblock_dev(rrtx_ctx *ctx, const int32_t *ids_dev, long long n); // ids already on the device, in [0, ge_n)
+// edge.dist = Inf (restore = false) or edge.distOriginal (restore = true) for the edges ids[i], all in [0, ge_n)
+int launch_graph_block(rrtx_ctx *ctx, bool restore, const int32_t *ids_host, long long n);      // synchronises
+int launch_graph_block_dev(rrtx_ctx *ctx, bool restore, const int32_t *ids_dev, long long n);   // ids already on the device
 int launch_graph_cost(rrtx_ctx *ctx, int root, bool update, double *lmc_dev, int32_t *parent_dev, int *passes_out);
 void graph_cost_forget(rrtx_ctx *ctx);
 int launch_graph_delta(rrtx_ctx *ctx, int root, bool store, int32_t *node_dev, double *lmc_dev, int32_t *par_dev, long long cap,

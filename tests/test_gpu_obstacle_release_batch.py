@@ -8,79 +8,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from mirror_model import DELTA, RR, Scene
 from rrtqx_3d_amd import _capi, drrt
-from rrtqx_3d_amd.context import Context
 
 pytestmark = pytest.mark.gpu
-RR, DELTA = 0.5, 8.0
-
-
-class Scene:
-    """The generator of test_gpu_obstacle_sweep_batch.Scene (a copy: same nodes, edges and spheres for the same n, K).
-    The oracle's tree is built once; release rows are computed once per (leaving set, position, range, blocked ids)."""
-
-    def __init__(self, oracle, n, K, inactive=()):
-        rng = np.random.default_rng(n + K)
-        self.n, self.K, self.oracle = n, K, oracle
-        self.pts = pts = rng.uniform(-30, 30, (n, 3))
-        es = np.repeat(np.arange(n), 7)
-        ee = (es + rng.integers(1, 50, len(es))) % n
-        ee[::7] = rng.integers(0, n, n)                    # long edges too
-        es[:5], ee[:5] = 0, [1, 2, 3, 4, 5]                # out-edges of the root
-        ee[5] = es[5]                                      # a zero-length edge
-        self.es, self.ee = es.astype(np.int32), ee.astype(np.int32)
-        sph = np.concatenate([rng.uniform(-25, 25, (K, 3)), rng.uniform(1.0, 6.0, (K, 1))], 1)
-        sph[3, :3] = pts[0] + [2.0, 0.0, 0.0]              # an obstacle right at the root
-        sph[K - 1] = (29.5, 29.5, -29.5, 0.05)             # a tiny one in a corner
-        self.sph = sph
-        self.active = np.ones(K, dtype=np.uint8)
-        self.active[list(inactive)] = 0
-        self.search = RR + DELTA + sph[:, 3]
-        self.tree = oracle.KDTree(3)
-        self.tree.insert_many(pts)
-        self._masks, self._rows = {}, {}
-
-    def in_range(self, pos, search_range):
-        key = (int(pos), float(search_range))
-        if key not in self._masks:
-            mask = np.zeros(self.n, dtype=np.uint8)
-            mask[self.tree.within_range(float(search_range), self.sph[pos, :3])[0]] = 1
-            self._masks[key] = mask
-        return self._masks[key]
-
-    def stay(self, leaving):
-        s = self.active.copy()
-        s[np.asarray(leaving, dtype=np.int64)] = 0
-        return s
-
-    def sweep_row(self, pos, search_range, es=None, ee=None):
-        """addNewObstacle's loop for sphere `pos` taken as in use, whatever its flag says (oracle)"""
-        a = np.zeros(self.K, dtype=np.uint8)
-        a[pos] = 1
-        ids = self.oracle.sweep_edges_batch(self.pts, self.es if es is None else es, self.ee if ee is None else ee,
-                                            self.in_range(pos, search_range), self.oracle.make_spheres(self.sph, a),
-                                            int(pos), RR)
-        return np.asarray(ids, dtype=np.int32)
-
-    def release_row(self, leaving, pos, search_range, dist_host, es=None, ee=None):
-        """the reference for one row: the oracle alone, the stay flags with position `pos` set to 1"""
-        key = (tuple(sorted(set(int(p) for p in leaving))), int(pos), float(search_range),
-               np.flatnonzero(np.isinf(dist_host)).tobytes(), len(dist_host))
-        if key not in self._rows:
-            a = self.stay(leaving)
-            a[pos] = 1
-            ids = self.oracle.sweep_edges_batch(self.pts, self.es if es is None else es, self.ee if ee is None else ee,
-                                                self.in_range(pos, search_range), self.oracle.make_spheres(self.sph, a),
-                                                int(pos), RR, remove=True, dist=dist_host)
-            self._rows[key] = np.asarray(ids, dtype=np.int32)
-        return self._rows[key]
-
-    def context(self, es=None, ee=None):
-        ctx = Context(3)
-        ctx.nodes_append(self.pts)
-        ctx.spheres_set(self.sph, self.active)
-        assert ctx.graph_edges_append(self.es if es is None else es, self.ee if ee is None else ee) == 0
-        return ctx
 
 
 def _rows_of(off, ids):
@@ -240,6 +171,26 @@ def test_counts_cross_a_scan_round(oracle):
         ctx.obstacle_sweep_batch(np.arange(s.K, dtype=np.int32), s.search, RR, block=True)
         _check(ctx, s, L, search, dist, cap=total)                           # exactly enough
         _check(ctx, s, L, search, dist, cap=total - 1)
+
+
+def test_release_of_everything_blocked_is_the_sweep(oracle):
+    """The seam of the head the two passes over the mirror share.  n = 300, K = 66, every flag 1: 2 100 edges = two
+    full blocks of 1024 and 52 edges, two groups of obstacles (64, 2).  With every edge of the mirror blocked and all 66
+    spheres leaving, no sphere stays, so the release's row j is the sweep's row j.  Seed n + K as generated: the oracle
+    finds 15 non-empty rows in the first group and position 64 (14 ids) in the second; position 65 is the tiny sphere."""
+    s = Scene(oracle, 300, 66)
+    assert len(s.es) == 2 * 1024 + 52 and s.active.all()
+    L = np.arange(s.K, dtype=np.int32)
+    want = [s.row(p, s.search[p]) for p in L]
+    assert any(len(w) > 0 for w in want[:64]) and any(len(w) > 0 for w in want[64:])
+    dist = np.full(len(s.es), np.inf)
+    with s.context() as ctx:
+        swept = _rows_of(*ctx.obstacle_sweep_batch(L, s.search, RR))
+        ctx.graph_edges_block(np.arange(len(s.es), dtype=np.int32))
+        freed = _check(ctx, s, L, s.search, dist)                            # every row against the oracle's release
+        for j in range(s.K):
+            assert np.array_equal(freed[j], swept[j]), j
+            assert np.array_equal(swept[j], want[j]), j
 
 
 def test_unblock_in_the_call_is_unblock_over_the_union(scene_a):

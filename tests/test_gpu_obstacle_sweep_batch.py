@@ -7,57 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from mirror_model import DELTA, RR, Scene
 from rrtqx_3d_amd import _capi, drrt
-from rrtqx_3d_amd.context import Context
 
 pytestmark = pytest.mark.gpu
-RR, DELTA = 0.5, 8.0
-
-
-class Scene:
-    """The generator of test_obstacle_sweep_matches_oracle with K spheres; the oracle's tree and sphere list are built
-    once, rows are computed once per (position, range) and shared."""
-
-    def __init__(self, oracle, n, K, inactive=()):
-        rng = np.random.default_rng(n + K)
-        self.n, self.K, self.oracle = n, K, oracle
-        self.pts = pts = rng.uniform(-30, 30, (n, 3))
-        es = np.repeat(np.arange(n), 7)
-        ee = (es + rng.integers(1, 50, len(es))) % n
-        ee[::7] = rng.integers(0, n, n)                    # long edges too
-        es[:5], ee[:5] = 0, [1, 2, 3, 4, 5]                # out-edges of the root
-        ee[5] = es[5]                                      # a zero-length edge
-        self.es, self.ee = es.astype(np.int32), ee.astype(np.int32)
-        sph = np.concatenate([rng.uniform(-25, 25, (K, 3)), rng.uniform(1.0, 6.0, (K, 1))], 1)
-        sph[3, :3] = pts[0] + [2.0, 0.0, 0.0]              # an obstacle right at the root
-        sph[K - 1] = (29.5, 29.5, -29.5, 0.05)             # a tiny one in a corner
-        self.sph = sph
-        self.active = np.ones(K, dtype=np.uint8)
-        self.active[list(inactive)] = 0
-        self.search = RR + DELTA + sph[:, 3]
-        self.rng = rng
-        self.tree = oracle.KDTree(3)
-        self.tree.insert_many(pts)
-        self.osph = oracle.make_spheres(sph, self.active)
-        self._rows = {}
-
-    def row(self, pos, search_range, es=None, ee=None):
-        """the oracle's sweep of sphere `pos` with this range (over another mirror of the same nodes when given)"""
-        key = (int(pos), float(search_range), None if es is None else id(es))
-        if key not in self._rows:
-            mask = np.zeros(self.n, dtype=np.uint8)
-            mask[self.tree.within_range(float(search_range), self.sph[pos, :3])[0]] = 1
-            ids = self.oracle.sweep_edges_batch(self.pts, self.es if es is None else es, self.ee if ee is None else ee,
-                                                mask, self.osph, int(pos), RR)
-            self._rows[key] = np.asarray(ids, dtype=np.int32)
-        return self._rows[key]
-
-    def context(self, es=None, ee=None):
-        ctx = Context(3)
-        ctx.nodes_append(self.pts)
-        ctx.spheres_set(self.sph, self.active)
-        assert ctx.graph_edges_append(self.es if es is None else es, self.ee if ee is None else ee) == 0
-        return ctx
 
 
 def _rows_of(off, ids):
