@@ -138,6 +138,7 @@ struct alignas(64) SampleSph { double cx, cy, cz, thr_in, thr_pt, reach, pad0, p
 constexpr int kSphListCap = 8;   // spheres listed per sample; a longer list sends the sample's edges to the full loop
 
 // what the fused extend() path reads about the sphere list (tables of sync_spheres)
+struct SampleList;
 struct ExtendDev {
   const SphRec *sph;           // exact records, packed (active only), list order
   const SampleSph *stab;
@@ -148,6 +149,7 @@ struct ExtendDev {
   int pad;
   double r_bound;              // radius of the ball the lists are built for; < 0: no lists (full loop)
   uint8_t *sample_unsafe;
+  const SampleList *lists;     // per sample (query number): what the pack launch's sample role found (sample_pass_group)
 };
 
 // fp32 screen state of a point or segment midpoint for the reach table: centre relative to the
@@ -249,6 +251,100 @@ __device__ __forceinline__ bool sample_exact(const ExtendDev &x, int j, double p
   const double B = base_b + sp.reach;
   *listed = x.r_bound >= 0.0 && !(s > B * B * (1.0 + 1e-12));
   return !(s >= sp.thr_in) | (s < sp.thr_pt);
+}
+
+// Sample pass of the fused extend() path for one GROUP of up to kSampleGroup consecutive samples, run by a pair of
+// waves (128 lanes) of the pack launch.  A lane owns a pair of spheres (one read of the fp32 reach table) and walks
+// the group's samples: the packed-fp32 screen leaves the near (sample, sphere) pairs, which are queued (one queue
+// of 64 per wave) and decided by sample_exact one pair per lane; a pair that finds its queue full is decided on the
+// spot.  The screen only ever drops pairs that can neither make the sample unsafe nor belong on its list.
+//   in : g.px / py / pz / base of samples [0, nsamp), g.snl = g.sbad = 0 (a barrier before the call); probe: lane
+//        cl < nsamp of EACH wave holds sample cl's probe of the reach table
+//   out: g.sbad, g.snl (raw count, may exceed kSphListCap) and g.ssl, complete after the caller's next barrier
+constexpr int kSampleGroup = 16;
+struct SampleGroupLds {
+  double px[kSampleGroup], py[kSampleGroup], pz[kSampleGroup];
+  double base[kSampleGroup];   // ball radius + slack of the exact list test
+  int snl[kSampleGroup];
+  int sbad[kSampleGroup];
+  int ssl[kSampleGroup][kSphListCap];
+  int sq[2][64];               // (sample, sphere) pairs the screen left over, one queue per wave
+};
+// What the pass leaves per sample (indexed by query number) for the tile kernel: one 64-byte record, one load
+struct alignas(64) SampleList {
+  int n;                       // spheres within reach of the sample's ball; > kSphListCap: the list does not hold them all
+  int unsafe;
+  int pad0, pad1;
+  int list[kSphListCap];       // positions in the packed sphere table (entries beyond n: 0)
+  int pad2[4];
+};
+static_assert(sizeof(SampleList) == 64 && kSphListCap == 8, "one record, two 16-byte rows of list positions");
+
+// gl: lane of the group (0 .. 127), qw = gl >> 6: wave of the pair.  Both waves of the pair call this together.
+__device__ __forceinline__ void sample_pass_group(const ExtendDev &x, SampleGroupLds &g, const int nsamp, const int gl,
+                                                  const ReachProbe probe) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const int lane = gl & 63, qw = gl >> 6;
+  const int n_pairs = (x.m + 1) / 2;
+  const float4 *tp = reinterpret_cast<const float4 *>(x.reach_f);
+  // exact part for one left-over pair
+  auto exact = [&](int cl, int j) {
+    bool listed;
+    if (sample_exact(x, j, g.px[cl], g.py[cl], g.pz[cl], g.base[cl], &listed)) g.sbad[cl] = 1;
+    if (listed) {
+      const int at = atomicAdd(&g.snl[cl], 1);
+      if (at < kSphListCap) g.ssl[cl][at] = j;
+    }
+  };
+  // the loop below takes the probes from the lanes with v_readlane (scalar operands of the packed arithmetic)
+  const int ipx = __float_as_int(probe.mx), ipy = __float_as_int(probe.my), ipz = __float_as_int(probe.mz),
+            ipw = __float_as_int(probe.h);
+  int nqueued = 0;                            // wave-uniform: near pairs this wave has queued
+  for (int pr0 = 0; pr0 < n_pairs; pr0 += 128) {
+    const int pr = pr0 + gl;
+    float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool pv = pr < n_pairs;
+    if (pv) { u = tp[2 * pr]; v = tp[2 * pr + 1]; }
+    const f32x2 ux = {u.x, u.y}, uy = {u.z, u.w}, uz = {v.x, v.y}, ur = {v.z, v.w};
+    const bool va = pv && 2 * pr < x.m, vb = pv && 2 * pr + 1 < x.m;
+    for (int cl = 0; cl < nsamp; ++cl) {      // (wave-uniform: the probes come by lane number)
+      const float px = __int_as_float(__builtin_amdgcn_readlane(ipx, cl));
+      const float py = __int_as_float(__builtin_amdgcn_readlane(ipy, cl));
+      const float pz = __int_as_float(__builtin_amdgcn_readlane(ipz, cl));
+      const float pw = __int_as_float(__builtin_amdgcn_readlane(ipw, cl));
+      // both spheres of the pair at once (v_pk_*): the same operations in the same order as one at a time
+      const f32x2 dx = ux - px, dy = uy - py, dz = uz - pz;
+      f32x2 d = dx * dx;
+      d = __builtin_elementwise_fma(dy, dy, d);
+      d = __builtin_elementwise_fma(dz, dz, d);
+      const f32x2 bnd = ur + pw;
+      const f32x2 b2 = bnd * bnd;
+      // the left-over pairs are queued (no load in this loop) and evaluated one per lane below
+      const bool na = va && !(d.x > b2.x), nb = vb && !(d.y > b2.y);
+      const unsigned long long ma = __ballot(na), mb = __ballot(nb);
+      if ((ma | mb) == 0ull) continue;
+      // queue places from the wave's masks
+      const int at_a = nqueued + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ma >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ma, 0u));
+      const int at_b = nqueued + __popcll(ma) +
+                       (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mb, 0u));
+      nqueued += __popcll(ma) + __popcll(mb);
+      if (na) {
+        if (at_a < 64) g.sq[qw][at_a] = cl | ((2 * pr) << 4);
+        else exact(cl, 2 * pr);               // queue full (dense obstacle field): right away
+      }
+      if (nb) {
+        if (at_b < 64) g.sq[qw][at_b] = cl | ((2 * pr + 1) << 4);
+        else exact(cl, 2 * pr + 1);
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  const int nq_ev = min(nqueued, 64);
+  if (lane < nq_ev) {
+    const int ev = g.sq[qw][lane];
+    exact(ev & 15, ev >> 4);
+  }
 }
 
 }  // namespace

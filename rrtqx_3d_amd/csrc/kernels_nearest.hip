@@ -399,7 +399,7 @@ static int launch_nn_nearest_screened(rrtx_ctx *ctx, const double *q_dev, int nq
       typename QRecT<DD>::type *copies = ctx->ws_copies.as<typename QRecT<DD>::type>();
       typename QRecFT<DD>::type *copies_f = ctx->ws_copies_f.as<typename QRecFT<DD>::type>();
       launch_nn_pack<DD>(ctx, q_dev, nq, nullptr, nullptr, inf, nan, sc, nullptr, 1, 1, nullptr, nullptr, PackFused{},
-                         ConfirmArgs{}, QSlots{});
+                         ConfirmArgs{}, QSlots{}, PackSamples{});
       hipLaunchKernelGGL(nn_filter_prep_kernel<DD>, pgrid, block, 0, st, copies, sc, absmax, (int)n_copies_max,
                          ctx->origin[0], ctx->origin[1], ctx->origin[2], ctx->origin[3], copies_f);
       hipLaunchKernelGGL(nn_nearest_f32_kernel<DD>, sgrid, block, 0, st, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2],

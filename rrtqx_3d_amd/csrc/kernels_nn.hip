@@ -10,14 +10,15 @@
 // kernels' arguments (radius_args) and then runs one function per stage:
 //   pack    : queries -> slot table (query + ghosts), copy records, grid bucket and rank of
 //             every copy, the root rule (<= instead of <, R/kdTree_general.jl:896 vs :830),
-//             per-call state
+//             per-call state; on the fused extend() path further workgroups of the same launch check
+//             every sample and list the spheres its edges can touch (pack_sample_role)
 //   place   : copies in bucket order + their fp32 screen records      (culled search with ghosts, or RRTX_OPT_TUNE
 //             bit 4; without ghosts the pack pass writes every copy, its screen record and its owner to slot
 //             (bucket, rank) of a table instead, and each tile finds its own copies there: three launches)
 //   tile    : per tile of 16 copies: groups of eight nodes within reach (cells of the slab index cut
 //             by bins of the third coordinate) -> fp32 screen -> exact confirmation -> hits into the
-//             queries' buckets; on the fused extend() path also the sample check and both edge flags
-//             of every neighbour                                          (culled search)
+//             queries' buckets; on the fused extend() path also both edge flags of every neighbour,
+//             against the sample's sphere list from the pack launch                                         (culled search)
 //   [ prep, scan, confirm : the same three steps for the brute-force search, every tile of 64
 //             copies streams every node ]
 //   finish  : offsets, order by node index, dist = sqrt(d2), owner, nearest, empty balls
@@ -498,17 +499,13 @@ struct TileLds {
   typename QRecFT<D>::type cf[kTileB];
   int own[kTileB];
   BktRec hrec[kTileB][kTbLcap];
-  // fused extend() path: per copy (= sample) the spheres its candidate edges can touch, and whether
-  // the sample itself is in collision
+  // fused extend() path: per copy (= sample) the spheres its candidate edges can touch, as the pack launch's
+  // sample role listed them (SampleList, by owner)
   int snl[kTileB];
-  int sbad[kTileB];
   int sok[kTileB];             // the sample's coordinates are finite and moderate (screens apply)
-  float4 srp[kTileB];          // the sample's probe of the fp32 reach table (centre, inflated ball radius)
-  double sbase[kTileB];        // ball radius + slack of the exact list test
-  int sq[2][64];               // (sample, sphere) pairs the screen left over, one queue per sample-pass wave
   int ssl[kTileB][kSphListCap];
-  SphRec ssr[kTileB][kSphListCap];   // ... and their records, fetched by the sample pass (the hand-out's edge tests
-                                     //     then wait for the neighbour's coordinates only)
+  SphRec ssr[kTileB][kSphListCap];   // ... and their records, fetched beside the list building (the hand-out's edge
+                                     //     tests then wait for the neighbour's coordinates only)
 };
 
 // the (x, y) cell structure of the sorted part of the slab index
@@ -824,16 +821,12 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
         }
         sm.cp[lane] = c;
         if constexpr (EXT) {
+          // (the sample role's own test of the sample: pack_sample_role, nn_device.hpp)
           const double rb = x.r_bound >= 0.0 ? x.r_bound : 0.0;
           const double pmax = fmax(fmax(fabs(c.x), fabs(c.y)), fabs(c.z));
-          // slack for the rounding of the foot point and of this distance; NaN / inf sample: everything is a candidate
           const double base_b = rb + 1e-12 * (pmax + 1.0);
           const bool usable = (pmax < 1e29) && (c.x == c.x) && (c.y == c.y) && (c.z == c.z) && (base_b < 1e29);
-          const ReachProbe rp = reach_probe(x, c.x, c.y, c.z, base_b, usable);
-          sm.srp[lane] = make_float4(rp.mx, rp.my, rp.mz, rp.h);
-          sm.sbase[lane] = base_b;
           sm.sok[lane] = (usable && x.r_bound >= 0.0) ? 1 : 0;
-          sm.snl[lane] = 0; sm.sbad[lane] = 0;
         }
         // thr NaN / <= 0, x or y NaN or +-inf: the copy can never have a neighbour
         // (a non-finite third coordinate gives s = NaN or inf, which is never < thr)
@@ -868,10 +861,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     RRTX_TILE_CLK(1);
     const double lo = sm.lo, hi = sm.hi, ylo = sm.ylo, yhi = sm.yhi;
     bool gmode_w0 = false;                  // (wave 0) this tile's sorted part is listed as groups
-    // (no copy of the tile can have a neighbour: nothing to list or screen -- but the fused path's sample pass,
-    // which sits in the list phase, runs all the same: explicitPointCheck of a sample does not depend on its ball;
-    // with lo > hi every range below is empty)
-    if (lo <= hi || EXT) {
+    // (no copy of the tile can have a neighbour: nothing to list or screen)
+    if (lo <= hi) {
       for (int cb = 0; cb < n_chunks; cb += kTbList) {
         // ---- 2. chunk list of this pass: chunk ids in [cb, ce) ----
         const int ce = min(cb + kTbList, n_chunks);
@@ -955,81 +946,28 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
             }
           }
         } else if (EXT && wave >= 2) {
-          // ---- 1b. sample pass beside the list building (waves 2 and 3): a lane owns a pair of
-          //      spheres (one table read) and walks the tile's samples, whose probes are in LDS ----
+          // ---- 1b. the samples' sphere lists beside the list building (waves 2 and 3): one lane per (copy, list
+          //      slot) reads the record the pack launch's sample role left for the copy's owner, then the listed
+          //      sphere's exact record ----
           if (cb == 0) {
-            const int n_pairs = (x.m + 1) / 2;
-            const float4 *tp = reinterpret_cast<const float4 *>(x.reach_f);
-            const int qw = wave - 2;
-            // exact part for one left-over pair
-            auto exact = [&](int cl, int j) {
-              const typename QRecT<D>::type c = sm.cp[cl];
-              bool listed;
-              const SphRec rec = x.sph[j];          // (requested beside the sample record, used if listed)
-              if (sample_exact(x, j, c.x, c.y, c.z, sm.sbase[cl], &listed)) sm.sbad[cl] = 1;
-              if (listed) {
-                const int at = atomicAdd(&sm.snl[cl], 1);
-                if (at < kSphListCap) { sm.ssl[cl][at] = j; sm.ssr[cl][at] = rec; }
-              }
-            };
-            // the tile's probes: lane cl < 16 of this wave holds sample cl's, the loop below takes them from
-            // there with v_readlane (scalar operands of the packed arithmetic: no LDS read and wait per sample)
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            float4 mypf = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (lane < q1 - q0) mypf = sm.srp[lane];
-            const int ipx = __float_as_int(mypf.x), ipy = __float_as_int(mypf.y), ipz = __float_as_int(mypf.z),
-                      ipw = __float_as_int(mypf.w);
-            const int nsamp = q1 - q0;
-            int nqueued = 0;                            // wave-uniform: near pairs this wave has queued
-            for (int pr0 = 0; pr0 < n_pairs; pr0 += 128) {
-              const int pr = pr0 + (t - 128);
-              float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = make_float4(0.f, 0.f, 0.f, 0.f);
-              const bool pv = pr < n_pairs;
-              if (pv) { u = tp[2 * pr]; v = tp[2 * pr + 1]; }
-              const f32x2 ux = {u.x, u.y}, uy = {u.z, u.w}, uz = {v.x, v.y}, ur = {v.z, v.w};
-              const bool va = pv && 2 * pr < x.m, vb = pv && 2 * pr + 1 < x.m;
-              for (int cl = 0; cl < nsamp; ++cl) {    // (wave-uniform: the probes come by lane number)
-                const float px = __int_as_float(__builtin_amdgcn_readlane(ipx, cl));
-                const float py = __int_as_float(__builtin_amdgcn_readlane(ipy, cl));
-                const float pz = __int_as_float(__builtin_amdgcn_readlane(ipz, cl));
-                const float pw = __int_as_float(__builtin_amdgcn_readlane(ipw, cl));
-                // both spheres of the pair at once (v_pk_*): the same operations in the same order as one at a time
-                const f32x2 dx = ux - px, dy = uy - py, dz = uz - pz;
-                f32x2 d = dx * dx;
-                d = __builtin_elementwise_fma(dy, dy, d);
-                d = __builtin_elementwise_fma(dz, dz, d);
-                const f32x2 bnd = ur + pw;
-                const f32x2 b2 = bnd * bnd;
-                // the left-over pairs are queued (no load in this loop) and evaluated one per lane below
-                const bool na = va && !(d.x > b2.x), nb = vb && !(d.y > b2.y);
-                const unsigned long long ma = __ballot(na), mb = __ballot(nb);
-                if ((ma | mb) == 0ull) continue;
-                // queue places from the wave's masks (a samples' worth of near pairs used to line up on one LDS counter)
-                const int at_a = nqueued + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ma >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ma, 0u));
-                const int at_b = nqueued + __popcll(ma) +
-                                 (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mb, 0u));
-                nqueued += __popcll(ma) + __popcll(mb);
-                if (na) {
-                  if (at_a < 64) sm.sq[qw][at_a] = cl | ((2 * pr) << 4);
-                  else exact(cl, 2 * pr);            // queue full (dense obstacle field): right away
-                }
-                if (nb) {
-                  if (at_b < 64) sm.sq[qw][at_b] = cl | ((2 * pr + 1) << 4);
-                  else exact(cl, 2 * pr + 1);
-                }
+            static_assert(kTileB * kSphListCap == 128, "two waves: one lane per (copy, list slot)");
+            int ts = t - 128;
+            asm volatile("" : "+v"(ts));         // (keeps the lane's LDS addresses from living across the tile loop)
+            const int cl = ts / kSphListCap, ls = ts % kSphListCap;
+            int n = 0, j = 0;
+            if (cl < q1 - q0) {
+              const int owner = SL ? sm.own[cl] : a.meta[q0 + cl].x;
+              if (owner >= 0) {
+                const SampleList *rec = x.lists + owner;
+                n = rec->n; j = rec->list[ls];
               }
             }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            const int nq_ev = min(nqueued, 64);
-            if (lane < nq_ev) {
-              const int ev = sm.sq[qw][lane];
-              exact(ev & 15, ev >> 4);
-            }
+            if (ls == 0) sm.snl[cl] = n;           // the raw count: beyond kSphListCap the edges take the full loop
+            if (ls < n) { sm.ssl[cl][ls] = j; sm.ssr[cl][ls] = x.sph[j]; }
           }
         } else {
           // appended since the last rebuild (and the chunk the sorted part ends in): by extent
-          const int nt = EXT ? 64 : 192;         // wave 1 (and waves 2, 3 unless they run the sample pass)
+          const int nt = EXT ? 64 : 192;         // wave 1 (and waves 2, 3 unless they fetch the sphere lists)
           for (int c = max(cb, tg.n_sorted_chunks) + (t - 64); c < ce; c += nt) {
             const ChunkExt cx = chunk_ext[c];
             if (dec_ord(cx.xhi) >= lo && dec_ord(cx.xlo) <= hi && dec_ord(cx.yhi) >= ylo && dec_ord(cx.ylo) <= yhi)
@@ -1038,7 +976,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
         }
         RRTX_TILE_CLK_AT(0, 8);        // wave 0: list written
         RRTX_TILE_CLK_AT(64, 9);       // wave 1: tail chunks by extent
-        RRTX_TILE_CLK_AT(128, 10);     // wave 2: sample pass
+        RRTX_TILE_CLK_AT(128, 10);     // wave 2: sphere lists fetched
         __syncthreads();
         RRTX_TILE_CLK(2);
         const int nl = sm.n_list;
@@ -1141,13 +1079,6 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
           if constexpr (EXT) flags = tile_edge_flags<D>(x, sm, h, h ? cl : 0, br.idx, br.d2);
           place_hit(a.hs, h, owner, base + j, br.idx, br.d2, flags);
         }
-      }
-    }
-    if constexpr (EXT) {
-      // explicitPointCheck of the samples (one part of a tile reports them)
-      if (part == 0 && t < q1 - q0 && x.sample_unsafe) {
-        const int owner = SL ? sm.own[t] : a.meta[q0 + t].x;
-        if (owner >= 0) x.sample_unsafe[owner] = sm.sbad[t] ? 1 : 0;
       }
     }
     RRTX_TILE_CLK(6);
@@ -1394,6 +1325,7 @@ int radius_workspaces(rrtx_ctx *ctx, const RadiusPlan &p) {
     if (p.slot_route) RRTX_HIP(ctx, ctx->ws_qslot.ensure((size_t)p.n_tab * rec_bytes));
   }
   RRTX_HIP(ctx, ctx->ws_bkt.ensure((size_t)p.nq * (size_t)p.bcap * sizeof(BktRec)));
+  if (p.fuse) RRTX_HIP(ctx, ctx->ws_sph_lists.ensure((size_t)p.nq * sizeof(SampleList)));
   RRTX_HIP(ctx, ctx->ws_confirm_args.ensure(sizeof(ConfirmArgs)));
   if (p.use_filter) {
     RRTX_HIP(ctx, ctx->ws_ev_a.ensure((size_t)p.n_slices * (size_t)p.slice_cap * sizeof(int2)));
@@ -1410,6 +1342,7 @@ struct RadiusArgs {
   int *qhist; int2 *cbk;  // bucket histogram and (bucket, rank) per copy; null without culling
   ConfirmArgs ca, *ca_dev;   // (ca.hs: the hit sink)
   PackFused pf; QSlots qs; ExtendDev xd;
+  PackSamples ps;         // the pack launch's sample role (fused route only)
 };
 
 void radius_args(rrtx_ctx *ctx, const RadiusPlan &p, int flip, const ExtendFuse *ext, RadiusArgs &d) {
@@ -1444,6 +1377,8 @@ void radius_args(rrtx_ctx *ctx, const RadiusPlan &p, int flip, const ExtendFuse 
     d.xd.r_bound = (ext->r >= 0.0 && d.xd.m > 0) ? ext->r * (1.0 + 1e-12) : -1.0;
     d.xd.sample_unsafe = ext->sample_unsafe;
     d.pf.sph = d.xd.sph; d.pf.m_sph = d.xd.m;
+    d.xd.lists = ctx->ws_sph_lists.as<SampleList>();
+    d.ps.x = d.xd; d.ps.out = ctx->ws_sph_lists.as<SampleList>();
   }
 }
 
@@ -1590,7 +1525,7 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   for_dim(ctx->dim, [&](auto dc) {        // pack
     launch_nn_pack<decltype(dc)::value>(ctx, q_dev, nq, r_dev_thr_lt, r_dev_thr_lt ? r_dev_thr_lt + nq : nullptr, tlt,
                                         tgt, d.sc, ctx->d_xrange.as<unsigned long long>(), p.g2, p.g3, d.qhist, d.cbk,
-                                        d.pf, d.ca, d.qs);
+                                        d.pf, d.ca, d.qs, d.ps);
   });
   span_end(ctx);
   ctx->scalars_flip = flip;

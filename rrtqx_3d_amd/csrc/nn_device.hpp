@@ -204,6 +204,58 @@ __device__ __forceinline__ int query_bucket(const QGrid &g, double x, double y, 
   return row * g.sx + ((row & 1) ? (g.sx - 1 - cx) : cx);
 }
 
+// The sample role of the pack launch (fused extend() route; out == null: no such workgroups).  The query role is a
+// chain of three memory round trips on a sixteenth of the chip, so the launch carries the per-sample work of
+// extend() beside it: workgroups at or above the query-workgroup count decide explicitPointCheck of every sample and
+// build its short sphere list (sample_pass_group, collide_device.hpp), two groups of kSampleGroup consecutive
+// queries per workgroup, one pair of waves each.  Nothing here depends on the query role or on the tree.
+struct PackSamples {
+  ExtendDev x;
+  SampleList *out;                 // [nq] records by query number (ws_sph_lists)
+};
+constexpr int kPackSampleGroups = 2;         // groups per workgroup of 256 threads
+
+__device__ __forceinline__ void pack_sample_role(const double *__restrict__ q, int nq, int wg, const PackSamples &ps) {
+  __shared__ SampleGroupLds grp[kPackSampleGroups];
+  const ExtendDev &x = ps.x;
+  const int t = threadIdx.x, lane = t & 63;
+  const int gi = __builtin_amdgcn_readfirstlane(t >> 7), gl = t & 127;
+  SampleGroupLds &g = grp[gi];
+  const int s0 = (wg * kPackSampleGroups + gi) * kSampleGroup;
+  const int nsamp = max(0, min(kSampleGroup, nq - s0));
+  // lane cl < nsamp of either wave: sample cl, with the probe arithmetic of the reach step
+  ReachProbe rp;
+  rp.mx = 0.f; rp.my = 0.f; rp.mz = 0.f; rp.h = 0.f;
+  if (lane < nsamp) {
+    const size_t i = (size_t)(s0 + lane);
+    const double cx = q[i * 3 + 0], cy = q[i * 3 + 1], cz = q[i * 3 + 2];
+    const double rb = x.r_bound >= 0.0 ? x.r_bound : 0.0;
+    const double pmax = fmax(fmax(fabs(cx), fabs(cy)), fabs(cz));
+    // slack for the rounding of the foot point and of this distance; NaN / inf sample: everything is a candidate
+    const double base_b = rb + 1e-12 * (pmax + 1.0);
+    const bool usable = (pmax < 1e29) && (cx == cx) && (cy == cy) && (cz == cz) && (base_b < 1e29);
+    rp = reach_probe(x, cx, cy, cz, base_b, usable);
+    if (gl < kSampleGroup) {
+      g.px[lane] = cx; g.py[lane] = cy; g.pz[lane] = cz; g.base[lane] = base_b;
+      g.snl[lane] = 0; g.sbad[lane] = 0;
+    }
+  }
+  __syncthreads();
+  sample_pass_group(x, g, nsamp, gl, rp);
+  __syncthreads();
+  if (gl < nsamp) {
+    const int n = g.snl[gl], bad = g.sbad[gl] ? 1 : 0;
+    int l[kSphListCap];
+#pragma unroll
+    for (int c = 0; c < kSphListCap; ++c) l[c] = c < n ? g.ssl[gl][c] : 0;
+    int4 *dst = reinterpret_cast<int4 *>(ps.out + (s0 + gl));
+    dst[0] = make_int4(n, bad, 0, 0);
+    dst[1] = make_int4(l[0], l[1], l[2], l[3]);
+    dst[2] = make_int4(l[4], l[5], l[6], l[7]);
+    if (x.sample_unsafe) x.sample_unsafe[s0 + gl] = (uint8_t)bad;
+  }
+}
+
 template <int D>
 __global__ void nn_pack_kernel(const double *__restrict__ q, int nq, const double *__restrict__ thr_lt_arr,
                                const double *__restrict__ thr_gt_arr, double thr_lt_s, double thr_gt_s,
@@ -213,7 +265,14 @@ __global__ void nn_pack_kernel(const double *__restrict__ q, int nq, const doubl
                                int2 *__restrict__ meta, Scalars *__restrict__ sc,
                                const unsigned long long *__restrict__ xrange, int g2, int g3,
                                int *__restrict__ qhist, int2 *__restrict__ cb, PackFused pf, ConfirmArgs ca,
-                               QSlots qs) {
+                               QSlots qs, PackSamples ps) {
+  if constexpr (D == 3) {
+    const int n_qwg = (nq + 255) / 256;          // (workgroup-uniform: the whole workgroup takes one role)
+    if ((int)blockIdx.x >= n_qwg) {
+      pack_sample_role(q, nq, (int)blockIdx.x - n_qwg, ps);
+      return;
+    }
+  }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool act = i < nq;
   if (i == 0 && pf.count) {
@@ -344,17 +403,21 @@ __global__ void nn_pack_kernel(const double *__restrict__ q, int nq, const doubl
 }
 
 // The one launch of the pack kernel (a template, so only the translation units that search instantiate it).  The
-// nearest search passes thresholds inf / nan, no grid (xrange and qhist null, g2 = g3 = 1) and empty pf / ca / qs.
+// nearest search passes thresholds inf / nan, no grid (xrange and qhist null, g2 = g3 = 1) and empty pf / ca / qs / ps.
+// ps.out set (3-D only): the workgroups of the sample role follow the query workgroups.
 template <int D>
 inline void launch_nn_pack(rrtx_ctx *ctx, const double *q, int nq, const double *thr_lt_arr, const double *thr_gt_arr,
                            double thr_lt_s, double thr_gt_s, Scalars *sc, const unsigned long long *xrange, int g2,
-                           int g3, int *qhist, int2 *cb, const PackFused &pf, const ConfirmArgs &ca, const QSlots &qs) {
-  hipLaunchKernelGGL(nn_pack_kernel<D>, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, q, nq, thr_lt_arr,
+                           int g3, int *qhist, int2 *cb, const PackFused &pf, const ConfirmArgs &ca, const QSlots &qs,
+                           const PackSamples &ps) {
+  constexpr int kPerWg = kPackSampleGroups * kSampleGroup;
+  const int n_swg = (D == 3 && ps.out) ? (nq + kPerWg - 1) / kPerWg : 0;
+  hipLaunchKernelGGL(nn_pack_kernel<D>, dim3((nq + 255) / 256 + n_swg), dim3(256), 0, ctx->stream, q, nq, thr_lt_arr,
                      thr_gt_arr, thr_lt_s, thr_gt_s, ctx->n_wraps, ctx->wrap_dim[0], ctx->wrap_dim[1], ctx->wrap_dim[2],
                      ctx->wrap_period[0], ctx->wrap_period[1], ctx->wrap_period[2], ctx->origin[0], ctx->origin[1],
                      ctx->origin[2], ctx->origin[3], ctx->ws_slots.as<SlotRec>(),
                      ctx->ws_copies.as<typename QRecT<D>::type>(), ctx->ws_copy_meta.as<int2>(), sc, xrange, g2, g3,
-                     qhist, cb, pf, ca, qs);
+                     qhist, cb, pf, ca, qs, ps);
 }
 
 // ---------------------------------------------------------------- scan ------

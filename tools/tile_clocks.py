@@ -17,8 +17,8 @@ from rrtqx_3d_amd.context import Context  # noqa: E402
 cfg = synth.CONFIGS["C4"]
 pts, Q = synth.nodes(cfg.n_nodes, 3), synth.queries(cfg.batch, 3)
 r = synth.ball_radius(cfg.n_nodes, 3)
-names = ["start", "reach", "list+sample pass", "screen (wave 0)", "fence+barrier", "confirm", "hand-out", "end",
-         "  wave 0 list done", "  wave 1 tail done", "  wave 2 sample done", "  placement scan"]
+names = ["start", "reach", "list barrier", "screen (wave 0)", "fence+barrier", "confirm", "hand-out", "end",
+         "  wave 0 list done", "  wave 1 tail done", "  wave 2 lists fetched", "  placement scan"]
 with Context(3, node_capacity=cfg.n_nodes) as ctx:
     if len(sys.argv) > 1:
         ctx.set_option(_capi.RRTX_OPT_TUNE, int(sys.argv[1]))
