@@ -64,7 +64,9 @@ typedef struct {
   /* (round 3, appended) the steering launches of the Dubins edge paths on their own: ms_dubins above then counts
    * the check kernels (and the stand-alone steer / trajectory calls) */
   double ms_dubins_steer; int64_t launches_dubins_steer;
-  int64_t last_sweep_candidates;  /* mirrored edges the last rrtx_obstacle_sweep_polygon put through explicitEdgeCheck */
+  int64_t last_sweep_candidates;  /* mirrored edges the last rrtx_obstacle_sweep_polygon put through explicitEdgeCheck;
+                                   * after rrtx_obstacle_sweep_polygon_batch: the distinct candidate edges of the call's
+                                   * groups of 64 entries, summed over the groups */
 } rrtx_stats_t;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -350,6 +352,40 @@ int rrtx_obstacle_release_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, 
  * edge_ids: ascending, two-call capacity pattern (RRTX_E_CAPACITY with *needed set). */
 int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius, double delta, double r_min, int mode,
                                 int32_t *edge_ids, int64_t cap, int64_t *needed);
+/* The appearing half for a BURST of polygon obstacles -- the polygons a robot discovers in one main-loop iteration, for
+ * each of which the reference runs addNewObstacle before a single reduceInconsistency: mode 0 of
+ * rrtx_obstacle_sweep_polygon for k list positions in one call (node query R/DRRT.jl:3048-3125, edge loop
+ * R/DRRT.jl:3127-3200).  obstacles[j] is a list position of rrtx_polygons_set.  CSR output: row j is
+ * edge_ids[offsets[j] .. offsets[j+1]) and holds exactly what rrtx_obstacle_sweep_polygon(ctx, obstacles[j], robot_radius,
+ * delta, r_min, 0, ...) returns -- the same ids, ascending; rows come in the order of `obstacles`.  An edge that collides
+ * with several listed obstacles is in each of their rows; an obstacle not in use gives an empty row (R/DRRT.jl:1525); a
+ * position listed twice gives two equal rows.  The edge type is the context's, as in the single call: dim = 3 SimpleEdge
+ * at z = 0, dim = 4 DubinsEdge with r_min; wraps, RRTX_OPT_SPACE_HAS_TIME, RRTX_OPT_DUBINS_TIME_COLUMN and
+ * RRTX_OPT_ROOT_RULE are honoured exactly as the single call honours them.  No row sees another's blocking: every row
+ * sees the mirror as it stood at entry (mode 0 does not read dist at all).
+ *   Arguments and state: 0 <= k <= 65536; k == 0 is RRTX_OK with offsets[0] = 0.  A NULL offsets, k > 0 with NULL
+ *   obstacles, cap < 0 and cap > 0 with NULL edge_ids are RRTX_E_INVALID; a position outside the list is RRTX_E_INVALID
+ *   and nothing runs.  An empty tree is RRTX_E_STATE.
+ *   Per-obstacle refusals: every listed obstacle is validated before anything runs, in the order j = 0 .. k-1, with the
+ *   single call's rules and messages -- a static kind in a space with time (R/DRRT.jl:3067), a moving kind without a
+ *   path and a kind that is not coded are RRTX_E_STATE; the `active` flag is not consulted for these checks (nor does
+ *   the single call consult it); the first obstacle that would be refused fails the whole call.  DIFFERENCE from the
+ *   single call: a dim = 4 context whose list holds a moving kind in use while RRTX_OPT_SPACE_HAS_TIME is off is refused
+ *   up front (RRTX_E_STATE, the message of the Dubins edge checks), whatever the mirror holds; the single call only
+ *   notices once it has a candidate edge to check.
+ *   An empty mirror gives k empty rows (k + 1 zero offsets).
+ *   Two-call capacity pattern: with more than cap ids in all rows together the call returns RRTX_E_CAPACITY with *needed
+ *   set and offsets valid.
+ *   block != 0: after a call that returns RRTX_OK every returned edge is left exactly as rrtx_graph_edges_block over the
+ *   union of the rows leaves it (dist = Inf, marked as touched for the next rrtx_graph_cost_update), on the device: the
+ *   ids make no round trip for it.  A call that does not return RRTX_OK blocks nothing.  Blocking never changes what this
+ *   or a later mode-0 sweep returns: mode 0 does not read dist.
+ *   rrtx_stats_t.last_sweep_candidates: the entries are taken in groups of 64 in the order given; a group's candidates
+ *   are the mirrored edges that start at a node some obstacle of the group is in conflict with, each counted once; the
+ *   field holds their sum over the groups (for k == 1 the single call's number). */
+int rrtx_obstacle_sweep_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, double robot_radius, double delta,
+                                      double r_min, int block, int64_t *offsets /* k + 1 */, int32_t *edge_ids,
+                                      int64_t cap, int64_t *needed);
 /* Cost propagation over the edge mirror: the fixed point that rewire / reduceInconsistency /
  * propogateDescendants (R/DRRT_Q.jl:2490-2541, 2647-2817) drive rrtLMC to when changeThresh = 0 and the queue
  * runs dry -- lmc(root) = 0, lmc(v) = min over mirrored edges v -> u with finite dist of lmc(u) + dist (one

@@ -682,6 +682,43 @@ function obstacleSweep(tree::HipTree, S::TS, ob::Obstacle, remove::Bool = false)
   end
 end
 
+# The appearing half for a burst of POLYGON obstacles -- the ones a robot discovers in one main-loop iteration, each of
+# which the reference hands to addNewObstacle (R/DRRT.jl:3127-3200) before one reduceInconsistency -- in ONE call
+# (rrtx_obstacle_sweep_polygon_batch): one id vector per obstacle, in the order given, each exactly what
+# obstacleSweep(tree, S, ob) returns.  block = true also sets dist = Inf for every returned edge in the device mirror
+# (blockEdges over all of them, without the ids travelling back); the caller still sets edge.dist = Inf on its own edge
+# objects.
+function obstacleSweepBatch(tree::HipTree, S::TS, obs::Vector{Obstacle}, block::Bool = false) where {TS}
+  syncPolygonObstacles(tree, S)
+  k = length(obs)
+  which = fill(Int32(-1), k)                  # list positions (0-based)
+  ptr = S.obstacles.front
+  for i = 1:S.obstacles.length
+    for j = 1:k
+      if ptr.data === obs[j]
+        which[j] = i - 1
+      end
+    end
+    ptr = ptr.child
+  end
+  all(which .>= 0) || error("obstacle is not in CSpace.obstacles")
+  offsets = Vector{Int64}(undef, k + 1)
+  cap = 4096
+  while true
+    ids = Vector{Int32}(undef, cap)
+    needed = Ref{Int64}(0)
+    rc = GC.@preserve which offsets ids ccall((:rrtx_obstacle_sweep_polygon_batch, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Int32}, Cint, Cdouble, Cdouble, Cdouble, Cint, Ptr{Int64}, Ptr{Int32}, Int64, Ref{Int64}),
+        tree.ctx, which, k, S.robotRadius, S.delta, S.minTurningRadius, block ? 1 : 0, offsets, ids, cap, needed)
+    if rc == RRTX_E_CAPACITY
+      cap = Int(needed[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    return [ids[Int(offsets[j]) + 1:Int(offsets[j + 1])] for j = 1:k]
+  end
+end
+
 # edge.dist of registered edges first_id, first_id+1, ... (ids from registerEdges); registerEdges itself
 # gives every edge the SimpleEdge cost of its two nodes.
 function syncEdgeCosts(tree::HipTree, first_id::Int, edges::Vector{TE}) where {TE}

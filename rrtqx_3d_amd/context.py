@@ -710,6 +710,27 @@ class Context:
         n, ids = self._two_call(cap, call)
         return ids[:n]
 
+    def obstacle_sweep_polygon_batch(self, obstacles, robot_radius: float, delta: float, r_min: float = 0.0,
+                                     block: bool = False, cap: Optional[int] = None):
+        """obstacle_sweep_polygon (addNewObstacle's loop, remove=False) for a burst of polygon list positions in one
+        call (rrtx_obstacle_sweep_polygon_batch): returns (offsets, edge_ids), row j =
+        edge_ids[offsets[j]:offsets[j + 1]] being exactly obstacle_sweep_polygon(obstacles[j], robot_radius, delta,
+        r_min); rows in the order given.  block=True also blocks every returned edge in the mirror, on the device (what
+        graph_edges_block over the union of the rows does)."""
+        obs = np.ascontiguousarray(obstacles, dtype=np.int32).reshape(-1)
+        k = obs.shape[0]
+        if cap is None:
+            cap = 4096
+
+        def call(cap, needed):
+            off = np.zeros(k + 1, dtype=np.int64)
+            ids = np.empty(max(cap, 1), dtype=np.int32)
+            return self._lib.rrtx_obstacle_sweep_polygon_batch(self._h, _capi._ptr(obs), k, robot_radius, delta, r_min,
+                                                               1 if block else 0, _capi._ptr(off), _capi._ptr(ids), cap,
+                                                               needed), (off, ids)
+        n, (off, ids) = self._two_call(cap, call)
+        return off, ids[:n]
+
     def dubins_edges_check_obstacle(self, s, g, r_min: float, robot_radius: float, obstacle: int):
         """explicitEdgeCheck(S, edge::DubinsEdge, ob) against polygon `obstacle` alone."""
         s = f64(s, (-1, 4))

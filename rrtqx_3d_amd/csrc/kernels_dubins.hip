@@ -1252,6 +1252,53 @@ __global__ __launch_bounds__(256, TIME ? 2 : 3) void dubins_check_rec_kernel(
   if (valid) hit[base + k] = (uint8_t)((h ? 1 : 0) | bad_move);
 }
 
+// The same check for the candidates of a batched polygon sweep (rrtx_obstacle_sweep_polygon_batch): the lane's edge and
+// steering record are loaded ONCE (the index source's `spread` lane mapping), then every obstacle of the group some
+// lane of the wave has in its word -- word[k] bit b = candidate k starts at a node in conflict with the group's entry
+// b -- is taken in turn, wave-uniformly: a bit no lane has is skipped, for any other the whole wave calls
+// wave_dubins_collides with valid = the lane has the bit, against a table of that ONE obstacle (the packed table
+// shifted to ppos[b], as tab_range shifts it, m = 1): what the single sweep's launch computes for that obstacle.
+// hit_word[k] bit b = the edge collides with it.  No validMove bit: the sweeps do not apply it.
+template <bool TIME, bool RSUM = false>
+__global__ __launch_bounds__(256, TIME ? 2 : 3) void dubins_check_words_kernel(
+    const EdgeSrc src, long long base, long long count, long long n, int spread, double r_min, double robot_radius,
+    const PolyTab tab, const double *__restrict__ rec, const unsigned long long *__restrict__ word,
+    const int32_t *__restrict__ ppos, int kg, unsigned long long *__restrict__ hit_word, const double *__restrict__ ckpt) {
+  __shared__ WaveDubinsT<TIME, RSUM> wd[4];
+  WaveDubinsT<TIME, RSUM> &w = wd[threadIdx.x >> 6];
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long k = t;
+  if (spread) {
+    const long long n_waves = (count + 63) / 64;
+    const long long gw = t >> 6;
+    k = (gw < n_waves) ? (long long)(threadIdx.x & 63) * n_waves + gw : count;
+  }
+  double s[4] = {0, 0, 0, 0}, g[4] = {1, 0, 0, 0};
+  const bool valid = k < count && load_edge(src, base + k, n, s, g);
+  if (__ballot(valid) == 0ull) return;
+  Steer st;
+  load_rec(rec + kRecDoubles * (valid ? k : 0), st);
+  if (!valid) { st.cost = __builtin_inf(); st.word = 6; st.pc[0].len = st.pc[1].len = st.pc[2].len = 0; }
+  const unsigned long long mine = valid ? word[base + k] : 0ull;
+  unsigned long long hits = 0ull;
+  for (int b = 0; b < kg; ++b) {                                 // (uniform: ppos[b] is a scalar load)
+    const bool on = ((mine >> b) & 1ull) != 0ull;
+    if (__ballot(on) == 0ull) continue;
+    const int p = ppos[b];
+    PolyTab one = tab;
+    one.meta = tab.meta + 4 * (size_t)p;
+    one.off = tab.off + p;
+    one.poff = tab.poff + p;
+    one.pbox = tab.pbox + 4 * (size_t)p;
+    one.m = 1;
+    bool h;
+    if constexpr (RSUM) h = wave_dubins_collides<TIME, RSUM>(w, on, st, s, g, r_min, robot_radius, one, ckpt + kCkptMax * (valid ? k : 0));
+    else h = wave_dubins_collides<TIME>(w, on, st, s, g, r_min, robot_radius, one);
+    if (h) hits |= 1ull << b;
+  }
+  if (valid) hit_word[base + k] = hits;
+}
+
 // edge.trajectory (R/DRRT_DubinsEdge_functions.jl:684-701): the polyline of every edge, written at
 // traj_off[i] (row units), rows of (x, y) -- with has_time rows of (x, y, t); traj == null only
 // reports P per edge.
@@ -1351,9 +1398,12 @@ extern "C" int rrtx_debug_dubins_clocks(unsigned long long *out, int reset) {
 
 // steer + check of the edges [0, n) of a source, chunk by chunk
 // cost2 / word2 / hit2 (candidate edges, src.mode == 1 with dir == 0): the reverse edges too, steered in the same launch
+// wc (the batched polygon sweep): the check is dubins_check_words_kernel -- per edge a word of obstacles in, a hit word out
+struct WordsCheck { const unsigned long long *word; const int32_t *ppos; int kg; unsigned long long *hit_word; };
 static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int spread, double r_min, double robot_radius,
                             const PolyTab &tab, bool check, double *cost, uint8_t *word, uint8_t *hit, int32_t *traj_len,
-                            double *cost2 = nullptr, uint8_t *word2 = nullptr, uint8_t *hit2 = nullptr) {
+                            double *cost2 = nullptr, uint8_t *word2 = nullptr, uint8_t *hit2 = nullptr,
+                            const WordsCheck *wc = nullptr) {
   const bool both = hit2 != nullptr;
   const long long chunk = n < kDubChunk ? n : kDubChunk;
   RRTX_HIP(ctx, ctx->ws_dub_rec.ensure(sizeof(double) * kRecDoubles * (size_t)chunk * (both ? 2 : 1)));
@@ -1387,7 +1437,16 @@ static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int 
         span_end(ctx);
       }
       span_begin(ctx, KF_DUBINS);
-      if (rsum)
+      if (wc && rsum)
+        hipLaunchKernelGGL((dubins_check_words_kernel<true, true>), grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
+                           robot_radius, tab, rc_, wc->word, wc->ppos, wc->kg, wc->hit_word, ckpt);
+      else if (wc && has_time)
+        hipLaunchKernelGGL(dubins_check_words_kernel<true>, grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
+                           robot_radius, tab, rc_, wc->word, wc->ppos, wc->kg, wc->hit_word, ckpt);
+      else if (wc)
+        hipLaunchKernelGGL(dubins_check_words_kernel<false>, grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
+                           robot_radius, tab, rc_, wc->word, wc->ppos, wc->kg, wc->hit_word, ckpt);
+      else if (rsum)
         hipLaunchKernelGGL((dubins_check_rec_kernel<true, true>), grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
                            robot_radius, ctx->dubins_vmin, ctx->dubins_vmax, tab, rc_, h, ckpt);
       else if (has_time)
@@ -1500,6 +1559,27 @@ int launch_dubins_edges_idx(rrtx_ctx *ctx, const int32_t *ids_dev, int64_t n, do
   src.n_nodes = (int)ctx->n_nodes;
   RRTX_HIP(ctx, hipMemsetAsync(hit_dev, 0, (size_t)n, ctx->stream));     // (an id that points nowhere is not written)
   return run_dubins_edges(ctx, src, (long long)n, 1, r_min, robot_radius, tab, true, nullptr, nullptr, hit_dev, nullptr);
+}
+
+int dubins_check_space(rrtx_ctx *ctx) { return check_space(ctx); }
+
+// the Dubins check of a group of rrtx_obstacle_sweep_polygon_batch: the candidates are steered once, whatever the number
+// of obstacles in their words (launch_dubins_edges_idx steers them once per obstacle)
+int launch_dubins_check_words(rrtx_ctx *ctx, const int32_t *cand_id, const unsigned long long *cand_word, int64_t n,
+                              double r_min, double robot_radius, const int32_t *ppos_dev, int kg,
+                              unsigned long long *hit_word) {
+  if (n <= 0) return RRTX_OK;
+  if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "Dubins steering needs a dim=4 [x y t theta] context");
+  const PolyTab tab = poly_tab(ctx);          // (the entry point has run sync_polygons and dubins_check_space before its groups)
+  EdgeSrc src = {};
+  src.mode = 2;
+  src.ids = cand_id; src.es = ctx->ge_start; src.ee = ctx->ge_end;
+  src.nx = ctx->nodes[0]; src.ny = ctx->nodes[1]; src.nz = ctx->nodes[2]; src.nw = ctx->nodes[3];
+  src.n_nodes = (int)ctx->n_nodes;
+  RRTX_HIP(ctx, hipMemsetAsync(hit_word, 0, sizeof(unsigned long long) * (size_t)n, ctx->stream));   // (an id that points nowhere is not written)
+  const WordsCheck wc = {cand_word, ppos_dev, kg, hit_word};
+  return run_dubins_edges(ctx, src, (long long)n, 1, r_min, robot_radius, tab, true, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, &wc);
 }
 
 int launch_dubins_edges_check(rrtx_ctx *ctx, const double *s_dev, const double *g_dev, int64_t ne, double r_min,

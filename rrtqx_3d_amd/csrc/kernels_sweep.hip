@@ -284,6 +284,127 @@ __global__ __launch_bounds__(kSweepBlock) void release_edges_words_kernel(
   block_list_write(hits, e, kg, nb, wcnt, lw, seg_id, seg_word, blk_n, cnt);
 }
 
+// ---- the batched polygon sweep (rrtx_obstacle_sweep_polygon_batch): up to 64 list entries a pass, mode 0 ----
+// word[i] bit b = some query of entry b of the group finds node i (sweep_mark_multi_kernel's test, query by query; the
+// queries of an obstacle that is not in use are not in the table, so its bit is never set)
+__global__ void sweep_mark_query_words_kernel(const double *__restrict__ nx, const double *__restrict__ ny,
+                                              const double *__restrict__ nz, const double *__restrict__ nw, int n, int dim,
+                                              const SweepQueryOwned *__restrict__ qs, int nqs,
+                                              unsigned long long *__restrict__ word) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x = nx[i], y = ny[i], z = nz[i], w = (dim == 4) ? nw[i] : 0.0;
+  unsigned long long in = 0ull;
+  for (int k = 0; k < nqs; ++k) {
+    const SweepQuery q = qs[k].q;                                // (uniform: scalar loads)
+    const unsigned long long owner = qs[k].owner;
+    const double s = (dim == 4) ? sq4(q.x, q.y, q.z, q.w, x, y, z, w) : sq3(q.x, q.y, q.z, x, y, z);
+    if ((s < q.thr_lt) || (i == 0 && s < q.thr_root)) in |= owner;
+  }
+  word[i] = in;
+}
+
+// the word of mirrored edge e's start node (0: past the end of the mirror, or a start index that points nowhere)
+__device__ __forceinline__ unsigned long long edge_start_word(const int32_t *__restrict__ e_start, long long e, long long ne,
+                                                              int n_nodes, const unsigned long long *__restrict__ word) {
+  if (e >= ne) return 0ull;
+  const int a = e_start[e];
+  return (unsigned)a < (unsigned)n_nodes ? word[a] : 0ull;
+}
+
+// The candidates of a group, two launches around the scan of the blocks' counts: an edge whose start node has a word
+// is a candidate; they leave as (id, word), ascending.
+__global__ __launch_bounds__(kSweepBlock) void sweep_cand_count_kernel(const int32_t *__restrict__ e_start, long long ne,
+                                                                       int n_nodes, const unsigned long long *__restrict__ word,
+                                                                       int *__restrict__ block_count) {
+  __shared__ int wcnt[kSweepBlock / 64];
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  block_votes<kSweepBlock>(edge_start_word(e_start, e, ne, n_nodes, word) != 0ull, wcnt);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = block_votes_total<kSweepBlock>(wcnt);
+}
+__global__ __launch_bounds__(kSweepBlock) void sweep_cand_write_kernel(const int32_t *__restrict__ e_start, long long ne,
+                                                                       int n_nodes, const unsigned long long *__restrict__ word,
+                                                                       const long long *__restrict__ block_start,
+                                                                       int32_t *__restrict__ cand_id,
+                                                                       unsigned long long *__restrict__ cand_word) {
+  __shared__ int wcnt[kSweepBlock / 64];
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long w = edge_start_word(e_start, e, ne, n_nodes, word);
+  const unsigned long long m = block_votes<kSweepBlock>(w != 0ull, wcnt);
+  if (w == 0ull) return;
+  const long long pos = block_start[blockIdx.x] + block_votes_before(wcnt, threadIdx.x >> 6) + __popcll(m & lanes_below(threadIdx.x & 63));
+  cand_id[pos] = (int32_t)e;                                     // (pos < the scan's total <= ne)
+  cand_word[pos] = w;
+}
+
+// The SimpleEdge check of a group's candidates, one lane per candidate: the edge's two nodes are loaded once ((x, y)
+// and, for obstacles that move, the time in z), then the reference's one-obstacle explicitEdgeCheck2D
+// (R/DRRT.jl:1523-1653) for every set bit of the candidate's word -- the arithmetic edges_polygons_kernel
+// (kernels_collide.hip) runs for one list position: the bounding-circle test, after which a ball (kind 1) is a hit and
+// a polygon (kind 3) is one when a side comes within robotRadius; kinds 6 / 7 by edge_hits_moving.  ppos[b] = the packed
+// table position of the group's entry b.  The node lists of these sweeps are short, so the lanes stay on their own.
+__global__ __launch_bounds__(256) void sweep_polygon_words_kernel(
+    const int32_t *__restrict__ cand_id, const unsigned long long *__restrict__ cand_word, long long n_c,
+    const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end, int n_nodes, const double *__restrict__ naos,
+    const double *__restrict__ meta, const int32_t *__restrict__ off, const double *__restrict__ vxy,
+    const int32_t *__restrict__ path_off, const double *__restrict__ path, const int32_t *__restrict__ ppos,
+    double robot_radius, unsigned long long *__restrict__ hit_word) {
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_c) return;
+  const int id = cand_id[c];
+  const int a = e_start[id], b = e_end[id];
+  unsigned long long hits = 0ull;
+  if ((unsigned)a < (unsigned)n_nodes && (unsigned)b < (unsigned)n_nodes) {
+    const double4 p0 = reinterpret_cast<const double4 *>(naos)[a];
+    const double4 p1 = reinterpret_cast<const double4 *>(naos)[b];
+    const double rr2 = robot_radius * robot_radius;
+    unsigned long long w = cand_word[c];
+    while (w != 0ull) {
+      const int bit = __ffsll((long long)w) - 1;
+      w &= w - 1ull;
+      const int j = ppos[bit];
+      const double cx = meta[4 * j + 0], cy = meta[4 * j + 1], rad = meta[4 * j + 2];
+      const int kind = (int)meta[4 * j + 3];
+      bool h = false;
+      if (kind == 6 || kind == 7) {
+        h = edge_hits_moving(p0.x, p0.y, p0.z, p1.x, p1.y, p1.z, robot_radius, cx, cy, rad, path + 3 * (size_t)path_off[j],
+                             path_off[j + 1] - path_off[j]);
+      } else {
+        const double dsq = dist_sqrd_point_to_segment(cx, cy, p0.x, p0.y, p1.x, p1.y);
+        const double rr = robot_radius + rad;
+        if (!(dsq > rr * rr)) {
+          if (kind == 1) h = true;
+          else if (kind == 3) {
+            const int vb = off[j], ve = off[j + 1];
+            if (ve - vb >= 2) {                                  // (:1551: fewer than two vertices never collide)
+              double Ax = vxy[2 * (ve - 1)], Ay = vxy[2 * (ve - 1) + 1];
+              for (int v = vb; v < ve && !h; ++v) {
+                const double Bx = vxy[2 * v], By = vxy[2 * v + 1];
+                h = segment_dist_sqrd(p0.x, p0.y, p1.x, p1.y, Ax, Ay, Bx, By) < rr2;
+                Ax = Bx; Ay = By;
+              }
+            }
+          }
+        }
+      }
+      if (h) hits |= 1ull << bit;
+    }
+  }
+  hit_word[c] = hits;
+}
+
+// The tail over a group's candidates: candidate c hands (cand_id[c], its hit word) to block_list_write, which stores
+// the id it is given -- here the edge id, not the position.  nb: blocks of this launch.
+__global__ __launch_bounds__(kSweepBlock) void sweep_cand_rows_kernel(
+    const int32_t *__restrict__ cand_id, const unsigned long long *__restrict__ hit_word, long long n_c, int kg, int nb,
+    int32_t *__restrict__ seg_id, unsigned long long *__restrict__ seg_word, int *__restrict__ blk_n, int *__restrict__ cnt) {
+  __shared__ int wcnt[kSweepBlock / 64];
+  __shared__ unsigned long long lw[kSweepBlock];
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = c < n_c;
+  block_list_write(in ? hit_word[c] : 0ull, in ? (long long)cand_id[c] : 0ll, kg, nb, wcnt, lw, seg_id, seg_word, blk_n, cnt);
+}
+
 }  // namespace
 
 // device side of rrtx_obstacle_sweep; needed_dev[0] = colliding edges, needed_dev[1] = block count scratch
@@ -366,6 +487,99 @@ int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, in
   }
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
+  *total_dev = base + ng;
+  return RRTX_OK;
+}
+
+// device side of rrtx_obstacle_sweep_polygon_batch: groups of kSweepGroup list entries in the order given.  Per group:
+// the word of every node from the group's queries, the candidates (edges that start at a node with a word) compacted
+// to (id, word), ONE read of their number, the check of every candidate against the obstacles of its word (Dubins
+// space: one steering pass, kernels_dubins.hip), and the sphere burst's tail over the candidates' hit words -- the rows
+// follow those of the group before (ws_swb_base).  No group writes the mirror.
+int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius, int32_t *out_dev, int64_t cap,
+                         long long **total_dev) {
+  const int n = (int)ctx->n_nodes;
+  const long long ne = ctx->ge_n;
+  const int nb = (int)((ne + kSweepBlock - 1) / kSweepBlock);
+  const int ng = (k + kSweepGroup - 1) / kSweepGroup;
+  const int kg_max = std::min(k, kSweepGroup);
+  const size_t nq_all = ctx->pswb_q_host.size();
+  if ((int)ctx->pswb_qoff_host.size() != ng + 1 || (size_t)ctx->pswb_qoff_host[ng] != nq_all || ctx->pswb_pos_host.size() != (size_t)k)
+    return fail(ctx, RRTX_E_STATE, "obstacle_sweep_polygon_batch: query tables of %zu groups for %d entries", ctx->pswb_qoff_host.size(), k);
+  RRTX_HIP(ctx, ctx->ws_pswb_q.ensure(sizeof(SweepQueryOwned) * (nq_all > 0 ? nq_all : 1)));
+  RRTX_HIP(ctx, ctx->ws_pswb_pos.ensure(sizeof(int32_t) * (size_t)k));
+  RRTX_HIP(ctx, ctx->ws_pswb_cand_id.ensure(sizeof(int32_t) * (size_t)ne));
+  RRTX_HIP(ctx, ctx->ws_pswb_cand_word.ensure(sizeof(unsigned long long) * (size_t)ne));
+  RRTX_HIP(ctx, ctx->ws_pswb_hit.ensure(sizeof(unsigned long long) * (size_t)ne));
+  RRTX_HIP(ctx, ctx->ws_sweep_cnt.ensure(sizeof(int) * (size_t)(nb + 1)));
+  RRTX_HIP(ctx, ctx->ws_sweep_start.ensure(sizeof(long long) * (size_t)(nb + 2)));
+  RRTX_HIP(ctx, ctx->ws_swb_word.ensure(sizeof(unsigned long long) * (size_t)n));
+  RRTX_HIP(ctx, ctx->ws_swb_seg_id.ensure(sizeof(int32_t) * (size_t)nb * kSweepBlock));
+  RRTX_HIP(ctx, ctx->ws_swb_seg_word.ensure(sizeof(unsigned long long) * (size_t)nb * kSweepBlock));
+  RRTX_HIP(ctx, ctx->ws_swb_blk_n.ensure(sizeof(int) * (size_t)nb));
+  RRTX_HIP(ctx, ctx->ws_swb_cnt.ensure(sizeof(int) * ((size_t)kg_max * nb + 1)));
+  RRTX_HIP(ctx, ctx->ws_swb_pos.ensure(sizeof(long long) * ((size_t)kg_max * nb + 2)));
+  RRTX_HIP(ctx, ctx->ws_swb_base.ensure(sizeof(long long) * (size_t)(ng + 1)));
+  RRTX_HIP(ctx, ctx->ws_swb_off.ensure(sizeof(int64_t) * (size_t)(k + 1)));
+  hipStream_t st = ctx->stream;
+  if (nq_all > 0)
+    RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_pswb_q.p, ctx->pswb_q_host.data(), sizeof(SweepQueryOwned) * nq_all, hipMemcpyHostToDevice, st));
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_pswb_pos.p, ctx->pswb_pos_host.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, st));
+  RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_swb_base.p, 0, sizeof(long long), st));
+  unsigned long long *word = ctx->ws_swb_word.as<unsigned long long>(), *seg_word = ctx->ws_swb_seg_word.as<unsigned long long>();
+  unsigned long long *cand_word = ctx->ws_pswb_cand_word.as<unsigned long long>(), *hit_word = ctx->ws_pswb_hit.as<unsigned long long>();
+  int32_t *seg_id = ctx->ws_swb_seg_id.as<int32_t>(), *cand_id = ctx->ws_pswb_cand_id.as<int32_t>();
+  int *blk_n = ctx->ws_swb_blk_n.as<int>(), *cnt = ctx->ws_swb_cnt.as<int>();
+  long long *pos = ctx->ws_swb_pos.as<long long>(), *base = ctx->ws_swb_base.as<long long>();
+  long long *cstart = ctx->ws_sweep_start.as<long long>();
+  const bool dubins = ctx->dim == 4;
+  int64_t cand_all = 0;
+  for (int g = 0; g < ng; ++g) {
+    const int kg = std::min(kSweepGroup, k - g * kSweepGroup);
+    const int q0 = ctx->pswb_qoff_host[g], nqs = ctx->pswb_qoff_host[g + 1] - q0;
+    const int32_t *ppos = ctx->ws_pswb_pos.as<int32_t>() + (size_t)g * kSweepGroup;
+    int64_t n_c = 0;
+    if (nqs > 0) {                                               // (no query: no obstacle of the group is in use)
+      span_begin(ctx, KF_EDGES);
+      hipLaunchKernelGGL(sweep_mark_query_words_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
+                         ctx->nodes[2], ctx->nodes[3], n, ctx->dim, ctx->ws_pswb_q.as<SweepQueryOwned>() + q0, nqs, word);
+      hipLaunchKernelGGL(sweep_cand_count_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ne, n, word,
+                         ctx->ws_sweep_cnt.as<int>());
+      launch_excl_scan(st, ctx->ws_sweep_cnt.as<int>(), cstart, nb);
+      hipLaunchKernelGGL(sweep_cand_write_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ne, n, word, cstart, cand_id,
+                         cand_word);
+      span_end(ctx);
+      RRTX_HIP(ctx, hipGetLastError());
+      RRTX_HIP(ctx, hipMemcpyAsync(&n_c, cstart + nb, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      RRTX_HIP(ctx, hipStreamSynchronize(st));                   // the group's one wait: the count sizes the check launch
+      if (n_c < 0 || n_c > ne) return fail(ctx, RRTX_E_DEVICE, "obstacle_sweep_polygon_batch: %lld candidates of %lld edges", (long long)n_c, ne);
+    }
+    cand_all += n_c;
+    if (n_c > 0) {
+      if (dubins) {
+        const int rc = launch_dubins_check_words(ctx, cand_id, cand_word, n_c, r_min, robot_radius, ppos, kg, hit_word);
+        if (rc) return rc;
+      } else {
+        span_begin(ctx, KF_EDGES);
+        hipLaunchKernelGGL(sweep_polygon_words_kernel, dim3((unsigned)((n_c + 255) / 256)), dim3(256), 0, st, cand_id, cand_word,
+                           (long long)n_c, ctx->ge_start, ctx->ge_end, n, ctx->nodes_aos, ctx->d_poly_meta.as<double>(),
+                           ctx->d_poly_off.as<int32_t>(), ctx->d_poly_vxy.as<double>(), ctx->d_poly_path_off.as<int32_t>(),
+                           ctx->d_poly_path.as<double>(), ppos, robot_radius, hit_word);
+        span_end(ctx);
+      }
+    }
+    // (a group without candidates still writes its kg empty rows: one block over no candidate)
+    const int nbc = n_c > 0 ? (int)((n_c + kSweepBlock - 1) / kSweepBlock) : 1;
+    span_begin(ctx, KF_EDGES);
+    hipLaunchKernelGGL(sweep_cand_rows_kernel, dim3(nbc), dim3(kSweepBlock), 0, st, cand_id, hit_word, (long long)n_c, kg, nbc,
+                       seg_id, seg_word, blk_n, cnt);
+    launch_excl_scan(st, cnt, pos, kg * nbc);
+    hipLaunchKernelGGL(sweep_rows_write_kernel, dim3(nbc), dim3(kSweepGroup), 0, st, seg_id, seg_word, blk_n, pos, nbc, kg, base + g,
+                       base + g + 1, ctx->ws_swb_off.as<int64_t>() + (size_t)g * kSweepGroup, out_dev, (long long)cap);
+    span_end(ctx);
+    RRTX_HIP(ctx, hipGetLastError());
+  }
+  ctx->last_sweep_candidates = cand_all;
   *total_dev = base + ng;
   return RRTX_OK;
 }

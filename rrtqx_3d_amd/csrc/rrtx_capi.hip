@@ -595,7 +595,8 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_ev_a, &ctx->ws_ev_cnt, &ctx->ws_confirm_args, &ctx->ws_sph_lists, &ctx->ws_poly_lists, &ctx->d_sph_sample,
                     &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
                     &ctx->ws_swb_tab, &ctx->ws_swb_word, &ctx->ws_swb_seg_id, &ctx->ws_swb_seg_word, &ctx->ws_swb_blk_n, &ctx->ws_swb_cnt,
-                    &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off, &ctx->ws_rel_stay,
+                    &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off, &ctx->ws_rel_stay, &ctx->ws_pswb_q, &ctx->ws_pswb_pos,
+                    &ctx->ws_pswb_cand_id, &ctx->ws_pswb_cand_word, &ctx->ws_pswb_hit,
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
                     &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
                     &ctx->gc.in_pos, &ctx->gc.rep_lmc, &ctx->gc.rep_parent, &ctx->gc.delta_cnt, &ctx->gc.delta_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
@@ -1290,19 +1291,15 @@ SweepObs sweep_obs(const double *c, double robot_radius, double range, bool acti
 }
 }  // namespace
 
-int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius, double delta, double r_min, int mode,
-                                int32_t *edge_ids, int64_t cap, int64_t *needed) {
-  CHECK_CTX(ctx);
-  const int m = (int)ctx->poly_active.size();
-  if (obstacle < 0 || obstacle >= m) return fail(ctx, RRTX_E_INVALID, "obstacle_sweep_polygon: obstacle %d out of range (%d polygons)", obstacle, m);
-  if (cap < 0 || (cap > 0 && !edge_ids) || (mode != 0 && mode != 1)) return fail(ctx, RRTX_E_INVALID, "obstacle_sweep_polygon: bad arguments");
-  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "obstacle_sweep_polygon on an empty tree");
+namespace {
+// findPointsInConflictWithObstacle(S, KD, ob) for list position `obstacle` (R/DRRT.jl:3048-3125) as range queries,
+// appended to qs: the static query, or one per path segment (kinds 6 / 7), each with its ghosts.  The obstacle's
+// `active` flag is not read.  RRTX_E_STATE for what the reference refuses or has not coded.
+int polygon_sweep_queries(rrtx_ctx *ctx, int obstacle, double robot_radius, double delta, std::vector<SweepQuery> &qs) {
   const bool dubins = ctx->dim == 4, has_time = ctx->opt_space_has_time;
   const int kind = ctx->poly_kind[obstacle];
   const double cx = ctx->poly_cr[3 * (size_t)obstacle], cy = ctx->poly_cr[3 * (size_t)obstacle + 1],
                rad = ctx->poly_cr[3 * (size_t)obstacle + 2];
-  // ---- findPointsInConflictWithObstacle (R/DRRT.jl:3048-3125) ----
-  std::vector<SweepQuery> qs;
   if (kind >= 1 && kind <= 5) {
     if (has_time) return fail(ctx, RRTX_E_STATE, "this type of obstacle not coded for this type of space (a static obstacle in a "
                               "space with time, R/DRRT.jl:3067)");
@@ -1330,12 +1327,27 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
   } else {
     return fail(ctx, RRTX_E_STATE, "this case not coded yet (obstacle kind %d, R/DRRT.jl:3121)", kind);
   }
+  return RRTX_OK;
+}
+}  // namespace
+
+int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius, double delta, double r_min, int mode,
+                                int32_t *edge_ids, int64_t cap, int64_t *needed) {
+  CHECK_CTX(ctx);
+  const int m = (int)ctx->poly_active.size();
+  if (obstacle < 0 || obstacle >= m) return fail(ctx, RRTX_E_INVALID, "obstacle_sweep_polygon: obstacle %d out of range (%d polygons)", obstacle, m);
+  if (cap < 0 || (cap > 0 && !edge_ids) || (mode != 0 && mode != 1)) return fail(ctx, RRTX_E_INVALID, "obstacle_sweep_polygon: bad arguments");
+  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "obstacle_sweep_polygon on an empty tree");
+  const bool dubins = ctx->dim == 4;
+  // ---- findPointsInConflictWithObstacle (R/DRRT.jl:3048-3125) ----
+  std::vector<SweepQuery> qs;
+  int rc = polygon_sweep_queries(ctx, obstacle, robot_radius, delta, qs);
+  if (rc) return rc;
   if (needed) *needed = 0;
   ctx->last_sweep_candidates = 0;
   const long long ne = ctx->ge_n;
   if (ne == 0) return RRTX_OK;
-  int rc = sync_polygons(ctx);
-  if (rc) return rc;
+  if ((rc = sync_polygons(ctx))) return rc;
   // the obstacle in the packed (in-use only) table: an unused obstacle collides with nothing (R/DRRT.jl:1525)
   const std::vector<int32_t> pos = active_positions(ctx->poly_active);
   int pb, pe;
@@ -1388,6 +1400,68 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
   int64_t total = 0;
   if ((rc = sweep_ids_out(ctx, "obstacle_sweep_polygon", "edges", total_dev, edge_ids, cap, needed, &total))) return rc;
   if (total > 0) RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
+}
+
+// rrtx_obstacle_sweep_polygon_batch: mode 0 of rrtx_obstacle_sweep_polygon for a burst of list positions, CSR rows
+int rrtx_obstacle_sweep_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, double robot_radius, double delta,
+                                      double r_min, int block, int64_t *offsets, int32_t *edge_ids, int64_t cap,
+                                      int64_t *needed) {
+  CHECK_CTX(ctx);
+  const char *fn = "obstacle_sweep_polygon_batch";
+  const int m = (int)ctx->poly_active.size();
+  if (k < 0 || k > 65536 || !offsets || (k > 0 && !obstacles) || cap < 0 || (cap > 0 && !edge_ids))
+    return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
+  for (int j = 0; j < k; ++j)
+    if (obstacles[j] < 0 || obstacles[j] >= m)
+      return fail(ctx, RRTX_E_INVALID, "%s: obstacle %d (entry %d) out of range (%d polygons)", fn, obstacles[j], j, m);
+  if (needed) *needed = 0;
+  if (k == 0) { offsets[0] = 0; return RRTX_OK; }
+  if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "%s on an empty tree", fn);
+  // every entry's queries first, in order: the first obstacle the single call would refuse fails the whole call before
+  // anything runs.  Group g = entries [64 g, 64 g + 64), bit b of its words = entry 64 g + b.
+  const int ng = (k + 63) / 64;
+  std::vector<SweepQuery> qs;
+  std::vector<int> qn((size_t)k);
+  int rc;
+  for (int j = 0; j < k; ++j) {
+    const size_t before = qs.size();
+    if ((rc = polygon_sweep_queries(ctx, obstacles[j], robot_radius, delta, qs))) return rc;
+    qn[(size_t)j] = (int)(qs.size() - before);
+  }
+  if ((rc = sync_polygons(ctx))) return rc;
+  // (the single call meets this only once it has a candidate to check; here it is asked before anything runs)
+  if (ctx->dim == 4 && (rc = dubins_check_space(ctx))) return rc;
+  ctx->last_sweep_candidates = 0;
+  if (ctx->ge_n == 0) { std::fill(offsets, offsets + k + 1, (int64_t)0); return RRTX_OK; }
+  // an obstacle that is not in use collides with nothing (R/DRRT.jl:1525): its queries stay out of the table
+  const std::vector<int32_t> pos = active_positions(ctx->poly_active);
+  std::vector<int32_t> packed((size_t)m, -1);
+  for (size_t a = 0; a < pos.size(); ++a) packed[(size_t)pos[a]] = (int32_t)a;
+  ctx->pswb_q_host.clear();
+  ctx->pswb_qoff_host.assign((size_t)ng + 1, 0);
+  ctx->pswb_pos_host.resize((size_t)k);
+  size_t at = 0;
+  for (int j = 0; j < k; ++j) {
+    const int32_t p = packed[(size_t)obstacles[j]];
+    ctx->pswb_pos_host[(size_t)j] = p;
+    if (p >= 0)
+      for (int i = 0; i < qn[(size_t)j]; ++i) ctx->pswb_q_host.push_back(SweepQueryOwned{qs[at + (size_t)i], 1ull << (j & 63), 0.0});
+    at += (size_t)qn[(size_t)j];
+    if ((j & 63) == 63 || j == k - 1) ctx->pswb_qoff_host[(size_t)(j >> 6) + 1] = (int)ctx->pswb_q_host.size();
+  }
+  const int64_t dcap = cap > 0 ? cap : 1;
+  RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)dcap));
+  long long *total_dev = nullptr;
+  if ((rc = launch_polygon_burst(ctx, k, r_min, robot_radius, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev))) return rc;
+  RRTX_HIP(ctx, copy_out(ctx, offsets, ctx->ws_swb_off.p, sizeof(int64_t) * (size_t)(k + 1)));
+  int64_t total = 0;
+  if ((rc = sweep_ids_out(ctx, fn, "colliding edges", total_dev, edge_ids, cap, needed, &total))) return rc;
+  if (total > 0) {
+    // addNewObstacle's dist = Inf for every id of every row, where the rows are
+    if (block && (rc = launch_graph_block_dev(ctx, false, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
   return RRTX_OK;
 }
 

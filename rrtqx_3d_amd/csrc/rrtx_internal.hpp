@@ -50,6 +50,10 @@ struct alignas(64) SweepObs { SphRec ob; double thr_lt, thr_gt; int32_t active, 
 // <=> s < thr_lt, the root: s < thr_root
 struct SweepQuery { double x, y, z, w, thr_lt, thr_root; };
 
+// A range query of the batched polygon sweep (rrtx_obstacle_sweep_polygon_batch) as sweep_mark_query_words_kernel reads
+// it: the query, and the bit of the group's word that stands for the obstacle the query belongs to
+struct alignas(64) SweepQueryOwned { SweepQuery q; unsigned long long owner; double pad; };
+
 // host-side mirror of exact_math.hpp's ChunkExt (this header is also read by plain C++)
 struct ChunkExtHost { unsigned long long xlo, xhi, ylo, yhi; };
 
@@ -254,6 +258,12 @@ struct rrtx_ctx {
   // the batched release: one byte per packed active sphere, 1 = it stays (is not among the call's leaving obstacles)
   rrtx::DevBuf ws_rel_stay;
   std::vector<uint8_t> rel_stay_host;         // what ws_rel_stay is copied from (lives until the call's sync)
+  // the batched polygon sweep: the groups' query tables (group g: pswb_qoff_host[g] .. [g + 1]), the packed table
+  // position of every entry (-1: not in use), the candidates of a group (edge id, word of its start node, hit word)
+  rrtx::DevBuf ws_pswb_q, ws_pswb_pos, ws_pswb_cand_id, ws_pswb_cand_word, ws_pswb_hit;
+  std::vector<rrtx::SweepQueryOwned> pswb_q_host;   // what ws_pswb_q is copied from (lives until the call's sync)
+  std::vector<int32_t> pswb_pos_host;               // what ws_pswb_pos is copied from (likewise)
+  std::vector<int> pswb_qoff_host;
 
   // parent / rewire selection over the extend lists (kernels_select.hip)
   double *node_lmc = nullptr;       // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
@@ -432,6 +442,19 @@ int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, 
 // Sweep: row j = obstacle j's sweep.  release (every obstacle of the table marked in use, ctx->rel_stay_host filled,
 // sync_spheres has run for the call's robot radius): row j = the blocked edges obstacle j hits and no staying sphere does.
 int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, int64_t cap, long long **total_dev);
+
+// device side of rrtx_obstacle_sweep_polygon_batch over ctx->pswb_q_host / pswb_qoff_host / pswb_pos_host (k entries,
+// the mirror is not empty, sync_polygons has run): the same CSR in ws_swb_off / out_dev / *total_dev, row j = entry j's
+// mode-0 sweep.  Synchronises once per group of 64 entries (the candidate count); ctx->last_sweep_candidates = their sum.
+int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius, int32_t *out_dev, int64_t cap,
+                         long long **total_dev);
+// explicitEdgeCheck(S, edge::DubinsEdge, ob) of the n mirrored edges cand_id[c] against the obstacles whose bit is set in
+// cand_word[c] (bit b = packed table position ppos_dev[b], b < kg): bit b of hit_word[c] = edge c collides with it.
+// The caller has run sync_polygons and dubins_check_space.
+int launch_dubins_check_words(rrtx_ctx *ctx, const int32_t *cand_id, const unsigned long long *cand_word, int64_t n,
+                              double r_min, double robot_radius, const int32_t *ppos_dev, int kg,
+                              unsigned long long *hit_word);
+int dubins_check_space(rrtx_ctx *ctx);   // moving obstacles in use need RRTX_OPT_SPACE_HAS_TIME (RRTX_E_STATE)
 
 int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n);
 int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n);

@@ -757,11 +757,26 @@ def obstacleSweepBatch(S: CSpace, KD: HipTree, obs: Sequence[SphereObstacle], bl
     S.bind(KD)
     _sync_obstacles(S)
     if any(isinstance(ob, Obstacle) for ob in obs):
-        error("obstacleSweepBatch takes sphere obstacles; polygons go through obstacleSweep one at a time")
+        error("obstacleSweepBatch takes sphere obstacles; polygons go through obstacleSweepPolygonBatch (or obstacleSweep one at a time)")
     if S.spaceHasTime or S.spaceHasTheta:
         error("this type of obstacle not coded for this type of space")
     off, ids = KD.ctx.obstacle_sweep_batch([_list_position(S, ob) for ob in obs],
                                            [S.robotRadius + S.delta + ob.radius for ob in obs], S.robotRadius, block=block)
+    return [ids[off[j]:off[j + 1]] for j in range(len(obs))]
+
+
+def obstacleSweepPolygonBatch(S: CSpace, KD: HipTree, obs: Sequence[Obstacle], block: bool = False) -> List[np.ndarray]:
+    """obstacleSweep for a burst of Obstacles (polygon list) of S.obstacles -- the polygons a robot discovers in one
+    iteration, each of which the reference hands to addNewObstacle before one reduceInconsistency (R/DRRT.jl:3127-3200)
+    -- in one call: one id array per obstacle, in the order given, each what obstacleSweep(S, KD, ob) returns.  The
+    edge type is the space's, r_min is S.minTurningRadius.  block=True is blockEdges over all of them as well, without
+    the ids travelling back."""
+    S.bind(KD)
+    _sync_obstacles(S)
+    if not all(isinstance(ob, Obstacle) for ob in obs):
+        error("obstacleSweepPolygonBatch takes Obstacles of the polygon list; spheres go through obstacleSweepBatch")
+    off, ids = KD.ctx.obstacle_sweep_polygon_batch([_list_position(S, ob) for ob in obs], S.robotRadius, S.delta,
+                                                   r_min=float(getattr(S, "minTurningRadius", 0.0) or 0.0), block=block)
     return [ids[off[j]:off[j + 1]] for j in range(len(obs))]
 
 
