@@ -66,7 +66,9 @@ typedef struct {
   double ms_dubins_steer; int64_t launches_dubins_steer;
   int64_t last_sweep_candidates;  /* mirrored edges the last rrtx_obstacle_sweep_polygon put through explicitEdgeCheck;
                                    * after rrtx_obstacle_sweep_polygon_batch: the distinct candidate edges of the call's
-                                   * groups of 64 entries, summed over the groups */
+                                   * groups of 64 entries, summed over the groups; after
+                                   * rrtx_obstacle_release_polygon_batch: the same sum over the BLOCKED (dist == Inf)
+                                   * candidate edges only */
 } rrtx_stats_t;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -221,6 +223,12 @@ int rrtx_polygons_set(rrtx_ctx *ctx, const int32_t *vert_off, const double *vxy,
  * edge checks against moving obstacles in a space WITHOUT time (their pieces carry no time stamp; see
  * RRTX_OPT_SPACE_HAS_TIME), fail with RRTX_E_STATE. */
 int rrtx_polygon_paths_set(rrtx_ctx *ctx, const int32_t *path_off, const double *path_xyt, int m);
+/* The in-use flag (!obstacleUnused) of k list positions of rrtx_polygons_set: what removeObstacle clears once its loop
+ * is over (R/DRRT.jl:3287) and what the discovery of an obstacle sets before its sweep.  active[j] != 0 = obstacles[j] is
+ * in use.  Vertices, kinds, centres, radii and paths are kept; everything rrtx_polygons_set derives from the flags (the
+ * packed device tables) is derived again at the next call that needs it.  A position outside the list is
+ * RRTX_E_INVALID and nothing changes; for a position given twice the last value wins; k == 0 is RRTX_OK. */
+int rrtx_polygons_set_active(rrtx_ctx *ctx, const int32_t *obstacles, int k, const uint8_t *active /* k */);
 /* obstacleAugmentation / expiry (R/obstacleAugmentation.jl:106-114,
  * R/DRRT_Q.jl:3301): change radius and/or active flag of sphere `which`. */
 int rrtx_obstacle_update(rrtx_ctx *ctx, int which, double radius, uint8_t active);
@@ -386,6 +394,50 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
 int rrtx_obstacle_sweep_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, double robot_radius, double delta,
                                       double r_min, int block, int64_t *offsets /* k + 1 */, int32_t *edge_ids,
                                       int64_t cap, int64_t *needed);
+/* The leaving half for a BURST of polygon obstacles -- the time-limited polygons that expire in one main-loop iteration
+ * (BASELINE config 5), for each of which the reference runs removeObstacle before a single reduceInconsistency: the edge
+ * loops of those calls (node query R/DRRT.jl:3048-3125, edge loop R/DRRT.jl:3202-3290) in one call, the members of the
+ * burst taken as gone together.  The call says which obstacles leave, the list's flags say which stay: with L the set of
+ * list positions in `obstacles`, polygon i STAYS when it is in use (active[i] as last given to rrtx_polygons_set /
+ * rrtx_polygons_set_active) and i is not in L.  CSR output as in rrtx_obstacle_sweep_polygon_batch: row j,
+ * edge_ids[offsets[j] .. offsets[j+1]), holds in ascending order the mirrored edges e for which all of
+ *   1. dist[e] == +Inf in the mirror when the call starts (the edge is blocked);
+ *   2. e starts at a node of findPointsInConflictWithObstacle for obstacles[j] -- queries, ghosts, root rule and
+ *      thresholds exactly those of rrtx_obstacle_sweep_polygon;
+ *   3. explicitEdgeCheck(S, e, obstacles[j]) is true.  The edge type is the context's: dim = 3 SimpleEdge at z = 0,
+ *      dim = 4 DubinsEdge with r_min; wraps, RRTX_OPT_SPACE_HAS_TIME, RRTX_OPT_DUBINS_TIME_COLUMN and RRTX_OPT_ROOT_RULE
+ *      are honoured exactly as the single call honours them;
+ *   4. explicitEdgeCheck(S, e, i) is true for no polygon i that stays
+ * hold.  THE FLAG OF obstacles[j] ITSELF IS READ (this differs from rrtx_obstacle_release_batch): the polygon reference
+ * keeps the obstacle in use until its loop is over (R/DRRT.jl:3287), so a listed obstacle that is not in use gives an
+ * empty row -- and does not stay.  Clear the flags afterwards with rrtx_polygons_set_active.  An edge is in the row of
+ * every leaving obstacle it satisfies 1-3 for; test 4 is the same for every row; every row sees the mirror as it stood
+ * at entry; a position listed twice gives two equal rows.  Equivalently: row j is what rrtx_obstacle_sweep_polygon(ctx',
+ * obstacles[j], robot_radius, delta, r_min, 1, ...) returns on a context ctx' whose OTHER members of L are not in use.
+ * The time-window condition of the reference (startTime <= timeElapsed <= startTime + lifeSpan of the others) is folded
+ * into the flags by the caller, as for mode 1 of the single call.
+ *   Relation to the reference's sequence (remove A, unblock, mark A unused, remove B, ...): while A is removed B still
+ *   counts as in use, so an edge blocked by both is freed at B's turn -- provided its start node is in B's node list.
+ *   The union of the sequence's rows is therefore always a SUBSET of the union of this call's rows, and the two are
+ *   EQUAL when no mirrored edge is longer than delta, which is the planner's invariant (an edge no longer than delta
+ *   that collides with B starts within robotRadius + delta + B.radius of B's centre).
+ *   Arguments and state, exactly as in rrtx_obstacle_sweep_polygon_batch: 0 <= k <= 65536; k == 0 is RRTX_OK with
+ *   offsets[0] = 0.  A NULL offsets, k > 0 with NULL obstacles, cap < 0 and cap > 0 with NULL edge_ids are
+ *   RRTX_E_INVALID; a position outside the list is RRTX_E_INVALID and nothing runs.  An empty tree is RRTX_E_STATE.
+ *   Every listed obstacle is validated before anything runs, in the order j = 0 .. k-1, with the single call's rules and
+ *   messages (RRTX_E_STATE); a dim = 4 context whose list holds a moving kind in use while RRTX_OPT_SPACE_HAS_TIME is off
+ *   is refused up front (RRTX_E_STATE).  An empty mirror gives k empty rows (k + 1 zero offsets).
+ *   Two-call capacity pattern: with more than cap ids in all rows together the call returns RRTX_E_CAPACITY with *needed
+ *   set and offsets valid.
+ *   unblock != 0: after a call that returns RRTX_OK every returned edge is left, on the device, exactly as
+ *   rrtx_graph_edges_unblock over the union of the rows leaves it (dist = distOriginal, marked as touched for the next
+ *   rrtx_graph_cost_update); the ids make no round trip for it.  A call that does not return RRTX_OK unblocks nothing.
+ *   rrtx_stats_t.last_sweep_candidates: the entries are taken in groups of 64 in the order given; a group's candidates
+ *   are the BLOCKED mirrored edges that start at a node some in-use obstacle of the group is in conflict with, each
+ *   counted once; the field holds their sum over the groups. */
+int rrtx_obstacle_release_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, double robot_radius, double delta,
+                                        double r_min, int unblock, int64_t *offsets /* k + 1 */, int32_t *edge_ids,
+                                        int64_t cap, int64_t *needed);
 /* Cost propagation over the edge mirror: the fixed point that rewire / reduceInconsistency /
  * propogateDescendants (R/DRRT_Q.jl:2490-2541, 2647-2817) drive rrtLMC to when changeThresh = 0 and the queue
  * runs dry -- lmc(root) = 0, lmc(v) = min over mirrored edges v -> u with finite dist of lmc(u) + dist (one

@@ -719,6 +719,69 @@ function obstacleSweepBatch(tree::HipTree, S::TS, obs::Vector{Obstacle}, block::
   end
 end
 
+# The leaving half for a burst of POLYGON obstacles -- the time-limited ones that expire in one main-loop iteration, each
+# of which the reference hands to removeObstacle (R/DRRT.jl:3202-3290) before one reduceInconsistency -- in ONE call
+# (rrtx_obstacle_release_polygon_batch), the burst taken as gone together: one id vector per obstacle, in the order
+# given -- the registered edges that are blocked, start at a node in conflict with ob, collide with it and with no
+# obstacle that is in use and not in obs; what obstacleSweep(tree, S, ob, true) returns with the others of obs marked
+# unused.  ob itself must still be in use (the reference marks it unused after its loop, :3287): call setObstaclesUsed!
+# afterwards.  unblock = true also sets dist = distOriginal for every returned edge in the device mirror (unblockEdges
+# over all of them, without the ids travelling back); the caller still resets edge.dist on its own edge objects.
+function obstacleReleaseBatch(tree::HipTree, S::TS, obs::Vector{Obstacle}, unblock::Bool = false) where {TS}
+  syncPolygonObstacles(tree, S)
+  k = length(obs)
+  which = fill(Int32(-1), k)                  # list positions (0-based)
+  ptr = S.obstacles.front
+  for i = 1:S.obstacles.length
+    for j = 1:k
+      if ptr.data === obs[j]
+        which[j] = i - 1
+      end
+    end
+    ptr = ptr.child
+  end
+  all(which .>= 0) || error("obstacle is not in CSpace.obstacles")
+  offsets = Vector{Int64}(undef, k + 1)
+  cap = 4096
+  while true
+    ids = Vector{Int32}(undef, cap)
+    needed = Ref{Int64}(0)
+    rc = GC.@preserve which offsets ids ccall((:rrtx_obstacle_release_polygon_batch, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Int32}, Cint, Cdouble, Cdouble, Cdouble, Cint, Ptr{Int64}, Ptr{Int32}, Int64, Ref{Int64}),
+        tree.ctx, which, k, S.robotRadius, S.delta, S.minTurningRadius, unblock ? 1 : 0, offsets, ids, cap, needed)
+    if rc == RRTX_E_CAPACITY
+      cap = Int(needed[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    return [ids[Int(offsets[j]) + 1:Int(offsets[j + 1])] for j = 1:k]
+  end
+end
+
+# obstacleUnused = !used on the obstacles obs and, without sending the list again, on their places in the device list
+# (rrtx_polygons_set_active): what removeObstacle does once its loop is over (R/DRRT.jl:3287), and what the discovery
+# of an obstacle does before its sweep.  The list on the device must be the one of S (syncPolygonObstacles).
+function setObstaclesUsed!(tree::HipTree, S::TS, obs::Vector{Obstacle}, used::Bool) where {TS}
+  k = length(obs)
+  which = fill(Int32(-1), k)                  # list positions (0-based)
+  ptr = S.obstacles.front
+  for i = 1:S.obstacles.length
+    for j = 1:k
+      if ptr.data === obs[j]
+        which[j] = i - 1
+      end
+    end
+    ptr = ptr.child
+  end
+  all(which .>= 0) || error("obstacle is not in CSpace.obstacles")
+  for ob in obs
+    ob.obstacleUnused = !used
+  end
+  active = fill(UInt8(used ? 1 : 0), k)
+  GC.@preserve which active rrtx_check(tree, ccall((:rrtx_polygons_set_active, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{UInt8}), tree.ctx, which, k, active))
+end
+
 # edge.dist of registered edges first_id, first_id+1, ... (ids from registerEdges); registerEdges itself
 # gives every edge the SimpleEdge cost of its two nodes.
 function syncEdgeCosts(tree::HipTree, first_id::Int, edges::Vector{TE}) where {TE}

@@ -102,6 +102,7 @@ SYMBOLS = [
     ("rrtx_spheres_set", C.c_int, [_VP, _VP, _VP, C.c_int]),
     ("rrtx_polygons_set", C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int]),
     ("rrtx_polygon_paths_set", C.c_int, [_VP, _VP, _VP, C.c_int]),
+    ("rrtx_polygons_set_active", C.c_int, [_VP, _VP, C.c_int, _VP]),
     ("rrtx_obstacle_update", C.c_int, [_VP, C.c_int, C.c_double, C.c_uint8]),
     ("rrtx_nn_nearest", C.c_int, [_VP, _VP, C.c_int, _VP, _VP]),
     ("rrtx_nn_knearest", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
@@ -133,6 +134,8 @@ SYMBOLS = [
     ("rrtx_obstacle_sweep_polygon", C.c_int, [_VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _VP, C.c_int64, c_int64_p]),
     ("rrtx_obstacle_sweep_polygon_batch", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _VP, _VP, C.c_int64,
                                                     c_int64_p]),
+    ("rrtx_obstacle_release_polygon_batch", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _VP, _VP,
+                                                      C.c_int64, c_int64_p]),
     ("rrtx_dubins_edges_check_obstacle", C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_double, C.c_double, C.c_int, _VP]),
     ("rrtx_extend_candidates", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP,
                                          C.c_int64, c_int64_p, _VP, _VP, _VP]),

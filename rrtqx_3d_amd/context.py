@@ -717,6 +717,20 @@ class Context:
         edge_ids[offsets[j]:offsets[j + 1]] being exactly obstacle_sweep_polygon(obstacles[j], robot_radius, delta,
         r_min); rows in the order given.  block=True also blocks every returned edge in the mirror, on the device (what
         graph_edges_block over the union of the rows does)."""
+        return self._polygon_burst(self._lib.rrtx_obstacle_sweep_polygon_batch, obstacles, robot_radius, delta, r_min, block, cap)
+
+    def obstacle_release_polygon_batch(self, obstacles, robot_radius: float, delta: float, r_min: float = 0.0,
+                                       unblock: bool = False, cap: Optional[int] = None):
+        """The edge loops of a burst of removeObstacle calls for the polygon list in one call
+        (rrtx_obstacle_release_polygon_batch): returns (offsets, edge_ids), row j = the blocked edges that start at a
+        node in conflict with polygon obstacles[j], collide with it (it must be in use: its flag is read) and with no
+        polygon that is in use and not among `obstacles` -- obstacle_sweep_polygon(obstacles[j], ..., remove=True) with
+        the other listed positions switched off; rows in the order given.  unblock=True also gives every returned edge
+        its original cost back in the mirror, on the device (what graph_edges_unblock over the union of the rows does).
+        Clear the flags afterwards with polygons_set_active."""
+        return self._polygon_burst(self._lib.rrtx_obstacle_release_polygon_batch, obstacles, robot_radius, delta, r_min, unblock, cap)
+
+    def _polygon_burst(self, fn, obstacles, robot_radius, delta, r_min, apply, cap):
         obs = np.ascontiguousarray(obstacles, dtype=np.int32).reshape(-1)
         k = obs.shape[0]
         if cap is None:
@@ -725,11 +739,18 @@ class Context:
         def call(cap, needed):
             off = np.zeros(k + 1, dtype=np.int64)
             ids = np.empty(max(cap, 1), dtype=np.int32)
-            return self._lib.rrtx_obstacle_sweep_polygon_batch(self._h, _capi._ptr(obs), k, robot_radius, delta, r_min,
-                                                               1 if block else 0, _capi._ptr(off), _capi._ptr(ids), cap,
-                                                               needed), (off, ids)
+            return fn(self._h, _capi._ptr(obs), k, robot_radius, delta, r_min, 1 if apply else 0, _capi._ptr(off),
+                      _capi._ptr(ids), cap, needed), (off, ids)
         n, (off, ids) = self._two_call(cap, call)
         return off, ids[:n]
+
+    def polygons_set_active(self, obstacles, active):
+        """The in-use flag of polygon list positions (rrtx_polygons_set_active): shapes and paths stay.  active: one
+        value per position (a scalar serves all)."""
+        obs = np.ascontiguousarray(obstacles, dtype=np.int32).reshape(-1)
+        k = obs.shape[0]
+        act = np.ascontiguousarray(np.broadcast_to(np.asarray(active).astype(bool).astype(np.uint8), (k,)))
+        self._check(self._lib.rrtx_polygons_set_active(self._h, _capi._ptr(obs), k, _capi._ptr(act)))
 
     def dubins_edges_check_obstacle(self, s, g, r_min: float, robot_radius: float, obstacle: int):
         """explicitEdgeCheck(S, edge::DubinsEdge, ob) against polygon `obstacle` alone."""

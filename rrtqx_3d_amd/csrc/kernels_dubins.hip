@@ -1299,6 +1299,55 @@ __global__ __launch_bounds__(256, TIME ? 2 : 3) void dubins_check_words_kernel(
   if (valid) hit_word[base + k] = hits;
 }
 
+// The second half of the batched polygon release (rrtx_obstacle_release_polygon_batch), launched behind
+// dubins_check_words_kernel over the same chunk and the same records: hit_word[k] is what that kernel left (the leaving
+// obstacles candidate k collides with); an edge that also collides with an obstacle that STAYS is not freed, so its word
+// is cleared.  Same lane mapping and the same load_rec; valid = the lane still has a word.  The wave walks the stay
+// ranges (stay[2 r], stay[2 r + 1] = packed positions [pb, pe), n_stay of them, clamped to the table) with scalar loads
+// and calls wave_dubins_collides on the table shifted to pb with m = pe - pb, as tab_range shifts it -- the single
+// call's passes over "the packed obstacles before it" and "after it", lane for lane.  It leaves when no lane has a word.
+template <bool TIME, bool RSUM = false>
+__global__ __launch_bounds__(256, TIME ? 2 : 3) void dubins_check_stay_kernel(
+    const EdgeSrc src, long long base, long long count, long long n, int spread, double r_min, double robot_radius,
+    const PolyTab tab, const double *__restrict__ rec, const int32_t *__restrict__ stay, int n_stay,
+    unsigned long long *__restrict__ hit_word, const double *__restrict__ ckpt) {
+  __shared__ WaveDubinsT<TIME, RSUM> wd[4];
+  WaveDubinsT<TIME, RSUM> &w = wd[threadIdx.x >> 6];
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long k = t;
+  if (spread) {
+    const long long n_waves = (count + 63) / 64;
+    const long long gw = t >> 6;
+    k = (gw < n_waves) ? (long long)(threadIdx.x & 63) * n_waves + gw : count;
+  }
+  double s[4] = {0, 0, 0, 0}, g[4] = {1, 0, 0, 0};
+  const bool valid = k < count && load_edge(src, base + k, n, s, g);
+  bool alive = valid && hit_word[base + k] != 0ull;
+  if (__ballot(alive) == 0ull) return;
+  Steer st;
+  load_rec(rec + kRecDoubles * (valid ? k : 0), st);
+  if (!valid) { st.cost = __builtin_inf(); st.word = 6; st.pc[0].len = st.pc[1].len = st.pc[2].len = 0; }
+  bool kept = false;
+  for (int r = 0; r < n_stay; ++r) {                             // (uniform: the range is two scalar loads)
+    int pb = stay[2 * r], pe = stay[2 * r + 1];
+    if (pb < 0) pb = 0;
+    if (pe > tab.m) pe = tab.m;
+    if (pe <= pb) continue;
+    PolyTab some = tab;
+    some.meta = tab.meta + 4 * (size_t)pb;
+    some.off = tab.off + pb;
+    some.poff = tab.poff + pb;
+    some.pbox = tab.pbox + 4 * (size_t)pb;
+    some.m = pe - pb;
+    bool h;
+    if constexpr (RSUM) h = wave_dubins_collides<TIME, RSUM>(w, alive, st, s, g, r_min, robot_radius, some, ckpt + kCkptMax * (valid ? k : 0));
+    else h = wave_dubins_collides<TIME>(w, alive, st, s, g, r_min, robot_radius, some);
+    if (alive && h) { alive = false; kept = true; }
+    if (__ballot(alive) == 0ull) break;
+  }
+  if (kept) hit_word[base + k] = 0ull;
+}
+
 // edge.trajectory (R/DRRT_DubinsEdge_functions.jl:684-701): the polyline of every edge, written at
 // traj_off[i] (row units), rows of (x, y) -- with has_time rows of (x, y, t); traj == null only
 // reports P per edge.
@@ -1399,7 +1448,8 @@ extern "C" int rrtx_debug_dubins_clocks(unsigned long long *out, int reset) {
 // steer + check of the edges [0, n) of a source, chunk by chunk
 // cost2 / word2 / hit2 (candidate edges, src.mode == 1 with dir == 0): the reverse edges too, steered in the same launch
 // wc (the batched polygon sweep): the check is dubins_check_words_kernel -- per edge a word of obstacles in, a hit word out
-struct WordsCheck { const unsigned long long *word; const int32_t *ppos; int kg; unsigned long long *hit_word; };
+// wc->n_stay > 0 (the batched polygon release): dubins_check_stay_kernel follows it over the same records
+struct WordsCheck { const unsigned long long *word; const int32_t *ppos; int kg; unsigned long long *hit_word; const int32_t *stay; int n_stay; };
 static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int spread, double r_min, double robot_radius,
                             const PolyTab &tab, bool check, double *cost, uint8_t *word, uint8_t *hit, int32_t *traj_len,
                             double *cost2 = nullptr, uint8_t *word2 = nullptr, uint8_t *hit2 = nullptr,
@@ -1455,6 +1505,17 @@ static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int 
       else
         hipLaunchKernelGGL(dubins_check_rec_kernel<false>, grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
                            robot_radius, ctx->dubins_vmin, ctx->dubins_vmax, tab, rc_, h, ckpt);
+      if (wc && wc->n_stay > 0) {
+        if (rsum)
+          hipLaunchKernelGGL((dubins_check_stay_kernel<true, true>), grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
+                             robot_radius, tab, rc_, wc->stay, wc->n_stay, wc->hit_word, ckpt);
+        else if (has_time)
+          hipLaunchKernelGGL(dubins_check_stay_kernel<true>, grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
+                             robot_radius, tab, rc_, wc->stay, wc->n_stay, wc->hit_word, ckpt);
+        else
+          hipLaunchKernelGGL(dubins_check_stay_kernel<false>, grid, block, 0, ctx->stream, cs, base, count, n, spread, r_min,
+                             robot_radius, tab, rc_, wc->stay, wc->n_stay, wc->hit_word, ckpt);
+      }
       span_end(ctx);
     }
   }
@@ -1564,10 +1625,11 @@ int launch_dubins_edges_idx(rrtx_ctx *ctx, const int32_t *ids_dev, int64_t n, do
 int dubins_check_space(rrtx_ctx *ctx) { return check_space(ctx); }
 
 // the Dubins check of a group of rrtx_obstacle_sweep_polygon_batch: the candidates are steered once, whatever the number
-// of obstacles in their words (launch_dubins_edges_idx steers them once per obstacle)
+// of obstacles in their words (launch_dubins_edges_idx steers them once per obstacle).  n_stay > 0: the release, whose
+// stay check runs over the same records (the single mode-1 call steers every candidate three times per obstacle)
 int launch_dubins_check_words(rrtx_ctx *ctx, const int32_t *cand_id, const unsigned long long *cand_word, int64_t n,
                               double r_min, double robot_radius, const int32_t *ppos_dev, int kg,
-                              unsigned long long *hit_word) {
+                              unsigned long long *hit_word, const int32_t *stay_dev, int n_stay) {
   if (n <= 0) return RRTX_OK;
   if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "Dubins steering needs a dim=4 [x y t theta] context");
   const PolyTab tab = poly_tab(ctx);          // (the entry point has run sync_polygons and dubins_check_space before its groups)
@@ -1577,7 +1639,7 @@ int launch_dubins_check_words(rrtx_ctx *ctx, const int32_t *cand_id, const unsig
   src.nx = ctx->nodes[0]; src.ny = ctx->nodes[1]; src.nz = ctx->nodes[2]; src.nw = ctx->nodes[3];
   src.n_nodes = (int)ctx->n_nodes;
   RRTX_HIP(ctx, hipMemsetAsync(hit_word, 0, sizeof(unsigned long long) * (size_t)n, ctx->stream));   // (an id that points nowhere is not written)
-  const WordsCheck wc = {cand_word, ppos_dev, kg, hit_word};
+  const WordsCheck wc = {cand_word, ppos_dev, kg, hit_word, stay_dev, n_stay};
   return run_dubins_edges(ctx, src, (long long)n, 1, r_min, robot_radius, tab, true, nullptr, nullptr, nullptr, nullptr, nullptr,
                           nullptr, nullptr, &wc);
 }

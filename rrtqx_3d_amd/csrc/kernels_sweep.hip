@@ -304,32 +304,44 @@ __global__ void sweep_mark_query_words_kernel(const double *__restrict__ nx, con
   word[i] = in;
 }
 
-// the word of mirrored edge e's start node (0: past the end of the mirror, or a start index that points nowhere)
+// the word of mirrored edge e's start node (0: past the end of the mirror, or a start index that points nowhere).
+// BLOCKED (the release form): and 0 for an edge that is not blocked, e_dist[e] != +Inf -- read first, so almost every
+// edge is done after that one coalesced read.
+template <bool BLOCKED>
 __device__ __forceinline__ unsigned long long edge_start_word(const int32_t *__restrict__ e_start, long long e, long long ne,
-                                                              int n_nodes, const unsigned long long *__restrict__ word) {
+                                                              int n_nodes, const unsigned long long *__restrict__ word,
+                                                              const double *__restrict__ e_dist) {
   if (e >= ne) return 0ull;
+  if constexpr (BLOCKED) {
+    if (e_dist[e] != __builtin_inf()) return 0ull;
+  }
   const int a = e_start[e];
   return (unsigned)a < (unsigned)n_nodes ? word[a] : 0ull;
 }
 
 // The candidates of a group, two launches around the scan of the blocks' counts: an edge whose start node has a word
-// is a candidate; they leave as (id, word), ascending.
+// (BLOCKED: and that is blocked in the mirror) is a candidate; they leave as (id, word), ascending.  e_dist is read by
+// the BLOCKED form only.
+template <bool BLOCKED>
 __global__ __launch_bounds__(kSweepBlock) void sweep_cand_count_kernel(const int32_t *__restrict__ e_start, long long ne,
                                                                        int n_nodes, const unsigned long long *__restrict__ word,
+                                                                       const double *__restrict__ e_dist,
                                                                        int *__restrict__ block_count) {
   __shared__ int wcnt[kSweepBlock / 64];
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  block_votes<kSweepBlock>(edge_start_word(e_start, e, ne, n_nodes, word) != 0ull, wcnt);
+  block_votes<kSweepBlock>(edge_start_word<BLOCKED>(e_start, e, ne, n_nodes, word, e_dist) != 0ull, wcnt);
   if (threadIdx.x == 0) block_count[blockIdx.x] = block_votes_total<kSweepBlock>(wcnt);
 }
+template <bool BLOCKED>
 __global__ __launch_bounds__(kSweepBlock) void sweep_cand_write_kernel(const int32_t *__restrict__ e_start, long long ne,
                                                                        int n_nodes, const unsigned long long *__restrict__ word,
+                                                                       const double *__restrict__ e_dist,
                                                                        const long long *__restrict__ block_start,
                                                                        int32_t *__restrict__ cand_id,
                                                                        unsigned long long *__restrict__ cand_word) {
   __shared__ int wcnt[kSweepBlock / 64];
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long w = edge_start_word(e_start, e, ne, n_nodes, word);
+  const unsigned long long w = edge_start_word<BLOCKED>(e_start, e, ne, n_nodes, word, e_dist);
   const unsigned long long m = block_votes<kSweepBlock>(w != 0ull, wcnt);
   if (w == 0ull) return;
   const long long pos = block_start[blockIdx.x] + block_votes_before(wcnt, threadIdx.x >> 6) + __popcll(m & lanes_below(threadIdx.x & 63));
@@ -388,6 +400,78 @@ __global__ __launch_bounds__(256) void sweep_polygon_words_kernel(
         }
       }
       if (h) hits |= 1ull << bit;
+    }
+  }
+  hit_word[c] = hits;
+}
+
+// The one-obstacle test of sweep_polygon_words_kernel's loop body as a function, for the release form below: the
+// reference's explicitEdgeCheck2D (R/DRRT.jl:1523-1653) of the edge p0 -> p1 against packed table position j, statement
+// for statement what that kernel runs for one set bit.  (sweep_polygon_words_kernel keeps its own copy: calling this
+// function from it moved its SGPR count, and mode 0 is to stay the code it was.)
+__device__ __forceinline__ bool polygon_hits_edge(const double4 p0, const double4 p1, int j, const double *__restrict__ meta,
+                                                  const int32_t *__restrict__ off, const double *__restrict__ vxy,
+                                                  const int32_t *__restrict__ path_off, const double *__restrict__ path,
+                                                  double robot_radius, double rr2) {
+  const double cx = meta[4 * j + 0], cy = meta[4 * j + 1], rad = meta[4 * j + 2];
+  const int kind = (int)meta[4 * j + 3];
+  bool h = false;
+  if (kind == 6 || kind == 7) {
+    h = edge_hits_moving(p0.x, p0.y, p0.z, p1.x, p1.y, p1.z, robot_radius, cx, cy, rad, path + 3 * (size_t)path_off[j],
+                         path_off[j + 1] - path_off[j]);
+  } else {
+    const double dsq = dist_sqrd_point_to_segment(cx, cy, p0.x, p0.y, p1.x, p1.y);
+    const double rr = robot_radius + rad;
+    if (!(dsq > rr * rr)) {
+      if (kind == 1) h = true;
+      else if (kind == 3) {
+        const int vb = off[j], ve = off[j + 1];
+        if (ve - vb >= 2) {                                      // (:1551: fewer than two vertices never collide)
+          double Ax = vxy[2 * (ve - 1)], Ay = vxy[2 * (ve - 1) + 1];
+          for (int v = vb; v < ve && !h; ++v) {
+            const double Bx = vxy[2 * v], By = vxy[2 * v + 1];
+            h = segment_dist_sqrd(p0.x, p0.y, p1.x, p1.y, Ax, Ay, Bx, By) < rr2;
+            Ax = Bx; Ay = By;
+          }
+        }
+      }
+    }
+  }
+  return h;
+}
+
+// The same check in the release form (rrtx_obstacle_release_polygon_batch), on polygon_hits_edge: a lane whose hit
+// word is not empty then walks the obstacles that stay -- stay[2 r], stay[2 r + 1] = the r-th range [pb, pe) of packed
+// positions, n_stay of them, clamped to the na obstacles of the table -- and drops its word at the first one its edge
+// collides with: the single mode-1 call's passes over "the packed obstacles before it" and "after it".  A wave without
+// a hit skips the walk.
+__global__ __launch_bounds__(256) void release_polygon_words_kernel(
+    const int32_t *__restrict__ cand_id, const unsigned long long *__restrict__ cand_word, long long n_c,
+    const int32_t *__restrict__ e_start, const int32_t *__restrict__ e_end, int n_nodes, const double *__restrict__ naos,
+    const double *__restrict__ meta, const int32_t *__restrict__ off, const double *__restrict__ vxy,
+    const int32_t *__restrict__ path_off, const double *__restrict__ path, const int32_t *__restrict__ ppos,
+    double robot_radius, unsigned long long *__restrict__ hit_word, const int32_t *__restrict__ stay, int n_stay, int na) {
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_c) return;
+  const int id = cand_id[c];
+  const int a = e_start[id], b = e_end[id];
+  unsigned long long hits = 0ull;
+  if ((unsigned)a < (unsigned)n_nodes && (unsigned)b < (unsigned)n_nodes) {
+    const double4 p0 = reinterpret_cast<const double4 *>(naos)[a];
+    const double4 p1 = reinterpret_cast<const double4 *>(naos)[b];
+    const double rr2 = robot_radius * robot_radius;
+    unsigned long long w = cand_word[c];
+    while (w != 0ull) {
+      const int bit = __ffsll((long long)w) - 1;
+      w &= w - 1ull;
+      if (polygon_hits_edge(p0, p1, ppos[bit], meta, off, vxy, path_off, path, robot_radius, rr2)) hits |= 1ull << bit;
+    }
+    if (__ballot(hits != 0ull) != 0ull) {
+      for (int r = 0; r < n_stay && hits != 0ull; ++r) {
+        const int pb = max(stay[2 * r], 0), pe = min(stay[2 * r + 1], na);
+        for (int j = pb; j < pe; ++j)
+          if (polygon_hits_edge(p0, p1, j, meta, off, vxy, path_off, path, robot_radius, rr2)) { hits = 0ull; break; }
+      }
     }
   }
   hit_word[c] = hits;
@@ -496,8 +580,13 @@ int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, in
 // to (id, word), ONE read of their number, the check of every candidate against the obstacles of its word (Dubins
 // space: one steering pass, kernels_dubins.hip), and the sphere burst's tail over the candidates' hit words -- the rows
 // follow those of the group before (ws_swb_base).  No group writes the mirror.
-int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius, int32_t *out_dev, int64_t cap,
+// release (rrtx_obstacle_release_polygon_batch): only BLOCKED edges are candidates, and a candidate that collides with an
+// obstacle of the stay ranges (ctx->prel_stay_host: pairs [pb, pe) of packed table positions, uploaded once) loses its
+// hit word before the tail -- SimpleEdge in the check kernel itself, Dubins in a second kernel over the same steering
+// records (kernels_dubins.hip).  The waits are the same: one per group.
+int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius, bool release, int32_t *out_dev, int64_t cap,
                          long long **total_dev) {
+  const char *fn = release ? "obstacle_release_polygon_batch" : "obstacle_sweep_polygon_batch";
   const int n = (int)ctx->n_nodes;
   const long long ne = ctx->ge_n;
   const int nb = (int)((ne + kSweepBlock - 1) / kSweepBlock);
@@ -505,7 +594,9 @@ int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius
   const int kg_max = std::min(k, kSweepGroup);
   const size_t nq_all = ctx->pswb_q_host.size();
   if ((int)ctx->pswb_qoff_host.size() != ng + 1 || (size_t)ctx->pswb_qoff_host[ng] != nq_all || ctx->pswb_pos_host.size() != (size_t)k)
-    return fail(ctx, RRTX_E_STATE, "obstacle_sweep_polygon_batch: query tables of %zu groups for %d entries", ctx->pswb_qoff_host.size(), k);
+    return fail(ctx, RRTX_E_STATE, "%s: query tables of %zu groups for %d entries", fn, ctx->pswb_qoff_host.size(), k);
+  const int n_stay = release ? (int)(ctx->prel_stay_host.size() / 2) : 0;
+  if (release) RRTX_HIP(ctx, ctx->ws_prel_stay.ensure(sizeof(int32_t) * 2 * (size_t)(n_stay > 0 ? n_stay : 1)));
   RRTX_HIP(ctx, ctx->ws_pswb_q.ensure(sizeof(SweepQueryOwned) * (nq_all > 0 ? nq_all : 1)));
   RRTX_HIP(ctx, ctx->ws_pswb_pos.ensure(sizeof(int32_t) * (size_t)k));
   RRTX_HIP(ctx, ctx->ws_pswb_cand_id.ensure(sizeof(int32_t) * (size_t)ne));
@@ -525,7 +616,10 @@ int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius
   if (nq_all > 0)
     RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_pswb_q.p, ctx->pswb_q_host.data(), sizeof(SweepQueryOwned) * nq_all, hipMemcpyHostToDevice, st));
   RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_pswb_pos.p, ctx->pswb_pos_host.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, st));
+  if (n_stay > 0)
+    RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_prel_stay.p, ctx->prel_stay_host.data(), sizeof(int32_t) * 2 * (size_t)n_stay, hipMemcpyHostToDevice, st));
   RRTX_HIP(ctx, hipMemsetAsync(ctx->ws_swb_base.p, 0, sizeof(long long), st));
+  const int32_t *stay = release ? ctx->ws_prel_stay.as<int32_t>() : nullptr;
   unsigned long long *word = ctx->ws_swb_word.as<unsigned long long>(), *seg_word = ctx->ws_swb_seg_word.as<unsigned long long>();
   unsigned long long *cand_word = ctx->ws_pswb_cand_word.as<unsigned long long>(), *hit_word = ctx->ws_pswb_hit.as<unsigned long long>();
   int32_t *seg_id = ctx->ws_swb_seg_id.as<int32_t>(), *cand_id = ctx->ws_pswb_cand_id.as<int32_t>();
@@ -543,28 +637,35 @@ int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius
       span_begin(ctx, KF_EDGES);
       hipLaunchKernelGGL(sweep_mark_query_words_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->nodes[0], ctx->nodes[1],
                          ctx->nodes[2], ctx->nodes[3], n, ctx->dim, ctx->ws_pswb_q.as<SweepQueryOwned>() + q0, nqs, word);
-      hipLaunchKernelGGL(sweep_cand_count_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ne, n, word,
-                         ctx->ws_sweep_cnt.as<int>());
+      hipLaunchKernelGGL((release ? sweep_cand_count_kernel<true> : sweep_cand_count_kernel<false>), dim3(nb), dim3(kSweepBlock), 0,
+                         st, ctx->ge_start, ne, n, word, ctx->ge_dist, ctx->ws_sweep_cnt.as<int>());
       launch_excl_scan(st, ctx->ws_sweep_cnt.as<int>(), cstart, nb);
-      hipLaunchKernelGGL(sweep_cand_write_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ne, n, word, cstart, cand_id,
-                         cand_word);
+      hipLaunchKernelGGL((release ? sweep_cand_write_kernel<true> : sweep_cand_write_kernel<false>), dim3(nb), dim3(kSweepBlock), 0,
+                         st, ctx->ge_start, ne, n, word, ctx->ge_dist, cstart, cand_id, cand_word);
       span_end(ctx);
       RRTX_HIP(ctx, hipGetLastError());
       RRTX_HIP(ctx, hipMemcpyAsync(&n_c, cstart + nb, sizeof(int64_t), hipMemcpyDeviceToHost, st));
       RRTX_HIP(ctx, hipStreamSynchronize(st));                   // the group's one wait: the count sizes the check launch
-      if (n_c < 0 || n_c > ne) return fail(ctx, RRTX_E_DEVICE, "obstacle_sweep_polygon_batch: %lld candidates of %lld edges", (long long)n_c, ne);
+      if (n_c < 0 || n_c > ne) return fail(ctx, RRTX_E_DEVICE, "%s: %lld candidates of %lld edges", fn, (long long)n_c, ne);
     }
     cand_all += n_c;
     if (n_c > 0) {
       if (dubins) {
-        const int rc = launch_dubins_check_words(ctx, cand_id, cand_word, n_c, r_min, robot_radius, ppos, kg, hit_word);
+        const int rc = launch_dubins_check_words(ctx, cand_id, cand_word, n_c, r_min, robot_radius, ppos, kg, hit_word, stay, n_stay);
         if (rc) return rc;
       } else {
         span_begin(ctx, KF_EDGES);
-        hipLaunchKernelGGL(sweep_polygon_words_kernel, dim3((unsigned)((n_c + 255) / 256)), dim3(256), 0, st, cand_id, cand_word,
-                           (long long)n_c, ctx->ge_start, ctx->ge_end, n, ctx->nodes_aos, ctx->d_poly_meta.as<double>(),
-                           ctx->d_poly_off.as<int32_t>(), ctx->d_poly_vxy.as<double>(), ctx->d_poly_path_off.as<int32_t>(),
-                           ctx->d_poly_path.as<double>(), ppos, robot_radius, hit_word);
+        const dim3 grid((unsigned)((n_c + 255) / 256));
+        if (release)
+          hipLaunchKernelGGL(release_polygon_words_kernel, grid, dim3(256), 0, st, cand_id, cand_word, (long long)n_c, ctx->ge_start,
+                             ctx->ge_end, n, ctx->nodes_aos, ctx->d_poly_meta.as<double>(), ctx->d_poly_off.as<int32_t>(),
+                             ctx->d_poly_vxy.as<double>(), ctx->d_poly_path_off.as<int32_t>(), ctx->d_poly_path.as<double>(), ppos,
+                             robot_radius, hit_word, stay, n_stay, ctx->poly_n_active);
+        else
+          hipLaunchKernelGGL(sweep_polygon_words_kernel, grid, dim3(256), 0, st, cand_id, cand_word, (long long)n_c, ctx->ge_start,
+                             ctx->ge_end, n, ctx->nodes_aos, ctx->d_poly_meta.as<double>(), ctx->d_poly_off.as<int32_t>(),
+                             ctx->d_poly_vxy.as<double>(), ctx->d_poly_path_off.as<int32_t>(), ctx->d_poly_path.as<double>(), ppos,
+                             robot_radius, hit_word);
         span_end(ctx);
       }
     }

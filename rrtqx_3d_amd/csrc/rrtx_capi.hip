@@ -596,7 +596,7 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
                     &ctx->ws_swb_tab, &ctx->ws_swb_word, &ctx->ws_swb_seg_id, &ctx->ws_swb_seg_word, &ctx->ws_swb_blk_n, &ctx->ws_swb_cnt,
                     &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off, &ctx->ws_rel_stay, &ctx->ws_pswb_q, &ctx->ws_pswb_pos,
-                    &ctx->ws_pswb_cand_id, &ctx->ws_pswb_cand_word, &ctx->ws_pswb_hit,
+                    &ctx->ws_pswb_cand_id, &ctx->ws_pswb_cand_word, &ctx->ws_pswb_hit, &ctx->ws_prel_stay,
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
                     &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
                     &ctx->gc.in_pos, &ctx->gc.rep_lmc, &ctx->gc.rep_parent, &ctx->gc.delta_cnt, &ctx->gc.delta_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
@@ -904,6 +904,21 @@ int rrtx_polygon_paths_set(rrtx_ctx *ctx, const int32_t *path_off, const double 
   if (path_off[m] > 0 && !path_xyt) return fail(ctx, RRTX_E_INVALID, "polygon_paths_set: bad arguments");
   ctx->poly_path_off.assign(path_off, path_off + m + 1);
   ctx->poly_path.assign(path_xyt, path_xyt + 3 * (size_t)path_off[m]);
+  ctx->poly_dirty = true;
+  return RRTX_OK;
+}
+
+// obstacle.obstacleUnused of k list positions (R/DRRT.jl:3287 and the discovery of an obstacle): the flags alone, the
+// shapes and paths stay; the device tables are packed again at the next sync, as after rrtx_polygons_set
+int rrtx_polygons_set_active(rrtx_ctx *ctx, const int32_t *obstacles, int k, const uint8_t *active) {
+  CHECK_CTX(ctx);
+  const int m = (int)ctx->poly_active.size();
+  if (k < 0 || (k > 0 && (!obstacles || !active))) return fail(ctx, RRTX_E_INVALID, "polygons_set_active: bad arguments");
+  for (int j = 0; j < k; ++j)
+    if (obstacles[j] < 0 || obstacles[j] >= m)
+      return fail(ctx, RRTX_E_INVALID, "polygons_set_active: obstacle %d (entry %d) out of range (%d polygons)", obstacles[j], j, m);
+  if (k == 0) return RRTX_OK;
+  for (int j = 0; j < k; ++j) ctx->poly_active[(size_t)obstacles[j]] = active[j] ? 1 : 0;
   ctx->poly_dirty = true;
   return RRTX_OK;
 }
@@ -1403,12 +1418,12 @@ int rrtx_obstacle_sweep_polygon(rrtx_ctx *ctx, int obstacle, double robot_radius
   return RRTX_OK;
 }
 
-// rrtx_obstacle_sweep_polygon_batch: mode 0 of rrtx_obstacle_sweep_polygon for a burst of list positions, CSR rows
-int rrtx_obstacle_sweep_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, double robot_radius, double delta,
-                                      double r_min, int block, int64_t *offsets, int32_t *edge_ids, int64_t cap,
-                                      int64_t *needed) {
-  CHECK_CTX(ctx);
-  const char *fn = "obstacle_sweep_polygon_batch";
+// rrtx_obstacle_sweep_polygon_batch (release = false; apply: block the rows): mode 0 of rrtx_obstacle_sweep_polygon for a
+// burst of list positions, CSR rows.  rrtx_obstacle_release_polygon_batch (release = true; apply: unblock them): the
+// edge loops of a burst of removeObstacle calls (R/DRRT.jl:3202-3290), the members of the burst taken as gone together.
+static int polygon_burst_host(rrtx_ctx *ctx, const char *fn, bool release, const int32_t *obstacles, int k, double robot_radius,
+                              double delta, double r_min, int apply, int64_t *offsets, int32_t *edge_ids, int64_t cap,
+                              int64_t *needed) {
   const int m = (int)ctx->poly_active.size();
   if (k < 0 || k > 65536 || !offsets || (k > 0 && !obstacles) || cap < 0 || (cap > 0 && !edge_ids))
     return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
@@ -1450,19 +1465,51 @@ int rrtx_obstacle_sweep_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, i
     at += (size_t)qn[(size_t)j];
     if ((j & 63) == 63 || j == k - 1) ctx->pswb_qoff_host[(size_t)(j >> 6) + 1] = (int)ctx->pswb_q_host.size();
   }
+  ctx->prel_stay_host.clear();
+  if (release) {
+    // the obstacles that stay: the packed table less the in-use entries of the call, as the ranges between them -- the
+    // single call's {0 .. pb}, {pe .. na} for one obstacle.  Empty ranges are dropped.
+    std::vector<int32_t> gone;
+    for (int j = 0; j < k; ++j)
+      if (ctx->pswb_pos_host[(size_t)j] >= 0) gone.push_back(ctx->pswb_pos_host[(size_t)j]);
+    std::sort(gone.begin(), gone.end());
+    gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
+    int32_t from = 0;
+    for (const int32_t p : gone) {
+      if (p > from) { ctx->prel_stay_host.push_back(from); ctx->prel_stay_host.push_back(p); }
+      from = p + 1;
+    }
+    if ((int32_t)pos.size() > from) { ctx->prel_stay_host.push_back(from); ctx->prel_stay_host.push_back((int32_t)pos.size()); }
+  }
   const int64_t dcap = cap > 0 ? cap : 1;
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)dcap));
   long long *total_dev = nullptr;
-  if ((rc = launch_polygon_burst(ctx, k, r_min, robot_radius, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev))) return rc;
+  if ((rc = launch_polygon_burst(ctx, k, r_min, robot_radius, release, ctx->ws_out_i32.as<int32_t>(), cap, &total_dev))) return rc;
   RRTX_HIP(ctx, copy_out(ctx, offsets, ctx->ws_swb_off.p, sizeof(int64_t) * (size_t)(k + 1)));
   int64_t total = 0;
-  if ((rc = sweep_ids_out(ctx, fn, "colliding edges", total_dev, edge_ids, cap, needed, &total))) return rc;
+  if ((rc = sweep_ids_out(ctx, fn, release ? "freed edges" : "colliding edges", total_dev, edge_ids, cap, needed, &total))) return rc;
   if (total > 0) {
-    // addNewObstacle's dist = Inf for every id of every row, where the rows are
-    if (block && (rc = launch_graph_block_dev(ctx, false, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
+    // addNewObstacle's dist = Inf / removeObstacle's dist = distOriginal for every id of every row, where the rows are
+    if (apply && (rc = launch_graph_block_dev(ctx, release, ctx->ws_out_i32.as<int32_t>(), total))) return rc;
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return RRTX_OK;
+}
+
+int rrtx_obstacle_sweep_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, double robot_radius, double delta,
+                                      double r_min, int block, int64_t *offsets, int32_t *edge_ids, int64_t cap,
+                                      int64_t *needed) {
+  CHECK_CTX(ctx);
+  return polygon_burst_host(ctx, "obstacle_sweep_polygon_batch", false, obstacles, k, robot_radius, delta, r_min, block, offsets,
+                            edge_ids, cap, needed);
+}
+
+int rrtx_obstacle_release_polygon_batch(rrtx_ctx *ctx, const int32_t *obstacles, int k, double robot_radius, double delta,
+                                        double r_min, int unblock, int64_t *offsets, int32_t *edge_ids, int64_t cap,
+                                        int64_t *needed) {
+  CHECK_CTX(ctx);
+  return polygon_burst_host(ctx, "obstacle_release_polygon_batch", true, obstacles, k, robot_radius, delta, r_min, unblock, offsets,
+                            edge_ids, cap, needed);
 }
 
 int rrtx_dubins_edges_check_obstacle(rrtx_ctx *ctx, const double *s, const double *g, int64_t ne, double r_min,

@@ -264,6 +264,9 @@ struct rrtx_ctx {
   std::vector<rrtx::SweepQueryOwned> pswb_q_host;   // what ws_pswb_q is copied from (lives until the call's sync)
   std::vector<int32_t> pswb_pos_host;               // what ws_pswb_pos is copied from (likewise)
   std::vector<int> pswb_qoff_host;
+  // the batched polygon release: the obstacles that stay, as ranges [pb, pe) of packed table positions (pairs)
+  rrtx::DevBuf ws_prel_stay;
+  std::vector<int32_t> prel_stay_host;              // what ws_prel_stay is copied from (lives until the call's sync)
 
   // parent / rewire selection over the extend lists (kernels_select.hip)
   double *node_lmc = nullptr;       // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
@@ -443,17 +446,20 @@ int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, 
 // sync_spheres has run for the call's robot radius): row j = the blocked edges obstacle j hits and no staying sphere does.
 int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, int64_t cap, long long **total_dev);
 
-// device side of rrtx_obstacle_sweep_polygon_batch over ctx->pswb_q_host / pswb_qoff_host / pswb_pos_host (k entries,
-// the mirror is not empty, sync_polygons has run): the same CSR in ws_swb_off / out_dev / *total_dev, row j = entry j's
-// mode-0 sweep.  Synchronises once per group of 64 entries (the candidate count); ctx->last_sweep_candidates = their sum.
-int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius, int32_t *out_dev, int64_t cap,
+// device side of rrtx_obstacle_sweep_polygon_batch / rrtx_obstacle_release_polygon_batch over ctx->pswb_q_host /
+// pswb_qoff_host / pswb_pos_host (k entries, the mirror is not empty, sync_polygons has run): the same CSR in ws_swb_off
+// / out_dev / *total_dev, row j = entry j's mode-0 sweep.  release (ctx->prel_stay_host filled): row j = the blocked edges
+// entry j hits and no obstacle of the stay ranges does.  Synchronises once per group of 64 entries (the candidate
+// count); ctx->last_sweep_candidates = their sum.
+int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius, bool release, int32_t *out_dev, int64_t cap,
                          long long **total_dev);
 // explicitEdgeCheck(S, edge::DubinsEdge, ob) of the n mirrored edges cand_id[c] against the obstacles whose bit is set in
 // cand_word[c] (bit b = packed table position ppos_dev[b], b < kg): bit b of hit_word[c] = edge c collides with it.
-// The caller has run sync_polygons and dubins_check_space.
+// stay_dev / n_stay (the release; null / 0 otherwise): n_stay ranges [pb, pe) of packed table positions; an edge that
+// collides with an obstacle of one of them loses its hit word.  The caller has run sync_polygons and dubins_check_space.
 int launch_dubins_check_words(rrtx_ctx *ctx, const int32_t *cand_id, const unsigned long long *cand_word, int64_t n,
                               double r_min, double robot_radius, const int32_t *ppos_dev, int kg,
-                              unsigned long long *hit_word);
+                              unsigned long long *hit_word, const int32_t *stay_dev = nullptr, int n_stay = 0);
 int dubins_check_space(rrtx_ctx *ctx);   // moving obstacles in use need RRTX_OPT_SPACE_HAS_TIME (RRTX_E_STATE)
 
 int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n);

@@ -790,12 +790,29 @@ def obstacleReleaseBatch(S: CSpace, KD: HipTree, obs: Sequence[SphereObstacle], 
     S.bind(KD)
     _sync_obstacles(S)
     if any(isinstance(ob, Obstacle) for ob in obs):
-        error("obstacleReleaseBatch takes sphere obstacles; polygons go through obstacleSweep(remove=True) one at a time")
+        error("obstacleReleaseBatch takes sphere obstacles; polygons go through obstacleReleasePolygonBatch")
     if S.spaceHasTime or S.spaceHasTheta:
         error("this type of obstacle not coded for this type of space")
     off, ids = KD.ctx.obstacle_release_batch([_list_position(S, ob) for ob in obs],
                                              [S.robotRadius + S.delta + ob.radius for ob in obs], S.robotRadius,
                                              unblock=unblock)
+    return [ids[off[j]:off[j + 1]] for j in range(len(obs))]
+
+
+def obstacleReleasePolygonBatch(S: CSpace, KD: HipTree, obs: Sequence[Obstacle], unblock: bool = False) -> List[np.ndarray]:
+    """The edge loops of removeObstacle (R/DRRT.jl:3202-3290) for a burst of Obstacles (polygon list) of S.obstacles
+    that expire in one iteration, taken as gone together: one id array per obstacle, in the order given -- the
+    registered edges that are blocked, start at a node in conflict with ob, collide with it and with no obstacle that is
+    in use and not in `obs`.  What obstacleSweep(S, KD, ob, remove=True) returns with the others of `obs` marked unused.
+    ob itself must still be in use (the reference marks it unused after its loop, :3287): set obstacleUnused afterwards.
+    The edge type is the space's, r_min is S.minTurningRadius.  unblock=True is unblockEdges over all of them as well,
+    without the ids travelling back."""
+    S.bind(KD)
+    _sync_obstacles(S)
+    if not all(isinstance(ob, Obstacle) for ob in obs):
+        error("obstacleReleasePolygonBatch takes Obstacles of the polygon list; spheres go through obstacleReleaseBatch")
+    off, ids = KD.ctx.obstacle_release_polygon_batch([_list_position(S, ob) for ob in obs], S.robotRadius, S.delta,
+                                                     r_min=float(getattr(S, "minTurningRadius", 0.0) or 0.0), unblock=unblock)
     return [ids[off[j]:off[j + 1]] for j in range(len(obs))]
 
 

@@ -1,5 +1,5 @@
-"""Soak of the obstacle sweeps and releases on a lattice: the five entry points that walk the edge mirror
-(rrtx_obstacle_sweep, _sweep_batch, _release_batch, _sweep_polygon, _sweep_polygon_batch) on scenes whose every
+"""Soak of the obstacle sweeps and releases on a lattice: the six entry points that walk the edge mirror
+(rrtx_obstacle_sweep, _sweep_batch, _release_batch, _sweep_polygon, _sweep_polygon_batch, _release_polygon_batch) on scenes whose every
 coordinate is a multiple of 1/4 (polygon centres: of 1/8) and whose ranges are distances between lattice points.  Random
 real scenes never put a node exactly at an obstacle's search range, an edge exactly tangent to an inflated sphere or an
 edge along a polygon's side; here many are, so the strict / non-strict decisions of the mark kernels, the per-bit root
@@ -606,6 +606,88 @@ def check_dubins(s):
     return out
 
 
+# ---- the release burst (rrtx_obstacle_release_polygon_batch) on scenes P and D -------------------------------------------
+def release_flags(active, entries):
+    """the in-use flags the rows of a release burst are judged under: what stays = in use and not listed"""
+    stay = np.array(active, dtype=np.uint8).copy()
+    stay[np.asarray(entries, dtype=np.int64)] = 0
+    return stay
+
+
+def release_rows_reference(s, entries, dist, delta, dubins, r_min=0.0):
+    """row j of the burst = remove_obstacle_edges(entries[j]) under flags where the OTHER listed positions are not in
+    use (the entry itself keeps its own flag)"""
+    stay = release_flags(s.active, entries)
+    rows = {}
+    for p in sorted(set(int(q) for q in entries)):
+        flags = stay.copy()
+        flags[p] = s.active[p]
+        ps = O.PolygonSet(s.polys, kinds=s.kinds, active=flags)
+        rows[p] = O.remove_obstacle_edges(s.tree, s.pts, s.es, s.ee, dist, ps, p, s.rr, delta, dubins=dubins, r_min=r_min)
+    return [rows[int(p)] for p in entries]
+
+
+def polygon_release_entries(s):
+    """scene P: every second of the first 20 positions (the rows that were blocked), the positions not in use, the root's
+    box and one in-use position a second time, shuffled by the scene's seed"""
+    idle = [int(j) for j in np.flatnonzero(s.active == 0)]
+    e = list(range(0, min(20, s.K), 2)) + idle + [ROOT_OB, 2 % s.K]
+    return np.random.default_rng(s.seed + 1).permutation(np.array(e, dtype=np.int32))
+
+
+def check_polygons_release(s):
+    """scene P: the release burst after the union of the first 20 rows is blocked, at DELTA and at DELTA + 2^-30, against
+    remove_obstacle_edges under the burst's flags; then unblock=True: a second call finds nothing left of those rows"""
+    from rrtqx_3d_amd.context import Context
+    out = {"rows": 0, "ids": 0}
+    entries = polygon_release_entries(s)
+    with Context(3) as ctx:
+        ctx.nodes_append(s.pts)
+        ctx.polygons_set(s.polys, kinds=s.kinds, active=s.active)
+        assert ctx.graph_edges_append(s.es, s.ee) == 0
+        for name, d, blocked in (("DELTA", s.delta, s.blocked), ("DELTA + 2^-30", s.delta_up, s.blocked_up)):
+            ctx.graph_edges_unblock(np.arange(len(s.es), dtype=np.int32))
+            ctx.graph_edges_block(blocked)
+            dist = np.ones(len(s.es))
+            dist[blocked] = np.inf
+            want = release_rows_reference(s, entries, dist, d, dubins=False)
+            rows = _rows_of(*ctx.obstacle_release_polygon_batch(entries, s.rr, d, cap=8))
+            for j, p in enumerate(entries):
+                assert np.array_equal(rows[j], want[j]), f"scene {s.seed}: release row {j} (position {p}) at {name} differs"
+            out["rows"] += len(rows); out["ids"] += sum(len(r) for r in rows)
+        rows = _rows_of(*ctx.obstacle_release_polygon_batch(entries, s.rr, s.delta_up, unblock=True))
+        assert all(np.array_equal(a, b) for a, b in zip(rows, want))
+        assert len(ctx.obstacle_release_polygon_batch(entries, s.rr, s.delta_up)[1]) == 0
+    return out
+
+
+def check_dubins_release(s):
+    """scene D: the rows of the first six positions blocked, then the release burst of four of them, the position not in
+    use and a repeat, at DELTA and DELTA + 2^-30, against remove_obstacle_edges(dubins=True) under the burst's flags"""
+    from rrtqx_3d_amd.context import Context
+    out = {"rows": 0, "ids": 0}
+    entries = np.array([1, 0, s.m - 2, 5, 2, 1], dtype=np.int32)
+    with Context(4) as ctx:
+        ctx.set_wrap(3, 2.0 * math.pi)
+        ctx.nodes_append(s.pts)
+        ctx.polygons_set(s.polys, kinds=s.kinds, active=s.active)
+        assert ctx.graph_edges_append(s.es, s.ee) == 0
+        cost, _ = ctx.dubins_steer(s.pts[s.es], s.pts[s.ee], s.r_min)
+        ctx.graph_edges_set_dist(0, cost)
+        for name, d, base in (("DELTA", s.delta, s.rows), ("DELTA + 2^-30", s.delta_up, s.rows_up)):
+            blocked = np.unique(np.concatenate(base[:6] + [np.zeros(0, np.int32)])).astype(np.int32)
+            ctx.graph_edges_unblock(np.arange(len(s.es), dtype=np.int32))
+            ctx.graph_edges_block(blocked)
+            dist = cost.copy()
+            dist[blocked] = np.inf
+            want = release_rows_reference(s, entries, dist, d, dubins=True, r_min=s.r_min)
+            rows = _rows_of(*ctx.obstacle_release_polygon_batch(entries, s.rr, d, r_min=s.r_min, cap=8))
+            for j, p in enumerate(entries):
+                assert np.array_equal(rows[j], want[j]), f"scene {s.seed}: Dubins release row {j} (position {p}) at {name} differs"
+            out["rows"] += len(rows); out["ids"] += sum(len(r) for r in rows)
+    return out
+
+
 # ---- the soak -------------------------------------------------------------------------------------------------------------
 def scene(sc):
     """soak scene sc: span, node count, K and RR drawn per scene; S, P and D (every third scene with a planted root)
@@ -624,10 +706,14 @@ def scene(sc):
                       delta=1.25 - rr, n_other=K // 5)            # rr + delta = 1.25: the root's 3-4-5 triple stays exact
     o = check_polygons(p)
     out["polygon_rows"], out["polygon_ids"] = o["rows"], o["ids"]
+    o = check_polygons_release(p)
+    out["polygon_release_rows"], out["polygon_release_ids"] = o["rows"], o["ids"]
     d = dubins_scene(440_000 + sc, root_planted=(sc % 3 == 0), n_draw=int(rng.choice([100, 300])), span=int(rng.choice([4, 6])),
                      rr=rr)
     o = check_dubins(d)
     out["dubins_rows"], out["dubins_ids"] = o["rows"], o["ids"]
+    o = check_dubins_release(d)
+    out["dubins_release_rows"], out["dubins_release_ids"] = o["rows"], o["ids"]
     return out
 
 
