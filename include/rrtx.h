@@ -565,6 +565,39 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
                            uint8_t *hit_in, int64_t cap, int64_t *needed, int32_t *nearest_idx,
                            double *nearest_dist, uint8_t *sample_unsafe);
 
+/* ---- the samples of one extend batch among themselves ------------------------- */
+/* The lists of rrtx_extend_candidates are against the tree as it stood: the samples of one batch do not see each
+ * other there.  This call supplies the rest.  For a batch q of nq samples it gives, per sample j, the samples i < j of
+ * the same batch with KDdist(q_j, q_i) < r -- exactly what kdFindWithinRange (R/kdTree_general.jl:830) adds to j's
+ * list when the samples are inserted one after the other -- with the SimpleEdge cost and both collision flags of
+ * extend (R/DRRT_Q.jl:1927-1979, 2581-2637).  The tree list of rrtx_extend_candidates followed by this list, with
+ * idx mapped to the node index each earlier sample received (entries of samples that were not inserted dropped), is
+ * the reference's list; the order stays ascending because the mapping is monotone.
+ *   Scope    SimpleEdge only: dim == 3 and no wrapped dimension, otherwise RRTX_E_STATE as in rrtx_extend_candidates;
+ *            bad pointers or negative counts are RRTX_E_INVALID; a radius is taken as rrtx_extend_candidates takes it
+ *            (r <= 0 or NaN: every list is empty).  Obstacles: the spheres or the polygons by
+ *            RRTX_OPT_EXTEND_OBSTACLES; kinds 6 / 7 read time from the third coordinate.  The tree is not read: the
+ *            call works whatever the tree holds, an empty tree included.  Dubins lists and a radius per sample are
+ *            out of scope.
+ *   Lists    CSR offsets[nq + 1] from 0.  Row j: the batch positions i < j, ascending, with s = sq3(q_j, q_i) < thr,
+ *            thr = the first_ge threshold of r (rrtx_sq_thresholds), the test the range search applies to a non-root
+ *            node.  There is no root rule: the root is a tree node, never a sample.  idx[e] = i, a 0-based position
+ *            in q, not a node index.
+ *   Entries  cost[e] = sqrt(s), correctly rounded: the key and the SimpleEdge cost at once.  hit_out[e] =
+ *            explicitEdgeCheck of the directed edge q_j -> q_i (new node -> earlier node), hit_in[e] of q_i -> q_j,
+ *            both by the kernels of rrtx_extend_candidates -- a zero-length edge collides with every active sphere
+ *            (two equal samples are neighbours at cost 0).  inWarmupTime stays with the caller.
+ *   skip     nq bytes or NULL.  A sample with skip[j] != 0 has an empty list and appears in no list; the
+ *            sample_unsafe bytes of the rrtx_extend_candidates call on the same batch can be passed as they are.
+ *            A sample with a non-finite coordinate likewise has an empty list and appears in none (no comparison with
+ *            NaN / Inf is true) and does not disturb the lists of the others.
+ *   Capacity the two-call pattern of rrtx_extend_candidates: more than cap entries is RRTX_E_CAPACITY with *needed set
+ *            and offsets valid; cap == 0 (arrays may be NULL) counts; nq == 0 is RRTX_OK with offsets[0] = 0.
+ * Exact, no tolerance; nothing in the result depends on launch geometry or on the order in which waves finish. */
+int rrtx_extend_candidates_self(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                const uint8_t *skip, int64_t *offsets, int32_t *idx, double *cost,
+                                uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
+
 /* The same preamble for Edge = DubinsEdge (BASELINE config 3; R/dubinsExperimentsForPaper.jl): tree in
  * [x y t theta] with theta wrapped (rrtx_set_wrap), polygon obstacle list.  Per neighbour entry:
  * key = the KDdist the range search stores, Dubins cost and word for sample->near (out) and
@@ -596,6 +629,13 @@ int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r,
                                double robot_radius, int64_t *offsets, int32_t *idx, double *cost,
                                uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed_dev,
                                int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe);
+
+/* device-pointer form of rrtx_extend_candidates_self (skip may be NULL): *needed_dev receives the number of entries, no
+ * entry at or beyond cap is written (with more than cap entries none is, offsets stays valid).  Only enqueues; the
+ * growth of a workspace may wait on the stream once. */
+int rrtx_extend_candidates_self_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                    const uint8_t *skip, int64_t *offsets, int32_t *idx, double *cost,
+                                    uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed_dev);
 
 /* device-pointer form of rrtx_extend_candidates_dubins; *needed_dev receives the number of entries (entries
  * beyond cap are not written).  Only enqueues work, never waits on the stream: with wrapped dimensions nearest_*
@@ -639,9 +679,9 @@ int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit
  *                   lmc[idx[e]] > lmc_new[s] + cost_in[e], as (rw_node = idx[e], rw_value = lmc_new[s] + cost_in[e]) in
  *                   list order: a second CSR rw_offsets[nq + 1], rw_node, rw_value with the two-call capacity pattern.
  * For SimpleEdge lists pass the one cost array as cost_out and cost_in.  The kd-tree root needs no special case:
- * lmc[root] = 0 never exceeds a non-negative sum.  Samples of one batch do not see each other -- the lists are against
- * the tree as it stood, as in rrtx_extend_candidates -- so a node may appear in the rewire lists of several samples;
- * settling that is the caller's bookkeeping. */
+ * lmc[root] = 0 never exceeds a non-negative sum.  The lists are against the tree as it stood, as in
+ * rrtx_extend_candidates (the samples' lists among themselves come from rrtx_extend_candidates_self), so a node may
+ * appear in the rewire lists of several samples; settling that is the caller's bookkeeping. */
 #define RRTX_SEL_OK 0
 #define RRTX_SEL_NO_PARENT 1
 #define RRTX_SEL_EMPTY 2

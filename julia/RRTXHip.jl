@@ -403,13 +403,54 @@ function extend_candidates(tree::HipTree, S::TS, positions::Array{Float64,2}, hy
   end
 end
 
+# The lists of extend_candidates are against the tree as it stood; this gives the lists of the batch's samples among
+# themselves.  Row j: the batch positions i < j (0-based, ascending) with KDdist(q_j, q_i) < hyberBallRad -- what
+# kdFindWithinRange adds to j's list when the samples are inserted one after the other -- with the SimpleEdge cost and
+# the flags of q_j -> q_i (hitOut) and q_i -> q_j (hitIn).  skip: one byte per sample, non-zero = the sample has no
+# list and is in none (sampleUnsafe of extend_candidates serves as it is).  The caller appends row j to the tree list of
+# sample j with idx mapped to the node index each earlier sample received, dropping the samples it did not insert.
+struct ExtendCandidatesSelf
+  offsets::Vector{Int64}      # nq + 1
+  idx::Vector{Int32}          # 0-based positions in the batch
+  cost::Vector{Float64}
+  hitOut::Vector{UInt8}
+  hitIn::Vector{UInt8}
+end
+
+function extend_candidates_self(tree::HipTree, S::TS, positions::Array{Float64,2}, hyberBallRad::Float64;
+                                skip::Union{Nothing,Vector{UInt8}} = nothing) where {TS}
+  syncObstacles(tree, S)
+  nq = size(positions, 2)                     # d x nq, each sample contiguous
+  skip === nothing || length(skip) == nq || error("skip needs one byte per sample")
+  skipArg = skip === nothing ? UInt8[] : skip
+  skipPtr = skip === nothing ? Ptr{UInt8}(C_NULL) : pointer(skipArg)
+  offsets = Vector{Int64}(undef, nq + 1)
+  cap = max(8 * nq, 1024)
+  while true
+    idx = Vector{Int32}(undef, cap); cost = Vector{Float64}(undef, cap)
+    hout = Vector{UInt8}(undef, cap); hin = Vector{UInt8}(undef, cap)
+    needed = Ref{Int64}(0)
+    rc = GC.@preserve positions skipArg offsets idx cost hout hin ccall((:rrtx_extend_candidates_self, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{UInt8},
+         Ptr{UInt8}, Int64, Ref{Int64}),
+        tree.ctx, positions, nq, hyberBallRad, S.robotRadius, skipPtr, offsets, idx, cost, hout, hin, cap, needed)
+    if rc == RRTX_E_CAPACITY
+      cap = Int(needed[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    n = Int(needed[])
+    return ExtendCandidatesSelf(offsets, idx[1:n], cost[1:n], hout[1:n], hin[1:n])
+  end
+end
+
 # ---------------------------------------------------------------------------
 # findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) on the device, for a batch of
 # samples: what comes back per sample is a status, a parent, the sample's rrtLMC and the neighbours to rewire -- the
 # neighbour lists themselves stay on the device.  setNodeCosts uploads rrtLMC of the nodes a step changed
 # (0-based first index; a node never set reads as Inf); extendSelect reads that array.  A sample with an empty ball
 # (status RRTX_SEL_EMPTY) keeps the closestNode rule of findBestParent (:1931-1935) on the host: nearestIdx says which
-# node.  Samples of one batch do not see each other.
+# node.  The lists are against the tree as it stood (extend_candidates_self gives the samples' lists among themselves).
 const RRTX_SEL_OK = UInt8(0)
 const RRTX_SEL_NO_PARENT = UInt8(1)
 const RRTX_SEL_EMPTY = UInt8(2)

@@ -366,6 +366,32 @@ class Context:
         return dict(offsets=offsets, idx=idx[:n], cost=cost[:n], hit_out=hout[:n], hit_in=hin[:n],
                     nearest_idx=nidx, nearest_dist=ndist, sample_unsafe=unsafe)
 
+    def extend_candidates_self(self, q, r: float, robot_radius: float, skip=None, cap: Optional[int] = None) -> dict:
+        """rrtx_extend_candidates_self: the samples of one batch among themselves.  Row j of the CSR holds the batch
+        positions i < j within r of sample j (ascending), with the SimpleEdge cost and the collision flags of
+        q_j -> q_i (hit_out) and q_i -> q_j (hit_in).  skip: one byte per sample, non-zero = the sample has no list
+        and is in none (the sample_unsafe bytes of extend_candidates serve as they are).  The tree is not read.
+        dict(offsets, idx, cost, hit_out, hit_in); cap grows on demand."""
+        q = f64(q, (-1, self.dim))
+        nq = q.shape[0]
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+        if sk is not None and sk.shape[0] != nq:
+            raise ValueError("skip needs one byte per sample")
+        if cap is None:
+            cap = max(8 * nq, 1024)
+        offsets = np.empty(nq + 1, dtype=np.int64)
+
+        def call(cap, needed):
+            idx = np.empty(cap, dtype=np.int32)
+            cost = np.empty(cap, dtype=np.float64)
+            hout = np.empty(cap, dtype=np.uint8)
+            hin = np.empty(cap, dtype=np.uint8)
+            return self._lib.rrtx_extend_candidates_self(self._h, _capi._ptr(q), nq, r, robot_radius, _capi._ptr(sk),
+                                                         _capi._ptr(offsets), _capi._ptr(idx), _capi._ptr(cost),
+                                                         _capi._ptr(hout), _capi._ptr(hin), cap, needed), (idx, cost, hout, hin)
+        n, (idx, cost, hout, hin) = self._two_call(cap, call)
+        return dict(offsets=offsets, idx=idx[:n], cost=cost[:n], hit_out=hout[:n], hit_in=hin[:n])
+
     # ---- findBestParent + rewire test on the device -------------------------------------------------
     def node_cost_set(self, first_index: int, lmc):
         """rrtLMC of nodes first_index .. first_index + len(lmc) - 1 in the context's own device array (+Inf for a node
@@ -554,6 +580,12 @@ class Context:
         self._check(self._lib.rrtx_extend_candidates_dev(self._h, q_ptr, nq, r, robot_radius, offsets_ptr, idx_ptr,
                                                          cost_ptr, hit_out_ptr, hit_in_ptr, cap, needed_ptr,
                                                          nearest_idx_ptr, nearest_dist_ptr, unsafe_ptr))
+
+    def extend_candidates_self_dev(self, q_ptr: int, nq: int, r: float, robot_radius: float, skip_ptr: Optional[int],
+                                   offsets_ptr: int, idx_ptr: int, cost_ptr: int, hit_out_ptr: int, hit_in_ptr: int,
+                                   cap: int, needed_ptr: int):
+        self._check(self._lib.rrtx_extend_candidates_self_dev(self._h, q_ptr, nq, r, robot_radius, skip_ptr, offsets_ptr,
+                                                              idx_ptr, cost_ptr, hit_out_ptr, hit_in_ptr, cap, needed_ptr))
 
     def extend_candidates_dubins_dev(self, q_ptr: int, nq: int, r: float, robot_radius: float, r_min: float,
                                      offsets_ptr: int, idx_ptr: int, key_ptr: int, cost_out_ptr: int, cost_in_ptr: int,

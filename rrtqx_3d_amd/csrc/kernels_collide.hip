@@ -1756,9 +1756,12 @@ int launch_edges_spheres(rrtx_ctx *ctx, const double *p0_dev, const double *p1_d
 
 int launch_candidate_edges(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                            const int32_t *idx_dev, const int32_t *owner_dev, int64_t cap, double robot_radius,
-                           uint8_t *hit_out_dev, uint8_t *hit_in_dev, double r, uint8_t *sample_unsafe_dev) {
+                           uint8_t *hit_out_dev, uint8_t *hit_in_dev, double r, uint8_t *sample_unsafe_dev,
+                           const double *near_aos, int64_t n_near) {
   // r >= 0: radius of the ball the lists were built with -> per-sample sphere lists; r < 0: full loop
+  // near_aos / n_near: the table idx points into (null: the context's nodes)
   if (nq <= 0) return RRTX_OK;
+  if (!near_aos) { near_aos = ctx->nodes_aos; n_near = ctx->n_nodes; }
   int rc = sync_spheres(ctx, robot_radius);
   if (rc) return rc;
   const int m = ctx->sph_n_active;
@@ -1784,8 +1787,8 @@ int launch_candidate_edges(rrtx_ctx *ctx, const double *q_dev, int nq, const int
   span_begin(ctx, KF_EDGES);
   // the grid covers the caller's capacity; lanes past offsets[nq] idle
   hipLaunchKernelGGL(candidate_edges_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, q_dev,
-                     ctx->dim, offsets_dev, nq, idx_dev, owner_dev, reinterpret_cast<const double4 *>(ctx->nodes_aos),
-                     (int)ctx->n_nodes, (long long)cap, ctx->d_sph.as<SphRec>(), ctx->d_sph_reach_f.as<float>(), ctx->origin[0],
+                     ctx->dim, offsets_dev, nq, idx_dev, owner_dev, reinterpret_cast<const double4 *>(near_aos),
+                     (int)n_near, (long long)cap, ctx->d_sph.as<SphRec>(), ctx->d_sph_reach_f.as<float>(), ctx->origin[0],
                      ctx->origin[1], ctx->origin[2], m, lists, list_n, kSphListCap, r_bound, hit_out_dev, hit_in_dev);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
@@ -1797,9 +1800,11 @@ int launch_candidate_edges(rrtx_ctx *ctx, const double *q_dev, int nq, const int
 int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                                     const int32_t *idx_dev, const int32_t *owner_dev, int64_t cap,
                                     double robot_radius, uint8_t *hit_out_dev, uint8_t *hit_in_dev,
-                                    uint8_t *sample_unsafe_dev, double r) {
+                                    uint8_t *sample_unsafe_dev, double r, const double *near_aos, int64_t n_near) {
   // r >= 0: radius of the ball the lists were built with -> per-sample obstacle lists from the sample pass
+  // near_aos / n_near: the table idx points into (null: the context's nodes)
   if (nq <= 0) return RRTX_OK;
+  if (!near_aos) { near_aos = ctx->nodes_aos; n_near = ctx->n_nodes; }
   int rc = sync_polygons(ctx);
   if (rc) return rc;
   const double list_r = (r >= 0.0 && r - r == 0.0) ? r * (1.0 + 1e-8) : -1.0;
@@ -1820,8 +1825,8 @@ int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, 
   }
   PolyCsr csr;
   csr.q = q_dev; csr.offsets = offsets_dev; csr.idx = idx_dev; csr.owner = owner_dev;
-  csr.nodes_aos = reinterpret_cast<const double4 *>(ctx->nodes_aos);
-  csr.hit_in = hit_in_dev; csr.cap = (long long)cap; csr.nq = nq; csr.n_nodes = (int)ctx->n_nodes;
+  csr.nodes_aos = reinterpret_cast<const double4 *>(near_aos);
+  csr.hit_in = hit_in_dev; csr.cap = (long long)cap; csr.nq = nq; csr.n_nodes = (int)n_near;
   span_begin(ctx, KF_EDGES);
   // (without a time column a wave's scratch is 8 KB: five waves per SIMD, with the register budget cut to match)
   // the last eighth of the entries in waves of 32 (measured: 1/8 0.1314, 2/8 0.1319, 3/8 0.1326, 4/8 0.1347, none 0.1345 ms)

@@ -8,9 +8,9 @@
 //            adopted, and of exactly equal candidates the lowest list position wins.
 //   rewire   (only with a parent) every entry with hit_in[e] == 0, idx[e] != parent and
 //            lmc[idx[e]] > best + cost_in[e], reported in list order as (idx[e], best + cost_in[e]).
-// Samples of one batch do not see each other -- the lists are against the tree as it stood, exactly as in
-// rrtx_extend_candidates -- so a node may appear in the rewire lists of several samples; settling that is the
-// caller's bookkeeping.
+// The lists are against the tree as it stood, exactly as in rrtx_extend_candidates (the samples' lists among
+// themselves come from rrtx_extend_candidates_self, kernels_self.hip) -- so a node may appear in the rewire lists of
+// several samples; settling that is the caller's bookkeeping.
 //
 // Layout.  Segments average ~25 entries at C4 size and range from 0 to a few hundred: a wave per sample would idle
 // most lanes, a lane per sample would serialise the long lists, so the samples are dealt to sub-wave groups sized from

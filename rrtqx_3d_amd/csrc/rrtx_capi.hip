@@ -592,7 +592,7 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->ws_slab_hist, &ctx->ws_slab_start, &ctx->ws_slab_sr, &ctx->ws_slab_params, &ctx->ws_run_hist, &ctx->ws_run_sr,
                     &ctx->ws_copies_s,
                     &ctx->ws_meta_s, &ctx->ws_cb, &ctx->ws_qhist, &ctx->ws_qslot, &ctx->ws_bkt,
-                    &ctx->ws_ev_a, &ctx->ws_ev_cnt, &ctx->ws_confirm_args, &ctx->ws_sph_lists, &ctx->ws_poly_lists, &ctx->d_sph_sample,
+                    &ctx->ws_ev_a, &ctx->ws_ev_cnt, &ctx->ws_confirm_args, &ctx->ws_sph_lists, &ctx->ws_poly_lists, &ctx->ws_self, &ctx->d_sph_sample,
                     &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
                     &ctx->ws_swb_tab, &ctx->ws_swb_word, &ctx->ws_swb_seg_id, &ctx->ws_swb_seg_word, &ctx->ws_swb_blk_n, &ctx->ws_swb_cnt,
                     &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off, &ctx->ws_rel_stay, &ctx->ws_pswb_q, &ctx->ws_pswb_pos,
@@ -1892,6 +1892,83 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
     arena_flush(ctx);
   }
   return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
+}
+
+// ---- the samples of one extend batch among themselves (kernels_self.hip) ---------------------------
+// (what rrtx_extend_candidates refuses, with its codes and before anything is staged)
+static int extend_self_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,
+                            const double *cost, const uint8_t *hit_out, const uint8_t *hit_in, int64_t cap) {
+  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))
+    return fail(ctx, RRTX_E_INVALID, "extend_candidates_self: bad arguments");
+  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_candidates_self is the SimpleEdge (dim=3) path");
+  if (ctx->n_wraps != 0)
+    return fail(ctx, RRTX_E_STATE, "extend_candidates_self completes the lists of rrtx_extend_candidates, which needs a "
+                                   "space without wrapped dimensions");
+  if (nq >= (1 << 30)) return fail(ctx, RRTX_E_INVALID, "extend_candidates_self: at most 2^30 - 1 samples per call");
+  return RRTX_OK;
+}
+
+int rrtx_extend_candidates_self_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                    const uint8_t *skip, int64_t *offsets, int32_t *idx, double *cost,
+                                    uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed_dev) {
+  CHECK_CTX(ctx);
+  int rc = extend_self_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
+  if (rc || nq == 0) return rc;
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
+  const double *table = nullptr;
+  rc = launch_self_join(ctx, q, nq, r, skip, offsets, idx, cost, ctx->ws_owner.as<int32_t>(), cap, needed_dev, &table);
+  if (rc) return rc;
+  // both directed edges of every entry, by the kernels of rrtx_extend_candidates: the "near" end of entry e is row
+  // idx[e] of the sample table instead of a node; the per-sample obstacle lists are built for this batch and ball
+  const double rl = (r >= 0.0) ? r : -1.0;
+  if (ctx->opt_extend_polygons)
+    return launch_candidate_edges_polygons(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, robot_radius, hit_out,
+                                           hit_in, nullptr, rl, table, nq);
+  return launch_candidate_edges(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, robot_radius, hit_out, hit_in, rl,
+                                nullptr, table, nq);
+}
+
+int rrtx_extend_candidates_self(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                const uint8_t *skip, int64_t *offsets, int32_t *idx, double *cost, uint8_t *hit_out,
+                                uint8_t *hit_in, int64_t cap, int64_t *needed) {
+  CHECK_CTX(ctx);
+  int rc = extend_self_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
+  if (rc) return rc;
+  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
+  const int64_t dcap = cap > 0 ? cap : 1;
+  const size_t off_bytes = sizeof(int64_t) * ((size_t)nq + 2);      // offsets[nq + 1], then the count
+  const size_t q_bytes = sizeof(double) * (size_t)nq * 3;
+  rc = arena_begin(ctx, off_bytes + q_bytes + (size_t)nq + 512);
+  if (rc) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
+  if (skip && (rc = stage_in_small(ctx, ctx->ws_q2, skip, (size_t)nq))) return rc;
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(off_bytes));
+  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)dcap));
+  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)dcap));
+  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)dcap));
+  RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)dcap));
+  int64_t *off_dev = ctx->ws_out_off.as<int64_t>();
+  rc = rrtx_extend_candidates_self_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius,
+                                       skip ? ctx->ws_q2.as<uint8_t>() : nullptr, off_dev, ctx->ws_out_idx.as<int32_t>(),
+                                       ctx->ws_out_dist.as<double>(), ctx->ws_out_u8a.as<uint8_t>(),
+                                       ctx->ws_out_u8b.as<uint8_t>(), cap, off_dev + nq + 1);
+  if (rc) return rc;
+  char *host_blk = arena_take(ctx, off_bytes);
+  if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "extend_candidates_self: staging arena");
+  RRTX_HIP(ctx, hipMemcpyAsync(host_blk, off_dev, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(offsets, host_blk, sizeof(int64_t) * ((size_t)nq + 1));
+  const int64_t total = reinterpret_cast<const int64_t *>(host_blk)[nq + 1];
+  if ((rc = check_capacity(ctx, "extend_candidates_self", "neighbours", total, cap, needed))) return rc;
+  if (total > 0) {
+    if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)total))) return rc;
+    if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
+    if ((rc = d2h(ctx, hit_out, ctx->ws_out_u8a.p, (size_t)total))) return rc;
+    if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    arena_flush(ctx);
+  }
+  return RRTX_OK;
 }
 
 static int extend_dubins_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,

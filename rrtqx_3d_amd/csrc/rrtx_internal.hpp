@@ -242,6 +242,7 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_i32a, ws_i32b;  // staged index arrays
   rrtx::DevBuf ws_sph_lists;      // per sample: spheres its candidate edges can touch (+ counts)
   rrtx::DevBuf ws_poly_lists;     // per sample: polygons its candidate edges can reach (+ counts), uint16
+  rrtx::DevBuf ws_self;           // rrtx_extend_candidates_self: sample table, its fp32 shadow, row counts, max |q - origin|
 
   // device mirror of the planner's directed edges (obstacle sweeps, kernels_sweep.hip)
   int32_t *ge_start = nullptr, *ge_end = nullptr;
@@ -424,15 +425,23 @@ int launch_detmath_eval(rrtx_ctx *ctx, int op, const double *x_dev, const double
 int launch_dubins_trajectory(rrtx_ctx *ctx, const double *s_dev, const double *g_dev, int64_t ne, double r_min,
                              const int64_t *traj_off_dev, double *traj_xy_dev, int64_t cap_rows,
                              int32_t *traj_len_dev);
-// candidate edges of extend(): for every CSR entry both directed edges vs the sphere list
+// candidate edges of extend(): for every CSR entry both directed edges vs the sphere list.  idx[e] is a row of
+// near_aos (four doubles a row, n_near rows): the context's nodes unless a table is given (the samples themselves,
+// rrtx_extend_candidates_self)
 int launch_candidate_edges(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                            const int32_t *idx_dev, const int32_t *owner_dev, int64_t cap, double robot_radius,
                            uint8_t *hit_out_dev, uint8_t *hit_in_dev, double r = -1.0,
-                           uint8_t *sample_unsafe_dev = nullptr);
+                           uint8_t *sample_unsafe_dev = nullptr, const double *near_aos = nullptr, int64_t n_near = 0);
 int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                                     const int32_t *idx_dev, const int32_t *owner_dev, int64_t cap,
                                     double robot_radius, uint8_t *hit_out_dev, uint8_t *hit_in_dev,
-                                    uint8_t *sample_unsafe_dev, double r = -1.0);
+                                    uint8_t *sample_unsafe_dev, double r = -1.0, const double *near_aos = nullptr,
+                                    int64_t n_near = 0);
+// the samples of a batch among themselves (kernels_self.hip): CSR of the earlier samples within r of every sample,
+// keys and owners; device pointers, *needed_dev = entries found, no entry at or beyond cap is written
+int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev, int64_t *offsets_dev,
+                     int32_t *idx_dev, double *cost_dev, int32_t *owner_dev, int64_t cap, int64_t *needed_dev,
+                     const double **table_out);
 int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                               const int32_t *idx_dev, const double *dist_dev, int32_t *nearest_idx_dev,
                               double *nearest_dist_dev);

@@ -546,6 +546,27 @@ def extend_candidates(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: flo
     return out
 
 
+def extend_candidates_self(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, skip=None):
+    """What extend_candidates leaves out: its lists are against the tree as it stood, this call gives the lists of the
+    batch's samples among themselves.  Row j: the batch positions i < j with KDdist(q_j, q_i) < hyberBallRad_ -- what
+    kdFindWithinRange adds to j's list when the samples are inserted one after the other -- with the SimpleEdge cost and
+    the flags of q_j -> q_i (hit_out) and q_i -> q_j (hit_in).  skip: non-zero bytes take a sample out of every list
+    (pass sample_unsafe of extend_candidates).  The caller maps idx to the node index each earlier sample received and
+    drops the entries of samples it did not insert; the tree list followed by this list is then the reference's."""
+    if tree.d != 3:
+        error("extend_candidates_self is the SimpleEdge (3-D) path")
+    S.bind(tree)
+    kind = _sync_obstacles(S)
+    from . import _capi
+    tree.ctx.set_option(_capi.RRTX_OPT_EXTEND_OBSTACLES, kind)
+    q = np.asarray(newPositions, dtype=np.float64).reshape(-1, 3)
+    out = tree.ctx.extend_candidates_self(q, float(hyberBallRad_), S.robotRadius, skip=skip)
+    if S.inWarmupTime:
+        out["hit_out"][:] = 0
+        out["hit_in"][:] = 0
+    return out
+
+
 def extend_select(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, lmc=None):
     """findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) for many samples at once, on
     the device: per sample the parent, its own rrtLMC and the neighbours whose rrtLMC it would lower, as
@@ -553,7 +574,8 @@ def extend_select(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, 
     sample_unsafe); status is one of _capi.RRTX_SEL_OK / NO_PARENT / UNSAFE.  lmc: rrtLMC per node in insertion
     order, or None for the values Context.node_cost_set left on the device (RRTNode.rrtLMC then answers for the
     closestNode rule).  A sample with an empty ball is linked to closestNode as the reference does (:1930-1935): one
-    edge each way through calculateTrajectory / explicitEdgeCheck.  Samples of one batch do not see each other."""
+    edge each way through calculateTrajectory / explicitEdgeCheck.  The lists are against the tree as it stood
+    (extend_candidates_self gives the lists of the batch's samples among themselves)."""
     if tree.d != 3:
         error("extend_select is the SimpleEdge (3-D) path")
     if S.inWarmupTime:
