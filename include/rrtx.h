@@ -126,7 +126,9 @@ int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out);
  *   per-query hit buckets of the range search in units of cap / nq; 2, 4, 8 or 16. */
 #define RRTX_OPT_BUCKET_MULT 10
 /*   RRTX_OPT_TUNE (default 0): bit mask of kernel variants under measurement; results are identical.  Bit 4:
- *   the culled range search without ghosts keeps the place pass (RRTX_OPT_LAST_PLACEMENT). */
+ *   the culled range search without ghosts keeps the place pass (RRTX_OPT_LAST_PLACEMENT).  Value 8 (bit 3): the tile
+ *   kernel of the culled range search keeps its looped form where the straight one would run
+ *   (rrtx_last_tile_form). */
 #define RRTX_OPT_TUNE 11
 /*   RRTX_OPT_SPACE_HAS_TIME (default 0; dim = 4 only): CSpace.spaceHasTime (R/DRRT_data_structures.jl:330) for the
  *   Dubins entry points.  The third coordinate of [x y t theta] is then time (planning runs in reverse time:
@@ -169,6 +171,12 @@ int rrtx_set_option(rrtx_ctx *ctx, int option, int64_t value);
 /* The value an option currently has (as rrtx_set_option normalised it): callers that size buffers by an
  * option -- the row width of rrtx_dubins_trajectory -- read it here instead of keeping a shadow copy. */
 int rrtx_get_option(rrtx_ctx *ctx, int option, int64_t *value);
+/* The form of the tile kernel in the last range search (read only, a fact about the last call and no option):
+ * 0 no tile kernel (no culling), 1 looped (a workgroup walks several tiles: more than 4096 (tile, part) pairs, i.e.
+ * batches beyond 65 536 copies; or several chunk passes: trees beyond 524 288 nodes; or RRTX_OPT_TUNE value 8),
+ * 2 straight (one tile and one chunk pass per workgroup, compiled without the two loops).  Both forms give the same
+ * lists. */
+int rrtx_last_tile_form(rrtx_ctx *ctx, int *form);
 /* Host-pointer entry points move their results through a pinned staging arena owned by the context (DMA at PCIe rate,
  * then one memcpy per output array).  A caller that keeps its output arrays alive across calls -- the Julia host
  * preallocates them -- can have them page-locked instead: after rrtx_host_register(ptr, bytes) every output pointer

@@ -93,6 +93,7 @@ SYMBOLS = [
     ("rrtx_stats", C.c_int, [_VP, C.POINTER(Stats)]),
     ("rrtx_set_option", C.c_int, [_VP, C.c_int, C.c_int64]),
     ("rrtx_get_option", C.c_int, [_VP, C.c_int, c_int64_p]),
+    ("rrtx_last_tile_form", C.c_int, [_VP, C.POINTER(C.c_int)]),
     ("rrtx_host_register", C.c_int, [_VP, _VP, C.c_size_t]),
     ("rrtx_host_unregister", C.c_int, [_VP, _VP]),
     ("rrtx_nodes_append", C.c_int, [_VP, _VP, C.c_int64, c_int64_p]),

@@ -91,6 +91,12 @@ class Context:
         self._check(self._lib.rrtx_get_option(self._h, option, C.byref(v)))
         return int(v.value)
 
+    def last_tile_form(self) -> int:
+        """rrtx_last_tile_form: 0 no tile kernel in the last range search, 1 its looped form, 2 its straight form"""
+        v = C.c_int()
+        self._check(self._lib.rrtx_last_tile_form(self._h, C.byref(v)))
+        return int(v.value)
+
     @property
     def space_has_time(self) -> bool:
         """CSpace.spaceHasTime as the CONTEXT holds it (no shadow copy: buffers are sized from this)."""

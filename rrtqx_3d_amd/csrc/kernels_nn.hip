@@ -686,7 +686,12 @@ __device__ __forceinline__ void load_qhist16(const int *__restrict__ qhist, int 
   }
 }
 
-template <int D, bool EXT, bool SL>
+// ONE (the straight form; plan_radius, RadiusPlan::straight): every workgroup has at most one tile and the tree at
+// most kTbList chunks, so the tile loop is one conditional pass and the chunk-pass loop one pass over [0, n_chunks).
+// Both loop bodies are the same text for both forms; only the loop heads, the list reset between passes and the
+// barrier before the next tile differ.  What the looped form hoists out of the two loops and keeps (or spills) for
+// the whole kernel is then computed where it is used.
+template <int D, bool EXT, bool SL, bool ONE>
 __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     const float *__restrict__ fx, const float *__restrict__ fy, const float *__restrict__ fz,
     const float *__restrict__ fw, const float *__restrict__ fpp, int n_nodes, int n_chunks,
@@ -712,7 +717,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
   const int n_slots = (int)gridDim.x / n_parts;            // tiles in flight per sweep of the grid
   const int slot = (int)blockIdx.x / n_parts;
   const int my = (n_slots % 8 == 0) ? (slot % 8) * (n_slots / 8) + slot / 8 : slot;   // a permutation of the slots
-  for (int tile = my; tile < n_tiles; tile += n_slots) {
+  for (int tile = my; tile < n_tiles; tile += n_slots) {     // (ONE: n_tiles <= n_slots, left after the first pass)
     const int q0 = tile * kTileB;
     const int q1 = min(q0 + kTileB, n_copies);
     int wn = 0;                             // wave-uniform: entries in the slice
@@ -863,9 +868,9 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     bool gmode_w0 = false;                  // (wave 0) this tile's sorted part is listed as groups
     // (no copy of the tile can have a neighbour: nothing to list or screen)
     if (lo <= hi) {
-      for (int cb = 0; cb < n_chunks; cb += kTbList) {
+      for (int cb = 0; ONE || cb < n_chunks; cb += kTbList) {   // (ONE: n_chunks <= kTbList, left after the first pass)
         // ---- 2. chunk list of this pass: chunk ids in [cb, ce) ----
-        const int ce = min(cb + kTbList, n_chunks);
+        const int ce = ONE ? n_chunks : min(cb + kTbList, n_chunks);
         if (wave == 0) {
           const int w_end = min(ce, tg.n_sorted_chunks);
           if (cb == 0 && tg.groups && w_end > 0) {
@@ -1017,6 +1022,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
                                    sm.cf);
           visited += kChunkF / 8;
         }
+        if constexpr (ONE) break;
         if (ce < n_chunks) {  // (trees beyond kTbList chunks) the list is rebuilt by the next pass
           __syncthreads();
           if (t == 0) sm.n_list = 0;
@@ -1082,8 +1088,9 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
       }
     }
     RRTX_TILE_CLK(6);
-    __syncthreads();          // LDS is reused by the next tile
+    if constexpr (!ONE) __syncthreads();          // LDS is reused by the next tile
     RRTX_TILE_CLK(7);
+    if constexpr (ONE) break;
   }
   if (lane == 0) visits[slice] = visited;
 }
@@ -1215,6 +1222,9 @@ struct RadiusPlan {
   unsigned scan_grid;   // workgroups: culled min(tiles * n_parts, 4096); screened min(n_tiles * n_seg,
                         // opt_scan_blocks in eights); exact n_tiles * n_seg
   int n_slices;         // entry slices = waves of the scan grid (exact scan: none)
+  bool straight;        // culled: the tile kernel's straight form (ONE) -- true iff use_cull, the grid is not capped
+                        // (n_tiles_b * n_parts <= 4096: a workgroup has at most one tile) and n_chunks <= kTbList
+                        // (one chunk pass), unless RRTX_OPT_TUNE bit 3 keeps the looped form
   int slice_cap;        // entries per slice.  Culled: 64 * kTileB + kTbSlack, a wave drains its slice when
                         // wn + 64 * kTileB > slice_cap; screened: 64 * tile_q + kEvSlack, drained likewise
 };
@@ -1276,6 +1286,7 @@ RadiusPlan plan_radius(const rrtx_ctx *ctx, int nq, int64_t cap, unsigned prev_o
     p.n_parts = std::min(64, (1024 + n_tiles_b - 1) / n_tiles_b);
     p.scan_grid = (unsigned)std::min(4096ll, (long long)n_tiles_b * p.n_parts);   // (capped: n_parts == 1)
     p.slice_cap = 64 * kTileB + kTbSlack;
+    p.straight = (long long)n_tiles_b * p.n_parts <= 4096 && p.n_chunks <= kTbList && !tune.loop_form;
   } else if (p.use_filter) {              // persistent grid striding over the work
     const unsigned pg = std::max(8u, (unsigned)ctx->opt_scan_blocks / 8u * 8u);
     p.scan_grid = std::min(p.scan_grid, pg);
@@ -1414,25 +1425,30 @@ void radius_scan_tiles(rrtx_ctx *ctx, const RadiusPlan &p, const RadiusArgs &d) 
   tpl.qhist = d.qhist; tpl.tab = d.qs.tab; tpl.spill_key = d.qs.spill_key;
   tpl.n_buckets = p.n_buckets; tpl.capb = p.capb; tpl.spill_base = p.spill_base; tpl.n_tab = p.n_tab;
   const int wi = ctx->dim == 4 ? 3 : 2;
-#define RRTX_TILE_LAUNCH(DD, EE, SS)                                                                                   \
-  hipLaunchKernelGGL((nn_tile_kernel<DD, EE, SS>), dim3(p.scan_grid), dim3(kScanThreads), 0, ctx->stream,              \
+#define RRTX_TILE_LAUNCH_F(DD, EE, SS, OO)                                                                             \
+  hipLaunchKernelGGL((nn_tile_kernel<DD, EE, SS, OO>), dim3(p.scan_grid), dim3(kScanThreads), 0, ctx->stream,          \
                      ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2], ctx->sl_f[wi], ctx->sl_pp, p.n_nodes, p.n_chunks,       \
                      reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),                                               \
                      SS ? nullptr : ctx->ws_copies_s.as<typename QRecT<DD>::type>(),                                   \
                      SS ? nullptr : ctx->ws_copies_f.as<typename QRecFT<DD>::type>(), d.sc, p.n_parts,                 \
                      ctx->ws_ev_a.as<int2>(), p.slice_cap, d.ca, d.ca_dev, tg, d.xd, ctx->ws_ev_cnt.as<int>(),         \
                      p.n_slots == 1 ? p.nq : -1, tpl)
+#define RRTX_TILE_LAUNCH(DD, EE, SS)                                                                                   \
+  do { if (p.straight) RRTX_TILE_LAUNCH_F(DD, EE, SS, true); else RRTX_TILE_LAUNCH_F(DD, EE, SS, false); } while (0)
   for_dim(ctx->dim, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     if constexpr (D == 3) {               // (only the 3-D search carries the extend() work)
       if (p.fuse) {
-        if (p.slot_route) RRTX_TILE_LAUNCH(3, true, true); else RRTX_TILE_LAUNCH(3, true, false);
+        if (p.slot_route) RRTX_TILE_LAUNCH(3, true, true);
+        else RRTX_TILE_LAUNCH(3, true, false);
         return;
       }
     }
-    if (p.slot_route) RRTX_TILE_LAUNCH(D, false, true); else RRTX_TILE_LAUNCH(D, false, false);
+    if (p.slot_route) RRTX_TILE_LAUNCH(D, false, true);
+    else RRTX_TILE_LAUNCH(D, false, false);
   });
 #undef RRTX_TILE_LAUNCH
+#undef RRTX_TILE_LAUNCH_F
 }
 
 // scan, brute force.  Screened: entries into the waves' slices, then their exact confirmation, one lane per entry;
@@ -1517,6 +1533,7 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   if (p.fuse) ext->fused = true;
   ctx->last_culled = p.use_cull;
   ctx->last_placement = p.slot_route ? 2 : (p.use_cull ? 1 : 0);
+  ctx->last_tile_form = p.use_cull ? (p.straight ? 2 : 1) : 0;
   ctx->last_tile_q = p.use_cull ? kTileB : p.tile_q;
   if (p.use_cull) ctx->last_visit_slices = p.n_slices;
   ctx->last_pairs = (int64_t)p.n_copies_max * p.n_nodes;

@@ -722,6 +722,13 @@ int rrtx_get_option(rrtx_ctx *ctx, int option, int64_t *value) {
   }
 }
 
+int rrtx_last_tile_form(rrtx_ctx *ctx, int *form) {
+  CHECK_CTX(ctx);
+  if (!form) return fail(ctx, RRTX_E_INVALID, "last_tile_form: null output");
+  *form = ctx->last_tile_form;
+  return RRTX_OK;
+}
+
 int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out) {
   CHECK_CTX(ctx);
   if (!out) return fail(ctx, RRTX_E_INVALID, "stats: out is NULL");

@@ -296,6 +296,7 @@ struct rrtx_ctx {
   int last_tile_q = 0;
   bool last_culled = false;         // the last range search used the slab-culled scan
   int last_placement = 0;           // RRTX_OPT_LAST_PLACEMENT of the last range search
+  int last_tile_form = 0;           // rrtx_last_tile_form: 0 none, 1 looped, 2 straight
   int64_t last_sweep_candidates = 0;
   int last_visit_slices = 0;        // entries of ws_ev_cnt holding its per-wave chunk counts
 };
@@ -324,13 +325,14 @@ struct TuneBits {
   bool xy_order;       // bit 0: order the query copies by (x, y) bucket only (g3 = 1)
   bool whole_chunks;   // bit 1: the tile kernel lists whole chunks, never groups of eight positions
   bool place_pass;     // bit 2 (value 4): the place pass orders the copies even without ghosts
+  bool loop_form;      // bit 3 (value 8): the tile kernel keeps its looped form where the straight one would run
   int kz_bins;         // bits 8-15: bins of the third coordinate inside a slab cell (0: kSlabKz)
   int g3_side;         // bits 16-20: side of the cubic grid of query buckets (0: from the batch size)
   int cell_shift;      // bits 24-25: slab cells of kSlabChunk >> cell_shift nodes
 };
 inline TuneBits tune_bits(const rrtx_ctx *ctx) {
   const int t = ctx->opt_tune;
-  return TuneBits{(t & 1) != 0, (t & 2) != 0, (t & 4) != 0, (t >> 8) & 0xff, (t >> 16) & 0x1f, (t >> 24) & 3};
+  return TuneBits{(t & 1) != 0, (t & 2) != 0, (t & 4) != 0, (t & 8) != 0, (t >> 8) & 0xff, (t >> 16) & 0x1f, (t >> 24) & 3};
 }
 
 // One launch site per kernel template: fn (a generic lambda) gets the dimension as std::integral_constant<int, 3>

@@ -33,6 +33,9 @@ with Context(3, node_capacity=cfg.n_nodes) as ctx:
         print(f"{n_runs} runs appended, {ctx.n_nodes} nodes")
     for _ in range(3):
         out = ctx.extend_candidates(Q, r, 0.5)
+    form = ctx.last_tile_form()
+    print(f"tile kernel form: {('none', 'looped', 'straight')[form]} (rrtx_last_tile_form = {form}; no barrier "
+          f"between hand-out and end in the straight form)")
     L = _capi.load()
     n_wg = (cfg.batch + 15) // 16
     buf = np.zeros(n_wg * 16, dtype=np.uint64)
