@@ -585,8 +585,8 @@ int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, dou
  *            bad pointers or negative counts are RRTX_E_INVALID; a radius is taken as rrtx_extend_candidates takes it
  *            (r <= 0 or NaN: every list is empty).  Obstacles: the spheres or the polygons by
  *            RRTX_OPT_EXTEND_OBSTACLES; kinds 6 / 7 read time from the third coordinate.  The tree is not read: the
- *            call works whatever the tree holds, an empty tree included.  Dubins lists and a radius per sample are
- *            out of scope.
+ *            call works whatever the tree holds, an empty tree included.  The Dubins lists come from
+ *            rrtx_extend_candidates_self_dubins; a radius per sample is out of scope.
  *   Lists    CSR offsets[nq + 1] from 0.  Row j: the batch positions i < j, ascending, with s = sq3(q_j, q_i) < thr,
  *            thr = the first_ge threshold of r (rrtx_sq_thresholds), the test the range search applies to a non-root
  *            node.  There is no root rule: the root is a tree node, never a sample.  idx[e] = i, a 0-based position
@@ -619,6 +619,41 @@ int rrtx_extend_candidates_dubins(rrtx_ctx *ctx, const double *q, int nq, double
                                   double *cost_in, uint8_t *word_out, uint8_t *word_in, uint8_t *hit_out,
                                   uint8_t *hit_in, int64_t cap, int64_t *needed, int32_t *nearest_idx,
                                   double *nearest_dist, uint8_t *sample_unsafe);
+
+/* ---- the samples of one Dubins extend batch among themselves ------------------- */
+/* What rrtx_extend_candidates_self is to rrtx_extend_candidates, for Edge = DubinsEdge: the lists of
+ * rrtx_extend_candidates_dubins are against the tree as it stood, this call gives, per sample j of a batch q
+ * (nq x 4, [x y t theta]), the batch positions i < j that kdFindWithinRange (R/kdTree_general.jl:830) and its ghost
+ * iterator (R/ghostPoint.jl:60-111) add to j's list when the samples are inserted one after the other.  The tree list
+ * of rrtx_extend_candidates_dubins followed by this list, with idx mapped to the node index each earlier sample
+ * received (entries of samples that were not inserted dropped), is the reference's list, keys included.
+ *   Scope    dim == 4, otherwise RRTX_E_STATE; the wrapped dimensions are the context's (rrtx_set_wrap, 0 to 3 of them);
+ *            bad pointers or negative counts are RRTX_E_INVALID; r <= 0 or NaN: every list is empty.  The tree is not
+ *            read.  A radius per sample is out of scope.
+ *   Copies   the query is sample j with its 2^w copies, by the rule of the range search: slot 0 is the sample, slot k
+ *            shifts the wrapped dimensions whose bit is set in k (the last wrapped dimension is the least significant
+ *            bit); a shifted coordinate p < period / 2 becomes p + period with closest unwrapped coordinate period,
+ *            otherwise p - period with closest unwrapped coordinate 0; a ghost is skipped when
+ *            sq4(closest, ghost) >= the first_gt threshold of r.  The earlier sample i is taken as it is.
+ *   Lists    CSR offsets[nq + 1] from 0.  Entry (j, i) exists iff both samples are live, i < j and some non-skipped
+ *            slot k has s_k = sq4(copy_k(q_j), q_i) < thr, thr = the first_ge threshold of r (rrtx_sq_thresholds).
+ *            key[e] = sqrt(s_k), correctly rounded, of the LOWEST such k: addToRangeList keeps the first discovery.
+ *            There is no root rule.  Rows are ascending in i; idx[e] = i is a 0-based position in q.
+ *   Entries  cost_out / word_out / hit_out: the directed Dubins edge q_j -> q_i (new node -> earlier node);
+ *            cost_in / word_in / hit_in: q_i -> q_j; by the steering and check kernels of
+ *            rrtx_extend_candidates_dubins, so RRTX_OPT_SPACE_HAS_TIME (bit 1 of a flag byte = !validMove),
+ *            rrtx_set_dubins_velocity, RRTX_OPT_DUBINS_TIME_COLUMN, moving polygons and the active flags hold as
+ *            there.  word_out / word_in (3 bytes per entry) may be NULL.
+ *   skip     nq bytes or NULL.  A sample with skip[j] != 0 has an empty list and appears in no list; the
+ *            sample_unsafe bytes of the rrtx_extend_candidates_dubins call on the same batch can be passed as they
+ *            are.  A sample with a non-finite coordinate, in any of the four, likewise.
+ *   Capacity the two-call pattern: more than cap entries is RRTX_E_CAPACITY with *needed set and offsets valid;
+ *            cap == 0 (arrays may be NULL) counts; nq == 0 is RRTX_OK with offsets[0] = 0.
+ * Exact, no tolerance; nothing in the result depends on launch geometry or on the order in which waves finish. */
+int rrtx_extend_candidates_self_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                       double r_min, const uint8_t *skip, int64_t *offsets, int32_t *idx, double *key,
+                                       double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
+                                       uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
 
 /* ---- device-resident variants (inputs/outputs are DEVICE pointers) ------------ */
 int rrtx_nn_nearest_dev(rrtx_ctx *ctx, const double *q, int nq, int32_t *idx, double *dist);
@@ -655,6 +690,15 @@ int rrtx_extend_candidates_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, do
                                       double *cost_in, uint8_t *word_out, uint8_t *word_in, uint8_t *hit_out,
                                       uint8_t *hit_in, int64_t cap, int64_t *needed_dev, int32_t *nearest_idx,
                                       double *nearest_dist, uint8_t *sample_unsafe);
+
+/* device-pointer form of rrtx_extend_candidates_self_dubins (skip, word_out, word_in may be NULL): *needed_dev receives
+ * the number of entries, no entry at or beyond cap is written (with more than cap entries none is, offsets stays
+ * valid).  Only enqueues; the growth of a workspace may wait on the stream once. */
+int rrtx_extend_candidates_self_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                           double r_min, const uint8_t *skip, int64_t *offsets, int32_t *idx,
+                                           double *key, double *cost_out, double *cost_in, uint8_t *word_out,
+                                           uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in, int64_t cap,
+                                           int64_t *needed_dev);
 
 /* Per-edge collision bitmask for the multi-GPU exchange (RCCL all-reduce over
  * xGMI): bit e (e < cap) = hit_out[e], bit cap+e = hit_in[e]; entries at or

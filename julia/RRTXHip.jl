@@ -1031,3 +1031,48 @@ function extend_candidates_dubins(tree::HipTree, S::TS, positions::Array{Float64
     return ExtendCandidatesDubins(offsets, idx[1:n], key[1:n], cout[1:n], cin[1:n], hout[1:n], hin[1:n], nidx, ndist, unsafe)
   end
 end
+
+# The lists of extend_candidates_dubins are against the tree as it stood; this gives the lists of the batch's samples
+# among themselves, in the wrapped space.  Row j: the batch positions i < j (0-based, ascending) that kdFindWithinRange
+# and its ghost iterator add to j's list when the samples are inserted one after the other, with the key of the first
+# copy of q_j that reaches q_i and the Dubins cost and flags of q_j -> q_i (Out) and q_i -> q_j (In).  skip: one byte
+# per sample, non-zero = the sample has no list and is in none (sampleUnsafe of extend_candidates_dubins serves as it
+# is).  The caller appends row j to the tree list of sample j with idx mapped to the node index each earlier sample
+# received, dropping the samples it did not insert.
+struct ExtendCandidatesSelfDubins
+  offsets::Vector{Int64}      # nq + 1
+  idx::Vector{Int32}          # 0-based positions in the batch
+  key::Vector{Float64}
+  costOut::Vector{Float64}
+  costIn::Vector{Float64}
+  hitOut::Vector{UInt8}
+  hitIn::Vector{UInt8}
+end
+
+function extend_candidates_self_dubins(tree::HipTree, S::TS, positions::Array{Float64,2}, hyberBallRad::Float64;
+                                       skip::Union{Nothing,Vector{UInt8}} = nothing) where {TS}
+  nq = size(positions, 2)                     # 4 x nq
+  skip === nothing || length(skip) == nq || error("skip needs one byte per sample")
+  skipArg = skip === nothing ? UInt8[] : skip
+  skipPtr = skip === nothing ? Ptr{UInt8}(C_NULL) : pointer(skipArg)
+  offsets = Vector{Int64}(undef, nq + 1)
+  cap = max(8 * nq, 1024)
+  while true
+    idx = Vector{Int32}(undef, cap); key = Vector{Float64}(undef, cap)
+    cout = Vector{Float64}(undef, cap); cin = Vector{Float64}(undef, cap)
+    hout = Vector{UInt8}(undef, cap); hin = Vector{UInt8}(undef, cap)
+    needed = Ref{Int64}(0)
+    rc = GC.@preserve positions skipArg offsets idx key cout cin hout hin ccall((:rrtx_extend_candidates_self_dubins, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Int64, Ref{Int64}),
+        tree.ctx, positions, nq, hyberBallRad, S.robotRadius, S.minTurningRadius, skipPtr, offsets, idx, key, cout, cin,
+        C_NULL, C_NULL, hout, hin, cap, needed)
+    if rc == RRTX_E_CAPACITY
+      cap = Int(needed[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    n = Int(needed[])
+    return ExtendCandidatesSelfDubins(offsets, idx[1:n], key[1:n], cout[1:n], cin[1:n], hout[1:n], hin[1:n])
+  end
+end

@@ -557,6 +557,40 @@ class Context:
                     word_out=wo[:n].view("S3").ravel(), word_in=wi[:n].view("S3").ravel(), hit_out=ho[:n],
                     hit_in=hi[:n], nearest_idx=nidx, nearest_dist=ndist, sample_unsafe=unsafe)
 
+    def extend_candidates_self_dubins(self, q, r: float, robot_radius: float, r_min: float, skip=None,
+                                      cap: Optional[int] = None) -> dict:
+        """rrtx_extend_candidates_self_dubins: the samples of one Dubins batch among themselves (dim 4, the wrapped
+        dimensions as set).  Row j of the CSR holds the batch positions i < j that a copy of sample j reaches within r
+        (ascending), with the key of the first such copy and the Dubins cost, word and flags of q_j -> q_i (out) and
+        q_i -> q_j (in), as extend_candidates_dubins reports them.  skip: one byte per sample, non-zero = the sample has
+        no list and is in none (the sample_unsafe bytes of extend_candidates_dubins serve as they are).  The tree is
+        not read.  dict(offsets, idx, key, cost_out, cost_in, word_out, word_in, hit_out, hit_in); cap grows on demand."""
+        q = f64(q, (-1, 4))
+        nq = q.shape[0]
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+        if sk is not None and sk.shape[0] != nq:
+            raise ValueError("skip needs one byte per sample")
+        if cap is None:
+            cap = max(8 * nq, 1024)
+        offsets = np.empty(nq + 1, dtype=np.int64)
+
+        def call(cap, needed):
+            idx = np.empty(cap, dtype=np.int32)
+            key = np.empty(cap, dtype=np.float64)
+            co = np.empty(cap, dtype=np.float64)
+            ci = np.empty(cap, dtype=np.float64)
+            wo = np.empty((cap, 3), dtype=np.uint8)
+            wi = np.empty((cap, 3), dtype=np.uint8)
+            ho = np.empty(cap, dtype=np.uint8)
+            hi = np.empty(cap, dtype=np.uint8)
+            return self._lib.rrtx_extend_candidates_self_dubins(
+                self._h, _capi._ptr(q), nq, r, robot_radius, r_min, _capi._ptr(sk), _capi._ptr(offsets), _capi._ptr(idx),
+                _capi._ptr(key), _capi._ptr(co), _capi._ptr(ci), _capi._ptr(wo), _capi._ptr(wi), _capi._ptr(ho),
+                _capi._ptr(hi), cap, needed), (idx, key, co, ci, wo, wi, ho, hi)
+        n, (idx, key, co, ci, wo, wi, ho, hi) = self._two_call(cap, call)
+        return dict(offsets=offsets, idx=idx[:n], key=key[:n], cost_out=co[:n], cost_in=ci[:n],
+                    word_out=wo[:n].view("S3").ravel(), word_in=wi[:n].view("S3").ravel(), hit_out=ho[:n], hit_in=hi[:n])
+
     # ---- device-pointer variants (pointers are ints, e.g. torch.Tensor.data_ptr()) ----------------
     def nn_nearest_dev(self, q_ptr: int, nq: int, idx_ptr: int, dist_ptr: int):
         self._check(self._lib.rrtx_nn_nearest_dev(self._h, q_ptr, nq, idx_ptr, dist_ptr))
@@ -602,6 +636,15 @@ class Context:
             self._h, q_ptr, nq, r, robot_radius, r_min, offsets_ptr, idx_ptr, key_ptr, cost_out_ptr, cost_in_ptr,
             word_out_ptr, word_in_ptr, hit_out_ptr, hit_in_ptr, cap, needed_ptr, nearest_idx_ptr, nearest_dist_ptr,
             unsafe_ptr))
+
+    def extend_candidates_self_dubins_dev(self, q_ptr: int, nq: int, r: float, robot_radius: float, r_min: float,
+                                          skip_ptr: Optional[int], offsets_ptr: int, idx_ptr: int, key_ptr: int,
+                                          cost_out_ptr: int, cost_in_ptr: int, word_out_ptr: Optional[int],
+                                          word_in_ptr: Optional[int], hit_out_ptr: int, hit_in_ptr: int, cap: int,
+                                          needed_ptr: int):
+        self._check(self._lib.rrtx_extend_candidates_self_dubins_dev(
+            self._h, q_ptr, nq, r, robot_radius, r_min, skip_ptr, offsets_ptr, idx_ptr, key_ptr, cost_out_ptr, cost_in_ptr,
+            word_out_ptr, word_in_ptr, hit_out_ptr, hit_in_ptr, cap, needed_ptr))
 
     def pack_hits_dev(self, hit_out_ptr: int, hit_in_ptr: int, n_valid_ptr: int, cap: int, words_ptr: int):
         self._check(self._lib.rrtx_pack_hits_dev(self._h, hit_out_ptr, hit_in_ptr, n_valid_ptr, cap, words_ptr))

@@ -2071,6 +2071,68 @@ int rrtx_extend_candidates_dubins(rrtx_ctx *ctx, const double *q, int nq, double
   return want_nearest ? nearest_fallback(ctx, q, nq, 4, nearest_idx, nearest_dist) : RRTX_OK;
 }
 
+// ---- the samples of one Dubins extend batch among themselves (kernels_self.hip) ----------------------
+int rrtx_extend_candidates_self_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                           double r_min, const uint8_t *skip, int64_t *offsets, int32_t *idx, double *key,
+                                           double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
+                                           uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed_dev) {
+  CHECK_CTX(ctx);
+  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
+  if (rc) return rc;
+  if (nq >= (1 << 30)) return fail(ctx, RRTX_E_INVALID, "extend_candidates_self_dubins: at most 2^30 - 1 samples per call");
+  if (nq == 0) return RRTX_OK;
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
+  const double *cols = nullptr;
+  rc = launch_self_join_dubins(ctx, q, nq, r, skip, offsets, idx, key, ctx->ws_owner.as<int32_t>(), cap, needed_dev, &cols);
+  if (rc) return rc;
+  // both directed edges of every entry, by the kernels of rrtx_extend_candidates_dubins: the "near" end of entry e is
+  // row idx[e] of the sample columns instead of a node
+  return launch_candidate_dubins(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, r_min, robot_radius, cost_out,
+                                 cost_in, word_out, word_in, hit_out, hit_in, cols, nq);
+}
+
+int rrtx_extend_candidates_self_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                       double r_min, const uint8_t *skip, int64_t *offsets, int32_t *idx, double *key,
+                                       double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
+                                       uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed) {
+  CHECK_CTX(ctx);
+  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
+  if (rc) return rc;
+  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * 4));
+  if (skip) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q2, skip, (size_t)nq));
+  const int64_t dcap = cap > 0 ? cap : 1;
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(sizeof(int64_t) * ((size_t)nq + 2)));
+  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)dcap));
+  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * 3 * (size_t)dcap));          // key, cost_out, cost_in
+  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(8 * (size_t)dcap));                             // words (3+3), hits (1+1)
+  int64_t *off_dev = ctx->ws_out_off.as<int64_t>();
+  int64_t *needed_dev = off_dev + nq + 1;
+  double *key_dev = ctx->ws_out_dist.as<double>(), *co_dev = key_dev + dcap, *ci_dev = co_dev + dcap;
+  uint8_t *wo_dev = ctx->ws_out_u8a.as<uint8_t>(), *wi_dev = wo_dev + 3 * dcap, *ho_dev = wi_dev + 3 * dcap,
+          *hi_dev = ho_dev + dcap;
+  rc = rrtx_extend_candidates_self_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, r_min,
+                                              skip ? ctx->ws_q2.as<uint8_t>() : nullptr, off_dev,
+                                              ctx->ws_out_idx.as<int32_t>(), key_dev, co_dev, ci_dev, wo_dev, wi_dev, ho_dev,
+                                              hi_dev, cap, needed_dev);
+  if (rc) return rc;
+  int64_t total = 0;
+  RRTX_HIP(ctx, copy_out(ctx, offsets, off_dev, sizeof(int64_t) * ((size_t)nq + 1)));
+  RRTX_HIP(ctx, read_count(ctx, needed_dev, &total));
+  if ((rc = check_capacity(ctx, "extend_candidates_self_dubins", "neighbours", total, cap, needed))) return rc;
+  const size_t n = (size_t)total;
+  RRTX_HIP(ctx, copy_out(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * n));
+  RRTX_HIP(ctx, copy_out(ctx, key, key_dev, sizeof(double) * n));
+  RRTX_HIP(ctx, copy_out(ctx, cost_out, co_dev, sizeof(double) * n));
+  RRTX_HIP(ctx, copy_out(ctx, cost_in, ci_dev, sizeof(double) * n));
+  RRTX_HIP(ctx, copy_out(ctx, word_out, wo_dev, 3 * n));
+  RRTX_HIP(ctx, copy_out(ctx, word_in, wi_dev, 3 * n));
+  RRTX_HIP(ctx, copy_out(ctx, hit_out, ho_dev, n));
+  RRTX_HIP(ctx, copy_out(ctx, hit_in, hi_dev, n));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
+}
+
 int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit_in, const int64_t *n_valid_dev,
                        int64_t cap, uint64_t *words) {
   CHECK_CTX(ctx);

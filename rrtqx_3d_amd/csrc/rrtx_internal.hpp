@@ -242,7 +242,7 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_i32a, ws_i32b;  // staged index arrays
   rrtx::DevBuf ws_sph_lists;      // per sample: spheres its candidate edges can touch (+ counts)
   rrtx::DevBuf ws_poly_lists;     // per sample: polygons its candidate edges can reach (+ counts), uint16
-  rrtx::DevBuf ws_self;           // rrtx_extend_candidates_self: sample table, its fp32 shadow, row counts, max |q - origin|
+  rrtx::DevBuf ws_self;           // rrtx_extend_candidates_self[_dubins]: sample table, its fp32 shadow, row counts, max |q - origin|
 
   // device mirror of the planner's directed edges (obstacle sweeps, kernels_sweep.hip)
   int32_t *ge_start = nullptr, *ge_end = nullptr;
@@ -419,10 +419,13 @@ int launch_sweep_finish(rrtx_ctx *ctx, const int32_t *ids_dev, long long n, cons
 int launch_sweep_gather(rrtx_ctx *ctx, const int32_t *ids_dev, long long n, double *p0_dev, double *p1_dev);
 void packed_range(const std::vector<int32_t> &orig, int begin, int end, int &pb, int &pe);
 std::vector<int32_t> active_positions(const std::vector<uint8_t> &active);
+// idx[e] is a row of near_cols (four columns of n_near doubles, x y t theta one after the other): the context's nodes
+// unless a table is given (the samples themselves, rrtx_extend_candidates_self_dubins)
 int launch_candidate_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                             const int32_t *idx_dev, const int32_t *owner_dev, int64_t cap, double r_min,
                             double robot_radius, double *cost_out, double *cost_in, uint8_t *word_out,
-                            uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in);
+                            uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in, const double *near_cols = nullptr,
+                            int64_t n_near = 0);
 int launch_detmath_eval(rrtx_ctx *ctx, int op, const double *x_dev, const double *y_dev, int64_t n, double *out_dev);
 int launch_dubins_trajectory(rrtx_ctx *ctx, const double *s_dev, const double *g_dev, int64_t ne, double r_min,
                              const int64_t *traj_off_dev, double *traj_xy_dev, int64_t cap_rows,
@@ -444,6 +447,11 @@ int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, 
 int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev, int64_t *offsets_dev,
                      int32_t *idx_dev, double *cost_dev, int32_t *owner_dev, int64_t cap, int64_t *needed_dev,
                      const double **table_out);
+// the same in [x y t theta] with the context's wrapped dimensions: the copies of the later sample against the earlier
+// sample as it is, the key of the first copy that reaches it; *columns_out = the samples as four columns of nq doubles
+int launch_self_join_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
+                            int64_t *offsets_dev, int32_t *idx_dev, double *key_dev, int32_t *owner_dev, int64_t cap,
+                            int64_t *needed_dev, const double **columns_out);
 int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                               const int32_t *idx_dev, const double *dist_dev, int32_t *nearest_idx_dev,
                               double *nearest_dist_dev);

@@ -567,6 +567,48 @@ def extend_candidates_self(tree: HipTree, S: CSpace, newPositions, hyberBallRad_
     return out
 
 
+def _dubins_space(tree: HipTree, S: CSpace, what: str):
+    """the context made ready for a Dubins extend call: obstacles (polygons) and the space's time setting"""
+    if tree.d != 4:
+        error(what + " is the DubinsEdge (4-D, [x y t theta]) path")
+    S.bind(tree)
+    if _sync_obstacles(S) != 1 and len(list(S.obstacles)) > 0:
+        error(what + " checks Dubins edges against the polygon list")
+    tree.ctx.set_space_has_time(bool(S.spaceHasTime))
+
+
+def extend_candidates_dubins(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float):
+    """extend_candidates for Edge = DubinsEdge (R/DRRT_Q.jl:1927-1979, 2546-2642 with the Dubins edge functions): per
+    sample the neighbour list in the wrapped space with its keys, the Dubins cost, word and flags of sample -> node
+    (out) and node -> sample (in), the nearest node and the sample's own point check.  S.minTurningRadius and
+    S.robotRadius are read; with S.spaceHasTime a flag byte also carries bit 1 = !validMove."""
+    _dubins_space(tree, S, "extend_candidates_dubins")
+    q = np.asarray(newPositions, dtype=np.float64).reshape(-1, 4)
+    out = tree.ctx.extend_candidates_dubins(q, float(hyberBallRad_), S.robotRadius, S.minTurningRadius)
+    if S.inWarmupTime:
+        out["hit_out"][:] = 0
+        out["hit_in"][:] = 0
+        out["sample_unsafe"][:] = 0
+    return out
+
+
+def extend_candidates_self_dubins(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, skip=None):
+    """What extend_candidates_dubins leaves out: the lists of the batch's samples among themselves, in the wrapped
+    space.  Row j: the batch positions i < j that kdFindWithinRange and its ghost iterator add to j's list when the
+    samples are inserted one after the other, with the key of the first copy of q_j that reaches q_i and the Dubins
+    cost, word and flags of q_j -> q_i (out) and q_i -> q_j (in).  skip: non-zero bytes take a sample out of every
+    list (pass sample_unsafe of extend_candidates_dubins).  The caller maps idx to the node index each earlier sample
+    received and drops the entries of samples it did not insert; the tree list followed by this list is then the
+    reference's."""
+    _dubins_space(tree, S, "extend_candidates_self_dubins")
+    q = np.asarray(newPositions, dtype=np.float64).reshape(-1, 4)
+    out = tree.ctx.extend_candidates_self_dubins(q, float(hyberBallRad_), S.robotRadius, S.minTurningRadius, skip=skip)
+    if S.inWarmupTime:
+        out["hit_out"][:] = 0
+        out["hit_in"][:] = 0
+    return out
+
+
 def extend_select(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, lmc=None):
     """findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) for many samples at once, on
     the device: per sample the parent, its own rrtLMC and the neighbours whose rrtLMC it would lower, as

@@ -1,0 +1,217 @@
+"""Scenes and the oracle-side reference for rrtx_extend_candidates_self_dubins (the samples of one Dubins extend batch
+among themselves, in the wrapped space).  The reference is built only from the oracle: one KDTree(4, wraps, wrap_points)
+over the tree points (or a far dummy root) followed by the samples, range_batch for every sample, the entries
+N0 <= idx < N0 + (row) kept -- what kdFindWithinRange and its ghost iterator return for sample j when the samples before
+it have been inserted and the later ones have not -- dubins_candidates_batch for costs and flags and dubins_edges_batch
+for the words.  tests/test_extend_self_dubins_scenes.py holds it to a plain all-pairs restatement of the ghost rule; the
+GPU tests compare against it bit for bit."""
+import functools
+import json
+import math
+import os
+
+import numpy as np
+
+from rrtqx_3d_amd import synth
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+RR, RMIN = 0.25, 0.5            # robot radius and minimum turning radius of every scene
+VMIN, VMAX = 1.0, 8.0           # validMove's velocity window in the scenes with time
+SEED = 5200
+TWO_PI = 2.0 * math.pi
+T0, T1 = 12.0, 13.5             # the samples' time coordinate
+THETA = ((3,), (TWO_PI,))       # the Dubins space: theta wrapped
+# name: samples, half-width of the box, ball radius, polygons (flat), factor the polygons are shrunk by about their mean
+RANDOM = {"large": (1000, 10.0, 3.5, 24, 0.5), "mid": (257, 6.0, 2.5, 16, 0.5), "small": (65, 3.0, 2.0, 10, 0.5)}
+# batch size -> the scene whose first B samples it is (a prefix of a batch has the batch's own first rows)
+SIZES = {1: "small", 2: "small", 63: "small", 64: "small", 65: "small", 257: "mid", 1000: "large"}
+TIME_SIZES = {65: "small", 257: "mid"}
+LATTICE_R = (3.25, 3.75)
+DUPLICATES = ((100, 5), (300, 5), (400, 17))        # Q[a] = Q[b]: pairs at distance 0
+# mode: what the context and the oracle are told about the space (piecewise: the oracle's name for time column 0)
+MODES = {"flat": dict(has_time=False, piecewise=False, v_min=0.0, v_max=0.0),
+         "time": dict(has_time=True, piecewise=True, v_min=VMIN, v_max=VMAX),
+         "moving": dict(has_time=True, piecewise=False, v_min=VMIN, v_max=VMAX)}
+
+
+def _k(name):
+    return list(RANDOM).index(name)
+
+
+def random_samples(name):
+    b, hw, _, _, _ = RANDOM[name]
+    rng = np.random.default_rng(SEED + _k(name))
+    return np.concatenate([rng.uniform(-hw, hw, (b, 2)), rng.uniform(T0, T1, (b, 1)), rng.uniform(0.0, TWO_PI, (b, 1))],
+                          axis=1)
+
+
+def _shrunk(polys, scale, shrink):
+    out = []
+    for p in polys:
+        p = p * scale
+        c = p.mean(axis=0)
+        out.append(c + (p - c) * shrink)
+    return out
+
+
+def polygon_args(name, mode):
+    """(polygons, kinds, paths) of a scene: static polygons; "moving": polygons that move along paths (kinds 6 and 7
+    in turn, tests/golden/env_inputs.json scaled to the box) beside a few static ones"""
+    _, hw, _, m, shrink = RANDOM[name]
+    stat = _shrunk(synth.polygons(m, seed=SEED + 20 + _k(name)), hw / synth.WORLD, shrink)
+    if mode == "time":
+        stat = stat[::3]                          # validMove blocks half of the edges already
+    if mode != "moving":
+        return stat, [3] * len(stat), None
+    d = json.load(open(os.path.join(ROOT, "golden", "env_inputs.json")))
+    mv = _shrunk([np.array(p, dtype=np.float64) for p in d["rand_StaticTime_7_polygons"]][:6], hw / synth.WORLD, shrink)
+    paths = []
+    for p in d["rand_StaticTime_7_paths"][:6]:
+        p = np.array(p, dtype=np.float64)
+        p[:, :2] *= hw / synth.WORLD
+        paths.append(p)
+    stat = stat[::6]
+    return mv + stat, [6, 7, 6, 7, 6, 7] + [3] * len(stat), paths + [None] * len(stat)
+
+
+def lattice_samples():
+    """600 samples, x y t multiples of 1/4 in [-4, 4] and theta a multiple of 1/4 in [0, 6.25]: the squared distances of
+    the samples themselves are exact, so pairs at distance exactly r exist (they are not neighbours: KDdist < r), and
+    planted duplicates are neighbours at key 0"""
+    rng = np.random.default_rng(SEED + 30)
+    q = np.concatenate([rng.integers(-16, 17, (600, 3)), rng.integers(0, 26, (600, 1))], axis=1) / 4.0
+    for a, b in DUPLICATES:
+        q[a] = q[b]
+    return q
+
+
+def lattice_polygons():
+    return _shrunk(synth.polygons(12, seed=SEED + 31), 4.0 / synth.WORLD, 0.5)
+
+
+def two_wrap_samples():
+    """theta and the time coordinate both wrapped (periods 2 pi and 4): up to four copies of a sample"""
+    rng = np.random.default_rng(SEED + 32)
+    return np.concatenate([rng.uniform(-6.0, 6.0, (257, 2)), rng.uniform(0.0, 4.0, (257, 1)),
+                           rng.uniform(0.0, TWO_PI, (257, 1))], axis=1)
+
+
+TWO_WRAPS = {"theta_t": ((3, 2), (TWO_PI, 4.0)), "t_theta": ((2, 3), (4.0, TWO_PI))}
+
+
+def tree_points(n=3000, hw=10.0):
+    rng = np.random.default_rng(SEED + 40)
+    return np.concatenate([rng.uniform(-hw, hw, (n, 2)), rng.uniform(T0, T1, (n, 1)), rng.uniform(0.0, TWO_PI, (n, 1))],
+                          axis=1)
+
+
+FAR_ROOT = np.array([[1.0e6, 1.0e6, 1.0e6, 1.0]])        # stands in for the tree where there is none: never in range
+
+
+def merged_reference(oracle, tree_pts, Q, r, ps, mode="flat", wraps=THETA, skip=None):
+    """The reference's lists with the samples inserted one after the other behind tree_pts: per sample the nodes
+    idx < N0 + j its copies reach (the root of tree_pts with <=), in ascending node index, with the key of the first
+    copy, both Dubins costs, words and flag bytes.  skip: samples that are not inserted (no list, in no list)."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, 4)
+    n0, b = len(tree_pts), len(Q)
+    nodes = np.vstack([tree_pts, Q])
+    t = oracle.KDTree(4, list(wraps[0]), list(wraps[1])) if wraps[0] else oracle.KDTree(4)
+    t.insert_many(nodes)
+    rng = oracle.range_batch(t, Q, r, nearest=False)
+    owner = np.repeat(np.arange(b), np.diff(rng["offsets"]))
+    idx = rng["idx"].astype(np.int64)
+    keep = idx < n0 + owner
+    if skip is not None:
+        sk = np.asarray(skip).astype(bool)
+        keep &= ~sk[owner] & ~((idx >= n0) & sk[np.clip(idx - n0, 0, b - 1)])
+    offsets = np.zeros(b + 1, dtype=np.int64)
+    np.cumsum(np.bincount(owner[keep], minlength=b), out=offsets[1:])
+    idx, owner = idx[keep].astype(np.int32), owner[keep]
+    opt = MODES[mode]
+    c = oracle.dubins_candidates_batch(Q, offsets, idx, nodes, RMIN, ps, RR, **opt)
+    eo = oracle.dubins_edges_batch(Q[owner], nodes[idx], RMIN, has_time=opt["has_time"], piecewise=opt["piecewise"])
+    ei = oracle.dubins_edges_batch(nodes[idx], Q[owner], RMIN, has_time=opt["has_time"], piecewise=opt["piecewise"])
+    assert np.array_equal(eo["cost"], c["cost_out"]) and np.array_equal(ei["cost"], c["cost_in"])
+    return dict(offsets=offsets, idx=idx, key=rng["key"][keep], cost_out=c["cost_out"], cost_in=c["cost_in"],
+                word_out=eo["word"], word_in=ei["word"], hit_out=c["hit_out"], hit_in=c["hit_in"])
+
+
+def self_reference(oracle, Q, r, ps, mode="flat", wraps=THETA, skip=None):
+    """What rrtx_extend_candidates_self_dubins returns, from the oracle: idx is a position in Q"""
+    ref = merged_reference(oracle, FAR_ROOT, Q, r, ps, mode, wraps, skip)
+    assert (ref["idx"] >= 1).all()
+    ref["idx"] = ref["idx"] - 1
+    return ref
+
+
+def prefix(ref, b):
+    """the first b rows of a CSR result: the result for the first b samples alone"""
+    n = int(ref["offsets"][b])
+    out = {k: v[:n] for k, v in ref.items() if k != "offsets"}
+    out["offsets"] = ref["offsets"][:b + 1]
+    return out
+
+
+def scene_inputs(name, mode="flat"):
+    """(samples, radius, (polygons, kinds, paths), wraps) of a scene; name: a key of RANDOM, "lattice", "nowrap" or a key
+    of TWO_WRAPS"""
+    if name == "lattice":
+        return lattice_samples(), None, (lattice_polygons(), None, None), THETA
+    if name in TWO_WRAPS:
+        return two_wrap_samples(), RANDOM["mid"][2], polygon_args("mid", mode), TWO_WRAPS[name]
+    if name == "nowrap":
+        return random_samples("mid"), RANDOM["mid"][2], polygon_args("mid", mode), ((), ())
+    return random_samples(name), RANDOM[name][2], polygon_args(name, mode), THETA
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(name, mode, r):
+    from oracle import oracle
+    oracle.lib()
+    Q, r0, (polys, kinds, paths), wraps = scene_inputs(name, mode)
+    ps = oracle.PolygonSet(polys, kinds=kinds, paths=paths)
+    return Q, self_reference(oracle, Q, r0 if r is None else r, ps, mode, wraps)
+
+
+def scene(name, mode="flat", r=None):
+    """(samples, reference) of a scene, computed once per session"""
+    return _scene(name, mode, r)
+
+
+def all_pairs(Q, r, wraps=THETA):
+    """The ghost rule in plain numpy over all pairs: (j, i, key, slot, reach) of every entry in list order -- rows
+    ascending in j, i < j ascending -- where copy `slot` of q_j is the lowest non-skipped copy with
+    sqrt(sq4(copy, q_i)) < r and reach[k] says which copies reach that pair at all.  Copy k shifts the wrapped
+    dimensions whose bit is set in k, the last wrapped dimension being the least significant bit; p < period / 2 goes to
+    p + period (closest unwrapped coordinate: period), anything else to p - period (closest: 0); a ghost is skipped when
+    sqrt(sq4(closest, ghost)) > r."""
+    Q = np.asarray(Q, dtype=np.float64)
+    dims, periods = wraps
+    w, b = len(dims), len(Q)
+
+    def sq4(a, c):
+        d = a - c
+        s = d[..., 0] * d[..., 0]
+        s = s + d[..., 1] * d[..., 1]
+        s = s + d[..., 2] * d[..., 2]
+        return s + d[..., 3] * d[..., 3]
+
+    first = np.full((b, b), -1)
+    key = np.zeros((b, b))
+    reach = np.zeros((1 << w, b, b), dtype=bool)
+    for k in range(1 << w):
+        g, c = Q.copy(), Q.copy()
+        for n, (dim, per) in enumerate(zip(dims, periods)):
+            if not (k >> (w - 1 - n)) & 1:
+                continue
+            low = Q[:, dim] < per / 2.0
+            g[:, dim] = np.where(low, Q[:, dim] + per, Q[:, dim] - per)
+            c[:, dim] = np.where(low, per, 0.0)
+        valid = np.ones(b, dtype=bool) if k == 0 else ~(np.sqrt(sq4(c, g)) > r)
+        s = sq4(g[:, None, :], Q[None, :, :])
+        reach[k] = np.tril(valid[:, None] & (np.sqrt(s) < r), k=-1)
+        new = reach[k] & (first < 0)
+        first[new] = k
+        key[new] = np.sqrt(s[new])
+    j, i = np.nonzero(first >= 0)
+    return j, i, key[j, i], first[j, i], reach[:, j, i]
