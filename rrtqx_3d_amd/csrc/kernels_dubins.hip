@@ -830,6 +830,24 @@ __device__ bool wave_dubins_collides(WaveDubinsT<TIME, RSUM> &w, bool valid, con
           }
           pm[pi] = keep;
         }
+        if constexpr (TIME) {
+          // In a space with time the last stored row is the end node itself, and that point lies on the circle of the
+          // LAST arc only.  When the last arc has a single row, the polyline's last piece is the join that belongs to the
+          // piece before it, and its far end is the end node, not the tangent point: it can leave that piece's disk
+          // (by up to the 0.1 rad the last arc falls short of).  The piece that owns it keeps every marked obstacle.
+          // Deliberately wider than needed: with no last arc and a middle arc of several rows the end node is on the middle
+          // arc's own circle, and a straight middle piece is never screened (pm[1] is not read for it); such edges are
+          // rare, and a wrongly kept obstacle only costs the full test of a few pieces.
+          const int l1 = st.pc[1].len, l2 = st.pc[2].len;
+          bool open0 = false, open1 = false;
+          if (l2 == 1) { if (l1 > 0) open1 = true; else open0 = true; }
+          else if (l2 <= 0) {
+            if (l1 > 0) { open1 = true; open0 = l1 == 1; }
+            else open0 = true;
+          }
+          if (open0) pm[0] = mask;
+          if (open1) pm[1] = mask;
+        }
       }
       w.pm[0][lane] = pm[0]; w.pm[1][lane] = pm[1]; w.pm[2][lane] = pm[2];
     }
