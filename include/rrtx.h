@@ -606,6 +606,48 @@ int rrtx_extend_candidates_self(rrtx_ctx *ctx, const double *q, int nq, double r
                                 const uint8_t *skip, int64_t *offsets, int32_t *idx, double *cost,
                                 uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
 
+/* ---- the closestNode rule for an extend batch: k nearest earlier samples -------- */
+/* A sample whose ball is empty is linked to closestNode (findBestParent, R/DRRT_Q.jl:1930-1935), which is kdFindNearest
+ * over the tree as sequential insertion would have it: it may be an earlier sample of the same batch.
+ * rrtx_extend_candidates gives the nearest node of the tree as it stood, rrtx_extend_candidates_self only the earlier
+ * samples inside the ball, and the long edge to closestNode is not served by their per-sample obstacle lists.  This call
+ * supplies the rest: per wanted sample j a short sorted row of its nearest live earlier samples, each with the SimpleEdge
+ * cost and both collision flags against the whole obstacle list, and the same flags for one tree node per sample.
+ * Whether an earlier sample was inserted is decided by the caller's sequential phase, which the device cannot know;
+ * hence a row of k instead of one index.
+ *   Scope    SimpleEdge only: dim == 3 and no wrapped dimension, otherwise RRTX_E_STATE as in
+ *            rrtx_extend_candidates_self.  1 <= k <= RRTX_CLOSEST_SELF_MAX_K, nq >= 0, non-NULL outputs when nq > 0,
+ *            tree_idx / tree_hit_out / tree_hit_in all NULL or all given; otherwise RRTX_E_INVALID.  Obstacles: the
+ *            spheres or the polygons by RRTX_OPT_EXTEND_OBSTACLES; kinds 6 / 7 read time from the third coordinate.
+ *            Apart from tree_idx the tree is not read; an empty tree is fine.  The Dubins spaces ([x y t theta], wrapped
+ *            dimensions, rrtx_extend_candidates_self_dubins) are out of scope.
+ *   Live     a sample is live when every coordinate is finite and skip[j] == 0 (skip: nq bytes or NULL; the
+ *            sample_unsafe bytes of rrtx_extend_candidates can be passed as they are).
+ *   Rows     idx, cost, hit_out, hit_in are nq x k, row-major, as in rrtx_nn_knearest; count is nq.  Row j is filled iff
+ *            j is live and (want == NULL or want[j] != 0).  A filled row holds the live samples i < j with finite
+ *            s = sq3(q_j, q_i) (the unfused fp64 expression of rrtx_extend_candidates_self), ordered by (s, i)
+ *            ascending: the first min(k, their number) of them, count[j] says how many.  Unused slots and rows that are
+ *            not filled have idx = -1, cost = +Inf, flags 0, count = 0.  idx is a 0-based position in q, not a node
+ *            index.  A sample with want[j] == 0 is still a candidate in the rows of the others: the caller sets want
+ *            where the tree list of rrtx_extend_candidates is empty, and with no row wanted the call costs a few launches.
+ *   Entries  cost = sqrt(s), correctly rounded: the key and the SimpleEdge cost at once.  hit_out = explicitEdgeCheck of
+ *            q_j -> q_i, hit_in of q_i -> q_j, over the WHOLE active obstacle list: byte for byte what rrtx_edges_check
+ *            returns for that directed edge.
+ *   Tree     for a filled row with 0 <= tree_idx[j] < rrtx_nodes_count, tree_hit_out[j] / tree_hit_in[j] are the same
+ *            full-list flags of q_j -> node and node -> q_j; otherwise 0 (an index out of range is not an error).  With
+ *            nearest_idx of rrtx_extend_candidates as tree_idx the one call hands the caller all the rule needs.
+ *   The rule walk row j and take the first entry whose sample was inserted.  Link to it if its cost < nearest_dist[j],
+ *            else to nearest_idx[j] (on an exact tie the tree node, which has the lower index, wins, as in
+ *            rrtx_nn_nearest).  If count[j] == k and none of the k was inserted the row is exhausted: the caller then
+ *            finds the nearest inserted earlier sample itself (brute force over the batch, then two rrtx_edges_check
+ *            calls).  It need not when the k-th cost is not below nearest_dist[j]: no later entry beats the tree node.
+ * Exact, no tolerance; nothing in the result depends on launch geometry or on the order in which waves finish. */
+#define RRTX_CLOSEST_SELF_MAX_K 32
+int rrtx_extend_closest_self(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius,
+                             const uint8_t *skip, const uint8_t *want, const int32_t *tree_idx,
+                             int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int32_t *count,
+                             uint8_t *tree_hit_out, uint8_t *tree_hit_in);
+
 /* The same preamble for Edge = DubinsEdge (BASELINE config 3; R/dubinsExperimentsForPaper.jl): tree in
  * [x y t theta] with theta wrapped (rrtx_set_wrap), polygon obstacle list.  Per neighbour entry:
  * key = the KDdist the range search stores, Dubins cost and word for sample->near (out) and
@@ -679,6 +721,14 @@ int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r,
 int rrtx_extend_candidates_self_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
                                     const uint8_t *skip, int64_t *offsets, int32_t *idx, double *cost,
                                     uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed_dev);
+
+/* device-pointer form of rrtx_extend_closest_self (skip, want and the three tree arrays may be NULL as there).  Only
+ * enqueues, never waits on the stream (the growth of a workspace may, once); every read of q and tree_idx and every
+ * write is bounded by nq, k and the node count on the device. */
+int rrtx_extend_closest_self_dev(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius,
+                                 const uint8_t *skip, const uint8_t *want, const int32_t *tree_idx,
+                                 int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int32_t *count,
+                                 uint8_t *tree_hit_out, uint8_t *tree_hit_in);
 
 /* device-pointer form of rrtx_extend_candidates_dubins; *needed_dev receives the number of entries (entries
  * beyond cap are not written).  Only enqueues work, never waits on the stream: with wrapped dimensions nearest_*

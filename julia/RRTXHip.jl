@@ -444,6 +444,56 @@ function extend_candidates_self(tree::HipTree, S::TS, positions::Array{Float64,2
   end
 end
 
+# The closestNode rule of findBestParent (R/DRRT_Q.jl:1930-1935) for a batch: a sample whose ball is empty is linked to
+# kdFindNearest over the tree as sequential insertion would have it, which may be an earlier sample of the same batch.
+# Column j (k slots, Julia is column-major) holds the nearest live earlier batch positions i < j (0-based) ordered by
+# (distance, i), with the SimpleEdge cost and the flags of q_j -> q_i (hitOut) and q_i -> q_j (hitIn) against the whole
+# obstacle list; count[j] slots are used, the others have idx -1 and cost Inf.  skip: non-zero bytes take a sample out
+# (sampleUnsafe of extend_candidates); want: the samples to fill (those whose tree list is empty; nothing: every live
+# one); treeNearest: nearestIdx of extend_candidates, whose flags come back as treeHitOut / treeHitIn (empty otherwise).
+# The caller walks column j, takes the first entry whose sample it inserted and links to it if its cost <
+# nearestDist[j], else to the tree node; with count[j] == k, no inserted entry and the k-th cost below nearestDist[j]
+# it searches the batch itself.
+struct ExtendClosestSelf
+  idx::Matrix{Int32}          # k x nq, 0-based positions in the batch, -1: unused
+  cost::Matrix{Float64}
+  hitOut::Matrix{UInt8}
+  hitIn::Matrix{UInt8}
+  count::Vector{Int32}
+  treeHitOut::Vector{UInt8}
+  treeHitIn::Vector{UInt8}
+end
+
+function extend_closest_self(tree::HipTree, S::TS, positions::Array{Float64,2}, k::Int;
+                             skip::Union{Nothing,Vector{UInt8}} = nothing, want::Union{Nothing,Vector{UInt8}} = nothing,
+                             treeNearest::Union{Nothing,Vector{Int32}} = nothing) where {TS}
+  syncObstacles(tree, S)
+  nq = size(positions, 2)                     # d x nq, each sample contiguous
+  skip === nothing || length(skip) == nq || error("skip needs one byte per sample")
+  want === nothing || length(want) == nq || error("want needs one byte per sample")
+  treeNearest === nothing || length(treeNearest) == nq || error("treeNearest needs one index per sample")
+  skipArg = skip === nothing ? UInt8[] : skip
+  skipPtr = skip === nothing ? Ptr{UInt8}(C_NULL) : pointer(skipArg)
+  wantArg = want === nothing ? UInt8[] : want
+  wantPtr = want === nothing ? Ptr{UInt8}(C_NULL) : pointer(wantArg)
+  nt = treeNearest === nothing ? 0 : nq
+  treeArg = treeNearest === nothing ? Int32[] : treeNearest
+  tho = Vector{UInt8}(undef, nt); thi = Vector{UInt8}(undef, nt)
+  treePtr = treeNearest === nothing ? Ptr{Int32}(C_NULL) : pointer(treeArg)
+  thoPtr = treeNearest === nothing ? Ptr{UInt8}(C_NULL) : pointer(tho)
+  thiPtr = treeNearest === nothing ? Ptr{UInt8}(C_NULL) : pointer(thi)
+  kk = max(k, 0)
+  idx = Matrix{Int32}(undef, kk, nq); cost = Matrix{Float64}(undef, kk, nq)
+  hout = Matrix{UInt8}(undef, kk, nq); hin = Matrix{UInt8}(undef, kk, nq)
+  count = Vector{Int32}(undef, nq)
+  rc = GC.@preserve positions skipArg wantArg treeArg idx cost hout hin count tho thi ccall((:rrtx_extend_closest_self, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{UInt8},
+       Ptr{UInt8}, Ptr{Int32}, Ptr{UInt8}, Ptr{UInt8}),
+      tree.ctx, positions, nq, k, S.robotRadius, skipPtr, wantPtr, treePtr, idx, cost, hout, hin, count, thoPtr, thiPtr)
+  rrtx_check(tree, rc)
+  return ExtendClosestSelf(idx, cost, hout, hin, count, tho, thi)
+end
+
 # ---------------------------------------------------------------------------
 # findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) on the device, for a batch of
 # samples: what comes back per sample is a status, a parent, the sample's rrtLMC and the neighbours to rewire -- the

@@ -20,6 +20,7 @@ RRTX_E_CAPACITY = -2
 RRTX_E_DEVICE = -3
 RRTX_E_NOMEM = -4
 RRTX_E_STATE = -5
+RRTX_CLOSEST_SELF_MAX_K = 32
 RRTX_OPT_NN_FILTER = 1
 RRTX_OPT_SCAN_BLOCKS = 2
 RRTX_OPT_SCAN_TILE_Q = 3
@@ -144,6 +145,10 @@ SYMBOLS = [
                                               C.c_int64, c_int64_p]),
     ("rrtx_extend_candidates_self_dev", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP,
                                                   C.c_int64, _VP]),
+    ("rrtx_extend_closest_self", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                           _VP, _VP]),
+    ("rrtx_extend_closest_self_dev", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                               _VP, _VP, _VP]),
     ("rrtx_extend_candidates_dubins", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, _VP, _VP, _VP, _VP,
                                                 _VP, _VP, _VP, _VP, _VP, C.c_int64, c_int64_p, _VP, _VP, _VP]),
     ("rrtx_extend_candidates_dubins_dev", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, _VP, _VP, _VP,

@@ -398,6 +398,40 @@ class Context:
         n, (idx, cost, hout, hin) = self._two_call(cap, call)
         return dict(offsets=offsets, idx=idx[:n], cost=cost[:n], hit_out=hout[:n], hit_in=hin[:n])
 
+    def extend_closest_self(self, q, k: int, robot_radius: float, skip=None, want=None, tree_idx=None) -> dict:
+        """rrtx_extend_closest_self: for the closestNode rule of a batch.  Row j (of k slots) holds the nearest live
+        earlier samples i < j of the batch ordered by (distance, i), with the SimpleEdge cost and the flags of
+        q_j -> q_i (hit_out) and q_i -> q_j (hit_in) against the whole obstacle list; count[j] of them are used, the
+        other slots have idx -1, cost +Inf.  skip: non-zero bytes take a sample out (sample_unsafe of
+        extend_candidates); want: non-zero bytes choose the rows to fill (None: every live row); tree_idx: one node
+        per sample whose two flags come back as tree_hit_out / tree_hit_in (an index outside the tree gives 0).
+        dict(idx, cost, hit_out, hit_in: (nq, k); count: (nq,); tree_hit_out, tree_hit_in: (nq,) or None)."""
+        q = f64(q, (-1, self.dim))
+        nq, k = q.shape[0], int(k)
+
+        def per_sample(a, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            if a.shape[0] != nq:
+                raise ValueError(what + " needs one entry per sample")
+            return a
+        sk, wa = per_sample(skip, np.uint8, "skip"), per_sample(want, np.uint8, "want")
+        ti = per_sample(tree_idx, np.int32, "tree_idx")
+        rows = max(k, 0)
+        idx = np.empty((nq, rows), dtype=np.int32)
+        cost = np.empty((nq, rows), dtype=np.float64)
+        hout = np.empty((nq, rows), dtype=np.uint8)
+        hin = np.empty((nq, rows), dtype=np.uint8)
+        count = np.empty(nq, dtype=np.int32)
+        tho = None if ti is None else np.empty(nq, dtype=np.uint8)
+        thi = None if ti is None else np.empty(nq, dtype=np.uint8)
+        self._check(self._lib.rrtx_extend_closest_self(self._h, _capi._ptr(q), nq, k, robot_radius, _capi._ptr(sk),
+                                                       _capi._ptr(wa), _capi._ptr(ti), _capi._ptr(idx), _capi._ptr(cost),
+                                                       _capi._ptr(hout), _capi._ptr(hin), _capi._ptr(count),
+                                                       _capi._ptr(tho), _capi._ptr(thi)))
+        return dict(idx=idx, cost=cost, hit_out=hout, hit_in=hin, count=count, tree_hit_out=tho, tree_hit_in=thi)
+
     # ---- findBestParent + rewire test on the device -------------------------------------------------
     def node_cost_set(self, first_index: int, lmc):
         """rrtLMC of nodes first_index .. first_index + len(lmc) - 1 in the context's own device array (+Inf for a node
@@ -626,6 +660,14 @@ class Context:
                                    cap: int, needed_ptr: int):
         self._check(self._lib.rrtx_extend_candidates_self_dev(self._h, q_ptr, nq, r, robot_radius, skip_ptr, offsets_ptr,
                                                               idx_ptr, cost_ptr, hit_out_ptr, hit_in_ptr, cap, needed_ptr))
+
+    def extend_closest_self_dev(self, q_ptr: int, nq: int, k: int, robot_radius: float, skip_ptr: Optional[int],
+                                want_ptr: Optional[int], tree_idx_ptr: Optional[int], idx_ptr: int, cost_ptr: int,
+                                hit_out_ptr: int, hit_in_ptr: int, count_ptr: int,
+                                tree_hit_out_ptr: Optional[int] = None, tree_hit_in_ptr: Optional[int] = None):
+        self._check(self._lib.rrtx_extend_closest_self_dev(self._h, q_ptr, nq, k, robot_radius, skip_ptr, want_ptr,
+                                                           tree_idx_ptr, idx_ptr, cost_ptr, hit_out_ptr, hit_in_ptr,
+                                                           count_ptr, tree_hit_out_ptr, tree_hit_in_ptr))
 
     def extend_candidates_dubins_dev(self, q_ptr: int, nq: int, r: float, robot_radius: float, r_min: float,
                                      offsets_ptr: int, idx_ptr: int, key_ptr: int, cost_out_ptr: int, cost_in_ptr: int,

@@ -1,7 +1,8 @@
 // kernels_self.hip -- the samples of one extend batch among themselves (rrtx_extend_candidates_self): for every
 // sample j the earlier samples i < j of the same batch with KDdist(q_j, q_i) < r, which is what kdFindWithinRange
 // adds to j's list when the samples are inserted one after the other (R/kdTree_general.jl:830).  The tree is not read.
-// The [x y t theta] form with wrapped dimensions (rrtx_extend_candidates_self_dubins) is the second half of the file.
+// The [x y t theta] form with wrapped dimensions (rrtx_extend_candidates_self_dubins) is the second half of the file,
+// the k nearest earlier samples for the closestNode rule (rrtx_extend_closest_self) the third.
 //
 // Semantics (exact, no tolerance): entry (j, i) exists  <=>  both samples are live (finite, not skipped), i < j and
 // s = sq3(q_j, q_i) < thr, thr = sq_first_ge(r) -- the test the range search applies to a non-root node; the key and
@@ -492,7 +493,305 @@ __global__ __launch_bounds__(kSelfThreads) void self_join4_kernel(const SelfJoin
   }
 }
 
+// ---- the k nearest earlier samples of a batch (rrtx_extend_closest_self) ------------------------------------------
+// For a wanted live sample j the first k of the live samples i < j, ordered by (s, i), s = sq3(q_j, q_i) finite: what the
+// closestNode rule of findBestParent needs when the ball of j is empty and kdFindNearest may answer with a sample of the
+// same batch.  Fixed-width rows, so one pass: no count / fill pair.
+//   self_table_kernel     as above: table, shadows, C.
+//   closest_fill_kernel   every slot of every row to "none" (idx -1, cost +Inf, flags 0, count 0), the owner row of
+//                         every slot for the edge kernels, the tree column's flags to 0.
+//   closest_plan_kernel   ONE workgroup: the wanted live rows, ascending, to a compact list, so that the row kernel's work
+//                         follows their number; the tree column's node index of a filled row (-1 otherwise); and the
+//                         number of slots / rows the edge kernels have to look at (up to the last filled row).
+//   closest_rows_kernel   a wave owns a row of the compact list and walks the earlier samples in ascending tiles staged
+//                         in LDS, as the join does.  It keeps the row's best k pairs (s, i) sorted, pair l in lane l;
+//                         tau is the k-th s, +Inf until the row is full.  The fp32 screen is the join's with thr = tau:
+//                         it drops a pair only when it proves s >= tau, which on a full row loses against every pair
+//                         held (columns arrive in ascending i, so a later index loses a tie).  Survivors are decided by
+//                         the unfused fp64 sq3 and inserted one at a time in ascending i (a v_readlane and a DPP wave
+//                         shift, no LDS crossbar); tau follows every insertion, the screen record once a tile.  The
+//                         groups of rows are dealt heaviest first.
+// A row's result is a function of its columns in ascending order alone: nothing depends on the launch geometry or on
+// which wave finishes first.
+// A row is a chain of dependent steps -- about 8 (1 + ln(j / 512)) + 8 survivors after the first tile, each a trip to the
+// fp64 table, and as many insertions -- so the kernel is bound by that chain's latency times the rows a wave owns, not
+// by the screen: at B = 16 384, k = 8, all rows wanted, it took 204 us with 4 rows a wave and 127 us with one
+// (DESIGN.md 4.19).
+constexpr int kClosestRows = 1;                               // rows a wave owns
+constexpr int kClosestGroup = kSelfWaves * kClosestRows;      // rows a workgroup owns
+constexpr int kPlanThreads = 1024;
+
+__global__ __launch_bounds__(256) void closest_fill_kernel(int nq, int k, int32_t *__restrict__ idx,
+                                                           double *__restrict__ cost, uint8_t *__restrict__ hit_out,
+                                                           uint8_t *__restrict__ hit_in, int32_t *__restrict__ count,
+                                                           int32_t *__restrict__ owner, int32_t *__restrict__ row_owner,
+                                                           uint8_t *__restrict__ tree_hit_out,
+                                                           uint8_t *__restrict__ tree_hit_in) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)nq * k) return;
+  idx[e] = -1;
+  cost[e] = __builtin_inf();
+  hit_out[e] = 0;
+  hit_in[e] = 0;
+  owner[e] = (int32_t)(e / k);
+  if (e < nq) {
+    count[e] = 0;
+    row_owner[e] = (int32_t)e;
+    if (tree_hit_out) { tree_hit_out[e] = 0; tree_hit_in[e] = 0; }
+  }
+}
+
+struct ClosestPlan {
+  const double4 *tab;
+  const uint8_t *want;           // [nq] or null: every live row
+  const int32_t *tree_idx;       // [nq] or null
+  int nq, k;
+  int *rows;                     // [nq] the filled rows, ascending
+  int *n_rows;                   // their number
+  int32_t *tree_near;            // [nq] tree_idx of a filled row, -1 otherwise (null with tree_idx)
+  int64_t *slots_end;            // (last filled row + 1) * k: the "offsets[nq]" of the slot entries
+  int64_t *rows_end;             // last filled row + 1: the same for the tree column
+};
+
+__global__ __launch_bounds__(kPlanThreads) void closest_plan_kernel(const ClosestPlan a) {
+  __shared__ int wcnt[2][kPlanThreads / 64], wlast[2][kPlanThreads / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int base = 0, last = -1, flip = 0;
+  for (int j0 = 0; j0 < a.nq; j0 += kPlanThreads, flip ^= 1) {
+    const int j = j0 + t;
+    const bool fill = j < a.nq && a.tab[j].w == 0.0 && (!a.want || a.want[j] != 0);
+    const unsigned long long votes = __ballot(fill);
+    if (lane == 0) {
+      wcnt[flip][wave] = __popcll(votes);
+      wlast[flip][wave] = votes != 0ull ? j0 + wave * 64 + 63 - __clzll((long long)votes) : -1;
+    }
+    __syncthreads();                       // (two sets of counts: the next round's writes cannot overtake this round's reads)
+    int before = 0, total = 0;
+    for (int w = 0; w < kPlanThreads / 64; ++w) {
+      const int c = wcnt[flip][w];
+      if (w < wave) before += c;
+      total += c;
+      last = max(last, wlast[flip][w]);
+    }
+    if (fill) a.rows[base + before + __popcll(votes & lanes_below(lane))] = j;
+    if (j < a.nq && a.tree_near) a.tree_near[j] = fill ? a.tree_idx[j] : -1;
+    base += total;
+  }
+  if (t == 0) {
+    *a.n_rows = base;
+    *a.slots_end = (int64_t)(last + 1) * a.k;
+    *a.rows_end = (int64_t)(last + 1);
+  }
+}
+
+// lane l's value to every lane (l wave-uniform), and every lane's value to the lane above it (lane 0 keeps its own):
+// v_readlane_b32 and a DPP wave shift, no LDS crossbar
+__device__ __forceinline__ int wave_read(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ double wave_read(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ int wave_shift_up(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ double wave_shift_up(double v) {
+  return __hiloint2double(wave_shift_up(__double2hiint(v)), wave_shift_up(__double2loint(v)));
+}
+
+struct ClosestRows {
+  const double4 *tab;
+  const float4 *shadow;
+  const unsigned long long *absmax;
+  const int *rows, *n_rows;
+  int nq, k;
+  double ox, oy, oz;
+  int32_t *idx, *count;
+  double *cost;
+};
+
+__global__ __launch_bounds__(kSelfThreads) void closest_rows_kernel(const ClosestRows a) {
+  __shared__ float4 tile[2][kSelfTile];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int nr = min(max(*a.n_rows, 0), a.nq);
+  const int G = (nr + kClosestGroup - 1) / kClosestGroup;
+  if ((int)blockIdx.x >= G) return;                         // (workgroup-uniform)
+  const int g = G - 1 - (int)blockIdx.x;                    // heaviest group first
+  const double C = __longlong_as_double((long long)*a.absmax);
+  // the wave's rows: sample, columns, the pairs held (pair l in lane l), tau and the screen record for it
+  int rj[kClosestRows], cnt[kClosestRows], bi[kClosestRows];
+  double px[kClosestRows], py[kClosestRows], pz[kClosestRows], tau[kClosestRows], tauf[kClosestRows], bs[kClosestRows];
+  const unsigned long long kmask = lanes_below(a.k);        // (k <= 32)
+  QRecF3 rf[kClosestRows];
+  int wmax = 0;
+#pragma unroll
+  for (int r = 0; r < kClosestRows; ++r) {
+    const int c = g * kClosestGroup + wave * kClosestRows + r;
+    int j = c < nr ? a.rows[c] : -1;
+    if ((unsigned)j >= (unsigned)a.nq) j = -1;
+    j = __builtin_amdgcn_readfirstlane(j);
+    double4 d = make_double4(0.0, 0.0, 0.0, 1.0);
+    if (j >= 0) d = a.tab[j];
+    rj[r] = j; cnt[r] = 0; bi[r] = -1;
+    px[r] = d.x; py[r] = d.y; pz[r] = d.z;
+    tau[r] = __builtin_inf(); tauf[r] = tau[r]; bs[r] = __builtin_inf();
+    QRec3 c3;
+    c3.x = d.x; c3.y = d.y; c3.z = d.z; c3.thr = tau[r];
+    rf[r] = j >= 0 ? make_qrecf<3>(c3, C, a.ox, a.oy, a.oz, 0.0) : never_pass_qrecf<3>();
+    wmax = max(wmax, j);
+  }
+  // the workgroup's last row is the last of its group (the list is ascending): columns 0 .. ncols - 1
+  int ncols = a.rows[min(nr, (g + 1) * kClosestGroup) - 1];
+  ncols = min(max(ncols, 0), a.nq - 1);
+  // (two tile buffers, one barrier a tile, the next tile's shadows asked for before this one is screened: as in the join)
+  float4 pre0 = make_float4(0.f, 0.f, 0.f, __builtin_inff()), pre1 = pre0;
+  if (0 < ncols) {
+    if (t < a.nq) pre0 = a.shadow[t];
+    if (kSelfThreads + t < a.nq) pre1 = a.shadow[kSelfThreads + t];
+  }
+  int buf = 0;
+  for (int tb = 0; tb < ncols; tb += kSelfTile, buf ^= 1) {
+    tile[buf][t] = pre0;
+    tile[buf][kSelfThreads + t] = pre1;
+    __syncthreads();
+    pre0 = make_float4(0.f, 0.f, 0.f, __builtin_inff());
+    pre1 = pre0;
+    if (tb + kSelfTile < ncols) {
+      const int i = tb + kSelfTile + t;
+      if (i < a.nq) pre0 = a.shadow[i];
+      if (i + kSelfThreads < a.nq) pre1 = a.shadow[i + kSelfThreads];
+    }
+    if (tb >= wmax) continue;              // (wave-uniform; the barrier above is passed by every wave all the same)
+    float x[kScanFU], y[kScanFU], z[kScanFU], pp[kScanFU];
+#pragma unroll
+    for (int u = 0; u < kScanFU; ++u) {
+      const float4 c = tile[buf][u * 64 + lane];
+      x[u] = c.x; y[u] = c.y; z[u] = c.z; pp[u] = c.w;
+    }
+#pragma unroll
+    for (int r = 0; r < kClosestRows; ++r) {
+      if (tb >= rj[r]) continue;
+      // "t > thr'" proves s >= tau (thr' = +Inf while the row is not full, and with a non-finite or huge C: nothing is
+      // dropped then); the values do not depend on tau, only the comparison does
+      float tv[kScanFU];
+      screen8<3>(rf[r], x, y, z, nullptr, pp, tv);
+      float lo = tv[0];
+#pragma unroll
+      for (int u = 1; u < kScanFU; ++u) lo = fminf(lo, tv[u]);
+      if (__ballot(!(lo > rf[r].thr)) == 0ull) continue;
+#pragma unroll
+      for (int u = 0; u < kScanFU; ++u) {
+        const bool surv = !(tv[u] > rf[r].thr);
+        if (__ballot(surv) == 0ull) continue;
+        const int i = tb + u * 64 + lane;
+        double s = __builtin_inf();
+        bool hit = false;
+        if (surv && i < rj[r]) {                           // i < j <= nq - 1: inside the table
+          const double4 ci = a.tab[i];
+          if (ci.w == 0.0) {
+            s = sq3(px[r], py[r], pz[r], ci.x, ci.y, ci.z);
+            hit = s < tau[r];                              // (a non-finite s is in no row)
+          }
+        }
+        // the lanes' pairs go in one at a time, ascending in i; each insertion may lower tau and drop the rest
+        unsigned long long b = __ballot(hit);
+        while (b != 0ull) {
+          const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)b) - 1);
+          const double ns = wave_read(s, l);
+          const int ni = tb + u * 64 + l;
+          // the pairs held have lower indices, so the new one goes behind every pair with the same s (lanes k and up
+          // hold what fell off the row: not counted, never read)
+          const int pos = __popcll(__ballot(bs[r] <= ns) & kmask);
+          const double us = wave_shift_up(bs[r]);
+          const int ui = wave_shift_up(bi[r]);
+          if (lane > pos) { bs[r] = us; bi[r] = ui; }
+          else if (lane == pos) { bs[r] = ns; bi[r] = ni; }
+          cnt[r] = min(cnt[r] + 1, a.k);
+          if (cnt[r] == a.k) tau[r] = wave_read(bs[r], a.k - 1);
+          hit = hit && lane != l && s < tau[r];
+          b = __ballot(hit);
+        }
+      }
+      // the screen record follows tau once a tile: a stale (higher) tau only lets more pairs through to the exact test
+      if (tau[r] != tauf[r]) {
+        tauf[r] = tau[r];
+        QRec3 c3;
+        c3.x = px[r]; c3.y = py[r]; c3.z = pz[r]; c3.thr = tau[r];
+        rf[r] = make_qrecf<3>(c3, C, a.ox, a.oy, a.oz, 0.0);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kClosestRows; ++r) {
+    if (rj[r] < 0) continue;
+    if (lane < cnt[r]) {
+      a.idx[(size_t)rj[r] * a.k + lane] = bi[r];
+      a.cost[(size_t)rj[r] * a.k + lane] = sqrt_rn(bs[r]);
+    }
+    if (lane == 0) a.count[rj[r]] = cnt[r];
+  }
+}
+
 }  // namespace
+
+int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, const uint8_t *skip_dev,
+                        const uint8_t *want_dev, const int32_t *tree_idx_dev, int32_t *idx_dev, double *cost_dev,
+                        uint8_t *hit_out_dev, uint8_t *hit_in_dev, int32_t *count_dev, uint8_t *tree_hit_out_dev,
+                        uint8_t *tree_hit_in_dev) {
+  if (nq <= 0) return RRTX_OK;
+  // ws_self: table (32 B a sample), shadow (16 B), the two "offsets" arrays of the edge kernels (only their last word
+  // is read: the number of entries), the compact row list, the tree column's node indices, the rows' own indices, C and
+  // the number of rows.  ws_owner: the owner row of every slot.
+  const size_t n = (size_t)nq, cap = n * (size_t)k;
+  const size_t off_shadow = sizeof(double4) * n, off_slots = off_shadow + sizeof(float4) * n;
+  const size_t off_rowsend = off_slots + sizeof(int64_t) * (n + 1), off_max = off_rowsend + sizeof(int64_t) * (n + 1);
+  const size_t off_rows = off_max + sizeof(unsigned long long), off_near = off_rows + sizeof(int) * n;
+  const size_t off_rown = off_near + sizeof(int32_t) * n, off_nrows = off_rown + sizeof(int32_t) * n;
+  RRTX_HIP(ctx, ctx->ws_self.ensure(off_nrows + sizeof(int)));
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * cap));
+  char *ws = ctx->ws_self.as<char>();
+  double4 *tab = reinterpret_cast<double4 *>(ws);
+  float4 *shadow = reinterpret_cast<float4 *>(ws + off_shadow);
+  int64_t *slots_off = reinterpret_cast<int64_t *>(ws + off_slots), *rows_off = reinterpret_cast<int64_t *>(ws + off_rowsend);
+  unsigned long long *absmax = reinterpret_cast<unsigned long long *>(ws + off_max);
+  int32_t *row_owner = reinterpret_cast<int32_t *>(ws + off_rown);
+  RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
+  ClosestPlan p;
+  p.tab = tab; p.want = want_dev; p.tree_idx = tree_idx_dev; p.nq = nq; p.k = k;
+  p.rows = reinterpret_cast<int *>(ws + off_rows); p.n_rows = reinterpret_cast<int *>(ws + off_nrows);
+  p.tree_near = tree_idx_dev ? reinterpret_cast<int32_t *>(ws + off_near) : nullptr;
+  p.slots_end = slots_off + n; p.rows_end = rows_off + n;
+  ClosestRows a;
+  a.tab = tab; a.shadow = shadow; a.absmax = absmax; a.rows = p.rows; a.n_rows = p.n_rows; a.nq = nq; a.k = k;
+  a.ox = ctx->origin[0]; a.oy = ctx->origin[1]; a.oz = ctx->origin[2];
+  a.idx = idx_dev; a.count = count_dev; a.cost = cost_dev;
+  span_begin(ctx, KF_NN_SCAN);
+  hipLaunchKernelGGL(self_table_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, q_dev, nq, skip_dev,
+                     a.ox, a.oy, a.oz, tab, shadow, absmax);
+  hipLaunchKernelGGL(closest_fill_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, nq, k, idx_dev,
+                     cost_dev, hit_out_dev, hit_in_dev, count_dev, ctx->ws_owner.as<int32_t>(), row_owner, tree_hit_out_dev,
+                     tree_hit_in_dev);
+  hipLaunchKernelGGL(closest_plan_kernel, dim3(1), dim3(kPlanThreads), 0, ctx->stream, p);
+  hipLaunchKernelGGL(closest_rows_kernel, dim3((unsigned)((nq + kClosestGroup - 1) / kClosestGroup)), dim3(kSelfThreads), 0,
+                     ctx->stream, a);
+  span_end(ctx);
+  RRTX_HIP(ctx, hipGetLastError());
+  // both directed edges of every slot against the WHOLE obstacle list (r < 0), by the kernels of rrtx_extend_candidates:
+  // slot e = (row e / k, sample idx[e]); an empty slot (idx -1) and everything past the last filled row is left alone
+  const double *table = reinterpret_cast<const double *>(tab);
+  int rc;
+  if (ctx->opt_extend_polygons)
+    rc = launch_candidate_edges_polygons(ctx, q_dev, nq, slots_off, idx_dev, ctx->ws_owner.as<int32_t>(), (int64_t)cap,
+                                         robot_radius, hit_out_dev, hit_in_dev, nullptr, -1.0, table, nq);
+  else
+    rc = launch_candidate_edges(ctx, q_dev, nq, slots_off, idx_dev, ctx->ws_owner.as<int32_t>(), (int64_t)cap, robot_radius,
+                                hit_out_dev, hit_in_dev, -1.0, nullptr, table, nq);
+  if (rc || !tree_idx_dev) return rc;
+  // the tree column: one entry a row, (row j, node tree_idx[j]); an index outside the tree is left alone by the kernels
+  if (ctx->n_nodes <= 0 || !ctx->nodes_aos) return RRTX_OK;
+  if (ctx->opt_extend_polygons)
+    return launch_candidate_edges_polygons(ctx, q_dev, nq, rows_off, p.tree_near, row_owner, (int64_t)nq, robot_radius,
+                                           tree_hit_out_dev, tree_hit_in_dev, nullptr, -1.0);
+  return launch_candidate_edges(ctx, q_dev, nq, rows_off, p.tree_near, row_owner, (int64_t)nq, robot_radius, tree_hit_out_dev,
+                                tree_hit_in_dev, -1.0);
+}
 
 int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev, int64_t *offsets_dev,
                      int32_t *idx_dev, double *cost_dev, int32_t *owner_dev, int64_t cap, int64_t *needed_dev,

@@ -1978,6 +1978,89 @@ int rrtx_extend_candidates_self(rrtx_ctx *ctx, const double *q, int nq, double r
   return RRTX_OK;
 }
 
+// ---- the closestNode rule for an extend batch: k nearest earlier samples (kernels_self.hip) --------
+static int extend_closest_args(rrtx_ctx *ctx, const double *q, int nq, int k, const int32_t *tree_idx, const int32_t *idx,
+                               const double *cost, const uint8_t *hit_out, const uint8_t *hit_in, const int32_t *count,
+                               const uint8_t *tree_hit_out, const uint8_t *tree_hit_in) {
+  const int n_tree = (tree_idx ? 1 : 0) + (tree_hit_out ? 1 : 0) + (tree_hit_in ? 1 : 0);
+  if (nq < 0 || k < 1 || k > RRTX_CLOSEST_SELF_MAX_K || (n_tree != 0 && n_tree != 3) ||
+      (nq > 0 && (!q || !idx || !cost || !hit_out || !hit_in || !count)))
+    return fail(ctx, RRTX_E_INVALID, "extend_closest_self: bad arguments");
+  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_closest_self is the SimpleEdge (dim=3) path");
+  if (ctx->n_wraps != 0)
+    return fail(ctx, RRTX_E_STATE, "extend_closest_self completes the lists of rrtx_extend_candidates, which needs a "
+                                   "space without wrapped dimensions");
+  if ((int64_t)nq * k >= (1ll << 30)) return fail(ctx, RRTX_E_INVALID, "extend_closest_self: at most 2^30 - 1 slots per call");
+  return RRTX_OK;
+}
+
+int rrtx_extend_closest_self_dev(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, const uint8_t *skip,
+                                 const uint8_t *want, const int32_t *tree_idx, int32_t *idx, double *cost,
+                                 uint8_t *hit_out, uint8_t *hit_in, int32_t *count, uint8_t *tree_hit_out,
+                                 uint8_t *tree_hit_in) {
+  CHECK_CTX(ctx);
+  int rc = extend_closest_args(ctx, q, nq, k, tree_idx, idx, cost, hit_out, hit_in, count, tree_hit_out, tree_hit_in);
+  if (rc || nq == 0) return rc;
+  return launch_closest_self(ctx, q, nq, k, robot_radius, skip, want, tree_idx, idx, cost, hit_out, hit_in, count,
+                             tree_hit_out, tree_hit_in);
+}
+
+int rrtx_extend_closest_self(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, const uint8_t *skip,
+                             const uint8_t *want, const int32_t *tree_idx, int32_t *idx, double *cost, uint8_t *hit_out,
+                             uint8_t *hit_in, int32_t *count, uint8_t *tree_hit_out, uint8_t *tree_hit_in) {
+  CHECK_CTX(ctx);
+  int rc = extend_closest_args(ctx, q, nq, k, tree_idx, idx, cost, hit_out, hit_in, count, tree_hit_out, tree_hit_in);
+  if (rc || nq == 0) return rc;
+  const size_t n = (size_t)nq, slots = n * (size_t)k, q_bytes = sizeof(double) * n * 3;
+  // inputs beside q in ws_q2: skip, want (a byte a sample each), tree_idx; per-sample outputs in ws_out_off: count, then
+  // the two bytes of the tree column
+  const size_t in_want = n, in_tree = (2 * n + 3) & ~(size_t)3, in_bytes = in_tree + sizeof(int32_t) * n;
+  const size_t out_tho = sizeof(int32_t) * n, out_thi = out_tho + n, out_bytes = out_thi + n;
+  rc = arena_begin(ctx, q_bytes + in_bytes + out_bytes + slots * 14 + 1024);
+  if (rc) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
+  RRTX_HIP(ctx, ctx->ws_q2.ensure(in_bytes));
+  char *in_dev = ctx->ws_q2.as<char>();
+  auto stage_at = [&](size_t off, const void *host, size_t bytes) -> int {
+    const void *from = host;
+    char *a = arena_take(ctx, bytes);
+    if (a) { std::memcpy(a, host, bytes); from = a; }
+    RRTX_HIP(ctx, hipMemcpyAsync(in_dev + off, from, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return RRTX_OK;
+  };
+  if (skip && (rc = stage_at(0, skip, n))) return rc;
+  if (want && (rc = stage_at(in_want, want, n))) return rc;
+  if (tree_idx && (rc = stage_at(in_tree, tree_idx, sizeof(int32_t) * n))) return rc;
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(out_bytes));
+  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * slots));
+  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * slots));
+  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(slots));
+  RRTX_HIP(ctx, ctx->ws_out_u8b.ensure(slots));
+  char *out_dev = ctx->ws_out_off.as<char>();
+  rc = rrtx_extend_closest_self_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius,
+                                    skip ? reinterpret_cast<const uint8_t *>(in_dev) : nullptr,
+                                    want ? reinterpret_cast<const uint8_t *>(in_dev + in_want) : nullptr,
+                                    tree_idx ? reinterpret_cast<const int32_t *>(in_dev + in_tree) : nullptr,
+                                    ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_dist.as<double>(),
+                                    ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(),
+                                    reinterpret_cast<int32_t *>(out_dev),
+                                    tree_idx ? reinterpret_cast<uint8_t *>(out_dev + out_tho) : nullptr,
+                                    tree_idx ? reinterpret_cast<uint8_t *>(out_dev + out_thi) : nullptr);
+  if (rc) return rc;
+  if ((rc = d2h(ctx, count, out_dev, sizeof(int32_t) * n))) return rc;
+  if (tree_idx) {
+    if ((rc = d2h(ctx, tree_hit_out, out_dev + out_tho, n))) return rc;
+    if ((rc = d2h(ctx, tree_hit_in, out_dev + out_thi, n))) return rc;
+  }
+  if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * slots))) return rc;
+  if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * slots))) return rc;
+  if ((rc = d2h(ctx, hit_out, ctx->ws_out_u8a.p, slots))) return rc;
+  if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, slots))) return rc;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  arena_flush(ctx);
+  return RRTX_OK;
+}
+
 static int extend_dubins_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,
                               const double *key, const double *cost_out, const double *cost_in, const uint8_t *hit_out,
                               const uint8_t *hit_in, int64_t cap) {

@@ -452,6 +452,13 @@ int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const
 int launch_self_join_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
                             int64_t *offsets_dev, int32_t *idx_dev, double *key_dev, int32_t *owner_dev, int64_t cap,
                             int64_t *needed_dev, const double **columns_out);
+// the k nearest earlier samples of every wanted live sample (kernels_self.hip): nq x k slots, both edge flags of every
+// slot against the whole obstacle list, and the same flags for (sample, node tree_idx) when a tree column is given;
+// device pointers, bounded by nq, k and the node count on the device
+int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, const uint8_t *skip_dev,
+                        const uint8_t *want_dev, const int32_t *tree_idx_dev, int32_t *idx_dev, double *cost_dev,
+                        uint8_t *hit_out_dev, uint8_t *hit_in_dev, int32_t *count_dev, uint8_t *tree_hit_out_dev,
+                        uint8_t *tree_hit_in_dev);
 int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                               const int32_t *idx_dev, const double *dist_dev, int32_t *nearest_idx_dev,
                               double *nearest_dist_dev);

@@ -567,6 +567,31 @@ def extend_candidates_self(tree: HipTree, S: CSpace, newPositions, hyberBallRad_
     return out
 
 
+def extend_closest_self(tree: HipTree, S: CSpace, newPositions, k: int, skip=None, want=None, treeNearest=None):
+    """For the closestNode rule of findBestParent (R/DRRT_Q.jl:1930-1935) in a batch: a sample whose ball is empty is
+    linked to kdFindNearest over the tree as sequential insertion would have it, which may be an earlier sample of the
+    same batch.  Row j holds the k nearest live earlier batch positions i < j by (distance, i), with the SimpleEdge cost
+    and the flags of q_j -> q_i (hit_out) and q_i -> q_j (hit_in) against the whole obstacle list; count[j] says how
+    many.  skip: non-zero bytes take a sample out (sample_unsafe of extend_candidates); want: the rows to fill (the
+    samples whose tree list is empty); treeNearest: nearest_idx of extend_candidates, whose two flags come back as
+    tree_hit_out / tree_hit_in.  The caller walks row j, takes the first entry whose sample it inserted and links to it
+    if its cost < nearest_dist[j], else to the tree node; a row with count == k, no inserted entry and its k-th cost
+    below nearest_dist[j] is exhausted and the caller searches the batch itself."""
+    if tree.d != 3:
+        error("extend_closest_self is the SimpleEdge (3-D) path")
+    S.bind(tree)
+    kind = _sync_obstacles(S)
+    from . import _capi
+    tree.ctx.set_option(_capi.RRTX_OPT_EXTEND_OBSTACLES, kind)
+    q = np.asarray(newPositions, dtype=np.float64).reshape(-1, 3)
+    out = tree.ctx.extend_closest_self(q, int(k), S.robotRadius, skip=skip, want=want, tree_idx=treeNearest)
+    if S.inWarmupTime:
+        for name in ("hit_out", "hit_in", "tree_hit_out", "tree_hit_in"):
+            if out[name] is not None:
+                out[name][:] = 0
+    return out
+
+
 def _dubins_space(tree: HipTree, S: CSpace, what: str):
     """the context made ready for a Dubins extend call: obstacles (polygons) and the space's time setting"""
     if tree.d != 4:
