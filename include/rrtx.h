@@ -620,7 +620,7 @@ int rrtx_extend_candidates_self(rrtx_ctx *ctx, const double *q, int nq, double r
  *            tree_idx / tree_hit_out / tree_hit_in all NULL or all given; otherwise RRTX_E_INVALID.  Obstacles: the
  *            spheres or the polygons by RRTX_OPT_EXTEND_OBSTACLES; kinds 6 / 7 read time from the third coordinate.
  *            Apart from tree_idx the tree is not read; an empty tree is fine.  The Dubins spaces ([x y t theta], wrapped
- *            dimensions, rrtx_extend_candidates_self_dubins) are out of scope.
+ *            dimensions, rrtx_extend_candidates_self_dubins) are out of scope here: rrtx_extend_closest_self_dubins.
  *   Live     a sample is live when every coordinate is finite and skip[j] == 0 (skip: nq bytes or NULL; the
  *            sample_unsafe bytes of rrtx_extend_candidates can be passed as they are).
  *   Rows     idx, cost, hit_out, hit_in are nq x k, row-major, as in rrtx_nn_knearest; count is nq.  Row j is filled iff
@@ -697,6 +697,57 @@ int rrtx_extend_candidates_self_dubins(rrtx_ctx *ctx, const double *q, int nq, d
                                        double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
                                        uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
 
+/* ---- the closestNode rule for a Dubins extend batch: k nearest in wrapped space - */
+/* What rrtx_extend_closest_self is to the SimpleEdge spaces, for Edge = DubinsEdge: a sample whose ball is empty is linked
+ * to closestNode (findBestParent, R/DRRT_Q.jl:1930-1935), kdFindNearest over the tree as sequential insertion would have
+ * it, which may be an earlier sample of the same batch.  Per wanted sample j of a batch q (nq x 4, [x y t theta]) this
+ * call gives its k nearest live earlier samples in the context's wrapped space, per entry what
+ * rrtx_extend_candidates_dubins reports (key, both Dubins costs, both words, both flag bytes), and the same for one tree
+ * node per sample.
+ *   Scope    dim == 4, otherwise RRTX_E_STATE; the wrapped dimensions are the context's (rrtx_set_wrap, 0 to 3 of them).
+ *            1 <= k <= RRTX_CLOSEST_SELF_MAX_K, nq >= 0, non-NULL outputs when nq > 0 except word_out, word_in,
+ *            tree_word_out, tree_word_in, which may be NULL; tree_idx, tree_cost_out, tree_cost_in, tree_hit_out,
+ *            tree_hit_in all NULL or all given (the tree words are not written without them); anything else is
+ *            RRTX_E_INVALID.  Obstacles: the polygon list, as in rrtx_extend_candidates_dubins.  Apart from tree_idx the
+ *            tree is not read; an empty tree is fine.
+ *   Live     a sample is live when all four coordinates are finite and skip[j] == 0 (skip: nq bytes or NULL).
+ *   Copies   sample j has 2^w copies by the rule of rrtx_extend_candidates_self_dubins, in its slot order: a shifted
+ *            coordinate p < period / 2 becomes p + period, anything else p - period.  NO copy is skipped: there is no
+ *            radius to skip by.  The column sample i is taken as it is.
+ *   Rows     idx, key, cost_out, cost_in, hit_out, hit_in are nq x k, row-major, word_out / word_in nq x k x 3 bytes;
+ *            count is nq.  s(j, i) = min over all 2^w slots of sq4(copy_slot(q_j), q_i), sq4 the unfused left-to-right
+ *            fp64 expression.  Row j is filled iff j is live and (want == NULL or want[j] != 0).  A filled row holds the
+ *            live i < j with finite s, ordered by (s, i) ascending: the first min(k, their number) of them, count[j]
+ *            says how many.  key = sqrt(s), correctly rounded.  Unused slots and rows that are not filled have idx = -1,
+ *            key = cost_out = cost_in = +Inf, words three zero bytes, flags 0, count = 0.  idx is a 0-based position in
+ *            q.  want only chooses rows: a sample with want[j] == 0 is still a candidate in the rows of the others.
+ *   Entries  cost_out / word_out / hit_out: the directed Dubins edge q_j -> q_i; cost_in / word_in / hit_in: q_i -> q_j;
+ *            by the steering and check kernels of rrtx_extend_candidates_dubins over the WHOLE polygon list, so
+ *            RRTX_OPT_SPACE_HAS_TIME (bit 1 of a flag byte = !validMove), rrtx_set_dubins_velocity,
+ *            RRTX_OPT_DUBINS_TIME_COLUMN, moving polygons and the active flags hold as there: byte for byte and bit for
+ *            bit what rrtx_dubins_edges_check (plus validMove with time) returns for that edge.
+ *   Tree     a filled row with 0 <= tree_idx[j] < rrtx_nodes_count gets the same fields for q_j <-> node in tree_cost_out
+ *            / tree_word_out / tree_hit_out (q_j -> node) and tree_cost_in / tree_word_in / tree_hit_in; otherwise cost
+ *            +Inf, words and flags 0 (an index out of range is not an error).  nearest_idx of
+ *            rrtx_extend_candidates_dubins is the intended input.
+ *   The rule as for rrtx_extend_closest_self: walk row j and take the first entry whose sample was inserted.  Link to it
+ *            if key < nearest_dist[j], else to the tree node (on a tie the tree node, which has the lower index, wins).
+ *            A row with count[j] == k and no inserted entry is exhausted: the caller then searches the batch itself and
+ *            calls rrtx_dubins_edges_check twice.  It need not when the k-th key is not below nearest_dist[j].
+ *   kdFindNearest  the reference hands out a ghost only while dist(closest unwrapped point, ghost) is not above the best
+ *            distance so far.  For a column whose wrapped coordinates lie in [0, period] every term of
+ *            sq4(ghost, column) is at least the matching term of sq4(closest, ghost) and fp rounding is monotone, so a
+ *            skipped ghost never improves the minimum and the row's order is kdFindNearest's.  The guarantee holds for
+ *            samples inside the period in their wrapped coordinates, which is what the planner draws; outside the period
+ *            the row is still exactly as defined above.
+ * Exact, no tolerance; nothing in the result depends on launch geometry or on the order in which waves finish. */
+int rrtx_extend_closest_self_dubins(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, double r_min,
+                                    const uint8_t *skip, const uint8_t *want, const int32_t *tree_idx, int32_t *idx,
+                                    double *key, double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
+                                    uint8_t *hit_out, uint8_t *hit_in, int32_t *count, double *tree_cost_out,
+                                    double *tree_cost_in, uint8_t *tree_word_out, uint8_t *tree_word_in,
+                                    uint8_t *tree_hit_out, uint8_t *tree_hit_in);
+
 /* ---- device-resident variants (inputs/outputs are DEVICE pointers) ------------ */
 int rrtx_nn_nearest_dev(rrtx_ctx *ctx, const double *q, int nq, int32_t *idx, double *dist);
 /* rows max(k, 2) wide as in rrtx_nn_knearest.  The list path (RRTX_OPT_KNN_LISTS) reads two small values
@@ -749,6 +800,16 @@ int rrtx_extend_candidates_self_dubins_dev(rrtx_ctx *ctx, const double *q, int n
                                            double *key, double *cost_out, double *cost_in, uint8_t *word_out,
                                            uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in, int64_t cap,
                                            int64_t *needed_dev);
+
+/* device-pointer form of rrtx_extend_closest_self_dubins (skip, want, the four word arrays and the tree arrays may be NULL
+ * as there).  Only enqueues; the growth of a workspace may wait on the stream once.  Every read of q and tree_idx and
+ * every write is bounded by nq, k and the node count on the device. */
+int rrtx_extend_closest_self_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, double r_min,
+                                        const uint8_t *skip, const uint8_t *want, const int32_t *tree_idx, int32_t *idx,
+                                        double *key, double *cost_out, double *cost_in, uint8_t *word_out,
+                                        uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in, int32_t *count,
+                                        double *tree_cost_out, double *tree_cost_in, uint8_t *tree_word_out,
+                                        uint8_t *tree_word_in, uint8_t *tree_hit_out, uint8_t *tree_hit_in);
 
 /* Per-edge collision bitmask for the multi-GPU exchange (RCCL all-reduce over
  * xGMI): bit e (e < cap) = hit_out[e], bit cap+e = hit_in[e]; entries at or

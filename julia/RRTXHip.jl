@@ -1126,3 +1126,63 @@ function extend_candidates_self_dubins(tree::HipTree, S::TS, positions::Array{Fl
     return ExtendCandidatesSelfDubins(offsets, idx[1:n], key[1:n], cout[1:n], cin[1:n], hout[1:n], hin[1:n])
   end
 end
+
+# extend_closest_self for Edge = DubinsEdge: the closestNode rule of findBestParent (R/DRRT_Q.jl:1930-1935) in a Dubins
+# batch.  Column j (k slots, Julia is column-major) holds the nearest live earlier batch positions i < j (0-based) in the
+# wrapped space, ordered by (distance, i), the distance being the minimum over the copies of q_j; per slot the key and the
+# Dubins cost and flags of q_j -> q_i (Out) and q_i -> q_j (In) against the whole polygon list; count[j] slots are used,
+# the others have idx -1 and key / cost Inf.  skip: non-zero bytes take a sample out (sampleUnsafe of
+# extend_candidates_dubins); want: the samples to fill (those whose tree list is empty; nothing: every live one);
+# treeNearest: nearestIdx of extend_candidates_dubins, whose costs and flags come back in the tree* fields (empty
+# otherwise).  The caller walks column j, takes the first entry whose sample it inserted and links to it if its key <
+# nearestDist[j], else to the tree node; with count[j] == k, no inserted entry and the k-th key below nearestDist[j] it
+# searches the batch itself.
+struct ExtendClosestSelfDubins
+  idx::Matrix{Int32}          # k x nq, 0-based positions in the batch, -1: unused
+  key::Matrix{Float64}
+  costOut::Matrix{Float64}
+  costIn::Matrix{Float64}
+  hitOut::Matrix{UInt8}
+  hitIn::Matrix{UInt8}
+  count::Vector{Int32}
+  treeCostOut::Vector{Float64}
+  treeCostIn::Vector{Float64}
+  treeHitOut::Vector{UInt8}
+  treeHitIn::Vector{UInt8}
+end
+
+function extend_closest_self_dubins(tree::HipTree, S::TS, positions::Array{Float64,2}, k::Int;
+                                    skip::Union{Nothing,Vector{UInt8}} = nothing,
+                                    want::Union{Nothing,Vector{UInt8}} = nothing,
+                                    treeNearest::Union{Nothing,Vector{Int32}} = nothing) where {TS}
+  nq = size(positions, 2)                     # 4 x nq
+  skip === nothing || length(skip) == nq || error("skip needs one byte per sample")
+  want === nothing || length(want) == nq || error("want needs one byte per sample")
+  treeNearest === nothing || length(treeNearest) == nq || error("treeNearest needs one index per sample")
+  skipArg = skip === nothing ? UInt8[] : skip
+  skipPtr = skip === nothing ? Ptr{UInt8}(C_NULL) : pointer(skipArg)
+  wantArg = want === nothing ? UInt8[] : want
+  wantPtr = want === nothing ? Ptr{UInt8}(C_NULL) : pointer(wantArg)
+  nt = treeNearest === nothing ? 0 : nq
+  treeArg = treeNearest === nothing ? Int32[] : treeNearest
+  tco = Vector{Float64}(undef, nt); tci = Vector{Float64}(undef, nt)
+  tho = Vector{UInt8}(undef, nt); thi = Vector{UInt8}(undef, nt)
+  treePtr = treeNearest === nothing ? Ptr{Int32}(C_NULL) : pointer(treeArg)
+  tcoPtr = treeNearest === nothing ? Ptr{Cdouble}(C_NULL) : pointer(tco)
+  tciPtr = treeNearest === nothing ? Ptr{Cdouble}(C_NULL) : pointer(tci)
+  thoPtr = treeNearest === nothing ? Ptr{UInt8}(C_NULL) : pointer(tho)
+  thiPtr = treeNearest === nothing ? Ptr{UInt8}(C_NULL) : pointer(thi)
+  kk = max(k, 0)
+  idx = Matrix{Int32}(undef, kk, nq); key = Matrix{Float64}(undef, kk, nq)
+  cout = Matrix{Float64}(undef, kk, nq); cin = Matrix{Float64}(undef, kk, nq)
+  hout = Matrix{UInt8}(undef, kk, nq); hin = Matrix{UInt8}(undef, kk, nq)
+  count = Vector{Int32}(undef, nq)
+  rc = GC.@preserve positions skipArg wantArg treeArg idx key cout cin hout hin count tco tci tho thi ccall((:rrtx_extend_closest_self_dubins, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble},
+       Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble},
+       Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt8}),
+      tree.ctx, positions, nq, k, S.robotRadius, S.minTurningRadius, skipPtr, wantPtr, treePtr, idx, key, cout, cin,
+      C_NULL, C_NULL, hout, hin, count, tcoPtr, tciPtr, C_NULL, C_NULL, thoPtr, thiPtr)
+  rrtx_check(tree, rc)
+  return ExtendClosestSelfDubins(idx, key, cout, cin, hout, hin, count, tco, tci, tho, thi)
+end

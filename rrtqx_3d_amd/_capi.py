@@ -157,6 +157,8 @@ SYMBOLS = [
                                                      _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, c_int64_p]),
     ("rrtx_extend_candidates_self_dubins_dev", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, _VP, _VP,
                                                          _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    ("rrtx_extend_closest_self_dubins", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, C.c_double] + [_VP] * 18),
+    ("rrtx_extend_closest_self_dubins_dev", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, C.c_double] + [_VP] * 18),
     ("rrtx_nn_nearest_dev", C.c_int, [_VP, _VP, C.c_int, _VP, _VP]),
     ("rrtx_nn_knearest_dev", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     ("rrtx_nn_radius_dev", C.c_int, [_VP, _VP, C.c_double, C.c_int, _VP, _VP, _VP, C.c_int64, _VP]),

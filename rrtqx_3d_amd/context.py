@@ -625,6 +625,53 @@ class Context:
         return dict(offsets=offsets, idx=idx[:n], key=key[:n], cost_out=co[:n], cost_in=ci[:n],
                     word_out=wo[:n].view("S3").ravel(), word_in=wi[:n].view("S3").ravel(), hit_out=ho[:n], hit_in=hi[:n])
 
+    def extend_closest_self_dubins(self, q, k: int, robot_radius: float, r_min: float, skip=None, want=None,
+                                   tree_idx=None) -> dict:
+        """rrtx_extend_closest_self_dubins: for the closestNode rule of a Dubins batch (dim 4, the wrapped dimensions as
+        set).  Row j (of k slots) holds the nearest live earlier samples i < j of the batch ordered by (s, i), s the
+        minimum over the copies of q_j of the squared distance to q_i, with key = sqrt(s) and the Dubins cost, word and
+        flags of q_j -> q_i (out) and q_i -> q_j (in) against the whole polygon list; count[j] of them are used, the other
+        slots have idx -1, key and costs +Inf.  skip: non-zero bytes take a sample out (sample_unsafe of
+        extend_candidates_dubins); want: non-zero bytes choose the rows to fill (None: every live row); tree_idx: one node
+        per sample whose fields come back as tree_cost_out, tree_cost_in, tree_word_out, tree_word_in, tree_hit_out,
+        tree_hit_in (an index outside the tree gives +Inf and 0).
+        dict(idx, key, cost_out, cost_in, word_out, word_in, hit_out, hit_in: (nq, k); count: (nq,); tree_*: (nq,) or
+        None)."""
+        q = f64(q, (-1, 4))
+        nq, k = q.shape[0], int(k)
+
+        def per_sample(a, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            if a.shape[0] != nq:
+                raise ValueError(what + " needs one entry per sample")
+            return a
+        sk, wa = per_sample(skip, np.uint8, "skip"), per_sample(want, np.uint8, "want")
+        ti = per_sample(tree_idx, np.int32, "tree_idx")
+        rows = max(k, 0)
+        idx = np.empty((nq, rows), dtype=np.int32)
+        key, co, ci = (np.empty((nq, rows), dtype=np.float64) for _ in range(3))
+        wo, wi = (np.empty((nq, rows, 3), dtype=np.uint8) for _ in range(2))
+        ho, hi = (np.empty((nq, rows), dtype=np.uint8) for _ in range(2))
+        count = np.empty(nq, dtype=np.int32)
+        tco = tci = two = twi = tho = thi = None
+        if ti is not None:
+            tco, tci = (np.empty(nq, dtype=np.float64) for _ in range(2))
+            two, twi = (np.empty((nq, 3), dtype=np.uint8) for _ in range(2))
+            tho, thi = (np.empty(nq, dtype=np.uint8) for _ in range(2))
+        self._check(self._lib.rrtx_extend_closest_self_dubins(
+            self._h, _capi._ptr(q), nq, k, robot_radius, r_min, _capi._ptr(sk), _capi._ptr(wa), _capi._ptr(ti),
+            _capi._ptr(idx), _capi._ptr(key), _capi._ptr(co), _capi._ptr(ci), _capi._ptr(wo), _capi._ptr(wi), _capi._ptr(ho),
+            _capi._ptr(hi), _capi._ptr(count), _capi._ptr(tco), _capi._ptr(tci), _capi._ptr(two), _capi._ptr(twi),
+            _capi._ptr(tho), _capi._ptr(thi)))
+
+        def words(w, shape):
+            return None if w is None else w.view("S3").reshape(shape)
+        return dict(idx=idx, key=key, cost_out=co, cost_in=ci, word_out=words(wo, (nq, rows)), word_in=words(wi, (nq, rows)),
+                    hit_out=ho, hit_in=hi, count=count, tree_cost_out=tco, tree_cost_in=tci,
+                    tree_word_out=words(two, (nq,)), tree_word_in=words(twi, (nq,)), tree_hit_out=tho, tree_hit_in=thi)
+
     # ---- device-pointer variants (pointers are ints, e.g. torch.Tensor.data_ptr()) ----------------
     def nn_nearest_dev(self, q_ptr: int, nq: int, idx_ptr: int, dist_ptr: int):
         self._check(self._lib.rrtx_nn_nearest_dev(self._h, q_ptr, nq, idx_ptr, dist_ptr))
@@ -687,6 +734,19 @@ class Context:
         self._check(self._lib.rrtx_extend_candidates_self_dubins_dev(
             self._h, q_ptr, nq, r, robot_radius, r_min, skip_ptr, offsets_ptr, idx_ptr, key_ptr, cost_out_ptr, cost_in_ptr,
             word_out_ptr, word_in_ptr, hit_out_ptr, hit_in_ptr, cap, needed_ptr))
+
+    def extend_closest_self_dubins_dev(self, q_ptr: int, nq: int, k: int, robot_radius: float, r_min: float,
+                                       skip_ptr: Optional[int], want_ptr: Optional[int], tree_idx_ptr: Optional[int],
+                                       idx_ptr: int, key_ptr: int, cost_out_ptr: int, cost_in_ptr: int,
+                                       word_out_ptr: Optional[int], word_in_ptr: Optional[int], hit_out_ptr: int,
+                                       hit_in_ptr: int, count_ptr: int, tree_cost_out_ptr: Optional[int] = None,
+                                       tree_cost_in_ptr: Optional[int] = None, tree_word_out_ptr: Optional[int] = None,
+                                       tree_word_in_ptr: Optional[int] = None, tree_hit_out_ptr: Optional[int] = None,
+                                       tree_hit_in_ptr: Optional[int] = None):
+        self._check(self._lib.rrtx_extend_closest_self_dubins_dev(
+            self._h, q_ptr, nq, k, robot_radius, r_min, skip_ptr, want_ptr, tree_idx_ptr, idx_ptr, key_ptr, cost_out_ptr,
+            cost_in_ptr, word_out_ptr, word_in_ptr, hit_out_ptr, hit_in_ptr, count_ptr, tree_cost_out_ptr, tree_cost_in_ptr,
+            tree_word_out_ptr, tree_word_in_ptr, tree_hit_out_ptr, tree_hit_in_ptr))
 
     def pack_hits_dev(self, hit_out_ptr: int, hit_in_ptr: int, n_valid_ptr: int, cap: int, words_ptr: int):
         self._check(self._lib.rrtx_pack_hits_dev(self._h, hit_out_ptr, hit_in_ptr, n_valid_ptr, cap, words_ptr))

@@ -729,6 +729,243 @@ __global__ __launch_bounds__(kSelfThreads) void closest_rows_kernel(const Closes
   }
 }
 
+// ---- the same rows in [x y t theta] with wrapped dimensions (rrtx_extend_closest_self_dubins) ---------------------
+// Sibling kernels once more, so everything above keeps its machine code.  The row sample j is the query with its 2^w
+// copies (self_copy's slots; NONE is skipped: there is no radius to skip by), the column sample i is taken as it is, and
+//   s(j, i) = min over the slots of sq4(copy_slot(q_j), q_i),
+// the distance kdFindNearest settles on once it has handed out its ghosts.  A row holds the first k of the live i < j
+// with finite s, ordered by (s, i); the key is sqrt_rn(s).
+//   self_table4_kernel     as above with thr_gt = +Inf: no copy is left out of C, which the screen's proof asks for.
+//   closest_fill4_kernel   every slot to "none" (idx -1, key and both costs +Inf, words and flags 0, count 0), the owner
+//                          row of every slot, the tree column's defaults.
+//   closest_plan4_kernel   closest_plan_kernel with the table's mark byte as the live mark.
+//   closest_rows4_kernel   closest_rows_kernel's walk.  The row's copies and their screen records are wave-uniform: a
+//                          small LDS block per wave, written by the wave's first lanes and read as a broadcast.  The slot
+//                          count is a loop bound (1, 2, 4, 8), one kernel for every w.  A column goes to the exact test
+//                          unless EVERY copy's screen proves s_slot >= tau; there s is the minimum over all slots from
+//                          the fp64 columns and the pair is taken iff s < tau.
+__global__ __launch_bounds__(256) void closest_fill4_kernel(int nq, int k, int32_t *__restrict__ idx, double *__restrict__ key,
+                                                            double *__restrict__ cost_out, double *__restrict__ cost_in,
+                                                            uint8_t *__restrict__ word_out, uint8_t *__restrict__ word_in,
+                                                            uint8_t *__restrict__ hit_out, uint8_t *__restrict__ hit_in,
+                                                            int32_t *__restrict__ count, int32_t *__restrict__ owner,
+                                                            int32_t *__restrict__ row_owner,
+                                                            double *__restrict__ tree_cost_out,
+                                                            double *__restrict__ tree_cost_in,
+                                                            uint8_t *__restrict__ tree_word_out,
+                                                            uint8_t *__restrict__ tree_word_in,
+                                                            uint8_t *__restrict__ tree_hit_out,
+                                                            uint8_t *__restrict__ tree_hit_in) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)nq * k) return;
+  idx[e] = -1;
+  key[e] = __builtin_inf();
+  cost_out[e] = __builtin_inf();
+  cost_in[e] = __builtin_inf();
+  if (word_out) { word_out[3 * e] = 0; word_out[3 * e + 1] = 0; word_out[3 * e + 2] = 0; }
+  if (word_in) { word_in[3 * e] = 0; word_in[3 * e + 1] = 0; word_in[3 * e + 2] = 0; }
+  hit_out[e] = 0;
+  hit_in[e] = 0;
+  owner[e] = (int32_t)(e / k);
+  if (e < nq) {
+    count[e] = 0;
+    row_owner[e] = (int32_t)e;
+    if (tree_hit_out) {
+      tree_cost_out[e] = __builtin_inf(); tree_cost_in[e] = __builtin_inf();
+      tree_hit_out[e] = 0; tree_hit_in[e] = 0;
+      if (tree_word_out) { tree_word_out[3 * e] = 0; tree_word_out[3 * e + 1] = 0; tree_word_out[3 * e + 2] = 0; }
+      if (tree_word_in) { tree_word_in[3 * e] = 0; tree_word_in[3 * e + 1] = 0; tree_word_in[3 * e + 2] = 0; }
+    }
+  }
+}
+
+struct ClosestPlan4 {
+  const uint8_t *mark;           // [nq] the table's mark byte: != 0: skipped or non-finite
+  const uint8_t *want;           // [nq] or null: every live row
+  const int32_t *tree_idx;       // [nq] or null
+  int nq, k;
+  int *rows;                     // [nq] the filled rows, ascending
+  int *n_rows;                   // their number
+  int32_t *tree_near;            // [nq] tree_idx of a filled row, -1 otherwise (null with tree_idx)
+  int64_t *slots_end;            // (last filled row + 1) * k: the "offsets[nq]" of the slot entries
+  int64_t *rows_end;             // last filled row + 1: the same for the tree column
+};
+
+__global__ __launch_bounds__(kPlanThreads) void closest_plan4_kernel(const ClosestPlan4 a) {
+  __shared__ int wcnt[2][kPlanThreads / 64], wlast[2][kPlanThreads / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int base = 0, last = -1, flip = 0;
+  for (int j0 = 0; j0 < a.nq; j0 += kPlanThreads, flip ^= 1) {
+    const int j = j0 + t;
+    const bool fill = j < a.nq && a.mark[j] == 0 && (!a.want || a.want[j] != 0);
+    const unsigned long long votes = __ballot(fill);
+    if (lane == 0) {
+      wcnt[flip][wave] = __popcll(votes);
+      wlast[flip][wave] = votes != 0ull ? j0 + wave * 64 + 63 - __clzll((long long)votes) : -1;
+    }
+    __syncthreads();                       // (two sets of counts, as in closest_plan_kernel)
+    int before = 0, total = 0;
+    for (int w = 0; w < kPlanThreads / 64; ++w) {
+      const int c = wcnt[flip][w];
+      if (w < wave) before += c;
+      total += c;
+      last = max(last, wlast[flip][w]);
+    }
+    if (fill) a.rows[base + before + __popcll(votes & lanes_below(lane))] = j;
+    if (j < a.nq && a.tree_near) a.tree_near[j] = fill ? a.tree_idx[j] : -1;
+    base += total;
+  }
+  if (t == 0) {
+    *a.n_rows = base;
+    *a.slots_end = (int64_t)(last + 1) * a.k;
+    *a.rows_end = (int64_t)(last + 1);
+  }
+}
+
+struct ClosestRows4 {
+  const double *nx, *ny, *nz, *nw;
+  const uint8_t *mark;
+  const float4 *shadow;
+  const float *spp;
+  const unsigned long long *absmax;
+  const int *rows, *n_rows;
+  int nq, k;
+  double ox, oy, oz, ow;
+  SelfWrap wr;                   // thr_gt = +Inf: no copy is skipped, and the rows' first tau
+  int32_t *idx, *count;
+  double *key;
+};
+
+__global__ __launch_bounds__(kSelfThreads) void closest_rows4_kernel(const ClosestRows4 a) {
+  __shared__ float4 tile[2][kSelfTile];
+  __shared__ float tilep[2][kSelfTile];
+  __shared__ double4 rowg[kSelfWaves][kSelfSlots];        // the copies of the wave's row sample
+  __shared__ QRecF4 rowf[kSelfWaves][kSelfSlots];         // ... and their screen records for the row's tau
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int nr = min(max(*a.n_rows, 0), a.nq);
+  const int G = (nr + kClosestGroup - 1) / kClosestGroup;
+  if ((int)blockIdx.x >= G) return;                         // (workgroup-uniform)
+  const int g = G - 1 - (int)blockIdx.x;                    // heaviest group first
+  const double C = __longlong_as_double((long long)*a.absmax);
+  const unsigned long long kmask = lanes_below(a.k);        // (k <= 32)
+  // the wave's row: sample, copies, the pairs held (pair l in lane l), tau and the tau the screen records were made for
+  const int c = g * kClosestGroup + wave;
+  int j = c < nr ? a.rows[c] : -1;
+  if ((unsigned)j >= (unsigned)a.nq) j = -1;
+  j = __builtin_amdgcn_readfirstlane(j);
+  const int ns = j >= 0 ? 1 << min(max(a.wr.n_wraps, 0), 3) : 0;      // a wave without a row screens and tests nothing
+  int cnt = 0, bi = -1;
+  // tau starts at +Inf, taken from the launch's thr_gt: a kernel argument, not a literal.  (As a literal the compiler keeps
+  // it in a scalar pair set by one s_mov_b64 with a 64-bit immediate, which gfx950 cannot encode -- the assembler refuses
+  // that line of the compiler's own listing -- and the kernel then ran with tau = 0: every row came back empty.)
+  double bs = __builtin_inf(), tau = a.wr.thr_gt, tauf = tau;
+  if (lane < ns) {
+    const double p[4] = {a.nx[j], a.ny[j], a.nz[j], a.nw[j]};
+    double gc[4];
+    (void)self_copy(a.wr, p, lane, gc);
+    QRec4 q4;
+    q4.x = gc[0]; q4.y = gc[1]; q4.z = gc[2]; q4.w = gc[3]; q4.thr = tau; q4.pad0 = 0.0; q4.pad1 = 0.0; q4.pad2 = 0.0;
+    rowg[wave][lane] = make_double4(gc[0], gc[1], gc[2], gc[3]);
+    rowf[wave][lane] = make_qrecf<4>(q4, C, a.ox, a.oy, a.oz, a.ow);
+  }
+  // (the block is the wave's own: the first barrier of the tile loop comes before its first read)
+  // the workgroup's last row is the last of its group (the list is ascending): columns 0 .. ncols - 1
+  int ncols = a.rows[min(nr, (g + 1) * kClosestGroup) - 1];
+  ncols = min(max(ncols, 0), a.nq - 1);
+  const float4 none4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 pre0 = none4, pre1 = none4;
+  float prep0 = __builtin_inff(), prep1 = prep0;
+  if (0 < ncols) {
+    if (t < a.nq) { pre0 = a.shadow[t]; prep0 = a.spp[t]; }
+    if (kSelfThreads + t < a.nq) { pre1 = a.shadow[kSelfThreads + t]; prep1 = a.spp[kSelfThreads + t]; }
+  }
+  int buf = 0;
+  for (int tb = 0; tb < ncols; tb += kSelfTile, buf ^= 1) {
+    tile[buf][t] = pre0; tilep[buf][t] = prep0;
+    tile[buf][kSelfThreads + t] = pre1; tilep[buf][kSelfThreads + t] = prep1;
+    __syncthreads();
+    pre0 = none4; pre1 = none4;
+    prep0 = __builtin_inff(); prep1 = prep0;
+    if (tb + kSelfTile < ncols) {
+      const int i = tb + kSelfTile + t;
+      if (i < a.nq) { pre0 = a.shadow[i]; prep0 = a.spp[i]; }
+      if (i + kSelfThreads < a.nq) { pre1 = a.shadow[i + kSelfThreads]; prep1 = a.spp[i + kSelfThreads]; }
+    }
+    if (tb >= j) continue;                 // (wave-uniform; the barrier above is passed by every wave all the same)
+    float x[kScanFU], y[kScanFU], z[kScanFU], w[kScanFU], pp[kScanFU];
+#pragma unroll
+    for (int u = 0; u < kScanFU; ++u) {
+      const float4 cf = tile[buf][u * 64 + lane];
+      x[u] = cf.x; y[u] = cf.y; z[u] = cf.z; w[u] = cf.w; pp[u] = tilep[buf][u * 64 + lane];
+    }
+    // bit u: the lane's column u survived the screen of some copy.  "t > thr'" proves s_slot >= tau (thr' = +Inf while
+    // the row is not full, and with a non-finite or huge C: nothing is dropped then); a column is dropped only when
+    // every copy proves it, and then min over the slots >= tau
+    unsigned sm = 0u;
+    for (int sl = 0; sl < ns; ++sl) {
+      const QRecF4 rf = rowf[wave][sl];
+      float tv[kScanFU];
+      screen8<4>(rf, x, y, z, w, pp, tv);
+#pragma unroll
+      for (int u = 0; u < kScanFU; ++u) sm |= !(tv[u] > rf.thr) ? (1u << u) : 0u;
+    }
+    if (__ballot(sm != 0u) == 0ull) continue;
+#pragma unroll
+    for (int u = 0; u < kScanFU; ++u) {
+      const bool surv = ((sm >> u) & 1u) != 0u;
+      if (__ballot(surv) == 0ull) continue;
+      const int i = tb + u * 64 + lane;
+      double s = __builtin_inf();
+      bool hit = false;
+      if (surv && i < j && a.mark[i] == 0) {               // i < j <= nq - 1: inside the table
+        const double cx = a.nx[i], cy = a.ny[i], cz = a.nz[i], cw = a.nw[i];
+        for (int sl = 0; sl < ns; ++sl) {
+          const double4 gc = rowg[wave][sl];
+          const double ss = sq4(gc.x, gc.y, gc.z, gc.w, cx, cy, cz, cw);
+          s = ss < s ? ss : s;
+        }
+        hit = s < tau;                                     // (a non-finite s is in no row)
+      }
+      // the lanes' pairs go in one at a time, ascending in i; each insertion may lower tau and drop the rest
+      unsigned long long b = __ballot(hit);
+      while (b != 0ull) {
+        const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)b) - 1);
+        const double nsq = wave_read(s, l);
+        const int ni = tb + u * 64 + l;
+        // the pairs held have lower indices, so the new one goes behind every pair with the same s (lanes k and up
+        // hold what fell off the row: not counted, never read)
+        const int pos = __popcll(__ballot(bs <= nsq) & kmask);
+        const double us = wave_shift_up(bs);
+        const int ui = wave_shift_up(bi);
+        if (lane > pos) { bs = us; bi = ui; }
+        else if (lane == pos) { bs = nsq; bi = ni; }
+        cnt = min(cnt + 1, a.k);
+        if (cnt == a.k) tau = wave_read(bs, a.k - 1);
+        hit = hit && lane != l && s < tau;
+        b = __ballot(hit);
+      }
+    }
+    // the screen records follow tau once a tile: a stale (higher) tau only lets more pairs through to the exact test.
+    // (The wave's own block, and its next read lies behind the next tile's barrier.)
+    if (tau != tauf) {
+      tauf = tau;
+      if (lane < ns) {
+        const double4 gc = rowg[wave][lane];
+        QRec4 q4;
+        q4.x = gc.x; q4.y = gc.y; q4.z = gc.z; q4.w = gc.w; q4.thr = tau; q4.pad0 = 0.0; q4.pad1 = 0.0; q4.pad2 = 0.0;
+        rowf[wave][lane] = make_qrecf<4>(q4, C, a.ox, a.oy, a.oz, a.ow);
+      }
+    }
+  }
+  if (j < 0) return;
+  if (lane < cnt) {
+    a.idx[(size_t)j * a.k + lane] = bi;
+    a.key[(size_t)j * a.k + lane] = sqrt_rn(bs);
+  }
+  if (lane == 0) a.count[j] = cnt;
+}
+
 }  // namespace
 
 int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, const uint8_t *skip_dev,
@@ -791,6 +1028,74 @@ int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, doubl
                                            tree_hit_out_dev, tree_hit_in_dev, nullptr, -1.0);
   return launch_candidate_edges(ctx, q_dev, nq, rows_off, p.tree_near, row_owner, (int64_t)nq, robot_radius, tree_hit_out_dev,
                                 tree_hit_in_dev, -1.0);
+}
+
+int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, double r_min,
+                               const uint8_t *skip_dev, const uint8_t *want_dev, const int32_t *tree_idx_dev,
+                               int32_t *idx_dev, double *key_dev, double *cost_out_dev, double *cost_in_dev,
+                               uint8_t *word_out_dev, uint8_t *word_in_dev, uint8_t *hit_out_dev, uint8_t *hit_in_dev,
+                               int32_t *count_dev, double *tree_cost_out_dev, double *tree_cost_in_dev,
+                               uint8_t *tree_word_out_dev, uint8_t *tree_word_in_dev, uint8_t *tree_hit_out_dev,
+                               uint8_t *tree_hit_in_dev) {
+  if (nq <= 0) return RRTX_OK;
+  // ws_self: four coordinate columns (32 B a sample), shadow (16 B), the two "offsets" arrays of the edge kernels (only
+  // their last word is read: the number of entries), C, the shadows' norms, the compact row list, the tree column's node
+  // indices, the rows' own indices, the number of rows, the marks.  ws_owner: the owner row of every slot.
+  const size_t n = (size_t)nq, cap = n * (size_t)k;
+  const size_t off_shadow = sizeof(double) * 4 * n, off_slots = off_shadow + sizeof(float4) * n;
+  const size_t off_rowsend = off_slots + sizeof(int64_t) * (n + 1), off_max = off_rowsend + sizeof(int64_t) * (n + 1);
+  const size_t off_spp = off_max + sizeof(unsigned long long), off_rows = off_spp + sizeof(float) * n;
+  const size_t off_near = off_rows + sizeof(int) * n, off_rown = off_near + sizeof(int32_t) * n;
+  const size_t off_nrows = off_rown + sizeof(int32_t) * n, off_mark = off_nrows + sizeof(int);
+  RRTX_HIP(ctx, ctx->ws_self.ensure(off_mark + n));
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * cap));
+  char *ws = ctx->ws_self.as<char>();
+  double *col = reinterpret_cast<double *>(ws);
+  float4 *shadow = reinterpret_cast<float4 *>(ws + off_shadow);
+  float *spp = reinterpret_cast<float *>(ws + off_spp);
+  uint8_t *mark = reinterpret_cast<uint8_t *>(ws + off_mark);
+  int64_t *slots_off = reinterpret_cast<int64_t *>(ws + off_slots), *rows_off = reinterpret_cast<int64_t *>(ws + off_rowsend);
+  unsigned long long *absmax = reinterpret_cast<unsigned long long *>(ws + off_max);
+  int32_t *row_owner = reinterpret_cast<int32_t *>(ws + off_rown);
+  RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
+  ClosestPlan4 p;
+  p.mark = mark; p.want = want_dev; p.tree_idx = tree_idx_dev; p.nq = nq; p.k = k;
+  p.rows = reinterpret_cast<int *>(ws + off_rows); p.n_rows = reinterpret_cast<int *>(ws + off_nrows);
+  p.tree_near = tree_idx_dev ? reinterpret_cast<int32_t *>(ws + off_near) : nullptr;
+  p.slots_end = slots_off + n; p.rows_end = rows_off + n;
+  ClosestRows4 a;
+  a.nx = col; a.ny = col + n; a.nz = col + 2 * n; a.nw = col + 3 * n;
+  a.mark = mark; a.shadow = shadow; a.spp = spp; a.absmax = absmax; a.rows = p.rows; a.n_rows = p.n_rows;
+  a.nq = nq; a.k = k;
+  a.ox = ctx->origin[0]; a.oy = ctx->origin[1]; a.oz = ctx->origin[2]; a.ow = ctx->origin[3];
+  a.wr.n_wraps = ctx->n_wraps;
+  for (int w = 0; w < 3; ++w) { a.wr.wd[w] = ctx->wrap_dim[w]; a.wr.wp[w] = ctx->wrap_period[w]; }
+  a.wr.thr_gt = __builtin_inf();             // no copy is skipped, so C covers every copy of every live sample; the first tau
+  a.idx = idx_dev; a.count = count_dev; a.key = key_dev;
+  span_begin(ctx, KF_NN_SCAN);
+  hipLaunchKernelGGL(self_table4_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, q_dev, nq, skip_dev,
+                     a.wr, a.ox, a.oy, a.oz, a.ow, col, col + n, col + 2 * n, col + 3 * n, mark, shadow, spp, absmax);
+  hipLaunchKernelGGL(closest_fill4_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, nq, k, idx_dev,
+                     key_dev, cost_out_dev, cost_in_dev, word_out_dev, word_in_dev, hit_out_dev, hit_in_dev, count_dev,
+                     ctx->ws_owner.as<int32_t>(), row_owner, tree_cost_out_dev, tree_cost_in_dev, tree_word_out_dev,
+                     tree_word_in_dev, tree_hit_out_dev, tree_hit_in_dev);
+  hipLaunchKernelGGL(closest_plan4_kernel, dim3(1), dim3(kPlanThreads), 0, ctx->stream, p);
+  hipLaunchKernelGGL(closest_rows4_kernel, dim3((unsigned)((nq + kClosestGroup - 1) / kClosestGroup)), dim3(kSelfThreads), 0,
+                     ctx->stream, a);
+  span_end(ctx);
+  RRTX_HIP(ctx, hipGetLastError());
+  // both directed Dubins edges of every slot, by the kernels of rrtx_extend_candidates_dubins: slot e = (row e / k, sample
+  // idx[e]) with the sample columns as the near table; an empty slot (idx -1) and everything past the last filled row is
+  // left alone
+  int rc = launch_candidate_dubins(ctx, q_dev, nq, slots_off, idx_dev, ctx->ws_owner.as<int32_t>(), (int64_t)cap, r_min,
+                                   robot_radius, cost_out_dev, cost_in_dev, word_out_dev, word_in_dev, hit_out_dev,
+                                   hit_in_dev, col, nq);
+  if (rc || !tree_idx_dev) return rc;
+  // the tree column: one entry a row, (row j, node tree_idx[j]); an index outside the tree is left alone by the kernels
+  if (ctx->n_nodes <= 0 || !ctx->nodes[0]) return RRTX_OK;
+  return launch_candidate_dubins(ctx, q_dev, nq, rows_off, p.tree_near, row_owner, (int64_t)nq, r_min, robot_radius,
+                                 tree_cost_out_dev, tree_cost_in_dev, tree_word_out_dev, tree_word_in_dev, tree_hit_out_dev,
+                                 tree_hit_in_dev);
 }
 
 int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev, int64_t *offsets_dev,

@@ -2216,6 +2216,97 @@ int rrtx_extend_candidates_self_dubins(rrtx_ctx *ctx, const double *q, int nq, d
   return RRTX_OK;
 }
 
+// ---- the closestNode rule for a Dubins extend batch: k nearest earlier samples in wrapped space (kernels_self.hip) ----
+static int extend_closest_dubins_args(rrtx_ctx *ctx, const double *q, int nq, int k, const int32_t *tree_idx,
+                                      const int32_t *idx, const double *key, const double *cost_out, const double *cost_in,
+                                      const uint8_t *hit_out, const uint8_t *hit_in, const int32_t *count,
+                                      const double *tree_cost_out, const double *tree_cost_in, const uint8_t *tree_hit_out,
+                                      const uint8_t *tree_hit_in) {
+  const int n_tree = (tree_idx ? 1 : 0) + (tree_cost_out ? 1 : 0) + (tree_cost_in ? 1 : 0) + (tree_hit_out ? 1 : 0) +
+                     (tree_hit_in ? 1 : 0);
+  if (nq < 0 || k < 1 || k > RRTX_CLOSEST_SELF_MAX_K || (n_tree != 0 && n_tree != 5) ||
+      (nq > 0 && (!q || !idx || !key || !cost_out || !cost_in || !hit_out || !hit_in || !count)))
+    return fail(ctx, RRTX_E_INVALID, "extend_closest_self_dubins: bad arguments");
+  if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "extend_closest_self_dubins needs a dim=4 [x y t theta] context");
+  if ((int64_t)nq * k >= (1ll << 30))
+    return fail(ctx, RRTX_E_INVALID, "extend_closest_self_dubins: at most 2^30 - 1 slots per call");
+  return RRTX_OK;
+}
+
+int rrtx_extend_closest_self_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, double r_min,
+                                        const uint8_t *skip, const uint8_t *want, const int32_t *tree_idx, int32_t *idx,
+                                        double *key, double *cost_out, double *cost_in, uint8_t *word_out,
+                                        uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in, int32_t *count,
+                                        double *tree_cost_out, double *tree_cost_in, uint8_t *tree_word_out,
+                                        uint8_t *tree_word_in, uint8_t *tree_hit_out, uint8_t *tree_hit_in) {
+  CHECK_CTX(ctx);
+  int rc = extend_closest_dubins_args(ctx, q, nq, k, tree_idx, idx, key, cost_out, cost_in, hit_out, hit_in, count,
+                                      tree_cost_out, tree_cost_in, tree_hit_out, tree_hit_in);
+  if (rc || nq == 0) return rc;
+  return launch_closest_self_dubins(ctx, q, nq, k, robot_radius, r_min, skip, want, tree_idx, idx, key, cost_out, cost_in,
+                                    word_out, word_in, hit_out, hit_in, count, tree_cost_out, tree_cost_in,
+                                    tree_idx ? tree_word_out : nullptr, tree_idx ? tree_word_in : nullptr, tree_hit_out,
+                                    tree_hit_in);
+}
+
+int rrtx_extend_closest_self_dubins(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, double r_min,
+                                    const uint8_t *skip, const uint8_t *want, const int32_t *tree_idx, int32_t *idx,
+                                    double *key, double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
+                                    uint8_t *hit_out, uint8_t *hit_in, int32_t *count, double *tree_cost_out,
+                                    double *tree_cost_in, uint8_t *tree_word_out, uint8_t *tree_word_in,
+                                    uint8_t *tree_hit_out, uint8_t *tree_hit_in) {
+  CHECK_CTX(ctx);
+  int rc = extend_closest_dubins_args(ctx, q, nq, k, tree_idx, idx, key, cost_out, cost_in, hit_out, hit_in, count,
+                                      tree_cost_out, tree_cost_in, tree_hit_out, tree_hit_in);
+  if (rc || nq == 0) return rc;
+  const size_t n = (size_t)nq, slots = n * (size_t)k;
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * n * 4));
+  if (skip) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q2, skip, n));
+  if (want) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_i32a, want, n));
+  if (tree_idx) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_i32b, tree_idx, sizeof(int32_t) * n));
+  // per slot: idx; key, cost_out, cost_in; words (3 + 3), hits (1 + 1).  Per sample, in ws_out_off: the tree column's two
+  // costs, count, then the tree column's words (3 + 3) and hits (1 + 1)
+  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * slots));
+  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * 3 * slots));
+  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(8 * slots));
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(28 * n));
+  double *key_dev = ctx->ws_out_dist.as<double>(), *co_dev = key_dev + slots, *ci_dev = co_dev + slots;
+  uint8_t *wo_dev = ctx->ws_out_u8a.as<uint8_t>(), *wi_dev = wo_dev + 3 * slots, *ho_dev = wi_dev + 3 * slots,
+          *hi_dev = ho_dev + slots;
+  double *tco_dev = ctx->ws_out_off.as<double>(), *tci_dev = tco_dev + n;
+  int32_t *count_dev = reinterpret_cast<int32_t *>(tci_dev + n);
+  uint8_t *two_dev = reinterpret_cast<uint8_t *>(count_dev + n), *twi_dev = two_dev + 3 * n, *tho_dev = twi_dev + 3 * n,
+          *thi_dev = tho_dev + n;
+  rc = rrtx_extend_closest_self_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius, r_min,
+                                           skip ? ctx->ws_q2.as<uint8_t>() : nullptr,
+                                           want ? ctx->ws_i32a.as<uint8_t>() : nullptr,
+                                           tree_idx ? ctx->ws_i32b.as<int32_t>() : nullptr, ctx->ws_out_idx.as<int32_t>(),
+                                           key_dev, co_dev, ci_dev, wo_dev, wi_dev, ho_dev, hi_dev, count_dev,
+                                           tree_idx ? tco_dev : nullptr, tree_idx ? tci_dev : nullptr,
+                                           tree_idx ? two_dev : nullptr, tree_idx ? twi_dev : nullptr,
+                                           tree_idx ? tho_dev : nullptr, tree_idx ? thi_dev : nullptr);
+  if (rc) return rc;
+  RRTX_HIP(ctx, copy_out(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * slots));
+  RRTX_HIP(ctx, copy_out(ctx, key, key_dev, sizeof(double) * slots));
+  RRTX_HIP(ctx, copy_out(ctx, cost_out, co_dev, sizeof(double) * slots));
+  RRTX_HIP(ctx, copy_out(ctx, cost_in, ci_dev, sizeof(double) * slots));
+  RRTX_HIP(ctx, copy_out(ctx, word_out, wo_dev, 3 * slots));
+  RRTX_HIP(ctx, copy_out(ctx, word_in, wi_dev, 3 * slots));
+  RRTX_HIP(ctx, copy_out(ctx, hit_out, ho_dev, slots));
+  RRTX_HIP(ctx, copy_out(ctx, hit_in, hi_dev, slots));
+  RRTX_HIP(ctx, copy_out(ctx, count, count_dev, sizeof(int32_t) * n));
+  if (tree_idx) {
+    RRTX_HIP(ctx, copy_out(ctx, tree_cost_out, tco_dev, sizeof(double) * n));
+    RRTX_HIP(ctx, copy_out(ctx, tree_cost_in, tci_dev, sizeof(double) * n));
+    RRTX_HIP(ctx, copy_out(ctx, tree_word_out, two_dev, 3 * n));
+    RRTX_HIP(ctx, copy_out(ctx, tree_word_in, twi_dev, 3 * n));
+    RRTX_HIP(ctx, copy_out(ctx, tree_hit_out, tho_dev, n));
+    RRTX_HIP(ctx, copy_out(ctx, tree_hit_in, thi_dev, n));
+  }
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
+}
+
 int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit_in, const int64_t *n_valid_dev,
                        int64_t cap, uint64_t *words) {
   CHECK_CTX(ctx);

@@ -459,6 +459,15 @@ int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, doubl
                         const uint8_t *want_dev, const int32_t *tree_idx_dev, int32_t *idx_dev, double *cost_dev,
                         uint8_t *hit_out_dev, uint8_t *hit_in_dev, int32_t *count_dev, uint8_t *tree_hit_out_dev,
                         uint8_t *tree_hit_in_dev);
+// the same in [x y t theta] with the context's wrapped dimensions: rows by the minimum over the later sample's copies,
+// per slot the key, both Dubins costs, words (may be null) and flag bytes, and the same fields of the tree column
+int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, double r_min,
+                               const uint8_t *skip_dev, const uint8_t *want_dev, const int32_t *tree_idx_dev,
+                               int32_t *idx_dev, double *key_dev, double *cost_out_dev, double *cost_in_dev,
+                               uint8_t *word_out_dev, uint8_t *word_in_dev, uint8_t *hit_out_dev, uint8_t *hit_in_dev,
+                               int32_t *count_dev, double *tree_cost_out_dev, double *tree_cost_in_dev,
+                               uint8_t *tree_word_out_dev, uint8_t *tree_word_in_dev, uint8_t *tree_hit_out_dev,
+                               uint8_t *tree_hit_in_dev);
 int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
                               const int32_t *idx_dev, const double *dist_dev, int32_t *nearest_idx_dev,
                               double *nearest_dist_dev);

@@ -634,6 +634,27 @@ def extend_candidates_self_dubins(tree: HipTree, S: CSpace, newPositions, hyberB
     return out
 
 
+def extend_closest_self_dubins(tree: HipTree, S: CSpace, newPositions, k: int, skip=None, want=None, treeNearest=None):
+    """extend_closest_self for Edge = DubinsEdge: the closestNode rule of findBestParent (R/DRRT_Q.jl:1930-1935) in a
+    Dubins batch.  Row j holds the k nearest live earlier batch positions i < j in the wrapped space by (distance, i),
+    the distance being the minimum over the copies of q_j, with the key and the Dubins cost, word and flags of q_j -> q_i
+    (out) and q_i -> q_j (in) against the whole polygon list; count[j] says how many.  skip: non-zero bytes take a sample
+    out (sample_unsafe of extend_candidates_dubins); want: the rows to fill (the samples whose tree list is empty);
+    treeNearest: nearest_idx of extend_candidates_dubins, whose fields come back as tree_cost_out ... tree_hit_in.
+    S.minTurningRadius and S.robotRadius are read.  The caller walks row j, takes the first entry whose sample it
+    inserted and links to it if its key < nearest_dist[j], else to the tree node; a row with count == k, no inserted
+    entry and its k-th key below nearest_dist[j] is exhausted and the caller searches the batch itself."""
+    _dubins_space(tree, S, "extend_closest_self_dubins")
+    q = np.asarray(newPositions, dtype=np.float64).reshape(-1, 4)
+    out = tree.ctx.extend_closest_self_dubins(q, int(k), S.robotRadius, S.minTurningRadius, skip=skip, want=want,
+                                              tree_idx=treeNearest)
+    if S.inWarmupTime:
+        for name in ("hit_out", "hit_in", "tree_hit_out", "tree_hit_in"):
+            if out[name] is not None:
+                out[name][:] = 0
+    return out
+
+
 def extend_select(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, lmc=None):
     """findBestParent (R/DRRT_Q.jl:1927-1979) and the rewire test of extend (:2619-2634) for many samples at once, on
     the device: per sample the parent, its own rrtLMC and the neighbours whose rrtLMC it would lower, as
