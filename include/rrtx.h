@@ -881,6 +881,65 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
                        int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe, int64_t *offsets,
                        int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
 
+/* ---- the extend lists become mirror edges, on the device ------------------------ */
+/* What extend() links for a batch (R/DRRT_Q.jl:2560-2640), written into the edge mirror from the CSR lists the
+ * rrtx_extend_candidates* calls wrote (offsets[nq + 1], idx, cost_out, cost_in, hit_out, hit_in; SimpleEdge lists pass
+ * the one cost array as cost_out and cost_in).  node_of[j] (int32, nq) is the node index sample j received
+ * (rrtx_nodes_append), or a negative value for a sample that was not inserted.  idx_is_batch == 0: idx[e] is a node
+ * index (lists against the tree); != 0: idx[e] is a batch position mapped through node_of (the lists of
+ * rrtx_extend_candidates_self[_dubins]), and an entry whose mapped value is negative is dropped.
+ * ORDER RULE: for j = 0 .. nq-1 with v = node_of[j] >= 0, in that order, and for every surviving entry e of row j in
+ * list order, u the near node:
+ *   1. the out-edge v -> u, always: distOriginal = cost_out[e], dist = cost_out[e] when hit_out[e] == 0 and +Inf
+ *      otherwise (extend links a blocked out-edge with dist = Inf; rrtx_graph_edges_unblock revives it);
+ *   2. the in-edge u -> v, only when hit_in[e] == 0: dist = distOriginal = cost_in[e].
+ * Edge ids are consecutive from rrtx_graph_edges_count at entry, in exactly that order; they never depend on launch
+ * geometry or on the order in which waves finish.  Through every call that reads the mirror (the sweeps, the releases,
+ * rrtx_graph_edges_unblock, the cost solvers, rrtx_graph_edges_get) the result is indistinguishable from
+ * rrtx_graph_edges_append of those (start, end) pairs in that order, rrtx_graph_edges_set_dist with those original
+ * costs and rrtx_graph_edges_block of the out-edges with hit_out != 0.  Duplicate edges and self loops are accepted,
+ * as there.  *first_id = the id of the first edge (the count at entry), *n_added = the edges appended (either may be
+ * NULL); row_first (nq + 1 int64, may be NULL) = the CSR of every sample's edges relative to *first_id, an empty row
+ * for a sample that was not inserted.  nq == 0 or no inserted sample: RRTX_OK, *n_added = 0.
+ * Refusals, nothing is appended on any of them (row_first may have been written): RRTX_E_CAPACITY when the extend
+ * call produced more entries than cap, or when the mirror would pass the int32 id range; RRTX_E_INVALID for a
+ * node_of[j] >= rrtx_nodes_count, for a surviving entry (of an inserted sample) whose near node is outside
+ * [0, rrtx_nodes_count) or whose batch position is outside [0, nq), and for offsets out of order or beyond cap.  The
+ * verdict is computed on the device, in the pass that counts the edges.
+ *
+ * rrtx_graph_edges_append_lists_dev: every list array, node_of, n_valid_dev (the count the extend call left on the
+ * device, needed_dev; NULL: not checked) and row_first are DEVICE pointers; first_id and n_added are host pointers.  The
+ * call waits on the stream ONCE, to read 24 bytes (surviving entries, edges, the verdict); it then grows the mirror if
+ * needed (that growth waits once more) and only enqueues the fill.
+ * rrtx_graph_edges_append_lists: the same with host arrays (n_valid by value), staged through the path of the
+ * host-pointer searches; row_first is a host array or NULL.  This is how a host-pointer caller feeds the self lists.
+ * rrtx_graph_edges_append_selected: the same over the lists the last successful rrtx_extend_select left in the context
+ * (always lists against the tree: idx_is_batch = 0); node_of and row_first are host arrays.  HOLD RULE: the context
+ * records that it holds such lists, with their nq and count.  The record survives rrtx_nodes_append[_dev],
+ * rrtx_node_cost_set, every rrtx_graph_* call (rrtx_graph_edges_append_lists, which stages into the list workspaces,
+ * excepted) and the getters (rrtx_sync, rrtx_get_option, rrtx_stats, rrtx_last_tile_form, the counts, the error text);
+ * EVERY other entry point drops it -- the searches, the extend calls, the checks and steers, the sweeps and releases,
+ * rrtx_find_new_target*, rrtx_set_option, the obstacle setters -- whether or not it succeeds.  Without a record, or
+ * with another nq, the call is RRTX_E_STATE and nothing is appended.
+ *
+ * rrtx_graph_edges_get reads mirror edges back: the range [first_id, first_id + n) when ids is NULL, else the n edges
+ * ids[i] (first_id is then ignored).  start, end, dist (edge.dist, +Inf = blocked) and dist_original may each be NULL.
+ * An id or a range outside the mirror is RRTX_E_INVALID and nothing is written.  A host working from
+ * rrtx_graph_cost_update_delta resolves the few parent-edge ids it is told about with it. */
+int rrtx_graph_edges_append_lists_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx,
+                                      const double *cost_out, const double *cost_in, const uint8_t *hit_out,
+                                      const uint8_t *hit_in, const int64_t *n_valid_dev, int64_t cap,
+                                      const int32_t *node_of, int idx_is_batch, int64_t *first_id, int64_t *n_added,
+                                      int64_t *row_first);
+int rrtx_graph_edges_append_lists(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx,
+                                  const double *cost_out, const double *cost_in, const uint8_t *hit_out,
+                                  const uint8_t *hit_in, int64_t n_valid, int64_t cap, const int32_t *node_of,
+                                  int idx_is_batch, int64_t *first_id, int64_t *n_added, int64_t *row_first);
+int rrtx_graph_edges_append_selected(rrtx_ctx *ctx, int nq, const int32_t *node_of, int64_t *first_id, int64_t *n_added,
+                                     int64_t *row_first);
+int rrtx_graph_edges_get(rrtx_ctx *ctx, const int32_t *ids, int64_t first_id, int64_t n, int32_t *start, int32_t *end,
+                         double *dist, double *dist_original);
+
 /* ---- a robot's new move target ------------------------------------------------- */
 /* findNewTarget (R/DRRT_Q.jl:2901-2994) for a batch of robot poses, on the device: kdFindWithinRange around the pose,
  * the edge pose -> neighbour steered and collision-checked for every neighbour, the neighbour with the lowest

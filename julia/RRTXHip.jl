@@ -931,6 +931,69 @@ function costUpdateDelta(tree::HipTree, root, store::Bool = false)
   end
 end
 
+# What extend() links for a batch (R/DRRT_Q.jl:2560-2640), registered on the device from the lists of
+# extend_candidates* (0-based CSR as the calls return it): per inserted sample j (nodeOf[j] >= 0, its 0-based node index)
+# and entry, the out-edge (dist = Inf when hitOut) and, when hitIn is clear, the in-edge -- in that order, ids consecutive
+# from the count.  selfLists: idx holds 0-based batch positions (extend_candidates_self*); an entry whose sample was not
+# inserted is dropped.  SimpleEdge lists pass the one cost array twice.  Returns (first id, edges registered, rowFirst):
+# rowFirst[j] + 1 : rowFirst[j + 1] are the edges of sample j relative to the first id.
+function registerEdgesFromLists(tree::HipTree, offsets::Vector{Int64}, idx::Vector{Int32}, costOut::Vector{Float64},
+                                costIn::Vector{Float64}, hitOut::Vector{UInt8}, hitIn::Vector{UInt8},
+                                nodeOf::Vector{Int32}, selfLists::Bool = false)
+  nq = length(nodeOf)
+  firstId = Ref{Int64}(0)
+  added = Ref{Int64}(0)
+  rowFirst = Vector{Int64}(undef, nq + 1)
+  GC.@preserve offsets idx costOut costIn hitOut hitIn nodeOf rowFirst rrtx_check(tree,
+    ccall((:rrtx_graph_edges_append_lists, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Int64, Int64,
+       Ptr{Int32}, Cint, Ref{Int64}, Ref{Int64}, Ptr{Int64}),
+      tree.ctx, nq, offsets, idx, costOut, costIn, hitOut, hitIn, offsets[end], length(idx), nodeOf, selfLists ? 1 : 0,
+      firstId, added, rowFirst))
+  return Int(firstId[]), Int(added[]), rowFirst
+end
+
+# The same over lists that are already on the device (the *_dev extend calls): every array is a device pointer, nValid
+# the count the extend call left there (C_NULL: not checked), rowFirst nq + 1 Int64 on the device or C_NULL.  Waits on
+# the stream once, for the counts.
+function registerEdgesFromListsDev(tree::HipTree, nq::Int, offsets::Ptr{Int64}, idx::Ptr{Int32}, costOut::Ptr{Cdouble},
+                                   costIn::Ptr{Cdouble}, hitOut::Ptr{UInt8}, hitIn::Ptr{UInt8}, nValid::Ptr{Int64},
+                                   cap::Int, nodeOf::Ptr{Int32}, selfLists::Bool = false,
+                                   rowFirst::Ptr{Int64} = Ptr{Int64}(C_NULL))
+  firstId = Ref{Int64}(0)
+  added = Ref{Int64}(0)
+  rrtx_check(tree, ccall((:rrtx_graph_edges_append_lists_dev, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int64}, Int64,
+       Ptr{Int32}, Cint, Ref{Int64}, Ref{Int64}, Ptr{Int64}),
+      tree.ctx, nq, offsets, idx, costOut, costIn, hitOut, hitIn, nValid, cap, nodeOf, selfLists ? 1 : 0, firstId, added,
+      rowFirst))
+  return Int(firstId[]), Int(added[])
+end
+
+# The same over the lists the last extendSelect left on the device: only nodeOf travels.  RRTX_E_STATE when another
+# call has used the lists' workspaces since (kdInsert, setNodeCosts and the edge / cost calls keep them).
+function registerSelectedEdges(tree::HipTree, nodeOf::Vector{Int32})
+  nq = length(nodeOf)
+  firstId = Ref{Int64}(0)
+  added = Ref{Int64}(0)
+  rowFirst = Vector{Int64}(undef, nq + 1)
+  GC.@preserve nodeOf rowFirst rrtx_check(tree, ccall((:rrtx_graph_edges_append_selected, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Cint, Ptr{Int32}, Ref{Int64}, Ref{Int64}, Ptr{Int64}), tree.ctx, nq, nodeOf, firstId, added, rowFirst))
+  return Int(firstId[]), Int(added[]), rowFirst
+end
+
+# (start, end, dist, distOriginal) of the registered edges ids (0-based ids, e.g. the parent edges costUpdateDelta names)
+function registeredEdges(tree::HipTree, ids::Vector{Int32})
+  n = length(ids)
+  s = Vector{Int32}(undef, n)
+  e = Vector{Int32}(undef, n)
+  d = Vector{Float64}(undef, n)
+  d0 = Vector{Float64}(undef, n)
+  GC.@preserve ids s e d d0 rrtx_check(tree, ccall((:rrtx_graph_edges_get, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Ptr{Int32}, Int64, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}), tree.ctx, ids, 0, n, s, e, d, d0))
+  return s, e, d, d0
+end
+
 
 # ---------------------------------------------------------------------------
 # Edge = DubinsEdge (R/DRRT_DubinsEdge.jl, R/DRRT_DubinsEdge_functions.jl; README's per-edge-type

@@ -123,6 +123,12 @@ SYMBOLS = [
     ("rrtx_graph_edges_set_dist", C.c_int, [_VP, C.c_int64, _VP, C.c_int64]),
     ("rrtx_graph_edges_block", C.c_int, [_VP, _VP, C.c_int64]),
     ("rrtx_graph_edges_unblock", C.c_int, [_VP, _VP, C.c_int64]),
+    ("rrtx_graph_edges_append_lists_dev", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_int,
+                                                    c_int64_p, c_int64_p, _VP]),
+    ("rrtx_graph_edges_append_lists", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int,
+                                                c_int64_p, c_int64_p, _VP]),
+    ("rrtx_graph_edges_append_selected", C.c_int, [_VP, C.c_int, _VP, c_int64_p, c_int64_p, _VP]),
+    ("rrtx_graph_edges_get", C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP]),
     ("rrtx_graph_cost_to_root", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("rrtx_graph_cost_to_root_dev", C.c_int, [_VP, C.c_int, _VP, _VP]),
     ("rrtx_graph_cost_update", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),

@@ -781,6 +781,73 @@ class Context:
         wrote last comes back (an id that is not blocked keeps its value)"""
         self._edge_ids_call(self._lib.rrtx_graph_edges_unblock, edge_ids)
 
+    # ---- the extend lists become mirror edges on the device (include/rrtx.h, "the extend lists become mirror edges")
+    def graph_edges_append_lists(self, offsets, idx, cost_out, cost_in, hit_out, hit_in, node_of, idx_is_batch: bool = False,
+                                 n_valid: Optional[int] = None, cap: Optional[int] = None, want_rows: bool = True):
+        """rrtx_graph_edges_append_lists over host arrays: per inserted sample j (node_of[j] >= 0) and surviving entry the
+        out-edge node_of[j] -> near (blocked when hit_out != 0) and, when hit_in == 0, the in-edge.  cost_in may be the
+        same array as cost_out (SimpleEdge).  Returns (first_id, n_added, row_first or None)."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        nq = off.shape[0] - 1 if off.shape[0] else 0
+        ia = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        co = f64(cost_out, (-1,))
+        ci = co if cost_in is cost_out else f64(cost_in, (-1,))
+        ho = np.ascontiguousarray(hit_out, dtype=np.uint8).reshape(-1)
+        hi = np.ascontiguousarray(hit_in, dtype=np.uint8).reshape(-1)
+        nd = np.ascontiguousarray(node_of, dtype=np.int32).reshape(-1)
+        if nd.shape[0] != nq:
+            raise ValueError("node_of needs one entry per sample")
+        room = min(ia.shape[0], co.shape[0], ci.shape[0], ho.shape[0], hi.shape[0])
+        cap = room if cap is None else int(cap)
+        if cap > room:
+            raise ValueError("cap exceeds the list arrays")
+        n_valid = (int(off[nq]) if nq else 0) if n_valid is None else int(n_valid)
+        rows = np.empty(nq + 1, dtype=np.int64) if want_rows else None
+        first, added = C.c_int64(), C.c_int64()
+        self._check(self._lib.rrtx_graph_edges_append_lists(
+            self._h, nq, _capi._ptr(off), _capi._ptr(ia), _capi._ptr(co), _capi._ptr(ci), _capi._ptr(ho), _capi._ptr(hi),
+            n_valid, cap, _capi._ptr(nd), 1 if idx_is_batch else 0, C.byref(first), C.byref(added), _capi._ptr(rows)))
+        return first.value, added.value, rows
+
+    def graph_edges_append_lists_dev(self, nq: int, offsets_ptr: int, idx_ptr: int, cost_out_ptr: int, cost_in_ptr: int,
+                                     hit_out_ptr: int, hit_in_ptr: int, n_valid_ptr: Optional[int], cap: int,
+                                     node_of_ptr: int, idx_is_batch: bool = False, row_first_ptr: Optional[int] = None):
+        """rrtx_graph_edges_append_lists_dev over device lists (those of extend_candidates_dev and its kin); waits on the
+        stream once for the counts.  Returns (first_id, n_added); row_first_ptr: nq + 1 int64 on the device, or None."""
+        first, added = C.c_int64(), C.c_int64()
+        self._check(self._lib.rrtx_graph_edges_append_lists_dev(
+            self._h, nq, offsets_ptr, idx_ptr, cost_out_ptr, cost_in_ptr, hit_out_ptr, hit_in_ptr, n_valid_ptr, cap,
+            node_of_ptr, 1 if idx_is_batch else 0, C.byref(first), C.byref(added), row_first_ptr))
+        return first.value, added.value
+
+    def graph_edges_append_selected(self, node_of, want_rows: bool = True):
+        """rrtx_graph_edges_append_selected: the same over the lists the last extend_select left on the device
+        (RRTX_E_STATE when another call has used their workspaces since, or node_of has another length).
+        Returns (first_id, n_added, row_first or None)."""
+        nd = np.ascontiguousarray(node_of, dtype=np.int32).reshape(-1)
+        nq = nd.shape[0]
+        rows = np.empty(nq + 1, dtype=np.int64) if want_rows else None
+        first, added = C.c_int64(), C.c_int64()
+        self._check(self._lib.rrtx_graph_edges_append_selected(self._h, nq, _capi._ptr(nd), C.byref(first), C.byref(added),
+                                                               _capi._ptr(rows)))
+        return first.value, added.value, rows
+
+    def graph_edges_get(self, ids=None, first_id: int = 0, n: Optional[int] = None):
+        """rrtx_graph_edges_get: (start, end, dist, dist_original) of the mirror edges `ids`, or of the range
+        [first_id, first_id + n) (n None: to the end of the mirror)."""
+        if ids is not None:
+            ia = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            n = ia.shape[0]
+        else:
+            ia = None
+            n = self.n_graph_edges - int(first_id) if n is None else int(n)
+        m = max(n, 0)
+        start, end = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        dist, dist0 = np.empty(m, dtype=np.float64), np.empty(m, dtype=np.float64)
+        self._check(self._lib.rrtx_graph_edges_get(self._h, _capi._ptr(ia), int(first_id), n, _capi._ptr(start),
+                                                   _capi._ptr(end), _capi._ptr(dist), _capi._ptr(dist0)))
+        return start, end, dist, dist0
+
     def _edge_ids_call(self, fn, edge_ids):
         ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
         self._check(fn(self._h, _capi._ptr(ids), ids.shape[0]))

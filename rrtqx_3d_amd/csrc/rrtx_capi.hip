@@ -239,6 +239,24 @@ int regrow(rrtx_ctx *ctx, T *&ptr, int64_t new_count, int64_t keep) {
   return RRTX_OK;
 }
 
+// room for n more edges in the mirror (the five arrays double from 4096, keeping what they hold); RRTX_E_CAPACITY
+// beyond the int32 id range.  Waits on the stream when it has to reallocate.
+int grow_edges(rrtx_ctx *ctx, int64_t n) {
+  if (ctx->ge_n + n > 0x7fffffffll) return fail(ctx, RRTX_E_CAPACITY, "edge ids are int32");
+  if (ctx->ge_n + n <= ctx->ge_cap) return RRTX_OK;
+  int64_t nc = ctx->ge_cap > 0 ? ctx->ge_cap : 4096;
+  while (nc < ctx->ge_n + n) nc *= 2;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int rc;
+  if ((rc = regrow(ctx, ctx->ge_start, nc, ctx->ge_n))) return rc;
+  if ((rc = regrow(ctx, ctx->ge_end, nc, ctx->ge_n))) return rc;
+  if ((rc = regrow(ctx, ctx->ge_dist, nc, ctx->ge_n))) return rc;
+  if ((rc = regrow(ctx, ctx->ge_dist0, nc, ctx->ge_n))) return rc;
+  if ((rc = regrow(ctx, ctx->ge_dirty, nc, ctx->ge_n))) return rc;
+  ctx->ge_cap = nc;
+  return RRTX_OK;
+}
+
 int grow_nodes(rrtx_ctx *ctx, int64_t need) {
   if (need <= ctx->cap_nodes) return RRTX_OK;
   int64_t nc = ctx->cap_nodes > 0 ? ctx->cap_nodes : 1024;
@@ -507,13 +525,19 @@ std::mutex g_create_mu;
 
 using namespace rrtx;
 
-#define CHECK_CTX(ctx)                 \
+#define CHECK_CTX_KEEP(ctx)            \
   ::rrtx::ApiRange _rrtx_api_range(__func__); \
   do {                                 \
     if (!(ctx)) return RRTX_E_INVALID; \
     hipError_t _sd = hipSetDevice((ctx)->device); \
     if (_sd != hipSuccess) return fail((ctx), RRTX_E_DEVICE, "hipSetDevice(%d): %s", (ctx)->device, hipGetErrorString(_sd)); \
   } while (0)
+// The lists rrtx_extend_select leaves for rrtx_graph_edges_append_selected live in workspaces most entry points write
+// (ws_out_idx / _dist / _u8a / _u8b, ws_sel_blk), so dropping the record of them is the rule and keeping it the
+// exception: CHECK_CTX_KEEP is for the entry points that write none of those workspaces (include/rrtx.h lists them).
+#define CHECK_CTX(ctx)  \
+  CHECK_CTX_KEEP(ctx);  \
+  (ctx)->sel_hold_nq = -1
 
 extern "C" {
 
@@ -600,7 +624,8 @@ int rrtx_destroy(rrtx_ctx *ctx) {
                     &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
                     &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
                     &ctx->gc.in_pos, &ctx->gc.rep_lmc, &ctx->gc.rep_parent, &ctx->gc.delta_cnt, &ctx->gc.delta_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
-                    &ctx->ws_tgt_blk[0], &ctx->ws_tgt_blk[1], &ctx->ws_tgt_res};
+                    &ctx->ws_tgt_blk[0], &ctx->ws_tgt_blk[1], &ctx->ws_tgt_res,
+                    &ctx->ws_link_cnt, &ctx->ws_link_row, &ctx->ws_link_res, &ctx->ws_link_node, &ctx->ws_link_get, &ctx->ws_delta_node};
   for (auto b : bufs) b->release();
   if (ctx->node_lmc) (void)hipFree(ctx->node_lmc);
   if (ctx->ge_start) (void)hipFree(ctx->ge_start);
@@ -628,7 +653,7 @@ int rrtx_set_stream(rrtx_ctx *ctx, void *hip_stream) {
 void *rrtx_get_stream(rrtx_ctx *ctx) { return ctx ? reinterpret_cast<void *>(ctx->stream) : nullptr; }
 
 int rrtx_sync(rrtx_ctx *ctx) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
@@ -699,7 +724,7 @@ int rrtx_host_unregister(rrtx_ctx *ctx, void *ptr) {
 }
 
 int rrtx_get_option(rrtx_ctx *ctx, int option, int64_t *value) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   if (!value) return fail(ctx, RRTX_E_INVALID, "get_option: null output");
   switch (option) {
     case RRTX_OPT_NN_FILTER: *value = ctx->opt_nn_filter ? 1 : 0; return RRTX_OK;
@@ -723,14 +748,14 @@ int rrtx_get_option(rrtx_ctx *ctx, int option, int64_t *value) {
 }
 
 int rrtx_last_tile_form(rrtx_ctx *ctx, int *form) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   if (!form) return fail(ctx, RRTX_E_INVALID, "last_tile_form: null output");
   *form = ctx->last_tile_form;
   return RRTX_OK;
 }
 
 int rrtx_stats(rrtx_ctx *ctx, rrtx_stats_t *out) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   if (!out) return fail(ctx, RRTX_E_INVALID, "stats: out is NULL");
   drain_spans(ctx);
   out->n_nodes = ctx->n_nodes;
@@ -768,7 +793,7 @@ static int nodes_append_args(rrtx_ctx *ctx, const double *pos, int64_t n) {
 }
 
 int rrtx_nodes_append_dev(rrtx_ctx *ctx, const double *pos_dev, int64_t n) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   int rc = nodes_append_args(ctx, pos_dev, n);
   if (rc || n == 0) return rc;
   if ((rc = grow_nodes(ctx, ctx->n_nodes + n))) return rc;
@@ -805,7 +830,7 @@ int rrtx_nodes_append_dev(rrtx_ctx *ctx, const double *pos_dev, int64_t n) {
 }
 
 int rrtx_nodes_append(rrtx_ctx *ctx, const double *pos, int64_t n, int64_t *first_index) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   int rc = nodes_append_args(ctx, pos, n);
   if (rc) return rc;
   if (first_index) *first_index = ctx->n_nodes;
@@ -1108,7 +1133,7 @@ int rrtx_edges_check_idx(rrtx_ctx *ctx, const int32_t *start_idx, const int32_t 
 int64_t rrtx_graph_edges_count(rrtx_ctx *ctx) { return ctx ? ctx->ge_n : 0; }
 
 int rrtx_graph_edges_clear(rrtx_ctx *ctx) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   ctx->ge_n = 0;
   graph_cost_forget(ctx);
   graph_delta_forget(ctx);
@@ -1117,7 +1142,7 @@ int rrtx_graph_edges_clear(rrtx_ctx *ctx) {
 
 int rrtx_graph_edges_append(rrtx_ctx *ctx, const int32_t *start_idx, const int32_t *end_idx, int64_t n,
                             int64_t *first_id) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   if (n < 0 || (n > 0 && (!start_idx || !end_idx))) return fail(ctx, RRTX_E_INVALID, "graph_edges_append: bad arguments");
   if (first_id) *first_id = ctx->ge_n;
   if (n == 0) return RRTX_OK;
@@ -1125,19 +1150,8 @@ int rrtx_graph_edges_append(rrtx_ctx *ctx, const int32_t *start_idx, const int32
     if (start_idx[i] < 0 || start_idx[i] >= ctx->n_nodes || end_idx[i] < 0 || end_idx[i] >= ctx->n_nodes)
       return fail(ctx, RRTX_E_INVALID, "graph_edges_append: edge %lld references a node outside [0, %lld)",
                   (long long)i, (long long)ctx->n_nodes);
-  if (ctx->ge_n + n > 0x7fffffffll) return fail(ctx, RRTX_E_CAPACITY, "edge ids are int32");
-  if (ctx->ge_n + n > ctx->ge_cap) {
-    int64_t nc = ctx->ge_cap > 0 ? ctx->ge_cap : 4096;
-    while (nc < ctx->ge_n + n) nc *= 2;
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int rc;
-    if ((rc = regrow(ctx, ctx->ge_start, nc, ctx->ge_n))) return rc;
-    if ((rc = regrow(ctx, ctx->ge_end, nc, ctx->ge_n))) return rc;
-    if ((rc = regrow(ctx, ctx->ge_dist, nc, ctx->ge_n))) return rc;
-    if ((rc = regrow(ctx, ctx->ge_dist0, nc, ctx->ge_n))) return rc;
-    if ((rc = regrow(ctx, ctx->ge_dirty, nc, ctx->ge_n))) return rc;
-    ctx->ge_cap = nc;
-  }
+  int rc = grow_edges(ctx, n);
+  if (rc) return rc;
   RRTX_HIP(ctx, hipMemcpyAsync(ctx->ge_start + ctx->ge_n, start_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   RRTX_HIP(ctx, hipMemcpyAsync(ctx->ge_end + ctx->ge_n, end_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   // edge.dist defaults to the SimpleEdge cost of the edge (rrtx_graph_edges_set_dist overrides it)
@@ -1149,7 +1163,7 @@ int rrtx_graph_edges_append(rrtx_ctx *ctx, const int32_t *start_idx, const int32
 }
 
 int rrtx_graph_edges_set_dist(rrtx_ctx *ctx, int64_t first_id, const double *dist, int64_t n) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   if (n < 0 || first_id < 0 || first_id + n > ctx->ge_n || (n > 0 && !dist))
     return fail(ctx, RRTX_E_INVALID, "graph_edges_set_dist: edges [%lld, %lld) of %lld", (long long)first_id,
                 (long long)(first_id + n), (long long)ctx->ge_n);
@@ -1169,13 +1183,188 @@ static int graph_edges_block_host(rrtx_ctx *ctx, const char *fn, bool restore, c
 }
 
 int rrtx_graph_edges_block(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   return graph_edges_block_host(ctx, "graph_edges_block", false, edge_ids, n);
 }
 
 int rrtx_graph_edges_unblock(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   return graph_edges_block_host(ctx, "graph_edges_unblock", true, edge_ids, n);
+}
+
+// ---- neighbour lists -> mirror edges on the device (kernels_link.hip) -------------------------------------------
+namespace {
+int append_lists_args(rrtx_ctx *ctx, const char *fn, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
+                      const double *cost_in, const uint8_t *hit_out, const uint8_t *hit_in, int64_t cap, const int32_t *node_of) {
+  if (nq < 0 || cap < 0 || (nq > 0 && (!offsets || !node_of)) || (cap > 0 && (!idx || !cost_out || !cost_in || !hit_out || !hit_in)))
+    return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
+  return RRTX_OK;
+}
+
+// The body the three entry points share, over lists on the device: the counting pass and the scan, ONE wait on the
+// stream to read {entries, edges, verdict}, then the refusal or the growth of the mirror and the fill (enqueued).
+// L.row_first null: the context's own array.
+int append_lists_dev(rrtx_ctx *ctx, const char *fn, LinkLists L, int64_t *first_id, int64_t *n_added) {
+  if (first_id) *first_id = ctx->ge_n;
+  if (n_added) *n_added = 0;
+  if (L.nq == 0) {
+    if (L.row_first) RRTX_HIP(ctx, hipMemsetAsync(L.row_first, 0, sizeof(int64_t), ctx->stream));
+    return RRTX_OK;
+  }
+  if (!L.row_first) {
+    RRTX_HIP(ctx, ctx->ws_link_row.ensure(sizeof(int64_t) * ((size_t)L.nq + 1)));
+    L.row_first = ctx->ws_link_row.as<int64_t>();
+  }
+  int rc = launch_link_count(ctx, L);
+  if (rc) return rc;
+  int64_t res[3] = {0, 0, 0};
+  RRTX_HIP(ctx, hipMemcpyAsync(res, ctx->ws_link_res.p, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const unsigned verdict = (unsigned)res[2];
+  if (verdict & kLinkOverflow)
+    return fail(ctx, RRTX_E_CAPACITY, "%s: the extend call produced more entries than the lists hold (%lld)", fn, (long long)L.cap);
+  if (verdict & kLinkBadOffsets) return fail(ctx, RRTX_E_INVALID, "%s: offsets out of order or beyond the lists", fn);
+  if (verdict & kLinkBadNode)
+    return fail(ctx, RRTX_E_INVALID, "%s: node_of references a node outside [0, %lld)", fn, (long long)ctx->n_nodes);
+  if (verdict & kLinkBadIndex)
+    return fail(ctx, RRTX_E_INVALID, "%s: a list entry references a %s", fn,
+                L.idx_is_batch ? "batch position outside [0, nq)" : "node outside the tree");
+  if (verdict & kLinkTooMany) return fail(ctx, RRTX_E_CAPACITY, "%s: edge ids are int32", fn);
+  const int64_t total = res[1];
+  if (total <= 0) return RRTX_OK;
+  if ((rc = grow_edges(ctx, total))) return rc;
+  if ((rc = launch_link_fill(ctx, L, ctx->ge_n, total))) return rc;
+  ctx->ge_n += total;
+  if (n_added) *n_added = total;
+  return RRTX_OK;
+}
+
+// what stage_in_small / d2h take from the arena for an array of that size
+size_t small_in(size_t bytes) { return bytes <= (1u << 20) ? bytes + 64 : 0; }
+size_t small_out(size_t bytes) { return bytes <= (256u << 10) ? bytes + 64 : 0; }
+}  // namespace
+
+int rrtx_graph_edges_append_lists_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx,
+                                      const double *cost_out, const double *cost_in, const uint8_t *hit_out,
+                                      const uint8_t *hit_in, const int64_t *n_valid_dev, int64_t cap, const int32_t *node_of,
+                                      int idx_is_batch, int64_t *first_id, int64_t *n_added, int64_t *row_first) {
+  CHECK_CTX_KEEP(ctx);
+  int rc = append_lists_args(ctx, "graph_edges_append_lists_dev", nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, cap, node_of);
+  if (rc) return rc;
+  return append_lists_dev(ctx, "graph_edges_append_lists_dev",
+                          LinkLists{nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, n_valid_dev, cap, node_of,
+                                    idx_is_batch != 0, row_first},
+                          first_id, n_added);
+}
+
+int rrtx_graph_edges_append_lists(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
+                                  const double *cost_in, const uint8_t *hit_out, const uint8_t *hit_in, int64_t n_valid,
+                                  int64_t cap, const int32_t *node_of, int idx_is_batch, int64_t *first_id, int64_t *n_added,
+                                  int64_t *row_first) {
+  CHECK_CTX(ctx);
+  const char *fn = "graph_edges_append_lists";
+  int rc = append_lists_args(ctx, fn, nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, cap, node_of);
+  if (rc) return rc;
+  if (n_valid < 0) return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
+  if (first_id) *first_id = ctx->ge_n;
+  if (n_added) *n_added = 0;
+  if (n_valid > cap) return fail(ctx, RRTX_E_CAPACITY, "%s: %lld entries, capacity %lld", fn, (long long)n_valid, (long long)cap);
+  if (nq == 0) { if (row_first) row_first[0] = 0; return RRTX_OK; }
+  // the lists go up through the staging path of the host-pointer searches, into their workspaces; only the n_valid
+  // entries the extend call produced travel, and they are the capacity the kernels check against
+  const size_t n = (size_t)n_valid, rows = (size_t)nq + 1;
+  const bool one_cost = cost_in == cost_out;
+  rc = arena_begin(ctx, small_in(sizeof(int64_t) * rows) + small_in(sizeof(int32_t) * (size_t)nq) + small_in(sizeof(int32_t) * n) +
+                            2 * small_in(sizeof(double) * n) + 2 * small_in(n) + small_out(sizeof(int64_t) * rows) + 512);
+  if (rc) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_out_off, offsets, sizeof(int64_t) * rows))) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_link_node, node_of, sizeof(int32_t) * (size_t)nq))) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_out_idx, idx, sizeof(int32_t) * n))) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_out_dist, cost_out, sizeof(double) * n))) return rc;
+  if (!one_cost && (rc = stage_in_small(ctx, ctx->ws_out_f64, cost_in, sizeof(double) * n))) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_out_u8a, hit_out, n))) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_out_u8b, hit_in, n))) return rc;
+  RRTX_HIP(ctx, ctx->ws_link_row.ensure(sizeof(int64_t) * rows));
+  const double *co = ctx->ws_out_dist.as<double>();
+  rc = append_lists_dev(ctx, fn,
+                        LinkLists{nq, ctx->ws_out_off.as<int64_t>(), ctx->ws_out_idx.as<int32_t>(), co,
+                                  one_cost ? co : ctx->ws_out_f64.as<double>(), ctx->ws_out_u8a.as<uint8_t>(),
+                                  ctx->ws_out_u8b.as<uint8_t>(), nullptr, n_valid, ctx->ws_link_node.as<int32_t>(),
+                                  idx_is_batch != 0, ctx->ws_link_row.as<int64_t>()},
+                        first_id, n_added);
+  if (rc) return rc;
+  if (row_first && (rc = d2h(ctx, row_first, ctx->ws_link_row.p, sizeof(int64_t) * rows))) return rc;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  arena_flush(ctx);
+  return RRTX_OK;
+}
+
+int rrtx_graph_edges_append_selected(rrtx_ctx *ctx, int nq, const int32_t *node_of, int64_t *first_id, int64_t *n_added,
+                                     int64_t *row_first) {
+  CHECK_CTX_KEEP(ctx);
+  const char *fn = "graph_edges_append_selected";
+  if (nq < 0 || (nq > 0 && !node_of)) return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
+  if (ctx->sel_hold_nq < 0)
+    return fail(ctx, RRTX_E_STATE, "%s: the context holds no lists of rrtx_extend_select (none made, or a later call used "
+                                   "their workspaces)", fn);
+  if (ctx->sel_hold_nq != nq)
+    return fail(ctx, RRTX_E_STATE, "%s: the held lists are those of %d samples, not %d", fn, ctx->sel_hold_nq, nq);
+  if (first_id) *first_id = ctx->ge_n;
+  if (n_added) *n_added = 0;
+  if (nq == 0) { if (row_first) row_first[0] = 0; return RRTX_OK; }
+  const size_t rows = (size_t)nq + 1;
+  int rc = arena_begin(ctx, small_in(sizeof(int32_t) * (size_t)nq) + small_out(sizeof(int64_t) * rows) + 512);
+  if (rc) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_link_node, node_of, sizeof(int32_t) * (size_t)nq))) return rc;
+  RRTX_HIP(ctx, ctx->ws_link_row.ensure(sizeof(int64_t) * rows));
+  const SelectBlock B{(size_t)nq};
+  char *blk = ctx->ws_sel_blk.as<char>();
+  const double *cost = ctx->ws_out_dist.as<double>();
+  rc = append_lists_dev(ctx, fn,
+                        LinkLists{nq, B.offsets.in(blk), ctx->ws_out_idx.as<int32_t>(), cost, cost, ctx->ws_out_u8a.as<uint8_t>(),
+                                  ctx->ws_out_u8b.as<uint8_t>(), B.counts.in(blk), ctx->sel_list_cap,
+                                  ctx->ws_link_node.as<int32_t>(), false, ctx->ws_link_row.as<int64_t>()},
+                        first_id, n_added);
+  if (rc) return rc;
+  if (row_first && (rc = d2h(ctx, row_first, ctx->ws_link_row.p, sizeof(int64_t) * rows))) return rc;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));      // node_of is the caller's
+  arena_flush(ctx);
+  return RRTX_OK;
+}
+
+int rrtx_graph_edges_get(rrtx_ctx *ctx, const int32_t *ids, int64_t first_id, int64_t n, int32_t *start, int32_t *end,
+                         double *dist, double *dist_original) {
+  CHECK_CTX_KEEP(ctx);
+  if (n < 0) return fail(ctx, RRTX_E_INVALID, "graph_edges_get: bad arguments");
+  if (n == 0) return RRTX_OK;
+  const size_t m = (size_t)n;
+  if (!ids) {
+    if (first_id < 0 || first_id > ctx->ge_n || n > ctx->ge_n - first_id)
+      return fail(ctx, RRTX_E_INVALID, "graph_edges_get: edges [%lld, %lld) of %lld", (long long)first_id,
+                  (long long)(first_id + n), (long long)ctx->ge_n);
+    RRTX_HIP(ctx, copy_out(ctx, start, ctx->ge_start + first_id, sizeof(int32_t) * m));
+    RRTX_HIP(ctx, copy_out(ctx, end, ctx->ge_end + first_id, sizeof(int32_t) * m));
+    RRTX_HIP(ctx, copy_out(ctx, dist, ctx->ge_dist + first_id, sizeof(double) * m));
+    RRTX_HIP(ctx, copy_out(ctx, dist_original, ctx->ge_dist0 + first_id, sizeof(double) * m));
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RRTX_OK;
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= ctx->ge_n) return fail(ctx, RRTX_E_INVALID, "graph_edges_get: edge id %d out of range", ids[i]);
+  RRTX_HIP(ctx, ctx->gc.ids.ensure(sizeof(int32_t) * m));
+  RRTX_HIP(ctx, ctx->ws_link_get.ensure((2 * sizeof(double) + 2 * sizeof(int32_t)) * m));
+  double *d_dist = ctx->ws_link_get.as<double>(), *d_dist0 = d_dist + m;
+  int32_t *d_start = reinterpret_cast<int32_t *>(d_dist0 + m), *d_end = d_start + m;
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->gc.ids.p, ids, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream));
+  int rc = launch_link_gather(ctx, ctx->gc.ids.as<int32_t>(), n, start ? d_start : nullptr, end ? d_end : nullptr,
+                              dist ? d_dist : nullptr, dist_original ? d_dist0 : nullptr);
+  if (rc) return rc;
+  RRTX_HIP(ctx, copy_out(ctx, start, d_start, sizeof(int32_t) * m));
+  RRTX_HIP(ctx, copy_out(ctx, end, d_end, sizeof(int32_t) * m));
+  RRTX_HIP(ctx, copy_out(ctx, dist, d_dist, sizeof(double) * m));
+  RRTX_HIP(ctx, copy_out(ctx, dist_original, d_dist0, sizeof(double) * m));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
 }
 
 namespace {
@@ -1209,28 +1398,28 @@ int graph_cost_dev(rrtx_ctx *ctx, const char *fn, int root_idx, bool update, dou
 }  // namespace
 
 int rrtx_graph_cost_to_root(rrtx_ctx *ctx, int root_idx, double *lmc, int32_t *parent_edge, int32_t *passes) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   return graph_cost_host(ctx, "graph_cost_to_root", root_idx, false, lmc, parent_edge, passes);
 }
 
 int rrtx_graph_cost_update(rrtx_ctx *ctx, int root_idx, double *lmc, int32_t *parent_edge, int32_t *passes) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   return graph_cost_host(ctx, "graph_cost_update", root_idx, true, lmc, parent_edge, passes);
 }
 
 int rrtx_graph_cost_to_root_dev(rrtx_ctx *ctx, int root_idx, double *lmc_dev, int32_t *parent_edge_dev) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   return graph_cost_dev(ctx, "graph_cost_to_root", root_idx, false, lmc_dev, parent_edge_dev);
 }
 
 int rrtx_graph_cost_update_dev(rrtx_ctx *ctx, int root_idx, double *lmc_dev, int32_t *parent_edge_dev) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   return graph_cost_dev(ctx, "graph_cost_update", root_idx, true, lmc_dev, parent_edge_dev);
 }
 
 int rrtx_graph_cost_update_delta(rrtx_ctx *ctx, int root_idx, int store, int32_t *node, double *lmc, int32_t *parent_edge,
                                  int64_t cap, int64_t *needed, int32_t *passes) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   if (cap < 0 || (cap > 0 && (!node || !lmc)) || !needed)
     return fail(ctx, RRTX_E_INVALID, "graph_cost_update_delta: bad arguments");
   if (ctx->n_nodes <= 0) return fail(ctx, RRTX_E_STATE, "graph_cost_update_delta on an empty tree");
@@ -1238,14 +1427,14 @@ int rrtx_graph_cost_update_delta(rrtx_ctx *ctx, int root_idx, int store, int32_t
     return fail(ctx, RRTX_E_INVALID, "graph_cost_update_delta: root %d out of range", root_idx);
   *needed = 0;
   const size_t dcap = cap > 0 ? (size_t)cap : 1;
-  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * dcap));
+  RRTX_HIP(ctx, ctx->ws_delta_node.ensure(sizeof(int32_t) * dcap));
   RRTX_HIP(ctx, ctx->ws_out_f64.ensure(sizeof(double) * dcap));
   RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * dcap));
   int rc = arena_begin(ctx, 16 * (size_t)std::min<int64_t>(cap, ctx->n_nodes) + 256);
   if (rc) return rc;
   int np = 0;
   int64_t *total_dev = nullptr;
-  rc = launch_graph_delta(ctx, root_idx, store != 0, ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_f64.as<double>(),
+  rc = launch_graph_delta(ctx, root_idx, store != 0, ctx->ws_delta_node.as<int32_t>(), ctx->ws_out_f64.as<double>(),
                           ctx->ws_out_i32.as<int32_t>(), (long long)cap, &total_dev, &np);
   if (rc) return rc;
   if (passes) *passes = np;
@@ -1253,7 +1442,7 @@ int rrtx_graph_cost_update_delta(rrtx_ctx *ctx, int root_idx, int store, int32_t
   RRTX_HIP(ctx, read_count(ctx, total_dev, &total));      // the call's one synchronisation before the records leave
   if ((rc = check_capacity(ctx, "graph_cost_update_delta", "changed nodes", total, cap, needed))) return rc;
   // the records fit: they go to the caller, and the baseline moves to the solver's state
-  if ((rc = d2h(ctx, node, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
+  if ((rc = d2h(ctx, node, ctx->ws_delta_node.p, sizeof(int32_t) * (size_t)total))) return rc;
   if ((rc = d2h(ctx, lmc, ctx->ws_out_f64.p, sizeof(double) * (size_t)total))) return rc;
   if (parent_edge && (rc = d2h(ctx, parent_edge, ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)total))) return rc;
   if ((rc = launch_graph_delta_advance(ctx, root_idx))) return rc;
@@ -2347,7 +2536,7 @@ int rrtx_extend_select_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const 
 }
 
 int rrtx_node_cost_set(rrtx_ctx *ctx, int64_t first_index, const double *lmc, int64_t n) {
-  CHECK_CTX(ctx);
+  CHECK_CTX_KEEP(ctx);
   if (n < 0 || first_index < 0 || (n > 0 && !lmc)) return fail(ctx, RRTX_E_INVALID, "node_cost_set: bad arguments");
   if (first_index > ctx->n_nodes || n > ctx->n_nodes - first_index)
     return fail(ctx, RRTX_E_INVALID, "node_cost_set: nodes %lld .. %lld of %lld", (long long)first_index,
@@ -2376,6 +2565,7 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
     if (rw_needed) *rw_needed = 0;
     if (want_lists) offsets[0] = 0;
     if (needed) *needed = 0;
+    ctx->sel_hold_nq = 0; ctx->sel_hold_count = 0;
     return RRTX_OK;
   }
   // Everything that is per sample sits in ONE device block (SelectBlock), so that it leaves in one transfer: without
@@ -2438,6 +2628,9 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     arena_flush(ctx);
   }
+  // the lists stay for rrtx_graph_edges_append_selected (a nearest fallback that has to search drops the record again:
+  // rrtx_nn_nearest writes their workspaces)
+  ctx->sel_hold_nq = nq; ctx->sel_hold_count = total;
   return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
 }
 

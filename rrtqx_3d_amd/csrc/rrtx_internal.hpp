@@ -276,6 +276,16 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_sel_blk;          // rrtx_extend_select: everything that is per sample, one block (SelectBlock, rrtx_capi.hip)
   rrtx::DevBuf ws_sel_rwn, ws_sel_rwv, ws_sel_lmc;   // ... its rewire lists and a caller-given rrtLMC array
   int64_t sel_list_cap = 0;         // ... entries its neighbour lists have room for
+  // the lists the last successful rrtx_extend_select left in ws_out_idx / _dist / _u8a / _u8b and ws_sel_blk, for
+  // rrtx_graph_edges_append_selected: its nq (-1: no such lists; every entry point that writes those workspaces drops
+  // the record, CHECK_CTX in rrtx_capi.hip) and its entry count
+  int sel_hold_nq = -1;
+  int64_t sel_hold_count = 0;
+
+  // neighbour lists -> mirror edges (kernels_link.hip): edges per row, their scan, {entries, edges, verdict}, the
+  // staged node_of, and what rrtx_graph_edges_get gathers into
+  rrtx::DevBuf ws_link_cnt, ws_link_row, ws_link_res, ws_link_node, ws_link_get;
+  rrtx::DevBuf ws_delta_node;       // rrtx_graph_cost_update_delta: the changed nodes
 
   // move-target selection (kernels_target.hip): the two query blocks the rounds alternate between, each
   // [pose | radius | thr_lt, thr_gt | slot] of the poses still searching, and [results | pending | header]
@@ -522,6 +532,28 @@ struct SelectLaunch {
   int64_t *rw_offsets; int32_t *rw_node; double *rw_value; int64_t rw_cap; int64_t *rw_needed_dev;
 };
 int launch_select(rrtx_ctx *ctx, const SelectLaunch &L);
+
+// neighbour lists -> mirror edges (kernels_link.hip); device pointers.  launch_link_count leaves {surviving entries,
+// edges, verdict} in ctx->ws_link_res and the CSR of every sample's edges in row_first (nq + 1); the caller reads the
+// three words, refuses or grows the mirror, and launch_link_fill writes edges [first, first + total).
+enum : unsigned {
+  kLinkOverflow = 1,      // *n_valid_dev > cap
+  kLinkBadNode = 2,       // node_of[j] >= the node count
+  kLinkBadIndex = 4,      // a surviving entry's near node / batch position out of range
+  kLinkBadOffsets = 8,    // offsets out of order or beyond cap
+  kLinkTooMany = 16,      // one row yields more than 2^31 - 1 edges
+};
+struct LinkLists {
+  int nq;
+  const int64_t *offsets; const int32_t *idx; const double *cost_out, *cost_in; const uint8_t *hit_out, *hit_in;
+  const int64_t *n_valid_dev; int64_t cap;
+  const int32_t *node_of; bool idx_is_batch;
+  int64_t *row_first;
+};
+int launch_link_count(rrtx_ctx *ctx, const LinkLists &L);
+int launch_link_fill(rrtx_ctx *ctx, const LinkLists &L, long long first, long long total);
+int launch_link_gather(rrtx_ctx *ctx, const int32_t *ids_dev, long long n, int32_t *start_dev, int32_t *end_dev,
+                       double *dist_dev, double *dist0_dev);
 
 // findNewTarget, one round (kernels_target.hip): the first minimum of lmc[node] + cost over the unblocked entries of
 // every pose still searching, then the poses without one move on to the next round's query block with twice the radius

@@ -942,6 +942,28 @@ def unblockEdges(KD: HipTree, ids):
     KD.ctx.graph_edges_unblock(ids)
 
 
+def registerEdgesFromLists(KD: HipTree, lists: dict, nodeOf, selfLists: bool = False) -> Tuple[int, int, np.ndarray]:
+    """What extend() links for a batch (R/DRRT_Q.jl:2560-2640), registered on the device from the host lists of
+    extend_candidates* (a dict with offsets, idx, hit_out, hit_in and cost, or cost_out / cost_in for Dubins lists):
+    per inserted sample j (nodeOf[j] >= 0, the index kdInsert gave it) and entry, the out-edge (blocked when hit_out)
+    and, when hit_in is clear, the in-edge.  selfLists: idx holds batch positions (extend_candidates_self*).
+    Returns (first id, edges registered, CSR of every sample's edges relative to the first id)."""
+    co = lists["cost_out"] if "cost_out" in lists else lists["cost"]
+    ci = lists["cost_in"] if "cost_in" in lists else co
+    return KD.ctx.graph_edges_append_lists(lists["offsets"], lists["idx"], co, ci, lists["hit_out"], lists["hit_in"], nodeOf,
+                                           idx_is_batch=selfLists)
+
+
+def registerSelectedEdges(KD: HipTree, nodeOf) -> Tuple[int, int, np.ndarray]:
+    """The same over the lists the last extend_select left on the device: nothing but nodeOf travels."""
+    return KD.ctx.graph_edges_append_selected(nodeOf)
+
+
+def registeredEdges(KD: HipTree, ids=None, first_id: int = 0, n: Optional[int] = None):
+    """(start index, end index, edge.dist, edge.distOriginal) of registered edges: the ids given, or a range."""
+    return KD.ctx.graph_edges_get(ids, first_id, n)
+
+
 def costToRoot(KD: HipTree, root: RRTNode) -> Tuple[np.ndarray, np.ndarray]:
     """The state propogateDescendants + reduceInconsistency (R/DRRT_Q.jl:2703-2817) reach with
     changeThresh = 0.0 once rrtXQueue is empty, computed over the registered edges: (rrtLMC per node in
