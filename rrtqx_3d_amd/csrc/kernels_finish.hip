@@ -123,15 +123,17 @@ __global__ __launch_bounds__(kFinThreads, KSORT > kBigSort ? 2 : 8) void nn_fini
   // the first 32 slots of the bucket are requested before the count has arrived (bcap >= 8; slots past
   // the count hold stale records and are masked below)
   if (qv && hl < a.bcap) e0 = a.bkt[(size_t)q * (size_t)a.bcap + (size_t)hl];
-  long long psum = 0;
+  unsigned long long psum = 0;
   if (!a.prescattered) {
-    // 16 b counts precede workgroup b
+    // 16 b counts precede workgroup b.  A count lies in [0, INT_MAX], so two of them add up exactly in 32 unsigned
+    // bits (at most 2^32 - 2): the sum is widened once per pair, not once per count.
     const int4 *c4 = reinterpret_cast<const int4 *>(a.count);
     const int n4 = (int)blockIdx.x * (kFinQ / 4);
 #pragma unroll 4
     for (int j = t; j < n4; j += kFinThreads) {
       const int4 v = c4[j];
-      psum += (long long)v.x + v.y + v.z + v.w;
+      psum += (unsigned)v.x + (unsigned)v.y;
+      psum += (unsigned)v.z + (unsigned)v.w;
     }
   }
   // a list the half wave cannot finish alone: longer than 64 entries, or overflowed its bucket
@@ -144,50 +146,31 @@ __global__ __launch_bounds__(kFinThreads, KSORT > kBigSort ? 2 : 8) void nn_fini
   // ---- short lists: rank by node index inside the half wave ----
   const int m0 = e0.idx, m1 = e1.idx;
   const double d0 = e0.d2, d1 = e1.d2;
-  int r0 = 0, r1 = 0;
-  {
-    const int kmax = max(kk, __shfl_xor(kk, 32));      // the two halves of a wave run the same loops
-    if (kmax <= 32) {
-      // the usual case, no second entry in either half of the wave: half the compares, four entries per round
-      // (slots past a list hold index INT_MAX, which ranks below nothing)
-      const int kr = (kmax + 3) & ~3;
-      for (int j = 0; j < kr; j += 4) {
-        const int o0 = __shfl(m0, j, 32), o1 = __shfl(m0, j + 1, 32), o2 = __shfl(m0, j + 2, 32), o3 = __shfl(m0, j + 3, 32);
-        r0 += ((o0 < m0) ? 1 : 0) + ((o1 < m0) ? 1 : 0) + ((o2 < m0) ? 1 : 0) + ((o3 < m0) ? 1 : 0);
-      }
-    } else {
-      for (int j = 0; j < 32; ++j) {
-        const int o = __shfl(m0, j, 32);
-        r0 += (o < m0) ? 1 : 0;
-        r1 += (o < m1) ? 1 : 0;
-      }
-      for (int j = 32; j < kmax; ++j) {
-        const int o = __shfl(m1, j - 32, 32);
-        r0 += (o < m0) ? 1 : 0;
-        r1 += (o < m1) ? 1 : 0;
-      }
-    }
-  }
+  // A node index lies in [0, INT_MAX) and an empty slot holds INT_MAX, which ranks below nothing: the rank of a key
+  // is a count over all 32 slots of the half wave, whatever the list's length (half_rank_below, wave_device.hpp).
+  int r0 = half_rank_below<false>(m0, m0), r1 = 0;
   double nbest = d0;
   int nbest_i = m0;
+  if (__ballot(kk > 32) != 0ull) {                     // a second entry in either half of the wave (wave-uniform)
+    r0 += half_rank_below<true>(m1, m0);
+    r1 = half_rank_below<true>(m0, m1) + half_rank_below<false>(m1, m1);
+    // the nearer of a lane's two entries (a lane without a second entry holds (+inf, INT_MAX) there and keeps its first)
+    const bool second = (d1 < d0) | ((d1 == d0) & (m1 < m0));
+    nbest = second ? d1 : d0;
+    nbest_i = second ? m1 : m0;
+  }
   if (a.nearest_idx) {
     // lexicographic minimum of (d2, index) over the half wave: the smallest d2 first (no NaN among confirmed
     // hits; empty slots hold +inf), then the lowest index among the lanes that attain it
-    if ((d1 < nbest) || (d1 == nbest && m1 < nbest_i)) { nbest = d1; nbest_i = m1; }
-    double dm = nbest;
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) dm = fmin(dm, __shfl_xor(dm, off));
-    int ci = (nbest == dm) ? nbest_i : kInt;
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) ci = min(ci, __shfl_xor(ci, off));
-    nbest = dm; nbest_i = ci;
+    const double dm = half_min_no_nan(nbest);
+    nbest_i = half_min((nbest == dm) ? nbest_i : kInt);
+    nbest = dm;
   }
 
   // ---- offsets of this workgroup's queries ----
   if (!a.prescattered) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) psum += __shfl_xor(psum, off);
-    if (lane == 0) sm.red[wave] = psum;
+    psum = wave_sum_last(psum);
+    if (lane == 63) sm.red[wave] = (long long)psum;
   }
   if (qv && hl == 0) {
     sm.kfull[hw] = kfull;
@@ -206,12 +189,8 @@ __global__ __launch_bounds__(kFinThreads, KSORT > kBigSort ? 2 : 8) void nn_fini
     }
     const int kf = lane < kFinQ ? sm.kfull[lane] : 0;
     const int td = lane < kFinQ ? sm.todo[lane] : 0;
-    long long v = kf;
-#pragma unroll
-    for (int off = 1; off < kFinQ; off <<= 1) {
-      const long long o = __shfl_up(v, off);
-      if (lane >= off) v += o;
-    }
+    static_assert(kFinQ == 16, "the sixteen lengths sit in one DPP row");
+    const long long v = (long long)row_incl_scan((unsigned long long)kf);
     if (lane < kFinQ) sm.off[lane] = p + v - kf;
     if (lane == kFinQ - 1) sm.off[kFinQ] = p + v;
     const unsigned long long tmb = __ballot(td != 0);
@@ -231,21 +210,32 @@ __global__ __launch_bounds__(kFinThreads, KSORT > kBigSort ? 2 : 8) void nn_fini
   {
     const long long b = qv ? sm.off[hw] : 0;
     const bool w0 = hl < kk && b + r0 < a.out_cap, w1 = hl + 32 < kk && b + r1 < a.out_cap;
-    if (w0) {
-      a.idx[b + r0] = m0;
-      a.dist[b + r0] = sqrt_rn(d0);
-      if (a.owner) a.owner[b + r0] = q;
-      if (a.hit_out) { a.hit_out[b + r0] = e0.pad & 1; a.hit_in[b + r0] = (e0.pad >> 1) & 1; }
+    // The nearest of the list is written by the lane that holds it, which has its root at hand (the indices of a
+    // list are distinct; records with the same index and d2 would write the same values).  The nearest does not
+    // depend on the caller's capacity, so the root is taken wherever there is a record.
+    const bool near = a.nearest_idx != nullptr;
+    if (hl < kk) {
+      const double s0 = sqrt_rn(d0);
+      if (w0) {
+        a.idx[b + r0] = m0;
+        a.dist[b + r0] = s0;
+        if (a.owner) a.owner[b + r0] = q;
+        if (a.hit_out) { a.hit_out[b + r0] = e0.pad & 1; a.hit_in[b + r0] = (e0.pad >> 1) & 1; }
+      }
+      if (near && m0 == nbest_i && d0 == nbest) { a.nearest_idx[q] = m0; a.nearest_dist[q] = s0; }
     }
-    if (w1) {
-      a.idx[b + r1] = m1;
-      a.dist[b + r1] = sqrt_rn(d1);
-      if (a.owner) a.owner[b + r1] = q;
-      if (a.hit_out) { a.hit_out[b + r1] = e1.pad & 1; a.hit_in[b + r1] = (e1.pad >> 1) & 1; }
+    if (hl + 32 < kk) {
+      const double s1 = sqrt_rn(d1);
+      if (w1) {
+        a.idx[b + r1] = m1;
+        a.dist[b + r1] = s1;
+        if (a.owner) a.owner[b + r1] = q;
+        if (a.hit_out) { a.hit_out[b + r1] = e1.pad & 1; a.hit_in[b + r1] = (e1.pad >> 1) & 1; }
+      }
+      if (near && m1 == nbest_i && d1 == nbest) { a.nearest_idx[q] = m1; a.nearest_dist[q] = s1; }
     }
-    if (a.nearest_idx && qv && small && hl == 0) {
-      if (kk > 0) { a.nearest_idx[q] = nbest_i; a.nearest_dist[q] = sqrt_rn(nbest); }
-      else if (a.want_nearest_fix) atomicOr(&sm.empty_mask, 1u << hw);
+    if (near && qv && small && hl == 0 && kk == 0) {
+      if (a.want_nearest_fix) atomicOr(&sm.empty_mask, 1u << hw);
       else { a.nearest_idx[q] = -1; a.nearest_dist[q] = __builtin_inf(); }
     }
   }

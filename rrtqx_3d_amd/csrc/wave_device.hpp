@@ -28,6 +28,85 @@ __device__ __forceinline__ T wave_sum(T v, int width = 64) {
   return v;
 }
 
+// ---- half waves (32 lanes = two DPP rows of 16) and waves without the LDS crossbar's address arithmetic ----
+// All lanes of the wave active.  A DPP move with bound_ctrl and full masks folds into the 32-bit VOP2 instruction that
+// uses it (v_sub_u32_dpp, v_min_i32_dpp), so such a step is one instruction where a __shfl step is a clamped lane
+// address, a ds_bpermute and a wait; a 64-bit step is two moves and the operation.
+template <int CTRL>
+__device__ __forceinline__ int dpp_move(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+constexpr int kDppRowShr = 0x110, kDppRowRor = 0x120, kDppRowBcast15 = 0x142, kDppRowBcast31 = 0x143;
+// the value of lane ^ 16: the other row of the half wave (ds_swizzle, bit mode: and 0x1f, or 0, xor 0x10)
+__device__ __forceinline__ int other_row(int v) { return __builtin_amdgcn_ds_swizzle(v, 0x401f); }
+
+// How many of the 32 keys `src` of the half wave are smaller than `mine`, for keys in [0, INT_MAX]: there
+// src - mine cannot overflow and its sign bit is the comparison, so a key costs a subtraction that reads its DPP row
+// rotation and a funnel shift that collects the sign.  SELF = false leaves the lane's own src out (src == mine).
+template <bool SELF>
+__device__ __forceinline__ int half_rank_below(int src, int mine) {
+  const int oth = other_row(src);
+  unsigned ba = 0u, bb = 0u;               // two collectors, taking turns: neither waits for its own last result
+#define RRTX_RANK_KEY(bits, o) bits = __builtin_amdgcn_alignbit(bits, (unsigned)((o) - mine), 31u);
+#define RRTX_RANK_ROT(bits, v, n) RRTX_RANK_KEY(bits, dpp_move<kDppRowRor + n>(v))
+#define RRTX_RANK_ROW(v)                                                                                              \
+  RRTX_RANK_ROT(ba, v, 1) RRTX_RANK_ROT(bb, v, 2) RRTX_RANK_ROT(ba, v, 3) RRTX_RANK_ROT(bb, v, 4)                     \
+  RRTX_RANK_ROT(ba, v, 5) RRTX_RANK_ROT(bb, v, 6) RRTX_RANK_ROT(ba, v, 7) RRTX_RANK_ROT(bb, v, 8)                     \
+  RRTX_RANK_ROT(ba, v, 9) RRTX_RANK_ROT(bb, v, 10) RRTX_RANK_ROT(ba, v, 11) RRTX_RANK_ROT(bb, v, 12)                  \
+  RRTX_RANK_ROT(ba, v, 13) RRTX_RANK_ROT(bb, v, 14) RRTX_RANK_ROT(ba, v, 15)
+  if (SELF) RRTX_RANK_KEY(bb, src)
+  RRTX_RANK_ROW(src)
+  RRTX_RANK_KEY(bb, oth)
+  RRTX_RANK_ROW(oth)
+#undef RRTX_RANK_ROW
+#undef RRTX_RANK_ROT
+#undef RRTX_RANK_KEY
+  return __popc(ba) + __popc(bb);          // 16 bits in ba, 15 or 16 in bb
+}
+
+// minimum over the half wave, in every lane of it
+__device__ __forceinline__ int half_min(int v) {
+  v = min(v, dpp_move<kDppRowRor + 1>(v));
+  v = min(v, dpp_move<kDppRowRor + 2>(v));
+  v = min(v, dpp_move<kDppRowRor + 4>(v));
+  v = min(v, dpp_move<kDppRowRor + 8>(v));
+  return min(v, other_row(v));
+}
+// ... of doubles that are never NaN (a compare and a select: fmin would canonicalise its operands first)
+template <int CTRL>
+__device__ __forceinline__ double dpp_move_d(double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = dpp_move<CTRL>((int)(b & 0xffffffffll)), hi = dpp_move<CTRL>((int)(b >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+__device__ __forceinline__ double min_no_nan(double a, double b) { return b < a ? b : a; }
+__device__ __forceinline__ double half_min_no_nan(double v) {
+  v = min_no_nan(v, dpp_move_d<kDppRowRor + 1>(v));
+  v = min_no_nan(v, dpp_move_d<kDppRowRor + 2>(v));
+  v = min_no_nan(v, dpp_move_d<kDppRowRor + 4>(v));
+  v = min_no_nan(v, dpp_move_d<kDppRowRor + 8>(v));
+  const long long b = __double_as_longlong(v);
+  const int lo = other_row((int)(b & 0xffffffffll)), hi = other_row((int)(b >> 32));
+  return min_no_nan(v, __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo));
+}
+
+// 64-bit sums by row shifts and row broadcasts (a lane without a source adds zero):
+// the inclusive scan over each row of 16 lanes, and from it the sum over the wave, valid in lane 63 only
+#define RRTX_SUM_STEP(ctrl)                                                                                           \
+  {                                                                                                                   \
+    const unsigned lo = (unsigned)dpp_move<ctrl>((int)(unsigned)(v & 0xffffffffull));                                 \
+    const unsigned hi = (unsigned)dpp_move<ctrl>((int)(unsigned)(v >> 32));                                           \
+    v += ((unsigned long long)hi << 32) | lo;                                                                         \
+  }
+__device__ __forceinline__ unsigned long long row_incl_scan(unsigned long long v) {
+  RRTX_SUM_STEP(kDppRowShr + 1) RRTX_SUM_STEP(kDppRowShr + 2) RRTX_SUM_STEP(kDppRowShr + 4) RRTX_SUM_STEP(kDppRowShr + 8)
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_last(unsigned long long v) {
+  v = row_incl_scan(v);
+  RRTX_SUM_STEP(kDppRowBcast15) RRTX_SUM_STEP(kDppRowBcast31)
+  return v;
+}
+#undef RRTX_SUM_STEP
+
 // the lanes below `lane`, and the aligned group of g lanes (a power of two) that holds `lane`, as ballot masks
 __device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 __device__ __forceinline__ unsigned long long lane_group_mask(int lane, int g) {
