@@ -880,6 +880,28 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
                        int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap, int64_t *rw_needed,
                        int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe, int64_t *offsets,
                        int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
+/* Host-pointer form for DubinsEdge (dim == 4, [x y t theta]; RRTX_E_STATE otherwise).  Defined through existing calls:
+ * rrtx_extend_candidates_dubins_dev on the staged samples into lists the context owns (word_out / word_in NULL), then
+ * rrtx_extend_select_dev over them with cost_out and cost_in as TWO arrays (cost_out decides the parent, cost_in the
+ * rewire test).  So it honours the wraps, RRTX_OPT_SPACE_HAS_TIME (a flag byte may then be 1, 2 or 3; the test stays
+ * "byte is zero"), rrtx_set_dubins_velocity and RRTX_OPT_DUBINS_TIME_COLUMN, and reads the polygon list.  Everything
+ * else is rrtx_extend_select's: lmc (NULL: the context's own array), the per-sample outputs, the rewire CSR with the
+ * two-call pattern (RRTX_E_CAPACITY with *rw_needed set, the per-sample outputs and rw_offsets valid), nq == 0, the
+ * growth of RRTX_OPT_SELECT_LIST_CAP with one more attempt.  The optional list outputs are offsets, idx, key, cost_out,
+ * cost_in, hit_out, hit_in (all or none; offsets NULL: none), as rrtx_extend_candidates_dubins would write them.
+ * nearest_idx / nearest_dist are kdFindNearest in the wrapped space (the minimum over the copies), which cannot be
+ * read off the lists: the full nearest scan is enqueued after the range search, and writes only its own search
+ * workspaces and the two per-sample columns.  Without wrapped dimensions the nearest is read off the lists and a
+ * sample with an empty ball is resolved by the same scan inside this call.  Either way the lists this call leaves are
+ * held (HOLD RULE below) whether or not the nearest was asked for; rrtx_extend_select drops them when its nearest
+ * fallback has to search.  The held lists have three cost columns (key, cost_out, cost_in):
+ * rrtx_graph_edges_append_selected links them with cost_out and cost_in. */
+int rrtx_extend_select_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, double r_min,
+                              const double *lmc, int32_t *parent_idx, int64_t *parent_entry, double *lmc_new,
+                              uint8_t *status, int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
+                              int64_t *rw_needed, int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe,
+                              int64_t *offsets, int32_t *idx, double *key, double *cost_out, double *cost_in,
+                              uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed);
 
 /* ---- the extend lists become mirror edges, on the device ------------------------ */
 /* What extend() links for a batch (R/DRRT_Q.jl:2560-2640), written into the edge mirror from the CSR lists the
@@ -913,9 +935,12 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
  * needed (that growth waits once more) and only enqueues the fill.
  * rrtx_graph_edges_append_lists: the same with host arrays (n_valid by value), staged through the path of the
  * host-pointer searches; row_first is a host array or NULL.  This is how a host-pointer caller feeds the self lists.
- * rrtx_graph_edges_append_selected: the same over the lists the last successful rrtx_extend_select left in the context
- * (always lists against the tree: idx_is_batch = 0); node_of and row_first are host arrays.  HOLD RULE: the context
- * records that it holds such lists, with their nq and count.  The record survives rrtx_nodes_append[_dev],
+ * rrtx_graph_edges_append_selected: the same over the lists the last successful rrtx_extend_select or
+ * rrtx_extend_select_dubins left in the context (always lists against the tree: idx_is_batch = 0); node_of and
+ * row_first are host arrays.  After rrtx_extend_select the one cost column serves as cost_out and cost_in; after
+ * rrtx_extend_select_dubins the held cost_out and cost_in columns are read, and the mirror is exactly what
+ * rrtx_graph_edges_append_lists of those lists gives.  HOLD RULE: the context
+ * records that it holds such lists, with their nq, their count and their cost columns (one or three).  The record survives rrtx_nodes_append[_dev],
  * rrtx_node_cost_set, every rrtx_graph_* call (rrtx_graph_edges_append_lists, which stages into the list workspaces,
  * excepted) and the getters (rrtx_sync, rrtx_get_option, rrtx_stats, rrtx_last_tile_form, the counts, the error text);
  * EVERY other entry point drops it -- the searches, the extend calls, the checks and steers, the sweeps and releases,

@@ -525,6 +525,7 @@ struct ExtendSelection
 end
 
 function extendSelect(tree::HipTree, S::TS, positions::Array{Float64,2}, hyberBallRad::Float64) where {TS}
+  tree.d == 4 && return extend_select_dubins(tree, S, positions, hyberBallRad)   # [x y t theta]: DubinsEdge
   syncObstacles(tree, S)
   nq = size(positions, 2)                     # d x nq, each sample contiguous
   pidx = Vector{Int32}(undef, nq); pentry = Vector{Int64}(undef, nq); lmcNew = Vector{Float64}(undef, nq)
@@ -970,7 +971,7 @@ function registerEdgesFromListsDev(tree::HipTree, nq::Int, offsets::Ptr{Int64}, 
   return Int(firstId[]), Int(added[])
 end
 
-# The same over the lists the last extendSelect left on the device: only nodeOf travels.  RRTX_E_STATE when another
+# The same over the lists the last extendSelect / extend_select_dubins left on the device: only nodeOf travels.  RRTX_E_STATE when another
 # call has used the lists' workspaces since (kdInsert, setNodeCosts and the edge / cost calls keep them).
 function registerSelectedEdges(tree::HipTree, nodeOf::Vector{Int32})
   nq = length(nodeOf)
@@ -1142,6 +1143,35 @@ function extend_candidates_dubins(tree::HipTree, S::TS, positions::Array{Float64
     rrtx_check(tree, rc)
     n = Int(needed[])
     return ExtendCandidatesDubins(offsets, idx[1:n], key[1:n], cout[1:n], cin[1:n], hout[1:n], hin[1:n], nidx, ndist, unsafe)
+  end
+end
+
+# extendSelect for a [x y t theta] tree: the lists of extend_candidates_dubins stay on the device, findBestParent and the
+# rewire test run there over their two cost columns (costOut for the parent, costIn for the rewire test), and
+# registerSelectedEdges then links them with both.  The polygon list and syncDubinsSpace are the caller's, as for
+# extend_candidates_dubins.  nearestIdx is kdFindNearest in the wrapped space; asking for it does not cost the held lists.
+function extend_select_dubins(tree::HipTree, S::TS, positions::Array{Float64,2}, hyberBallRad::Float64) where {TS}
+  nq = size(positions, 2)                     # 4 x nq
+  pidx = Vector{Int32}(undef, nq); pentry = Vector{Int64}(undef, nq); lmcNew = Vector{Float64}(undef, nq)
+  status = Vector{UInt8}(undef, nq); rwoff = Vector{Int64}(undef, nq + 1)
+  nidx = Vector{Int32}(undef, nq); ndist = Vector{Float64}(undef, nq); unsafe = Vector{UInt8}(undef, nq)
+  rwcap = 16 * nq
+  while true
+    rwnode = Vector{Int32}(undef, rwcap); rwval = Vector{Float64}(undef, rwcap)
+    rwneeded = Ref{Int64}(0); needed = Ref{Int64}(0)
+    rc = GC.@preserve positions pidx pentry lmcNew status rwoff rwnode rwval nidx ndist unsafe ccall((:rrtx_extend_select_dubins, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble},
+         Ptr{UInt8}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Int64, Ref{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{UInt8},
+         Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Int64, Ref{Int64}),
+        tree.ctx, positions, nq, hyberBallRad, S.robotRadius, S.minTurningRadius, C_NULL, pidx, pentry, lmcNew, status, rwoff,
+        rwnode, rwval, rwcap, rwneeded, nidx, ndist, unsafe, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, 0, needed)
+    if rc == RRTX_E_CAPACITY
+      rwcap = Int(rwneeded[])
+      continue
+    end
+    rrtx_check(tree, rc)
+    n = Int(rwneeded[])
+    return ExtendSelection(status, pidx, lmcNew, rwoff, rwnode[1:n], rwval[1:n], nidx, ndist, unsafe)
   end
 end
 

@@ -179,6 +179,9 @@ SYMBOLS = [
     ("rrtx_node_cost_set", C.c_int, [_VP, C.c_int64, _VP, C.c_int64]),
     ("rrtx_extend_select", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                      C.c_int64, c_int64_p, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, c_int64_p]),
+    ("rrtx_extend_select_dubins", C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP,
+                                            _VP, _VP, _VP, C.c_int64, c_int64_p, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                            _VP, _VP, C.c_int64, c_int64_p]),
     ("rrtx_find_new_target", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP,
                                        _VP, _VP]),
     ("rrtx_find_new_target_dubins", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_double, C.c_double, C.c_double, _VP, _VP,

@@ -439,10 +439,12 @@ class Context:
         v = f64(lmc, (-1,))
         self._check(self._lib.rrtx_node_cost_set(self._h, int(first_index), _capi._ptr(v), v.shape[0]))
 
-    def select_out_buffers(self, nq: int, rw_cap: int, register: bool = False, list_cap: int = 0) -> dict:
+    def select_out_buffers(self, nq: int, rw_cap: int, register: bool = False, list_cap: int = 0,
+                           dubins: bool = False) -> dict:
         """Output arrays for extend_select(..., out=...) that a caller keeps across calls.  register=True page-locks
         them; the context keeps them alive and unregisters them in close().  list_cap > 0 adds room for the neighbour
-        lists themselves (a planner that keeps RRT^X neighbour sets)."""
+        lists themselves (a planner that keeps RRT^X neighbour sets); dubins: the three double columns of
+        extend_select_dubins instead of the one cost column."""
         out = dict(parent_idx=np.empty(nq, dtype=np.int32), parent_entry=np.empty(nq, dtype=np.int64),
                    lmc_new=np.empty(nq, dtype=np.float64), status=np.empty(nq, dtype=np.uint8),
                    rw_offsets=np.empty(nq + 1, dtype=np.int64), rw_node=np.empty(max(rw_cap, 1), dtype=np.int32),
@@ -450,8 +452,9 @@ class Context:
                    nearest_dist=np.empty(nq, dtype=np.float64), sample_unsafe=np.empty(nq, dtype=np.uint8))
         if list_cap > 0:
             out.update(offsets=np.empty(nq + 1, dtype=np.int64), idx=np.empty(list_cap, dtype=np.int32),
-                       cost=np.empty(list_cap, dtype=np.float64), hit_out=np.empty(list_cap, dtype=np.uint8),
-                       hit_in=np.empty(list_cap, dtype=np.uint8))
+                       hit_out=np.empty(list_cap, dtype=np.uint8), hit_in=np.empty(list_cap, dtype=np.uint8))
+            out.update({k: np.empty(list_cap, dtype=np.float64)
+                        for k in (("key", "cost_out", "cost_in") if dubins else ("cost",))})
         if register:
             for a in out.values():
                 if a.nbytes:
@@ -467,6 +470,20 @@ class Context:
         out: arrays of select_out_buffers (no allocation, no growth: a count beyond their room raises
         RRTX_E_CAPACITY); otherwise the arrays are allocated here and grown on demand.  want_lists also returns
         the neighbour lists (offsets, idx, cost, hit_out, hit_in)."""
+        return self._extend_select(self._lib.rrtx_extend_select, q, (r, robot_radius), ("cost",), lmc, rw_cap, out,
+                                   want_lists, cap)
+
+    def extend_select_dubins(self, q, r: float, robot_radius: float, r_min: float, lmc=None,
+                             rw_cap: Optional[int] = None, out: Optional[dict] = None, want_lists: bool = False,
+                             cap: Optional[int] = None):
+        """rrtx_extend_select_dubins: extend_select for a dim=4 [x y t theta] context (wraps, time, the polygon list as
+        in extend_candidates_dubins).  want_lists returns offsets, idx, key, cost_out, cost_in, hit_out, hit_in.  The
+        lists stay on the device for graph_edges_append_selected, which links them with their two cost columns."""
+        return self._extend_select(self._lib.rrtx_extend_select_dubins, q, (r, robot_radius, r_min),
+                                   ("key", "cost_out", "cost_in"), lmc, rw_cap, out, want_lists, cap)
+
+    def _extend_select(self, fn, q, scalars, cols, lmc, rw_cap, out, want_lists, cap):
+        # (the two select calls differ in their scalars and in the double columns of their lists, `cols`)
         q = f64(q, (-1, self.dim))
         nq = q.shape[0]
         lmc_a = None if lmc is None else f64(lmc, (-1,))
@@ -489,17 +506,18 @@ class Context:
                     out["rw_node"] = np.empty(max(rw_cap, 1), dtype=np.int32)
                     out["rw_value"] = np.empty(max(rw_cap, 1), dtype=np.float64)
                 if want_lists and ("idx" not in out or out["idx"].shape[0] < max(cap, 1)):
-                    out.update(idx=np.empty(max(cap, 1), dtype=np.int32), cost=np.empty(max(cap, 1), dtype=np.float64),
-                               hit_out=np.empty(max(cap, 1), dtype=np.uint8), hit_in=np.empty(max(cap, 1), dtype=np.uint8))
+                    out.update(idx=np.empty(max(cap, 1), dtype=np.int32), hit_out=np.empty(max(cap, 1), dtype=np.uint8),
+                               hit_in=np.empty(max(cap, 1), dtype=np.uint8))
+                    out.update({k: np.empty(max(cap, 1), dtype=np.float64) for k in cols})
             rw_needed, needed = C.c_int64(), C.c_int64()
             g = (lambda k: _capi._ptr(out[k])) if want_lists else (lambda k: None)
-            rc = self._lib.rrtx_extend_select(
-                self._h, _capi._ptr(q), nq, r, robot_radius, _capi._ptr(lmc_a), _capi._ptr(out["parent_idx"]),
+            rc = fn(
+                self._h, _capi._ptr(q), nq, *scalars, _capi._ptr(lmc_a), _capi._ptr(out["parent_idx"]),
                 _capi._ptr(out["parent_entry"]), _capi._ptr(out["lmc_new"]), _capi._ptr(out["status"]),
                 _capi._ptr(out["rw_offsets"]), _capi._ptr(out["rw_node"]), _capi._ptr(out["rw_value"]), rw_cap,
                 C.byref(rw_needed), _capi._ptr(out["nearest_idx"]), _capi._ptr(out["nearest_dist"]),
-                _capi._ptr(out["sample_unsafe"]), g("offsets"), g("idx"), g("cost"), g("hit_out"), g("hit_in"), cap,
-                C.byref(needed))
+                _capi._ptr(out["sample_unsafe"]), g("offsets"), g("idx"), *[g(k) for k in cols], g("hit_out"), g("hit_in"),
+                cap, C.byref(needed))
             if rc != _capi.RRTX_E_CAPACITY or fixed:
                 self._check(rc)
                 break
@@ -510,8 +528,8 @@ class Context:
                                    "nearest_dist", "sample_unsafe")}
         res.update(rw_node=out["rw_node"][:nrw], rw_value=out["rw_value"][:nrw], n_neighbors=n)
         if want_lists:
-            res.update(offsets=out["offsets"], idx=out["idx"][:n], cost=out["cost"][:n], hit_out=out["hit_out"][:n],
-                       hit_in=out["hit_in"][:n])
+            res.update(offsets=out["offsets"], idx=out["idx"][:n], hit_out=out["hit_out"][:n], hit_in=out["hit_in"][:n])
+            res.update({k: out[k][:n] for k in cols})
         return res
 
     def extend_select_dev(self, nq: int, offsets_ptr: int, idx_ptr: int, cost_out_ptr: int, cost_in_ptr: int,

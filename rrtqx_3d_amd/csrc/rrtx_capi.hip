@@ -532,7 +532,7 @@ using namespace rrtx;
     hipError_t _sd = hipSetDevice((ctx)->device); \
     if (_sd != hipSuccess) return fail((ctx), RRTX_E_DEVICE, "hipSetDevice(%d): %s", (ctx)->device, hipGetErrorString(_sd)); \
   } while (0)
-// The lists rrtx_extend_select leaves for rrtx_graph_edges_append_selected live in workspaces most entry points write
+// The lists rrtx_extend_select[_dubins] leaves for rrtx_graph_edges_append_selected live in workspaces most entry points write
 // (ws_out_idx / _dist / _u8a / _u8b, ws_sel_blk), so dropping the record of them is the rule and keeping it the
 // exception: CHECK_CTX_KEEP is for the entry points that write none of those workspaces (include/rrtx.h lists them).
 #define CHECK_CTX(ctx)  \
@@ -1319,9 +1319,12 @@ int rrtx_graph_edges_append_selected(rrtx_ctx *ctx, int nq, const int32_t *node_
   RRTX_HIP(ctx, ctx->ws_link_row.ensure(sizeof(int64_t) * rows));
   const SelectBlock B{(size_t)nq};
   char *blk = ctx->ws_sel_blk.as<char>();
-  const double *cost = ctx->ws_out_dist.as<double>();
+  // (a three-column hold, rrtx_extend_select_dubins: key | cost_out | cost_in at a stride of the list capacity)
+  const bool three = ctx->sel_hold_cols == 3;
+  const double *col = ctx->ws_out_dist.as<double>();
+  const double *cost_out = three ? col + ctx->sel_list_cap : col, *cost_in = three ? col + 2 * ctx->sel_list_cap : col;
   rc = append_lists_dev(ctx, fn,
-                        LinkLists{nq, B.offsets.in(blk), ctx->ws_out_idx.as<int32_t>(), cost, cost, ctx->ws_out_u8a.as<uint8_t>(),
+                        LinkLists{nq, B.offsets.in(blk), ctx->ws_out_idx.as<int32_t>(), cost_out, cost_in, ctx->ws_out_u8a.as<uint8_t>(),
                                   ctx->ws_out_u8b.as<uint8_t>(), B.counts.in(blk), ctx->sel_list_cap,
                                   ctx->ws_link_node.as<int32_t>(), false, ctx->ws_link_row.as<int64_t>()},
                         first_id, n_added);
@@ -2548,24 +2551,52 @@ int rrtx_node_cost_set(rrtx_ctx *ctx, int64_t first_index, const double *lmc, in
   return RRTX_OK;
 }
 
-int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, const double *lmc,
-                       int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
-                       int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap, int64_t *rw_needed,
-                       int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe, int64_t *offsets,
-                       int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed) {
-  CHECK_CTX(ctx);
-  const bool want_lists = offsets != nullptr;
-  if (nq < 0 || rw_cap < 0 || !rw_offsets || (nq > 0 && (!q || !parent_idx || !parent_entry || !lmc_new || !status)) ||
-      (rw_cap > 0 && (!rw_node || !rw_value)) ||
-      (want_lists && (cap < 0 || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))))
-    return fail(ctx, RRTX_E_INVALID, "extend_select: bad arguments");
-  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_select is the SimpleEdge (dim=3) path");
+// (the lists a host-pointer select call may hand back: all or none, offsets null for none.  SimpleEdge has the one cost
+// column, given as `key`; Dubins has key, cost_out and cost_in)
+struct SelectListsOut {
+  int64_t *offsets; int32_t *idx; double *key, *cost_out, *cost_in; uint8_t *hit_out, *hit_in; int64_t cap; int64_t *needed;
+};
+// samples with an empty ball, resolved like nearest_fallback but through no entry point: the misses go up into ws_q2,
+// the full scan answers into ws_out_i32 / ws_out_f64.  Neither those nor the scan's own workspaces (ws_slots, ws_copies*,
+// ws_copy_meta, ws_scalars_nn, ws_recs, ws_partial) hold a list or the select block, so the held lists stay valid.
+static int nearest_fallback_keep(rrtx_ctx *ctx, const double *q, int nq, int dim, int32_t *nearest_idx, double *nearest_dist) {
+  std::vector<int> miss;
+  for (int i = 0; i < nq; ++i) if (nearest_idx[i] < 0) miss.push_back(i);
+  if (miss.empty() || ctx->n_nodes <= 0) return RRTX_OK;
+  const int nm = (int)miss.size();
+  std::vector<double> mq((size_t)nm * (size_t)dim);
+  for (int k = 0; k < nm; ++k) std::memcpy(&mq[(size_t)k * dim], q + (size_t)miss[k] * dim, sizeof(double) * dim);
+  std::vector<int32_t> mi((size_t)nm);
+  std::vector<double> md((size_t)nm);
+  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q2, mq.data(), sizeof(double) * mq.size()));
+  RRTX_HIP(ctx, ctx->ws_out_i32.ensure(sizeof(int32_t) * (size_t)nm));
+  RRTX_HIP(ctx, ctx->ws_out_f64.ensure(sizeof(double) * (size_t)nm));
+  int rc = launch_nn_nearest(ctx, ctx->ws_q2.as<double>(), nm, ctx->ws_out_i32.as<int32_t>(), ctx->ws_out_f64.as<double>());
+  if (rc) return rc;
+  RRTX_HIP(ctx, copy_out(ctx, mi.data(), ctx->ws_out_i32.p, sizeof(int32_t) * (size_t)nm));
+  RRTX_HIP(ctx, copy_out(ctx, md.data(), ctx->ws_out_f64.p, sizeof(double) * (size_t)nm));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < nm; ++k) { nearest_idx[miss[k]] = mi[k]; nearest_dist[miss[k]] = md[k]; }
+  return RRTX_OK;
+}
+
+// The body rrtx_extend_select and rrtx_extend_select_dubins share: the extend preamble into lists the context owns,
+// the selection over them, the per-sample block down in one transfer, then the rewire lists and (asked for) the
+// neighbour lists.  dubins: three double columns key | cost_out | cost_in at a stride of the list capacity in
+// ws_out_dist, as find_new_target lays them out; else the one column.  On success the context holds the lists.
+static int extend_select_host(rrtx_ctx *ctx, const char *fn, bool dubins, const double *q, int nq, double r, double robot_radius,
+                              double r_min, const double *lmc, int32_t *parent_idx, int64_t *parent_entry, double *lmc_new,
+                              uint8_t *status, int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
+                              int64_t *rw_needed, int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe,
+                              const SelectListsOut &out) {
+  const bool want_lists = out.offsets != nullptr;
+  const int cols = dubins ? 3 : 1;
   if (nq == 0) {
     rw_offsets[0] = 0;
     if (rw_needed) *rw_needed = 0;
-    if (want_lists) offsets[0] = 0;
-    if (needed) *needed = 0;
-    ctx->sel_hold_nq = 0; ctx->sel_hold_count = 0;
+    if (want_lists) out.offsets[0] = 0;
+    if (out.needed) *out.needed = 0;
+    ctx->sel_hold_nq = 0; ctx->sel_hold_count = 0; ctx->sel_hold_cols = cols;
     return RRTX_OK;
   }
   // Everything that is per sample sits in ONE device block (SelectBlock), so that it leaves in one transfer: without
@@ -2575,7 +2606,7 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
   const size_t out_bytes = want_lists ? B.bytes : B.bytes_without_lists;
   const size_t q_bytes = sizeof(double) * n * (size_t)ctx->dim;
   const size_t staged = (256u << 10) + 64;   // what d2h may take per small output array
-  int rc = arena_begin(ctx, out_bytes + q_bytes + lmc_arena_need(ctx, lmc) + 6 * staged + 512);
+  int rc = arena_begin(ctx, out_bytes + q_bytes + lmc_arena_need(ctx, lmc) + (size_t)(5 + cols) * staged + 512);
   if (rc) return rc;
   if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
   Lmc lmc_dev;
@@ -2585,15 +2616,23 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
   RRTX_HIP(ctx, ctx->ws_sel_rwv.ensure(sizeof(double) * (size_t)(rw_cap > 0 ? rw_cap : 1)));
   char *blk = ctx->ws_sel_blk.as<char>();
   char *host_blk = arena_take(ctx, out_bytes);
-  if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "extend_select: staging arena");
+  if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "%s: staging arena", fn);
   const bool want_nearest = nearest_idx && nearest_dist;
-  rc = with_neighbour_lists(ctx, "extend_select", nq, 0, 1, false, host_blk, blk, out_bytes, [&](const NeighbourLists &L) {
-    int rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, B.offsets.in(blk), L.idx, L.key,
-                                        L.hit_out, L.hit_in, L.cap, B.counts.in(blk),
-                                        want_nearest ? B.nearest_idx.in(blk) : nullptr,
-                                        want_nearest ? B.nearest_dist.in(blk) : nullptr, B.sample_unsafe.in(blk));
+  rc = with_neighbour_lists(ctx, fn, nq, 0, cols, dubins, host_blk, blk, out_bytes, [&](const NeighbourLists &L) {
+    const double *co = dubins ? L.key + L.cap : L.key, *ci = dubins ? L.key + 2 * L.cap : L.key;
+    int32_t *ni = want_nearest ? B.nearest_idx.in(blk) : nullptr;
+    double *nd = want_nearest ? B.nearest_dist.in(blk) : nullptr;
+    // (in a wrapped Dubins space the preamble ends with the full nearest scan: it writes the two columns of the select
+    // block and its own search workspaces, never a list)
+    int rc = dubins ? rrtx_extend_candidates_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, r_min,
+                                                        B.offsets.in(blk), L.idx, L.key, L.key + L.cap, L.key + 2 * L.cap,
+                                                        nullptr, nullptr, L.hit_out, L.hit_in, L.cap, B.counts.in(blk), ni, nd,
+                                                        B.sample_unsafe.in(blk))
+                    : rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, B.offsets.in(blk), L.idx,
+                                                 L.key, L.hit_out, L.hit_in, L.cap, B.counts.in(blk), ni, nd,
+                                                 B.sample_unsafe.in(blk));
     if (rc) return rc;
-    return select_over_lists(ctx, nq, B.offsets.in(blk), L.idx, L.key, L.key, L.hit_out, L.hit_in, B.counts.in(blk), L.cap,
+    return select_over_lists(ctx, nq, B.offsets.in(blk), L.idx, co, ci, L.hit_out, L.hit_in, B.counts.in(blk), L.cap,
                              B.sample_unsafe.in(blk), lmc_dev, B.parent_idx.in(blk), B.parent_entry.in(blk),
                              B.lmc_new.in(blk), B.status.in(blk), B.rw_offsets.in(blk), ctx->ws_sel_rwn.as<int32_t>(),
                              ctx->ws_sel_rwv.as<double>(), rw_cap, B.counts.in(blk) + 1);
@@ -2610,28 +2649,72 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
     B.nearest_dist.to(nearest_dist, host_blk);
     B.nearest_idx.to(nearest_idx, host_blk);
   }
-  if (want_lists) B.offsets.to(offsets, host_blk);
-  if (needed) *needed = total;
-  if ((rc = check_capacity(ctx, "extend_select", "rewire entries", rw_total, rw_cap, rw_needed))) return rc;
-  if (want_lists && (rc = check_capacity(ctx, "extend_select", "neighbours", total, cap, needed))) return rc;
+  if (want_lists) B.offsets.to(out.offsets, host_blk);
+  if (out.needed) *out.needed = total;
+  if ((rc = check_capacity(ctx, fn, "rewire entries", rw_total, rw_cap, rw_needed))) return rc;
+  if (want_lists && (rc = check_capacity(ctx, fn, "neighbours", total, out.cap, out.needed))) return rc;
   if (rw_total > 0) {
     if ((rc = d2h(ctx, rw_value, ctx->ws_sel_rwv.p, sizeof(double) * (size_t)rw_total))) return rc;
     if ((rc = d2h(ctx, rw_node, ctx->ws_sel_rwn.p, sizeof(int32_t) * (size_t)rw_total))) return rc;
   }
   if (want_lists && total > 0) {
-    if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)total))) return rc;
-    if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
-    if ((rc = d2h(ctx, hit_out, ctx->ws_out_u8a.p, (size_t)total))) return rc;
-    if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
+    const double *col = ctx->ws_out_dist.as<double>();
+    const size_t stride = (size_t)ctx->sel_list_cap;
+    if ((rc = d2h(ctx, out.key, col, sizeof(double) * (size_t)total))) return rc;
+    if (dubins) {
+      if ((rc = d2h(ctx, out.cost_out, col + stride, sizeof(double) * (size_t)total))) return rc;
+      if ((rc = d2h(ctx, out.cost_in, col + 2 * stride, sizeof(double) * (size_t)total))) return rc;
+    }
+    if ((rc = d2h(ctx, out.idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
+    if ((rc = d2h(ctx, out.hit_out, ctx->ws_out_u8a.p, (size_t)total))) return rc;
+    if ((rc = d2h(ctx, out.hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
   }
   if (rw_total > 0 || (want_lists && total > 0)) {
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     arena_flush(ctx);
   }
-  // the lists stay for rrtx_graph_edges_append_selected (a nearest fallback that has to search drops the record again:
-  // rrtx_nn_nearest writes their workspaces)
-  ctx->sel_hold_nq = nq; ctx->sel_hold_count = total;
-  return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
+  // Dubins without wrapped dimensions reads the nearest off the lists like SimpleEdge; its empty balls are resolved
+  // here, before the record is set and through no entry point, so the hold is valid whatever the caller asked for
+  if (dubins && want_nearest && (rc = nearest_fallback_keep(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist))) return rc;
+  // the lists stay for rrtx_graph_edges_append_selected (the SimpleEdge nearest fallback, when it has to search, drops
+  // the record again: rrtx_nn_nearest writes their workspaces)
+  ctx->sel_hold_nq = nq; ctx->sel_hold_count = total; ctx->sel_hold_cols = cols;
+  return want_nearest && !dubins ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
+}
+
+int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, const double *lmc,
+                       int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
+                       int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap, int64_t *rw_needed,
+                       int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe, int64_t *offsets,
+                       int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed) {
+  CHECK_CTX(ctx);
+  const bool want_lists = offsets != nullptr;
+  if (nq < 0 || rw_cap < 0 || !rw_offsets || (nq > 0 && (!q || !parent_idx || !parent_entry || !lmc_new || !status)) ||
+      (rw_cap > 0 && (!rw_node || !rw_value)) ||
+      (want_lists && (cap < 0 || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))))
+    return fail(ctx, RRTX_E_INVALID, "extend_select: bad arguments");
+  if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_select is the SimpleEdge (dim=3) path");
+  return extend_select_host(ctx, "extend_select", false, q, nq, r, robot_radius, 0.0, lmc, parent_idx, parent_entry, lmc_new,
+                            status, rw_offsets, rw_node, rw_value, rw_cap, rw_needed, nearest_idx, nearest_dist, sample_unsafe,
+                            SelectListsOut{offsets, idx, cost, nullptr, nullptr, hit_out, hit_in, cap, needed});
+}
+
+int rrtx_extend_select_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, double r_min,
+                              const double *lmc, int32_t *parent_idx, int64_t *parent_entry, double *lmc_new,
+                              uint8_t *status, int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
+                              int64_t *rw_needed, int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe,
+                              int64_t *offsets, int32_t *idx, double *key, double *cost_out, double *cost_in,
+                              uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed) {
+  CHECK_CTX(ctx);
+  const bool want_lists = offsets != nullptr;
+  if (nq < 0 || rw_cap < 0 || !rw_offsets || (nq > 0 && (!q || !parent_idx || !parent_entry || !lmc_new || !status)) ||
+      (rw_cap > 0 && (!rw_node || !rw_value)) ||
+      (want_lists && (cap < 0 || (cap > 0 && (!idx || !key || !cost_out || !cost_in || !hit_out || !hit_in)))))
+    return fail(ctx, RRTX_E_INVALID, "extend_select_dubins: bad arguments");
+  if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "extend_select_dubins needs a dim=4 [x y t theta] context");
+  return extend_select_host(ctx, "extend_select_dubins", true, q, nq, r, robot_radius, r_min, lmc, parent_idx, parent_entry,
+                            lmc_new, status, rw_offsets, rw_node, rw_value, rw_cap, rw_needed, nearest_idx, nearest_dist,
+                            sample_unsafe, SelectListsOut{offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap, needed});
 }
 
 // ---- findNewTarget over a batch of poses (kernels_target.hip) ---------------------------------------

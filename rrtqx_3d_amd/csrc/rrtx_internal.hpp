@@ -276,11 +276,12 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_sel_blk;          // rrtx_extend_select: everything that is per sample, one block (SelectBlock, rrtx_capi.hip)
   rrtx::DevBuf ws_sel_rwn, ws_sel_rwv, ws_sel_lmc;   // ... its rewire lists and a caller-given rrtLMC array
   int64_t sel_list_cap = 0;         // ... entries its neighbour lists have room for
-  // the lists the last successful rrtx_extend_select left in ws_out_idx / _dist / _u8a / _u8b and ws_sel_blk, for
+  // the lists the last successful rrtx_extend_select[_dubins] left in ws_out_idx / _dist / _u8a / _u8b and ws_sel_blk, for
   // rrtx_graph_edges_append_selected: its nq (-1: no such lists; every entry point that writes those workspaces drops
   // the record, CHECK_CTX in rrtx_capi.hip) and its entry count
   int sel_hold_nq = -1;
   int64_t sel_hold_count = 0;
+  int sel_hold_cols = 1;            // ... 1: the one SimpleEdge cost column; 3: key | cost_out | cost_in (rrtx_extend_select_dubins)
 
   // neighbour lists -> mirror edges (kernels_link.hip): edges per row, their scan, {entries, edges, verdict}, the
   // staged node_of, and what rrtx_graph_edges_get gathers into

@@ -689,6 +689,21 @@ def extend_select(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, 
     return out
 
 
+def extend_select_dubins(tree: HipTree, S: CSpace, newPositions, hyberBallRad_: float, lmc=None, wantLists: bool = False):
+    """extend_select for Edge = DubinsEdge: the lists of extend_candidates_dubins (wrapped space, polygon list,
+    S.minTurningRadius, S.robotRadius, S.spaceHasTime) stay on the device, findBestParent and the rewire test run over
+    their two cost columns there, and registerSelectedEdges then links them.  Returns the dict of extend_select;
+    wantLists adds offsets, idx, key, cost_out, cost_in, hit_out, hit_in.  A sample with an empty ball keeps status
+    RRTX_SEL_EMPTY: the closestNode rule stays with the caller, who has nearest_idx / nearest_dist (the nearest in the
+    wrapped space) and extend_closest_self_dubins for it."""
+    if S.inWarmupTime:
+        error("extend_select_dubins checks obstacles; during warm-up use extend_candidates_dubins")
+    _dubins_space(tree, S, "extend_select_dubins")
+    q = np.asarray(newPositions, dtype=np.float64).reshape(-1, 4)
+    return tree.ctx.extend_select_dubins(q, float(hyberBallRad_), S.robotRadius, S.minTurningRadius, lmc=lmc,
+                                         want_lists=wantLists)
+
+
 class RobotData:
     """The fields of RobotData{T} that findNewTarget reads and writes (R/DRRT_data_structures.jl)."""
 
