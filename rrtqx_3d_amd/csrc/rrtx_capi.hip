@@ -336,11 +336,15 @@ static char *arena_take(rrtx_ctx *ctx, size_t bytes) {
 // Only SMALL results are staged (a 16 KB pageable destination costs a driver-side bounce of its own, ~35 us against
 // ~20 us pinned): measured on the MI355X box (tools/pcie_probe.py), a pageable destination of a megabyte or more
 // receives its DMA at the same ~50 GB/s as a pinned one, while a staged copy has to be read back from DRAM by one host
-// thread at a third of that.
+// thread at a third of that.  An output the caller did not ask for (null) or an empty one is skipped.
+constexpr size_t kSmallIn = 1u << 20, kSmallOut = 256u << 10;
+// what stage_in_small / d2h take from the arena for an array of that size (a call's reservation is the sum of these)
+size_t small_in(size_t bytes) { return bytes <= kSmallIn ? bytes + 64 : 0; }
+size_t small_out(size_t bytes) { return bytes <= kSmallOut ? bytes + 64 : 0; }
 static int d2h(rrtx_ctx *ctx, void *dst, const void *src_dev, size_t bytes) {
-  if (!bytes) return RRTX_OK;
+  if (!dst || !bytes) return RRTX_OK;
   void *to = dst;
-  if (bytes <= (256u << 10) && !host_registered(ctx, dst, bytes)) {
+  if (bytes <= kSmallOut && !host_registered(ctx, dst, bytes)) {
     char *a = arena_take(ctx, bytes);
     if (a) { to = a; ctx->h_pending.push_back({dst, a, bytes}); }
   }
@@ -399,7 +403,7 @@ static int stage_in_small(rrtx_ctx *ctx, DevBuf &buf, const void *host, size_t b
   RRTX_HIP(ctx, buf.ensure(bytes ? bytes : 8));
   if (!bytes) return RRTX_OK;
   const void *from = host;
-  if (bytes <= (1u << 20) && !host_registered(ctx, host, bytes)) {
+  if (bytes <= kSmallIn && !host_registered(ctx, host, bytes)) {
     char *a = arena_take(ctx, bytes);
     if (a) { std::memcpy(a, host, bytes); from = a; }
   }
@@ -415,7 +419,8 @@ struct Field {
   size_t off, count;
   T *in(void *base) const { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
   size_t bytes() const { return sizeof(T) * count; }
-  void to(T *dst, void *base) const { std::memcpy(dst, in(base), bytes()); }
+  void to(T *dst, void *base) const { if (dst) std::memcpy(dst, in(base), bytes()); }          // (null: not asked for)
+  void from(const T *src, void *base) const { if (src) std::memcpy(in(base), src, bytes()); }  // (null: not given)
 };
 // `n` elements of T appended to a block of `bytes` bytes, at T's own alignment unless one is given
 template <class T>
@@ -427,12 +432,31 @@ Field<T> take(size_t &bytes, size_t n, size_t align = alignof(T)) {
 }
 // (a block is made from its sample count alone, B{n}: the fields are then initialised in the order they are declared,
 // which is the layout, and `bytes` grows with them to the size of the block)
-struct CandidatesBlock {            // rrtx_extend_candidates
+struct CandidatesBlock {            // rrtx_extend_candidates[_dubins]; the _self calls: its CSR prefix alone
   size_t n, bytes = 0;
   Field<int64_t> offsets = take<int64_t>(bytes, n + 1), count = take<int64_t>(bytes, 1);
+  size_t csr_bytes = bytes;
   Field<double> nearest_dist = take<double>(bytes, n);
   Field<int32_t> nearest_idx = take<int32_t>(bytes, n);
   Field<uint8_t> sample_unsafe = take<uint8_t>(bytes, n);
+};
+struct ClosestInBlock {             // rrtx_extend_closest_self[_dubins]: what goes up beside the samples
+  size_t n, bytes = 0;
+  Field<int32_t> tree_idx = take<int32_t>(bytes, n);
+  Field<uint8_t> skip = take<uint8_t>(bytes, n), want = take<uint8_t>(bytes, n);
+};
+struct ClosestBlock {               // rrtx_extend_closest_self: per sample, the row length and the tree column
+  size_t n, bytes = 0;
+  Field<int32_t> count = take<int32_t>(bytes, n);
+  Field<uint8_t> tree_hit_out = take<uint8_t>(bytes, n), tree_hit_in = take<uint8_t>(bytes, n);
+};
+constexpr size_t kWordBytes = 3;    // a Dubins word: three bytes an edge
+struct ClosestDubinsBlock {         // rrtx_extend_closest_self_dubins: the same, the tree column with costs and words
+  size_t n, bytes = 0;
+  Field<double> tree_cost_out = take<double>(bytes, n), tree_cost_in = take<double>(bytes, n);
+  Field<int32_t> count = take<int32_t>(bytes, n);
+  Field<uint8_t> tree_word_out = take<uint8_t>(bytes, kWordBytes * n), tree_word_in = take<uint8_t>(bytes, kWordBytes * n);
+  Field<uint8_t> tree_hit_out = take<uint8_t>(bytes, n), tree_hit_in = take<uint8_t>(bytes, n);
 };
 struct SelectBlock {                // rrtx_extend_select
   size_t n, bytes = 0;
@@ -459,6 +483,25 @@ struct TargetResultBlock {          // find_new_target: what leaves at the end, 
   Field<int32_t> pending = take<int32_t>(bytes, n, 8);
   Field<int64_t> hdr = take<int64_t>(bytes, 3, 8);              // TargetRound::hdr
 };
+// The first `bytes` of a device block on their way down into the pinned arena (queued; after arena_begin, which has
+// reserved block_need(bytes) for it): *host = where the fields are read once the stream has been waited for.
+size_t block_need(size_t bytes) { return bytes + 64; }
+int block_down(rrtx_ctx *ctx, const char *fn, const void *dev, size_t bytes, char **host) {
+  if (!(*host = arena_take(ctx, bytes))) return fail(ctx, RRTX_E_NOMEM, "%s: staging arena", fn);
+  RRTX_HIP(ctx, hipMemcpyAsync(*host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return RRTX_OK;
+}
+// skip, want and tree_idx of a closest call (null: the field stays as it is) gathered in the arena and sent up to ws_q2
+// in one transfer (after arena_begin, which has reserved block_need(I.bytes) for it)
+int closest_inputs_up(rrtx_ctx *ctx, const char *fn, const ClosestInBlock &I, const uint8_t *skip, const uint8_t *want,
+                      const int32_t *tree_idx) {
+  RRTX_HIP(ctx, ctx->ws_q2.ensure(I.bytes));
+  char *up = arena_take(ctx, I.bytes);
+  if (!up) return fail(ctx, RRTX_E_NOMEM, "%s: staging arena", fn);
+  I.tree_idx.from(tree_idx, up); I.skip.from(skip, up); I.want.from(want, up);
+  RRTX_HIP(ctx, hipMemcpyAsync(ctx->ws_q2.p, up, I.bytes, hipMemcpyHostToDevice, ctx->stream));
+  return RRTX_OK;
+}
 
 // thr_first_ge / thr_first_gt of per-query radii r[i * r_stride] (a run of equal radii is worked out once)
 void fill_thresholds(const double *r, int r_stride, int nq, double *lt, double *gt) {
@@ -475,8 +518,7 @@ void fill_thresholds(const double *r, int r_stride, int nq, double *lt, double *
 // takes from the arena for an array of that size).
 struct Lmc { const double *dev; int64_t n; };
 size_t lmc_arena_need(const rrtx_ctx *ctx, const double *lmc_host) {
-  const size_t bytes = lmc_host ? sizeof(double) * (size_t)ctx->n_nodes : 0;
-  return bytes <= (1u << 20) ? bytes : 0;
+  return lmc_host ? small_in(sizeof(double) * (size_t)ctx->n_nodes) : 0;
 }
 int resolve_lmc(rrtx_ctx *ctx, const double *lmc_host, Lmc *lmc) {
   int rc = lmc_host ? stage_in_small(ctx, ctx->ws_sel_lmc, lmc_host, sizeof(double) * (size_t)ctx->n_nodes) : node_cost_ensure(ctx);
@@ -484,28 +526,81 @@ int resolve_lmc(rrtx_ctx *ctx, const double *lmc_host, Lmc *lmc) {
   return rc;
 }
 
-// The neighbour lists of rrtx_extend_select and find_new_target stay on the device, in ws_out_idx / _dist / _u8a / _u8b
-// (and ws_owner).  Their capacity is the context's business: sized once from what the last search produced, and when an
-// attempt produces more, grown to that with an eighth of headroom and the attempt made once more.  `attempt` enqueues
-// the search and what follows it over lists of L.cap entries; the `bytes` at `dev`, which begin with the int64 count of
-// entries the search produced, are then read back into the arena at `host`.
-struct NeighbourLists { int32_t *idx, *owner; double *key; uint8_t *hit_out, *hit_in; int64_t cap; };
+// The neighbour lists of a call on the device, `cap` entries a column (the closest calls: nq * k slots).  Here and
+// nowhere else is it written which workspace holds which column: idx in ws_out_idx, owner in ws_owner, the double
+// columns one after the other in ws_out_dist, the flag bytes out / in in ws_out_u8a / _u8b with the words behind them.
+// cols = 1: SimpleEdge's one cost column, which is key, cost_out and cost_in alike; cols = 3: the Dubins key | cost_out |
+// cost_in.  words: the Dubins word columns (null without).  The addresses are taken after every ensure; lists that are
+// held (sel_hold_*) are found again with the arguments they were made with, which then ensure nothing anew.
+struct NeighbourLists {
+  int32_t *idx, *owner; double *key, *cost_out, *cost_in; uint8_t *word_out, *word_in, *hit_out, *hit_in; int64_t cap;
+};
+int neighbour_lists(rrtx_ctx *ctx, int64_t cap, int cols, bool words, NeighbourLists *L) {
+  const size_t n = (size_t)std::max<int64_t>(cap, 1);
+  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * n));
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * n));
+  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)cols * n));
+  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((words ? 1 + kWordBytes : 1) * n));
+  RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((words ? 1 + kWordBytes : 1) * n));
+  double *key = ctx->ws_out_dist.as<double>();
+  uint8_t *out = ctx->ws_out_u8a.as<uint8_t>(), *in = ctx->ws_out_u8b.as<uint8_t>();
+  *L = NeighbourLists{ctx->ws_out_idx.as<int32_t>(), ctx->ws_owner.as<int32_t>(), key, cols == 3 ? key + n : key,
+                      cols == 3 ? key + 2 * n : key, words ? out + n : nullptr, words ? in + n : nullptr, out, in, cap};
+  return RRTX_OK;
+}
+// the caller's arrays for the columns of a call's lists (null: not asked for, or the call has no such column)
+struct ListsOut { int32_t *idx; double *key, *cost_out, *cost_in; uint8_t *word_out, *word_in, *hit_out, *hit_in; };
+// fn(caller's array, device column, bytes an entry) for every column
+template <class Fn>
+int each_column_out(const NeighbourLists &L, const ListsOut &to, Fn fn) {
+  int rc = fn(to.key, L.key, sizeof(double));
+  if (!rc) rc = fn(to.cost_out, L.cost_out, sizeof(double));
+  if (!rc) rc = fn(to.cost_in, L.cost_in, sizeof(double));
+  if (!rc) rc = fn(to.idx, L.idx, sizeof(int32_t));
+  if (!rc) rc = fn(to.word_out, L.word_out, kWordBytes);
+  if (!rc) rc = fn(to.word_in, L.word_in, kWordBytes);
+  if (!rc) rc = fn(to.hit_out, L.hit_out, 1);
+  return rc ? rc : fn(to.hit_in, L.hit_in, 1);
+}
+// the first n entries of the columns the caller asked for, queued (d2h skips a null array)
+int lists_down(rrtx_ctx *ctx, const NeighbourLists &L, int64_t n, const ListsOut &to) {
+  return each_column_out(L, to, [&](void *dst, const void *src, size_t entry) { return d2h(ctx, dst, src, entry * (size_t)n); });
+}
+// what d2h may take from the arena for up to `cap` entries of `entry` bytes, ...
+size_t out_need(const void *dst, size_t entry, int64_t cap) {
+  return !dst ? 0 : small_out((size_t)cap > kSmallOut / entry ? kSmallOut : entry * (size_t)cap);
+}
+// ... and for the lists of a call
+size_t lists_need(const ListsOut &to, int64_t cap) {
+  size_t need = 0;
+  each_column_out(NeighbourLists{}, to, [&](const void *dst, const void *, size_t entry) { need += out_need(dst, entry, cap); return 0; });
+  return need;
+}
+// the end of a call that queued n entries or slots: the transfers waited for, the staged ones copied to the caller
+int lists_finish(rrtx_ctx *ctx, int64_t n) {
+  if (n <= 0) return RRTX_OK;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  arena_flush(ctx);
+  return RRTX_OK;
+}
+
+// The lists of rrtx_extend_select and find_new_target stay on the device.  Their capacity is the context's business:
+// sized once from what the last search produced, and when an attempt produces more, grown to that with an eighth of
+// headroom and the attempt made once more.  `attempt` enqueues the search and what follows it over lists of L.cap
+// entries; the `bytes` at `dev`, which begin with the int64 count of entries the search produced, are then read back
+// into the arena at `host`.
 template <class Attempt>
-int with_neighbour_lists(rrtx_ctx *ctx, const char *fn, int nq, int64_t at_least, int key_arrays, bool want_owner, void *host,
-                         const void *dev, size_t bytes, Attempt attempt) {
+int with_neighbour_lists(rrtx_ctx *ctx, const char *fn, int nq, int64_t at_least, int cols, void *host, const void *dev,
+                         size_t bytes, Attempt attempt) {
   int64_t cap = ctx->sel_list_cap > 0 ? ctx->sel_list_cap
                                       : std::max<int64_t>(ctx->last_neighbors + ctx->last_neighbors / 8, std::max<int64_t>(64 * (int64_t)nq, 1024));
   cap = std::max(cap, at_least);
   for (int again = 0;; ++again) {
-    RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)cap));
-    RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)key_arrays * (size_t)cap));   // Dubins: key, cost_out, cost_in
-    RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)cap));
-    RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)cap));
-    if (want_owner) RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)cap));
+    NeighbourLists L;
+    int rc = neighbour_lists(ctx, cap, cols, false, &L);
+    if (rc) return rc;
     ctx->sel_list_cap = cap;
-    const NeighbourLists L = {ctx->ws_out_idx.as<int32_t>(), ctx->ws_owner.as<int32_t>(), ctx->ws_out_dist.as<double>(),
-                              ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(), cap};
-    int rc = attempt(L);
+    rc = attempt(L);
     if (rc) return rc;
     RRTX_HIP(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
     RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1238,10 +1333,6 @@ int append_lists_dev(rrtx_ctx *ctx, const char *fn, LinkLists L, int64_t *first_
   if (n_added) *n_added = total;
   return RRTX_OK;
 }
-
-// what stage_in_small / d2h take from the arena for an array of that size
-size_t small_in(size_t bytes) { return bytes <= (1u << 20) ? bytes + 64 : 0; }
-size_t small_out(size_t bytes) { return bytes <= (256u << 10) ? bytes + 64 : 0; }
 }  // namespace
 
 int rrtx_graph_edges_append_lists_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx,
@@ -1319,14 +1410,11 @@ int rrtx_graph_edges_append_selected(rrtx_ctx *ctx, int nq, const int32_t *node_
   RRTX_HIP(ctx, ctx->ws_link_row.ensure(sizeof(int64_t) * rows));
   const SelectBlock B{(size_t)nq};
   char *blk = ctx->ws_sel_blk.as<char>();
-  // (a three-column hold, rrtx_extend_select_dubins: key | cost_out | cost_in at a stride of the list capacity)
-  const bool three = ctx->sel_hold_cols == 3;
-  const double *col = ctx->ws_out_dist.as<double>();
-  const double *cost_out = three ? col + ctx->sel_list_cap : col, *cost_in = three ? col + 2 * ctx->sel_list_cap : col;
+  NeighbourLists L;      // the held lists, as the select call made them
+  if ((rc = neighbour_lists(ctx, ctx->sel_list_cap, ctx->sel_hold_cols, false, &L))) return rc;
   rc = append_lists_dev(ctx, fn,
-                        LinkLists{nq, B.offsets.in(blk), ctx->ws_out_idx.as<int32_t>(), cost_out, cost_in, ctx->ws_out_u8a.as<uint8_t>(),
-                                  ctx->ws_out_u8b.as<uint8_t>(), B.counts.in(blk), ctx->sel_list_cap,
-                                  ctx->ws_link_node.as<int32_t>(), false, ctx->ws_link_row.as<int64_t>()},
+                        LinkLists{nq, B.offsets.in(blk), L.idx, L.cost_out, L.cost_in, L.hit_out, L.hit_in, B.counts.in(blk),
+                                  L.cap, ctx->ws_link_node.as<int32_t>(), false, ctx->ws_link_row.as<int64_t>()},
                         first_id, n_added);
   if (rc) return rc;
   if (row_first && (rc = d2h(ctx, row_first, ctx->ws_link_row.p, sizeof(int64_t) * rows))) return rc;
@@ -1987,11 +2075,20 @@ int rrtx_detmath_eval(rrtx_ctx *ctx, int op, const double *x, const double *y, i
 }
 
 // ---- fused extend() preamble ------------------------------------------------------------------
+// what every call of the family that returns a CSR refuses first; lists: every per-entry array it requires is given
+static int extend_csr_args(rrtx_ctx *ctx, const char *fn, const double *q, int nq, const int64_t *offsets, int64_t cap, bool lists) {
+  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && !lists)) return fail(ctx, RRTX_E_INVALID, "%s: bad arguments", fn);
+  return RRTX_OK;
+}
+// ... and what its host form answers for an empty batch
+static int extend_empty(int64_t *offsets, int64_t *needed) {
+  if (needed) *needed = 0;
+  if (offsets) offsets[0] = 0;
+  return RRTX_OK;
+}
 static int extend_candidates_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,
                                   const double *cost, const uint8_t *hit_out, const uint8_t *hit_in, int64_t cap) {
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))
-    return fail(ctx, RRTX_E_INVALID, "extend_candidates: bad arguments");
-  return RRTX_OK;
+  return extend_csr_args(ctx, "extend_candidates", q, nq, offsets, cap, idx && cost && hit_out && hit_in);
 }
 
 int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
@@ -2036,69 +2133,76 @@ int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r,
                                 hit_in, (r >= 0.0) ? r : -1.0, sample_unsafe);
 }
 
+// The host form of the calls that return a CSR, after their own refusals.  Everything that is per sample sits in ONE small
+// device block (CandidatesBlock), so that it leaves in one transfer; the per-entry arrays follow once the count is known.
+// Small transfers go through the context's pinned arena, large ones straight to the caller.  self: the _self calls, which
+// take skip and have the CSR prefix of the block alone; dubins: three double columns and the words.
+static int extend_csr_host(rrtx_ctx *ctx, const char *fn, bool self, bool dubins, const double *q, int nq, double r,
+                           double robot_radius, double r_min, const uint8_t *skip, int64_t *offsets, const ListsOut &to, int64_t cap,
+                           int64_t *needed, int32_t *nearest_idx = nullptr, double *nearest_dist = nullptr,
+                           uint8_t *sample_unsafe = nullptr) {
+  if (nq == 0) return extend_empty(offsets, needed);
+  const CandidatesBlock B{(size_t)nq};
+  const size_t blk_bytes = self ? B.csr_bytes : B.bytes;
+  const size_t q_bytes = sizeof(double) * (size_t)nq * ctx->dim, skip_bytes = skip ? (size_t)nq : 0;
+  NeighbourLists L;
+  int rc = neighbour_lists(ctx, cap, dubins ? 3 : 1, dubins, &L);
+  if (rc) return rc;
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(blk_bytes));
+  if ((rc = arena_begin(ctx, small_in(q_bytes) + small_in(skip_bytes) + block_need(blk_bytes) + lists_need(to, cap)))) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
+  if (skip && (rc = stage_in_small(ctx, ctx->ws_q2, skip, skip_bytes))) return rc;
+  const double *q_dev = ctx->ws_q.as<double>();
+  const uint8_t *skip_dev = skip ? ctx->ws_q2.as<uint8_t>() : nullptr;
+  char *blk = ctx->ws_out_off.as<char>(), *host_blk;
+  const bool want_nearest = nearest_idx && nearest_dist;
+  if (!self)
+    rc = rrtx_extend_candidates_dev(ctx, q_dev, nq, r, robot_radius, B.offsets.in(blk), L.idx, L.key, L.hit_out, L.hit_in, cap,
+                                    B.count.in(blk), want_nearest ? B.nearest_idx.in(blk) : nullptr,
+                                    want_nearest ? B.nearest_dist.in(blk) : nullptr,
+                                    sample_unsafe ? B.sample_unsafe.in(blk) : nullptr);
+  else if (dubins)
+    rc = rrtx_extend_candidates_self_dubins_dev(ctx, q_dev, nq, r, robot_radius, r_min, skip_dev, B.offsets.in(blk), L.idx, L.key,
+                                                L.cost_out, L.cost_in, L.word_out, L.word_in, L.hit_out, L.hit_in, cap,
+                                                B.count.in(blk));
+  else
+    rc = rrtx_extend_candidates_self_dev(ctx, q_dev, nq, r, robot_radius, skip_dev, B.offsets.in(blk), L.idx, L.key, L.hit_out,
+                                         L.hit_in, cap, B.count.in(blk));
+  if (rc) return rc;
+  if ((rc = block_down(ctx, fn, blk, blk_bytes, &host_blk))) return rc;
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  B.offsets.to(offsets, host_blk);
+  const int64_t total = *B.count.in(host_blk);
+  if (!self) ctx->last_neighbors = total;
+  if ((rc = check_capacity(ctx, fn, "neighbours", total, cap, needed))) return rc;
+  if ((rc = lists_down(ctx, L, total, to))) return rc;
+  // (the per-sample results are copied out of the arena while the per-entry transfers are in flight)
+  B.sample_unsafe.to(sample_unsafe, host_blk);
+  if (want_nearest) {
+    B.nearest_dist.to(nearest_dist, host_blk);
+    B.nearest_idx.to(nearest_idx, host_blk);
+  }
+  if ((rc = lists_finish(ctx, total))) return rc;
+  return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
+}
+
 int rrtx_extend_candidates(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, int64_t *offsets,
                            int32_t *idx, double *cost, uint8_t *hit_out, uint8_t *hit_in, int64_t cap,
                            int64_t *needed, int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe) {
   CHECK_CTX(ctx);
   int rc = extend_candidates_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
   if (rc) return rc;
-  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
-  // Everything that is per sample sits in ONE small device block (CandidatesBlock), so that it leaves in one transfer;
-  // the per-entry arrays follow once the count is known.  Small transfers go through the context's pinned arena, large
-  // ones straight to the caller.
-  const int64_t dcap = cap > 0 ? cap : 1;
-  const CandidatesBlock B{(size_t)nq};
-  rc = arena_begin(ctx, B.bytes + sizeof(double) * (size_t)nq * ctx->dim + 256);
-  if (rc) return rc;
-  rc = stage_in_small(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * ctx->dim);
-  if (rc) return rc;
-  RRTX_HIP(ctx, ctx->ws_out_off.ensure(B.bytes + 64));
-  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)dcap));
-  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)dcap));
-  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)dcap));
-  RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)dcap));
-  char *blk = ctx->ws_out_off.as<char>();
-  const bool want_nearest = nearest_idx && nearest_dist;
-  rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, B.offsets.in(blk),
-                                  ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_dist.as<double>(),
-                                  ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(), cap, B.count.in(blk),
-                                  want_nearest ? B.nearest_idx.in(blk) : nullptr,
-                                  want_nearest ? B.nearest_dist.in(blk) : nullptr,
-                                  sample_unsafe ? B.sample_unsafe.in(blk) : nullptr);
-  if (rc) return rc;
-  char *host_blk = arena_take(ctx, B.bytes);
-  if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "extend_candidates: staging arena");
-  RRTX_HIP(ctx, hipMemcpyAsync(host_blk, blk, B.bytes, hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  B.offsets.to(offsets, host_blk);
-  const int64_t total = *B.count.in(host_blk);
-  ctx->last_neighbors = total;
-  if ((rc = check_capacity(ctx, "extend_candidates", "neighbours", total, cap, needed))) return rc;
-  if (total > 0) {
-    if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)total))) return rc;
-    if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
-    if ((rc = d2h(ctx, hit_out, ctx->ws_out_u8a.p, (size_t)total))) return rc;
-    if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
-  }
-  // (the per-sample results are copied out of the arena while the per-entry transfers are in flight)
-  if (sample_unsafe) B.sample_unsafe.to(sample_unsafe, host_blk);
-  if (want_nearest) {
-    B.nearest_dist.to(nearest_dist, host_blk);
-    B.nearest_idx.to(nearest_idx, host_blk);
-  }
-  if (total > 0) {
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    arena_flush(ctx);
-  }
-  return want_nearest ? nearest_fallback(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist) : RRTX_OK;
+  return extend_csr_host(ctx, "extend_candidates", false, false, q, nq, r, robot_radius, 0.0, nullptr, offsets,
+                         ListsOut{idx, cost, nullptr, nullptr, nullptr, nullptr, hit_out, hit_in}, cap, needed, nearest_idx,
+                         nearest_dist, sample_unsafe);
 }
 
 // ---- the samples of one extend batch among themselves (kernels_self.hip) ---------------------------
 // (what rrtx_extend_candidates refuses, with its codes and before anything is staged)
 static int extend_self_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,
                             const double *cost, const uint8_t *hit_out, const uint8_t *hit_in, int64_t cap) {
-  if (nq < 0 || cap < 0 || (nq > 0 && (!q || !offsets)) || (cap > 0 && (!idx || !cost || !hit_out || !hit_in)))
-    return fail(ctx, RRTX_E_INVALID, "extend_candidates_self: bad arguments");
+  int rc = extend_csr_args(ctx, "extend_candidates_self", q, nq, offsets, cap, idx && cost && hit_out && hit_in);
+  if (rc) return rc;
   if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_candidates_self is the SimpleEdge (dim=3) path");
   if (ctx->n_wraps != 0)
     return fail(ctx, RRTX_E_STATE, "extend_candidates_self completes the lists of rrtx_extend_candidates, which needs a "
@@ -2133,41 +2237,8 @@ int rrtx_extend_candidates_self(rrtx_ctx *ctx, const double *q, int nq, double r
   CHECK_CTX(ctx);
   int rc = extend_self_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
   if (rc) return rc;
-  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
-  const int64_t dcap = cap > 0 ? cap : 1;
-  const size_t off_bytes = sizeof(int64_t) * ((size_t)nq + 2);      // offsets[nq + 1], then the count
-  const size_t q_bytes = sizeof(double) * (size_t)nq * 3;
-  rc = arena_begin(ctx, off_bytes + q_bytes + (size_t)nq + 512);
-  if (rc) return rc;
-  if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
-  if (skip && (rc = stage_in_small(ctx, ctx->ws_q2, skip, (size_t)nq))) return rc;
-  RRTX_HIP(ctx, ctx->ws_out_off.ensure(off_bytes));
-  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)dcap));
-  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * (size_t)dcap));
-  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure((size_t)dcap));
-  RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((size_t)dcap));
-  int64_t *off_dev = ctx->ws_out_off.as<int64_t>();
-  rc = rrtx_extend_candidates_self_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius,
-                                       skip ? ctx->ws_q2.as<uint8_t>() : nullptr, off_dev, ctx->ws_out_idx.as<int32_t>(),
-                                       ctx->ws_out_dist.as<double>(), ctx->ws_out_u8a.as<uint8_t>(),
-                                       ctx->ws_out_u8b.as<uint8_t>(), cap, off_dev + nq + 1);
-  if (rc) return rc;
-  char *host_blk = arena_take(ctx, off_bytes);
-  if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "extend_candidates_self: staging arena");
-  RRTX_HIP(ctx, hipMemcpyAsync(host_blk, off_dev, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(offsets, host_blk, sizeof(int64_t) * ((size_t)nq + 1));
-  const int64_t total = reinterpret_cast<const int64_t *>(host_blk)[nq + 1];
-  if ((rc = check_capacity(ctx, "extend_candidates_self", "neighbours", total, cap, needed))) return rc;
-  if (total > 0) {
-    if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * (size_t)total))) return rc;
-    if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
-    if ((rc = d2h(ctx, hit_out, ctx->ws_out_u8a.p, (size_t)total))) return rc;
-    if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    arena_flush(ctx);
-  }
-  return RRTX_OK;
+  return extend_csr_host(ctx, "extend_candidates_self", true, false, q, nq, r, robot_radius, 0.0, skip, offsets,
+                         ListsOut{idx, cost, nullptr, nullptr, nullptr, nullptr, hit_out, hit_in}, cap, needed);
 }
 
 // ---- the closestNode rule for an extend batch: k nearest earlier samples (kernels_self.hip) --------
@@ -2202,54 +2273,34 @@ int rrtx_extend_closest_self(rrtx_ctx *ctx, const double *q, int nq, int k, doub
                              uint8_t *hit_in, int32_t *count, uint8_t *tree_hit_out, uint8_t *tree_hit_in) {
   CHECK_CTX(ctx);
   int rc = extend_closest_args(ctx, q, nq, k, tree_idx, idx, cost, hit_out, hit_in, count, tree_hit_out, tree_hit_in);
-  if (rc || nq == 0) return rc;
-  const size_t n = (size_t)nq, slots = n * (size_t)k, q_bytes = sizeof(double) * n * 3;
-  // inputs beside q in ws_q2: skip, want (a byte a sample each), tree_idx; per-sample outputs in ws_out_off: count, then
-  // the two bytes of the tree column
-  const size_t in_want = n, in_tree = (2 * n + 3) & ~(size_t)3, in_bytes = in_tree + sizeof(int32_t) * n;
-  const size_t out_tho = sizeof(int32_t) * n, out_thi = out_tho + n, out_bytes = out_thi + n;
-  rc = arena_begin(ctx, q_bytes + in_bytes + out_bytes + slots * 14 + 1024);
   if (rc) return rc;
+  if (nq == 0) return extend_empty(nullptr, nullptr);
+  const size_t n = (size_t)nq, q_bytes = sizeof(double) * n * 3;
+  const int64_t slots = (int64_t)nq * k;
+  const ClosestInBlock I{n};
+  const ClosestBlock B{n};
+  const ListsOut to{idx, cost, nullptr, nullptr, nullptr, nullptr, hit_out, hit_in};
+  NeighbourLists L;
+  if ((rc = neighbour_lists(ctx, slots, 1, false, &L))) return rc;
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(B.bytes));
+  if ((rc = arena_begin(ctx, small_in(q_bytes) + block_need(I.bytes) + block_need(B.bytes) + lists_need(to, L.cap)))) return rc;
   if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
-  RRTX_HIP(ctx, ctx->ws_q2.ensure(in_bytes));
-  char *in_dev = ctx->ws_q2.as<char>();
-  auto stage_at = [&](size_t off, const void *host, size_t bytes) -> int {
-    const void *from = host;
-    char *a = arena_take(ctx, bytes);
-    if (a) { std::memcpy(a, host, bytes); from = a; }
-    RRTX_HIP(ctx, hipMemcpyAsync(in_dev + off, from, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return RRTX_OK;
-  };
-  if (skip && (rc = stage_at(0, skip, n))) return rc;
-  if (want && (rc = stage_at(in_want, want, n))) return rc;
-  if (tree_idx && (rc = stage_at(in_tree, tree_idx, sizeof(int32_t) * n))) return rc;
-  RRTX_HIP(ctx, ctx->ws_out_off.ensure(out_bytes));
-  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * slots));
-  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * slots));
-  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(slots));
-  RRTX_HIP(ctx, ctx->ws_out_u8b.ensure(slots));
-  char *out_dev = ctx->ws_out_off.as<char>();
-  rc = rrtx_extend_closest_self_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius,
-                                    skip ? reinterpret_cast<const uint8_t *>(in_dev) : nullptr,
-                                    want ? reinterpret_cast<const uint8_t *>(in_dev + in_want) : nullptr,
-                                    tree_idx ? reinterpret_cast<const int32_t *>(in_dev + in_tree) : nullptr,
-                                    ctx->ws_out_idx.as<int32_t>(), ctx->ws_out_dist.as<double>(),
-                                    ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>(),
-                                    reinterpret_cast<int32_t *>(out_dev),
-                                    tree_idx ? reinterpret_cast<uint8_t *>(out_dev + out_tho) : nullptr,
-                                    tree_idx ? reinterpret_cast<uint8_t *>(out_dev + out_thi) : nullptr);
+  if ((rc = closest_inputs_up(ctx, "extend_closest_self", I, skip, want, tree_idx))) return rc;
+  char *in = ctx->ws_q2.as<char>(), *blk = ctx->ws_out_off.as<char>(), *host_blk;
+  rc = rrtx_extend_closest_self_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius, skip ? I.skip.in(in) : nullptr,
+                                    want ? I.want.in(in) : nullptr, tree_idx ? I.tree_idx.in(in) : nullptr, L.idx, L.key,
+                                    L.hit_out, L.hit_in, B.count.in(blk), tree_idx ? B.tree_hit_out.in(blk) : nullptr,
+                                    tree_idx ? B.tree_hit_in.in(blk) : nullptr);
   if (rc) return rc;
-  if ((rc = d2h(ctx, count, out_dev, sizeof(int32_t) * n))) return rc;
+  // (no count to wait for: the block and the slots come down behind one another)
+  if ((rc = block_down(ctx, "extend_closest_self", blk, B.bytes, &host_blk))) return rc;
+  if ((rc = lists_down(ctx, L, slots, to))) return rc;
+  if ((rc = lists_finish(ctx, slots))) return rc;
+  B.count.to(count, host_blk);
   if (tree_idx) {
-    if ((rc = d2h(ctx, tree_hit_out, out_dev + out_tho, n))) return rc;
-    if ((rc = d2h(ctx, tree_hit_in, out_dev + out_thi, n))) return rc;
+    B.tree_hit_out.to(tree_hit_out, host_blk);
+    B.tree_hit_in.to(tree_hit_in, host_blk);
   }
-  if ((rc = d2h(ctx, cost, ctx->ws_out_dist.p, sizeof(double) * slots))) return rc;
-  if ((rc = d2h(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * slots))) return rc;
-  if ((rc = d2h(ctx, hit_out, ctx->ws_out_u8a.p, slots))) return rc;
-  if ((rc = d2h(ctx, hit_in, ctx->ws_out_u8b.p, slots))) return rc;
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  arena_flush(ctx);
   return RRTX_OK;
 }
 
@@ -2373,39 +2424,8 @@ int rrtx_extend_candidates_self_dubins(rrtx_ctx *ctx, const double *q, int nq, d
   CHECK_CTX(ctx);
   int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
   if (rc) return rc;
-  if (nq == 0) { if (needed) *needed = 0; if (offsets) offsets[0] = 0; return RRTX_OK; }
-  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * (size_t)nq * 4));
-  if (skip) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q2, skip, (size_t)nq));
-  const int64_t dcap = cap > 0 ? cap : 1;
-  RRTX_HIP(ctx, ctx->ws_out_off.ensure(sizeof(int64_t) * ((size_t)nq + 2)));
-  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * (size_t)dcap));
-  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * 3 * (size_t)dcap));          // key, cost_out, cost_in
-  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(8 * (size_t)dcap));                             // words (3+3), hits (1+1)
-  int64_t *off_dev = ctx->ws_out_off.as<int64_t>();
-  int64_t *needed_dev = off_dev + nq + 1;
-  double *key_dev = ctx->ws_out_dist.as<double>(), *co_dev = key_dev + dcap, *ci_dev = co_dev + dcap;
-  uint8_t *wo_dev = ctx->ws_out_u8a.as<uint8_t>(), *wi_dev = wo_dev + 3 * dcap, *ho_dev = wi_dev + 3 * dcap,
-          *hi_dev = ho_dev + dcap;
-  rc = rrtx_extend_candidates_self_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, r_min,
-                                              skip ? ctx->ws_q2.as<uint8_t>() : nullptr, off_dev,
-                                              ctx->ws_out_idx.as<int32_t>(), key_dev, co_dev, ci_dev, wo_dev, wi_dev, ho_dev,
-                                              hi_dev, cap, needed_dev);
-  if (rc) return rc;
-  int64_t total = 0;
-  RRTX_HIP(ctx, copy_out(ctx, offsets, off_dev, sizeof(int64_t) * ((size_t)nq + 1)));
-  RRTX_HIP(ctx, read_count(ctx, needed_dev, &total));
-  if ((rc = check_capacity(ctx, "extend_candidates_self_dubins", "neighbours", total, cap, needed))) return rc;
-  const size_t n = (size_t)total;
-  RRTX_HIP(ctx, copy_out(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * n));
-  RRTX_HIP(ctx, copy_out(ctx, key, key_dev, sizeof(double) * n));
-  RRTX_HIP(ctx, copy_out(ctx, cost_out, co_dev, sizeof(double) * n));
-  RRTX_HIP(ctx, copy_out(ctx, cost_in, ci_dev, sizeof(double) * n));
-  RRTX_HIP(ctx, copy_out(ctx, word_out, wo_dev, 3 * n));
-  RRTX_HIP(ctx, copy_out(ctx, word_in, wi_dev, 3 * n));
-  RRTX_HIP(ctx, copy_out(ctx, hit_out, ho_dev, n));
-  RRTX_HIP(ctx, copy_out(ctx, hit_in, hi_dev, n));
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RRTX_OK;
+  return extend_csr_host(ctx, "extend_candidates_self_dubins", true, true, q, nq, r, robot_radius, r_min, skip, offsets,
+                         ListsOut{idx, key, cost_out, cost_in, word_out, word_in, hit_out, hit_in}, cap, needed);
 }
 
 // ---- the closestNode rule for a Dubins extend batch: k nearest earlier samples in wrapped space (kernels_self.hip) ----
@@ -2450,52 +2470,41 @@ int rrtx_extend_closest_self_dubins(rrtx_ctx *ctx, const double *q, int nq, int 
   CHECK_CTX(ctx);
   int rc = extend_closest_dubins_args(ctx, q, nq, k, tree_idx, idx, key, cost_out, cost_in, hit_out, hit_in, count,
                                       tree_cost_out, tree_cost_in, tree_hit_out, tree_hit_in);
-  if (rc || nq == 0) return rc;
-  const size_t n = (size_t)nq, slots = n * (size_t)k;
-  RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q, q, sizeof(double) * n * 4));
-  if (skip) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_q2, skip, n));
-  if (want) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_i32a, want, n));
-  if (tree_idx) RRTX_HIP(ctx, stage_in(ctx, ctx->ws_i32b, tree_idx, sizeof(int32_t) * n));
-  // per slot: idx; key, cost_out, cost_in; words (3 + 3), hits (1 + 1).  Per sample, in ws_out_off: the tree column's two
-  // costs, count, then the tree column's words (3 + 3) and hits (1 + 1)
-  RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * slots));
-  RRTX_HIP(ctx, ctx->ws_out_dist.ensure(sizeof(double) * 3 * slots));
-  RRTX_HIP(ctx, ctx->ws_out_u8a.ensure(8 * slots));
-  RRTX_HIP(ctx, ctx->ws_out_off.ensure(28 * n));
-  double *key_dev = ctx->ws_out_dist.as<double>(), *co_dev = key_dev + slots, *ci_dev = co_dev + slots;
-  uint8_t *wo_dev = ctx->ws_out_u8a.as<uint8_t>(), *wi_dev = wo_dev + 3 * slots, *ho_dev = wi_dev + 3 * slots,
-          *hi_dev = ho_dev + slots;
-  double *tco_dev = ctx->ws_out_off.as<double>(), *tci_dev = tco_dev + n;
-  int32_t *count_dev = reinterpret_cast<int32_t *>(tci_dev + n);
-  uint8_t *two_dev = reinterpret_cast<uint8_t *>(count_dev + n), *twi_dev = two_dev + 3 * n, *tho_dev = twi_dev + 3 * n,
-          *thi_dev = tho_dev + n;
-  rc = rrtx_extend_closest_self_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius, r_min,
-                                           skip ? ctx->ws_q2.as<uint8_t>() : nullptr,
-                                           want ? ctx->ws_i32a.as<uint8_t>() : nullptr,
-                                           tree_idx ? ctx->ws_i32b.as<int32_t>() : nullptr, ctx->ws_out_idx.as<int32_t>(),
-                                           key_dev, co_dev, ci_dev, wo_dev, wi_dev, ho_dev, hi_dev, count_dev,
-                                           tree_idx ? tco_dev : nullptr, tree_idx ? tci_dev : nullptr,
-                                           tree_idx ? two_dev : nullptr, tree_idx ? twi_dev : nullptr,
-                                           tree_idx ? tho_dev : nullptr, tree_idx ? thi_dev : nullptr);
   if (rc) return rc;
-  RRTX_HIP(ctx, copy_out(ctx, idx, ctx->ws_out_idx.p, sizeof(int32_t) * slots));
-  RRTX_HIP(ctx, copy_out(ctx, key, key_dev, sizeof(double) * slots));
-  RRTX_HIP(ctx, copy_out(ctx, cost_out, co_dev, sizeof(double) * slots));
-  RRTX_HIP(ctx, copy_out(ctx, cost_in, ci_dev, sizeof(double) * slots));
-  RRTX_HIP(ctx, copy_out(ctx, word_out, wo_dev, 3 * slots));
-  RRTX_HIP(ctx, copy_out(ctx, word_in, wi_dev, 3 * slots));
-  RRTX_HIP(ctx, copy_out(ctx, hit_out, ho_dev, slots));
-  RRTX_HIP(ctx, copy_out(ctx, hit_in, hi_dev, slots));
-  RRTX_HIP(ctx, copy_out(ctx, count, count_dev, sizeof(int32_t) * n));
+  if (nq == 0) return extend_empty(nullptr, nullptr);
+  const size_t n = (size_t)nq, q_bytes = sizeof(double) * n * 4;
+  const int64_t slots = (int64_t)nq * k;
+  const ClosestInBlock I{n};
+  const ClosestDubinsBlock B{n};
+  const ListsOut to{idx, key, cost_out, cost_in, word_out, word_in, hit_out, hit_in};
+  NeighbourLists L;
+  if ((rc = neighbour_lists(ctx, slots, 3, true, &L))) return rc;
+  RRTX_HIP(ctx, ctx->ws_out_off.ensure(B.bytes));
+  if ((rc = arena_begin(ctx, small_in(q_bytes) + block_need(I.bytes) + block_need(B.bytes) + lists_need(to, L.cap)))) return rc;
+  if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
+  if ((rc = closest_inputs_up(ctx, "extend_closest_self_dubins", I, skip, want, tree_idx))) return rc;
+  char *in = ctx->ws_q2.as<char>(), *blk = ctx->ws_out_off.as<char>(), *host_blk;
+  rc = rrtx_extend_closest_self_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius, r_min,
+                                           skip ? I.skip.in(in) : nullptr, want ? I.want.in(in) : nullptr,
+                                           tree_idx ? I.tree_idx.in(in) : nullptr, L.idx, L.key, L.cost_out, L.cost_in,
+                                           L.word_out, L.word_in, L.hit_out, L.hit_in, B.count.in(blk),
+                                           tree_idx ? B.tree_cost_out.in(blk) : nullptr, tree_idx ? B.tree_cost_in.in(blk) : nullptr,
+                                           tree_idx ? B.tree_word_out.in(blk) : nullptr, tree_idx ? B.tree_word_in.in(blk) : nullptr,
+                                           tree_idx ? B.tree_hit_out.in(blk) : nullptr, tree_idx ? B.tree_hit_in.in(blk) : nullptr);
+  if (rc) return rc;
+  // (no count to wait for: the block and the slots come down behind one another)
+  if ((rc = block_down(ctx, "extend_closest_self_dubins", blk, B.bytes, &host_blk))) return rc;
+  if ((rc = lists_down(ctx, L, slots, to))) return rc;
+  if ((rc = lists_finish(ctx, slots))) return rc;
+  B.count.to(count, host_blk);
   if (tree_idx) {
-    RRTX_HIP(ctx, copy_out(ctx, tree_cost_out, tco_dev, sizeof(double) * n));
-    RRTX_HIP(ctx, copy_out(ctx, tree_cost_in, tci_dev, sizeof(double) * n));
-    RRTX_HIP(ctx, copy_out(ctx, tree_word_out, two_dev, 3 * n));
-    RRTX_HIP(ctx, copy_out(ctx, tree_word_in, twi_dev, 3 * n));
-    RRTX_HIP(ctx, copy_out(ctx, tree_hit_out, tho_dev, n));
-    RRTX_HIP(ctx, copy_out(ctx, tree_hit_in, thi_dev, n));
+    B.tree_cost_out.to(tree_cost_out, host_blk);
+    B.tree_cost_in.to(tree_cost_in, host_blk);
+    B.tree_word_out.to(tree_word_out, host_blk);
+    B.tree_word_in.to(tree_word_in, host_blk);
+    B.tree_hit_out.to(tree_hit_out, host_blk);
+    B.tree_hit_in.to(tree_hit_in, host_blk);
   }
-  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RRTX_OK;
 }
 
@@ -2553,9 +2562,7 @@ int rrtx_node_cost_set(rrtx_ctx *ctx, int64_t first_index, const double *lmc, in
 
 // (the lists a host-pointer select call may hand back: all or none, offsets null for none.  SimpleEdge has the one cost
 // column, given as `key`; Dubins has key, cost_out and cost_in)
-struct SelectListsOut {
-  int64_t *offsets; int32_t *idx; double *key, *cost_out, *cost_in; uint8_t *hit_out, *hit_in; int64_t cap; int64_t *needed;
-};
+struct SelectListsOut { int64_t *offsets; ListsOut to; int64_t cap; int64_t *needed; };
 // samples with an empty ball, resolved like nearest_fallback but through no entry point: the misses go up into ws_q2,
 // the full scan answers into ws_out_i32 / ws_out_f64.  Neither those nor the scan's own workspaces (ws_slots, ws_copies*,
 // ws_copy_meta, ws_scalars_nn, ws_recs, ws_partial) hold a list or the select block, so the held lists stay valid.
@@ -2582,8 +2589,8 @@ static int nearest_fallback_keep(rrtx_ctx *ctx, const double *q, int nq, int dim
 
 // The body rrtx_extend_select and rrtx_extend_select_dubins share: the extend preamble into lists the context owns,
 // the selection over them, the per-sample block down in one transfer, then the rewire lists and (asked for) the
-// neighbour lists.  dubins: three double columns key | cost_out | cost_in at a stride of the list capacity in
-// ws_out_dist, as find_new_target lays them out; else the one column.  On success the context holds the lists.
+// neighbour lists.  dubins: the three double columns of neighbour_lists, else the one.  On success the context holds
+// the lists.
 static int extend_select_host(rrtx_ctx *ctx, const char *fn, bool dubins, const double *q, int nq, double r, double robot_radius,
                               double r_min, const double *lmc, int32_t *parent_idx, int64_t *parent_entry, double *lmc_new,
                               uint8_t *status, int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
@@ -2605,34 +2612,35 @@ static int extend_select_host(rrtx_ctx *ctx, const char *fn, bool dubins, const 
   const SelectBlock B{n};
   const size_t out_bytes = want_lists ? B.bytes : B.bytes_without_lists;
   const size_t q_bytes = sizeof(double) * n * (size_t)ctx->dim;
-  const size_t staged = (256u << 10) + 64;   // what d2h may take per small output array
-  int rc = arena_begin(ctx, out_bytes + q_bytes + lmc_arena_need(ctx, lmc) + (size_t)(5 + cols) * staged + 512);
+  int rc = arena_begin(ctx, small_in(q_bytes) + lmc_arena_need(ctx, lmc) + block_need(out_bytes) + out_need(rw_value, sizeof(double), rw_cap) +
+                                out_need(rw_node, sizeof(int32_t), rw_cap) + (want_lists ? lists_need(out.to, out.cap) : 0));
   if (rc) return rc;
   if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
   Lmc lmc_dev;
   if ((rc = resolve_lmc(ctx, lmc, &lmc_dev))) return rc;
-  RRTX_HIP(ctx, ctx->ws_sel_blk.ensure(B.bytes + 64));
+  RRTX_HIP(ctx, ctx->ws_sel_blk.ensure(B.bytes));
   RRTX_HIP(ctx, ctx->ws_sel_rwn.ensure(sizeof(int32_t) * (size_t)(rw_cap > 0 ? rw_cap : 1)));
   RRTX_HIP(ctx, ctx->ws_sel_rwv.ensure(sizeof(double) * (size_t)(rw_cap > 0 ? rw_cap : 1)));
   char *blk = ctx->ws_sel_blk.as<char>();
   char *host_blk = arena_take(ctx, out_bytes);
   if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "%s: staging arena", fn);
   const bool want_nearest = nearest_idx && nearest_dist;
-  rc = with_neighbour_lists(ctx, fn, nq, 0, cols, dubins, host_blk, blk, out_bytes, [&](const NeighbourLists &L) {
-    const double *co = dubins ? L.key + L.cap : L.key, *ci = dubins ? L.key + 2 * L.cap : L.key;
+  NeighbourLists lists;
+  rc = with_neighbour_lists(ctx, fn, nq, 0, cols, host_blk, blk, out_bytes, [&](const NeighbourLists &L) {
+    lists = L;
     int32_t *ni = want_nearest ? B.nearest_idx.in(blk) : nullptr;
     double *nd = want_nearest ? B.nearest_dist.in(blk) : nullptr;
     // (in a wrapped Dubins space the preamble ends with the full nearest scan: it writes the two columns of the select
     // block and its own search workspaces, never a list)
     int rc = dubins ? rrtx_extend_candidates_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, r_min,
-                                                        B.offsets.in(blk), L.idx, L.key, L.key + L.cap, L.key + 2 * L.cap,
+                                                        B.offsets.in(blk), L.idx, L.key, L.cost_out, L.cost_in,
                                                         nullptr, nullptr, L.hit_out, L.hit_in, L.cap, B.counts.in(blk), ni, nd,
                                                         B.sample_unsafe.in(blk))
                     : rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, B.offsets.in(blk), L.idx,
                                                  L.key, L.hit_out, L.hit_in, L.cap, B.counts.in(blk), ni, nd,
                                                  B.sample_unsafe.in(blk));
     if (rc) return rc;
-    return select_over_lists(ctx, nq, B.offsets.in(blk), L.idx, co, ci, L.hit_out, L.hit_in, B.counts.in(blk), L.cap,
+    return select_over_lists(ctx, nq, B.offsets.in(blk), L.idx, L.cost_out, L.cost_in, L.hit_out, L.hit_in, B.counts.in(blk), L.cap,
                              B.sample_unsafe.in(blk), lmc_dev, B.parent_idx.in(blk), B.parent_entry.in(blk),
                              B.lmc_new.in(blk), B.status.in(blk), B.rw_offsets.in(blk), ctx->ws_sel_rwn.as<int32_t>(),
                              ctx->ws_sel_rwv.as<double>(), rw_cap, B.counts.in(blk) + 1);
@@ -2644,7 +2652,7 @@ static int extend_select_host(rrtx_ctx *ctx, const char *fn, bool dubins, const 
   B.lmc_new.to(lmc_new, host_blk);
   B.parent_idx.to(parent_idx, host_blk);
   B.status.to(status, host_blk);
-  if (sample_unsafe) B.sample_unsafe.to(sample_unsafe, host_blk);
+  B.sample_unsafe.to(sample_unsafe, host_blk);
   if (want_nearest) {
     B.nearest_dist.to(nearest_dist, host_blk);
     B.nearest_idx.to(nearest_idx, host_blk);
@@ -2653,26 +2661,10 @@ static int extend_select_host(rrtx_ctx *ctx, const char *fn, bool dubins, const 
   if (out.needed) *out.needed = total;
   if ((rc = check_capacity(ctx, fn, "rewire entries", rw_total, rw_cap, rw_needed))) return rc;
   if (want_lists && (rc = check_capacity(ctx, fn, "neighbours", total, out.cap, out.needed))) return rc;
-  if (rw_total > 0) {
-    if ((rc = d2h(ctx, rw_value, ctx->ws_sel_rwv.p, sizeof(double) * (size_t)rw_total))) return rc;
-    if ((rc = d2h(ctx, rw_node, ctx->ws_sel_rwn.p, sizeof(int32_t) * (size_t)rw_total))) return rc;
-  }
-  if (want_lists && total > 0) {
-    const double *col = ctx->ws_out_dist.as<double>();
-    const size_t stride = (size_t)ctx->sel_list_cap;
-    if ((rc = d2h(ctx, out.key, col, sizeof(double) * (size_t)total))) return rc;
-    if (dubins) {
-      if ((rc = d2h(ctx, out.cost_out, col + stride, sizeof(double) * (size_t)total))) return rc;
-      if ((rc = d2h(ctx, out.cost_in, col + 2 * stride, sizeof(double) * (size_t)total))) return rc;
-    }
-    if ((rc = d2h(ctx, out.idx, ctx->ws_out_idx.p, sizeof(int32_t) * (size_t)total))) return rc;
-    if ((rc = d2h(ctx, out.hit_out, ctx->ws_out_u8a.p, (size_t)total))) return rc;
-    if ((rc = d2h(ctx, out.hit_in, ctx->ws_out_u8b.p, (size_t)total))) return rc;
-  }
-  if (rw_total > 0 || (want_lists && total > 0)) {
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    arena_flush(ctx);
-  }
+  if ((rc = d2h(ctx, rw_value, ctx->ws_sel_rwv.p, sizeof(double) * (size_t)rw_total))) return rc;
+  if ((rc = d2h(ctx, rw_node, ctx->ws_sel_rwn.p, sizeof(int32_t) * (size_t)rw_total))) return rc;
+  if (want_lists && (rc = lists_down(ctx, lists, total, out.to))) return rc;
+  if ((rc = lists_finish(ctx, rw_total + (want_lists ? total : 0)))) return rc;
   // Dubins without wrapped dimensions reads the nearest off the lists like SimpleEdge; its empty balls are resolved
   // here, before the record is set and through no entry point, so the hold is valid whatever the caller asked for
   if (dubins && want_nearest && (rc = nearest_fallback_keep(ctx, q, nq, ctx->dim, nearest_idx, nearest_dist))) return rc;
@@ -2696,7 +2688,7 @@ int rrtx_extend_select(rrtx_ctx *ctx, const double *q, int nq, double r, double 
   if (ctx->dim != 3) return fail(ctx, RRTX_E_STATE, "extend_select is the SimpleEdge (dim=3) path");
   return extend_select_host(ctx, "extend_select", false, q, nq, r, robot_radius, 0.0, lmc, parent_idx, parent_entry, lmc_new,
                             status, rw_offsets, rw_node, rw_value, rw_cap, rw_needed, nearest_idx, nearest_dist, sample_unsafe,
-                            SelectListsOut{offsets, idx, cost, nullptr, nullptr, hit_out, hit_in, cap, needed});
+                            SelectListsOut{offsets, ListsOut{idx, cost, nullptr, nullptr, nullptr, nullptr, hit_out, hit_in}, cap, needed});
 }
 
 int rrtx_extend_select_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius, double r_min,
@@ -2714,7 +2706,7 @@ int rrtx_extend_select_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, 
   if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "extend_select_dubins needs a dim=4 [x y t theta] context");
   return extend_select_host(ctx, "extend_select_dubins", true, q, nq, r, robot_radius, r_min, lmc, parent_idx, parent_entry,
                             lmc_new, status, rw_offsets, rw_node, rw_value, rw_cap, rw_needed, nearest_idx, nearest_dist,
-                            sample_unsafe, SelectListsOut{offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap, needed});
+                            sample_unsafe, SelectListsOut{offsets, ListsOut{idx, key, cost_out, cost_in, nullptr, nullptr, hit_out, hit_in}, cap, needed});
 }
 
 // ---- findNewTarget over a batch of poses (kernels_target.hip) ---------------------------------------
@@ -2766,12 +2758,12 @@ int find_new_target(rrtx_ctx *ctx, const char *fn, bool dubins, const double *po
     if (round > 64) return fail(ctx, RRTX_E_STATE, "%s: %d poses still searching after 64 rounds", fn, n_act);
     char *cur = ctx->ws_tgt_blk[side].as<char>(), *nxt = ctx->ws_tgt_blk[side ^ 1].as<char>();
     const double *q_dev = Q.pose.in(cur);
-    rc = with_neighbour_lists(ctx, fn, nq, room, dubins ? 3 : 1, true, host_hdr, hdr_dev, R.hdr.bytes(), [&](const NeighbourLists &L) {
+    rc = with_neighbour_lists(ctx, fn, nq, room, dubins ? 3 : 1, host_hdr, hdr_dev, R.hdr.bytes(), [&](const NeighbourLists &L) {
       int rc = launch_nn_radius(ctx, q_dev, Q.thr.in(cur), 0.0, n_act, off_dev, L.idx, L.key, L.cap, hdr_dev, L.owner);
       if (rc) return rc;
-      if (dubins) {      // (cost_out, cost_in follow the keys)
-        rc = launch_candidate_dubins(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, r_min, robot_radius, L.key + L.cap,
-                                     L.key + 2 * L.cap, nullptr, nullptr, L.hit_out, L.hit_in);
+      if (dubins) {
+        rc = launch_candidate_dubins(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, r_min, robot_radius, L.cost_out,
+                                     L.cost_in, nullptr, nullptr, L.hit_out, L.hit_in);
       } else if (ctx->opt_extend_polygons) {
         rc = launch_candidate_edges_polygons(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, robot_radius, L.hit_out,
                                              L.hit_in, nullptr, -1.0);
@@ -2782,7 +2774,7 @@ int find_new_target(rrtx_ctx *ctx, const char *fn, bool dubins, const double *po
       if (rc) return rc;
       TargetRound T;
       T.n_act = n_act; T.nq = nq; T.round = round; T.dim = ctx->dim; T.r_max = r_max;
-      T.offsets = off_dev; T.idx = L.idx; T.cost = dubins ? L.key + L.cap : L.key; T.hit_out = L.hit_out;
+      T.offsets = off_dev; T.idx = L.idx; T.cost = L.cost_out; T.hit_out = L.hit_out;
       T.n_valid = hdr_dev; T.cap = (long long)L.cap;
       T.lmc = lmc_dev.dev; T.n_lmc = (long long)lmc_dev.n;
       T.q = q_dev; T.rad = Q.rad.in(cur); T.slot = Q.slot.in(cur);
