@@ -505,7 +505,7 @@ int launch_nn_finish(rrtx_ctx *ctx, const FinishLaunch &f) {
   a.want_nearest_fix = (f.nearest_idx && ctx->n_wraps == 0) ? 1 : 0;
   a.ni.sx = ctx->sl_d[0]; a.ni.sy = ctx->sl_d[1]; a.ni.sz = ctx->sl_d[2]; a.ni.sw = ctx->sl_d[D == 4 ? 3 : 2];
   a.ni.sid = ctx->sl_id;
-  a.ni.chunk_ext = reinterpret_cast<const ChunkExt *>(ctx->chunk_ext);
+  a.ni.chunk_ext = reinterpret_cast<const ChunkExt *>(ctx->chunk_ext.get());
   a.ni.n_nodes = (int)ctx->n_nodes;
   a.ni.n_chunks = (int)((ctx->n_nodes + kSlabChunk - 1) / kSlabChunk);
   a.hit_out = f.hit_out; a.hit_in = f.hit_in;

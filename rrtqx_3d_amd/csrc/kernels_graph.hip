@@ -399,22 +399,6 @@ __global__ void graph_delta_unreported_kernel(long long first, long long m, unsi
   base_par[first + i] = -1;
 }
 
-// grow a buffer whose first keep bytes must survive
-hipError_t ensure_keep(DevBuf &b, size_t need, size_t keep, hipStream_t st) {
-  if (need <= b.bytes) return hipSuccess;
-  DevBuf nb;
-  hipError_t e = nb.ensure(need);
-  if (e != hipSuccess) return e;
-  if (keep > 0 && b.p) {
-    e = hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { nb.release(); return e; }
-  }
-  b.release();
-  b = nb;
-  return hipSuccess;
-}
-
 inline dim3 grid_for(long long n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
 int read_flags(rrtx_ctx *ctx, int *host) {
@@ -455,7 +439,7 @@ int build_in_csr(rrtx_ctx *ctx, int n, long long ne) {
 int launch_graph_edge_dist(rrtx_ctx *ctx, long long first, long long n) {
   if (n <= 0) return RRTX_OK;
   hipLaunchKernelGGL(graph_edge_dist_kernel, grid_for(n), dim3(256), 0, ctx->stream, ctx->ge_start, ctx->ge_end, first, n,
-                     ctx->dim, reinterpret_cast<const double4 *>(ctx->nodes_aos), ctx->ge_dist, ctx->ge_dist0, ctx->ge_dirty);
+                     ctx->dim, reinterpret_cast<const double4 *>(ctx->nodes_aos.get()), ctx->ge_dist, ctx->ge_dist0, ctx->ge_dirty);
   RRTX_HIP(ctx, hipGetLastError());
   return RRTX_OK;
 }
@@ -515,8 +499,8 @@ static int graph_cost_impl(rrtx_ctx *ctx, int root, bool update, double *lmc_dev
   const long long ne = ctx->ge_n;
   hipStream_t st = ctx->stream;
   const size_t keep = (size_t)gc.solved_nodes;
-  RRTX_HIP(ctx, ensure_keep(gc.lmc, sizeof(unsigned long long) * (size_t)n, sizeof(unsigned long long) * keep, st));
-  RRTX_HIP(ctx, ensure_keep(gc.parent, sizeof(int32_t) * (size_t)n, sizeof(int32_t) * keep, st));
+  RRTX_HIP(ctx, gc.lmc.ensure_keep(sizeof(unsigned long long) * (size_t)n, sizeof(unsigned long long) * keep, st));
+  RRTX_HIP(ctx, gc.parent.ensure_keep(sizeof(int32_t) * (size_t)n, sizeof(int32_t) * keep, st));
   RRTX_HIP(ctx, gc.stamp.ensure(sizeof(int) * (size_t)n));
   RRTX_HIP(ctx, gc.flags.ensure(sizeof(int) * kFlagInts));
   NodeState s{gc.lmc.as<unsigned long long>(), gc.parent.as<int32_t>(), gc.stamp.as<int>()};
@@ -651,8 +635,8 @@ int launch_graph_delta(rrtx_ctx *ctx, int root, bool store, int32_t *node_dev, d
   hipStream_t st = ctx->stream;
   // the baseline grows with the tree; nodes it has not seen yet read as never reported
   const size_t keep = (size_t)gc.rep_nodes;
-  RRTX_HIP(ctx, ensure_keep(gc.rep_lmc, sizeof(unsigned long long) * (size_t)n, sizeof(unsigned long long) * keep, st));
-  RRTX_HIP(ctx, ensure_keep(gc.rep_parent, sizeof(int32_t) * (size_t)n, sizeof(int32_t) * keep, st));
+  RRTX_HIP(ctx, gc.rep_lmc.ensure_keep(sizeof(unsigned long long) * (size_t)n, sizeof(unsigned long long) * keep, st));
+  RRTX_HIP(ctx, gc.rep_parent.ensure_keep(sizeof(int32_t) * (size_t)n, sizeof(int32_t) * keep, st));
   if (n > gc.rep_nodes) {
     const long long m = n - gc.rep_nodes;
     hipLaunchKernelGGL(graph_delta_unreported_kernel, grid_for(m), dim3(256), 0, st, (long long)gc.rep_nodes, m,

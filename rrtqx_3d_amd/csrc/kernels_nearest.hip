@@ -414,7 +414,7 @@ static int launch_nn_nearest_screened(rrtx_ctx *ctx, const double *q_dev, int nq
     NearestIndex ni;
     ni.sx = ctx->sl_d[0]; ni.sy = ctx->sl_d[1]; ni.sz = ctx->sl_d[2]; ni.sw = ctx->sl_d[D == 4 ? 3 : 2];
     ni.sid = ctx->sl_id;
-    ni.chunk_ext = reinterpret_cast<const ChunkExt *>(ctx->chunk_ext);
+    ni.chunk_ext = reinterpret_cast<const ChunkExt *>(ctx->chunk_ext.get());
     ni.n_nodes = n_nodes;
     ni.n_chunks = (n_nodes + kSlabChunk - 1) / kSlabChunk;
     const dim3 fgrid((unsigned)(nq < 2048 ? nq : 2048));

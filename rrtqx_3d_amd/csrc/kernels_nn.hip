@@ -1311,9 +1311,9 @@ int radius_workspaces(rrtx_ctx *ctx, const RadiusPlan &p) {
   }
   RRTX_HIP(ctx, ctx->ws_recs.ensure((size_t)p.rec_cap * sizeof(HitRec)));
   RRTX_HIP(ctx, ctx->ws_tmp.ensure((size_t)p.rec_cap * sizeof(BktRec)));
-  if (!ctx->mailbox) {                    // host-mapped words the finish kernel reports to
-    RRTX_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->mailbox), 64, hipHostMallocMapped));
-    std::memset(ctx->mailbox, 0, 64);
+  if (!ctx->mailbox.p) {                  // host-mapped words the finish kernel reports to
+    RRTX_HIP(ctx, ctx->mailbox.alloc(64, hipHostMallocMapped));
+    std::memset(ctx->mailbox.p, 0, 64);
   }
   if (!p.slot_route) {                    // (the slot route needs none of these: its copies live in the table)
     const size_t qf_bytes = (ctx->dim == 4) ? sizeof(QRecF4) : sizeof(QRecF3);
@@ -1370,7 +1370,7 @@ void radius_args(rrtx_ctx *ctx, const RadiusPlan &p, int flip, const ExtendFuse 
   HitSink &hs = d.ca.hs;
   hs.count = d.count; hs.bkt = ctx->ws_bkt.as<BktRec>(); hs.bcap = p.bcap;
   hs.recs = ctx->ws_recs.as<HitRec>(); hs.cap = p.rec_cap; hs.sc = d.sc;
-  double *const *pd = p.use_cull ? ctx->sl_d : ctx->nodes;
+  const DevArray<double> *pd = p.use_cull ? ctx->sl_d : ctx->nodes;
   d.ca.nx = pd[0]; d.ca.ny = pd[1]; d.ca.nz = pd[2]; d.ca.nw = pd[wi];
   // (slot route: the tile kernel confirms against its copies in LDS and takes the owners from there)
   d.ca.copies = p.slot_route ? nullptr : (p.use_cull ? ctx->ws_copies_s.p : ctx->ws_copies.p);
@@ -1383,7 +1383,7 @@ void radius_args(rrtx_ctx *ctx, const RadiusPlan &p, int flip, const ExtendFuse 
   d.xd.r_bound = -1.0;
   if (p.fuse) {                           // (sphere list; the caller has synced the tables)
     d.xd.sph = ctx->d_sph.as<SphRec>(); d.xd.stab = ctx->d_sph_sample.as<SampleSph>();
-    d.xd.reach_f = ctx->d_sph_reach_f.as<float>(); d.xd.naos = reinterpret_cast<const double4 *>(ctx->nodes_aos);
+    d.xd.reach_f = ctx->d_sph_reach_f.as<float>(); d.xd.naos = reinterpret_cast<const double4 *>(ctx->nodes_aos.get());
     d.xd.ox = ctx->origin[0]; d.xd.oy = ctx->origin[1]; d.xd.oz = ctx->origin[2]; d.xd.m = ctx->sph_n_active;
     d.xd.r_bound = (ext->r >= 0.0 && d.xd.m > 0) ? ext->r * (1.0 + 1e-12) : -1.0;
     d.xd.sample_unsafe = ext->sample_unsafe;
@@ -1428,7 +1428,7 @@ void radius_scan_tiles(rrtx_ctx *ctx, const RadiusPlan &p, const RadiusArgs &d) 
 #define RRTX_TILE_LAUNCH_F(DD, EE, SS, OO)                                                                             \
   hipLaunchKernelGGL((nn_tile_kernel<DD, EE, SS, OO>), dim3(p.scan_grid), dim3(kScanThreads), 0, ctx->stream,          \
                      ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2], ctx->sl_f[wi], ctx->sl_pp, p.n_nodes, p.n_chunks,       \
-                     reinterpret_cast<const ChunkExt *>(ctx->chunk_ext),                                               \
+                     reinterpret_cast<const ChunkExt *>(ctx->chunk_ext.get()),                                               \
                      SS ? nullptr : ctx->ws_copies_s.as<typename QRecT<DD>::type>(),                                   \
                      SS ? nullptr : ctx->ws_copies_f.as<typename QRecFT<DD>::type>(), d.sc, p.n_parts,                 \
                      ctx->ws_ev_a.as<int2>(), p.slice_cap, d.ca, d.ca_dev, tg, d.xd, ctx->ws_ev_cnt.as<int>(),         \
@@ -1519,7 +1519,7 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
   // stale, which is fine: this only tunes, every setting gives the same lists).  Lists that outgrew
   // their buckets: wider buckets from now on; many such records: offsets + scatter as launches of their
   // own in front of the finish kernel instead of every overflowed query collecting its own records.
-  const unsigned prev_overflow = ctx->mailbox ? *reinterpret_cast<volatile unsigned *>(ctx->mailbox) : 0u;
+  const unsigned prev_overflow = ctx->mailbox.p ? *ctx->mailbox.as<volatile unsigned>() : 0u;
   if (prev_overflow > 0 && ctx->bkt_mult < 16) ctx->bkt_mult *= 2;
 
   const RadiusPlan p = plan_radius(ctx, nq, cap, prev_overflow, ext != nullptr);
@@ -1569,7 +1569,7 @@ int launch_nn_radius(rrtx_ctx *ctx, const double *q_dev, const double *r_dev_thr
     f.offsets = offsets_dev; f.needed = needed_dev; f.idx = idx_dev; f.dist = dist_dev; f.out_cap = (long long)cap;
     f.owner = owner_dev; f.nearest_idx = nearest_idx_dev; f.nearest_dist = nearest_dist_dev;
     f.qhist = d.qhist; f.n_qhist = p.use_cull ? p.n_buckets + 1 : 0;
-    f.mailbox = ctx->mailbox;
+    f.mailbox = ctx->mailbox.as<unsigned>();
     f.q = q_dev;
     f.r_start = (!r_dev_thr_lt && r_scalar > 0.0) ? 2.0 * r_scalar : 1.0;
     f.hit_out = p.fuse ? ext->hit_out : nullptr; f.hit_in = p.fuse ? ext->hit_in : nullptr;

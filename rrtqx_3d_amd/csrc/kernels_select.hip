@@ -154,21 +154,12 @@ int node_cost_ensure(rrtx_ctx *ctx) {
   const int64_t n = ctx->n_nodes;
   if (n > ctx->node_lmc_cap || !ctx->node_lmc) {
     const int64_t nc = std::max<int64_t>(std::max<int64_t>(ctx->cap_nodes, n), 1024);
-    double *nb = nullptr;
-    hipError_t e = hipMalloc(&nb, sizeof(double) * (size_t)nc);
-    if (e != hipSuccess) return fail(ctx, RRTX_E_NOMEM, "hipMalloc of %lld node costs failed: %s", (long long)nc, hipGetErrorString(e));
-    if (ctx->node_lmc) {
-      if (ctx->node_lmc_n > 0)
-        RRTX_HIP(ctx, hipMemcpyAsync(nb, ctx->node_lmc, sizeof(double) * (size_t)ctx->node_lmc_n, hipMemcpyDeviceToDevice, ctx->stream));
-      RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      RRTX_HIP(ctx, hipFree(ctx->node_lmc));
-    }
-    ctx->node_lmc = nb;
+    if (int rc = regrow(ctx, ctx->node_lmc, nc, ctx->node_lmc_n)) return rc;
     ctx->node_lmc_cap = nc;
   }
   if (n > ctx->node_lmc_n) {
     const long long m = (long long)(n - ctx->node_lmc_n);
-    hipLaunchKernelGGL(select_fill_inf_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, ctx->node_lmc,
+    hipLaunchKernelGGL(select_fill_inf_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, ctx->node_lmc.get(),
                        (long long)ctx->node_lmc_n, m);
     RRTX_HIP(ctx, hipGetLastError());
     ctx->node_lmc_n = n;

@@ -28,6 +28,7 @@
 // screen proves s >= thr; survivors are decided by the unfused fp64 sq3 from the fp64 table.  Nearly every (row, lane)
 // has no survivor, so the common path only takes the minimum of the lane's kScanFU screen values and compares once.
 #include "nn_device.hpp"
+#include "block_layout.hpp"
 
 namespace rrtx {
 namespace {
@@ -973,27 +974,20 @@ int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, doubl
                         uint8_t *hit_out_dev, uint8_t *hit_in_dev, int32_t *count_dev, uint8_t *tree_hit_out_dev,
                         uint8_t *tree_hit_in_dev) {
   if (nq <= 0) return RRTX_OK;
-  // ws_self: table (32 B a sample), shadow (16 B), the two "offsets" arrays of the edge kernels (only their last word
-  // is read: the number of entries), the compact row list, the tree column's node indices, the rows' own indices, C and
-  // the number of rows.  ws_owner: the owner row of every slot.
-  const size_t n = (size_t)nq, cap = n * (size_t)k;
-  const size_t off_shadow = sizeof(double4) * n, off_slots = off_shadow + sizeof(float4) * n;
-  const size_t off_rowsend = off_slots + sizeof(int64_t) * (n + 1), off_max = off_rowsend + sizeof(int64_t) * (n + 1);
-  const size_t off_rows = off_max + sizeof(unsigned long long), off_near = off_rows + sizeof(int) * n;
-  const size_t off_rown = off_near + sizeof(int32_t) * n, off_nrows = off_rown + sizeof(int32_t) * n;
-  RRTX_HIP(ctx, ctx->ws_self.ensure(off_nrows + sizeof(int)));
-  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * cap));
-  char *ws = ctx->ws_self.as<char>();
-  double4 *tab = reinterpret_cast<double4 *>(ws);
-  float4 *shadow = reinterpret_cast<float4 *>(ws + off_shadow);
-  int64_t *slots_off = reinterpret_cast<int64_t *>(ws + off_slots), *rows_off = reinterpret_cast<int64_t *>(ws + off_rowsend);
-  unsigned long long *absmax = reinterpret_cast<unsigned long long *>(ws + off_max);
-  int32_t *row_owner = reinterpret_cast<int32_t *>(ws + off_rown);
+  const ClosestSelfBlock B{(size_t)nq, (size_t)k, false};   // ws_self (block_layout.hpp)
+  const size_t n = B.n, cap = B.slots;
+  RRTX_HIP(ctx, ctx->ws_self.ensure(B.bytes));
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(B.owner_bytes));
+  void *ws = ctx->ws_self.p;
+  double4 *tab = B.tab.in_as<double4>(ws);
+  float4 *shadow = B.shadow.in_as<float4>(ws);
+  int64_t *slots_off = B.slots_off.in(ws), *rows_off = B.rows_off.in(ws);
+  unsigned long long *absmax = B.absmax.in(ws);
+  int32_t *row_owner = B.row_owner.in(ws), *tree_near = tree_idx_dev ? B.tree_near.in(ws) : nullptr;
   RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
   ClosestPlan p;
   p.tab = tab; p.want = want_dev; p.tree_idx = tree_idx_dev; p.nq = nq; p.k = k;
-  p.rows = reinterpret_cast<int *>(ws + off_rows); p.n_rows = reinterpret_cast<int *>(ws + off_nrows);
-  p.tree_near = tree_idx_dev ? reinterpret_cast<int32_t *>(ws + off_near) : nullptr;
+  p.rows = B.rows.in(ws); p.n_rows = B.n_rows.in(ws); p.tree_near = tree_near;
   p.slots_end = slots_off + n; p.rows_end = rows_off + n;
   ClosestRows a;
   a.tab = tab; a.shadow = shadow; a.absmax = absmax; a.rows = p.rows; a.n_rows = p.n_rows; a.nq = nq; a.k = k;
@@ -1038,30 +1032,22 @@ int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k
                                uint8_t *tree_word_out_dev, uint8_t *tree_word_in_dev, uint8_t *tree_hit_out_dev,
                                uint8_t *tree_hit_in_dev) {
   if (nq <= 0) return RRTX_OK;
-  // ws_self: four coordinate columns (32 B a sample), shadow (16 B), the two "offsets" arrays of the edge kernels (only
-  // their last word is read: the number of entries), C, the shadows' norms, the compact row list, the tree column's node
-  // indices, the rows' own indices, the number of rows, the marks.  ws_owner: the owner row of every slot.
-  const size_t n = (size_t)nq, cap = n * (size_t)k;
-  const size_t off_shadow = sizeof(double) * 4 * n, off_slots = off_shadow + sizeof(float4) * n;
-  const size_t off_rowsend = off_slots + sizeof(int64_t) * (n + 1), off_max = off_rowsend + sizeof(int64_t) * (n + 1);
-  const size_t off_spp = off_max + sizeof(unsigned long long), off_rows = off_spp + sizeof(float) * n;
-  const size_t off_near = off_rows + sizeof(int) * n, off_rown = off_near + sizeof(int32_t) * n;
-  const size_t off_nrows = off_rown + sizeof(int32_t) * n, off_mark = off_nrows + sizeof(int);
-  RRTX_HIP(ctx, ctx->ws_self.ensure(off_mark + n));
-  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * cap));
-  char *ws = ctx->ws_self.as<char>();
-  double *col = reinterpret_cast<double *>(ws);
-  float4 *shadow = reinterpret_cast<float4 *>(ws + off_shadow);
-  float *spp = reinterpret_cast<float *>(ws + off_spp);
-  uint8_t *mark = reinterpret_cast<uint8_t *>(ws + off_mark);
-  int64_t *slots_off = reinterpret_cast<int64_t *>(ws + off_slots), *rows_off = reinterpret_cast<int64_t *>(ws + off_rowsend);
-  unsigned long long *absmax = reinterpret_cast<unsigned long long *>(ws + off_max);
-  int32_t *row_owner = reinterpret_cast<int32_t *>(ws + off_rown);
+  const ClosestSelfBlock B{(size_t)nq, (size_t)k, true};   // ws_self (block_layout.hpp)
+  const size_t n = B.n, cap = B.slots;
+  RRTX_HIP(ctx, ctx->ws_self.ensure(B.bytes));
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(B.owner_bytes));
+  void *ws = ctx->ws_self.p;
+  double *col = B.tab.in(ws);
+  float4 *shadow = B.shadow.in_as<float4>(ws);
+  float *spp = B.spp.in(ws);
+  uint8_t *mark = B.mark.in(ws);
+  int64_t *slots_off = B.slots_off.in(ws), *rows_off = B.rows_off.in(ws);
+  unsigned long long *absmax = B.absmax.in(ws);
+  int32_t *row_owner = B.row_owner.in(ws), *tree_near = tree_idx_dev ? B.tree_near.in(ws) : nullptr;
   RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
   ClosestPlan4 p;
   p.mark = mark; p.want = want_dev; p.tree_idx = tree_idx_dev; p.nq = nq; p.k = k;
-  p.rows = reinterpret_cast<int *>(ws + off_rows); p.n_rows = reinterpret_cast<int *>(ws + off_nrows);
-  p.tree_near = tree_idx_dev ? reinterpret_cast<int32_t *>(ws + off_near) : nullptr;
+  p.rows = B.rows.in(ws); p.n_rows = B.n_rows.in(ws); p.tree_near = tree_near;
   p.slots_end = slots_off + n; p.rows_end = rows_off + n;
   ClosestRows4 a;
   a.nx = col; a.ny = col + n; a.nz = col + 2 * n; a.nw = col + 3 * n;
@@ -1102,16 +1088,13 @@ int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const
                      int32_t *idx_dev, double *cost_dev, int32_t *owner_dev, int64_t cap, int64_t *needed_dev,
                      const double **table_out) {
   if (nq <= 0) return RRTX_OK;
-  // ws_self: table (32 B a sample), shadow (16 B), row counts, C
-  const size_t n = (size_t)nq;
-  const size_t off_shadow = sizeof(double4) * n, off_count = off_shadow + sizeof(float4) * n;
-  const size_t off_max = (off_count + sizeof(int) * (n + 1) + 7) & ~(size_t)7;
-  RRTX_HIP(ctx, ctx->ws_self.ensure(off_max + sizeof(unsigned long long)));
-  char *ws = ctx->ws_self.as<char>();
-  double4 *tab = reinterpret_cast<double4 *>(ws);
-  float4 *shadow = reinterpret_cast<float4 *>(ws + off_shadow);
-  int *count = reinterpret_cast<int *>(ws + off_count);
-  unsigned long long *absmax = reinterpret_cast<unsigned long long *>(ws + off_max);
+  const SelfJoinBlock B{(size_t)nq, false};   // ws_self (block_layout.hpp)
+  RRTX_HIP(ctx, ctx->ws_self.ensure(B.bytes));
+  void *ws = ctx->ws_self.p;
+  double4 *tab = B.tab.in_as<double4>(ws);
+  float4 *shadow = B.shadow.in_as<float4>(ws);
+  int *count = B.count.in(ws);
+  unsigned long long *absmax = B.absmax.in(ws);
   RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
   SelfJoin a;
   a.tab = tab; a.shadow = shadow; a.absmax = absmax; a.nq = nq;
@@ -1137,37 +1120,30 @@ int launch_self_join_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, double r
                             int64_t *offsets_dev, int32_t *idx_dev, double *key_dev, int32_t *owner_dev, int64_t cap,
                             int64_t *needed_dev, const double **columns_out) {
   if (nq <= 0) return RRTX_OK;
-  // ws_self: four coordinate columns (32 B a sample), shadow (16 B), its norms (4 B), row counts, C, marks
-  const size_t n = (size_t)nq;
-  const size_t off_shadow = sizeof(double) * 4 * n, off_spp = off_shadow + sizeof(float4) * n;
-  const size_t off_count = off_spp + sizeof(float) * n;
-  const size_t off_max = (off_count + sizeof(int) * (n + 1) + 7) & ~(size_t)7;
-  const size_t off_mark = off_max + sizeof(unsigned long long);
-  RRTX_HIP(ctx, ctx->ws_self.ensure(off_mark + n));
-  char *ws = ctx->ws_self.as<char>();
-  double *col = reinterpret_cast<double *>(ws);
-  unsigned long long *absmax = reinterpret_cast<unsigned long long *>(ws + off_max);
+  const SelfJoinBlock B{(size_t)nq, true};   // ws_self (block_layout.hpp)
+  const size_t n = B.n;
+  RRTX_HIP(ctx, ctx->ws_self.ensure(B.bytes));
+  void *ws = ctx->ws_self.p;
+  double *col = B.tab.in(ws);
+  unsigned long long *absmax = B.absmax.in(ws);
   RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
   SelfJoin4 a;
   a.nx = col; a.ny = col + n; a.nz = col + 2 * n; a.nw = col + 3 * n;
-  a.mark = reinterpret_cast<const uint8_t *>(ws + off_mark);
-  a.shadow = reinterpret_cast<const float4 *>(ws + off_shadow);
-  a.spp = reinterpret_cast<const float *>(ws + off_spp);
+  a.mark = B.mark.in(ws); a.shadow = B.shadow.in_as<float4>(ws); a.spp = B.spp.in(ws);
   a.absmax = absmax; a.nq = nq;
   a.thr = thr_first_ge(r);
   a.ox = ctx->origin[0]; a.oy = ctx->origin[1]; a.oz = ctx->origin[2]; a.ow = ctx->origin[3];
   a.wr.n_wraps = ctx->n_wraps;
   for (int w = 0; w < 3; ++w) { a.wr.wd[w] = ctx->wrap_dim[w]; a.wr.wp[w] = ctx->wrap_period[w]; }
   a.wr.thr_gt = thr_first_gt(r);
-  a.count = reinterpret_cast<int *>(ws + off_count); a.offsets = offsets_dev; a.cap = (long long)cap;
+  a.count = B.count.in(ws); a.offsets = offsets_dev; a.cap = (long long)cap;
   a.idx = idx_dev; a.owner = owner_dev; a.key = key_dev;
   const int G = (nq + kSelfGroup - 1) / kSelfGroup;
   const dim3 grid((unsigned)((G + 1) / 2));
   span_begin(ctx, KF_NN_SCAN);
   hipLaunchKernelGGL(self_table4_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, q_dev, nq, skip_dev,
                      a.wr, a.ox, a.oy, a.oz, a.ow, col, col + n, col + 2 * n, col + 3 * n,
-                     reinterpret_cast<uint8_t *>(ws + off_mark), reinterpret_cast<float4 *>(ws + off_shadow),
-                     reinterpret_cast<float *>(ws + off_spp), absmax);
+                     B.mark.in(ws), B.shadow.in_as<float4>(ws), B.spp.in(ws), absmax);
   hipLaunchKernelGGL(self_join4_kernel<false>, grid, dim3(kSelfThreads), 0, ctx->stream, a);
   launch_excl_scan<int64_t>(ctx->stream, a.count, offsets_dev, nq, needed_dev);
   if (cap > 0) hipLaunchKernelGGL(self_join4_kernel<true>, grid, dim3(kSelfThreads), 0, ctx->stream, a);

@@ -220,7 +220,7 @@ int slab_append_run(rrtx_ctx *ctx, int64_t base, int64_t n) {
                      hist, ctx->nodes_f[0], ctx->nodes_f[1], ctx->nodes_f[2], ctx->nodes_f[wi],
                      ctx->nodes_pp, ctx->dim, ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2], ctx->sl_f[wi], ctx->sl_pp, ctx->sl_id,
                      ctx->nodes[0], ctx->nodes[1], ctx->nodes[2], ctx->nodes[wi], ctx->sl_d[0], ctx->sl_d[1], ctx->sl_d[2],
-                     ctx->sl_d[wi], reinterpret_cast<ChunkExt *>(ctx->chunk_ext), hist_next);
+                     ctx->sl_d[wi], reinterpret_cast<ChunkExt *>(ctx->chunk_ext.get()), hist_next);
   RRTX_HIP(ctx, hipGetLastError());
   // chunks of the run (a chunk shared with the batch before counts once)
   ctx->sl_run_chunks += (double)((base + n + kSlabChunk - 1) / kSlabChunk - (base + kSlabChunk - 1) / kSlabChunk);
@@ -290,10 +290,10 @@ int slab_refresh(rrtx_ctx *ctx, long long n_tiles) {
   launch_excl_scan(st, hist, start, KK);
   hipLaunchKernelGGL(slab_sid_kernel, dim3(nb), dim3(256), 0, st, (int)n, sr, start, ctx->sl_id);
   hipLaunchKernelGGL(slab_gather_kernel, dim3(n_chunks), dim3(kSlabChunk), 0, st, (int)n, ctx->sl_id,
-                     reinterpret_cast<const double4 *>(ctx->nodes_aos), ctx->origin[0], ctx->origin[1], ctx->origin[2],
+                     reinterpret_cast<const double4 *>(ctx->nodes_aos.get()), ctx->origin[0], ctx->origin[1], ctx->origin[2],
                      ctx->origin[3], ctx->dim, ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2], ctx->sl_f[ctx->dim == 4 ? 3 : 2],
                      ctx->sl_pp, ctx->sl_d[0], ctx->sl_d[1], ctx->sl_d[2], ctx->sl_d[ctx->dim == 4 ? 3 : 2],
-                     reinterpret_cast<ChunkExt *>(ctx->chunk_ext));
+                     reinterpret_cast<ChunkExt *>(ctx->chunk_ext.get()));
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
   ctx->sl_n_sorted = n;

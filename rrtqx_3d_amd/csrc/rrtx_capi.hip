@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <mutex>
 
+#include "block_layout.hpp"
 #include "exact_math.hpp"
 #include "rrtx_internal.hpp"
 
@@ -226,19 +227,6 @@ __global__ __launch_bounds__(256) void aos_to_soa_kernel(const double *__restric
   }
 }
 
-// reallocate one device array of the node store, keeping the first `keep` elements
-template <class T>
-int regrow(rrtx_ctx *ctx, T *&ptr, int64_t new_count, int64_t keep) {
-  T *nb = nullptr;
-  hipError_t e = hipMalloc(&nb, sizeof(T) * (size_t)new_count);
-  if (e != hipSuccess)
-    return fail(ctx, RRTX_E_NOMEM, "hipMalloc of %lld node slots failed: %s", (long long)new_count, hipGetErrorString(e));
-  if (keep > 0 && ptr) RRTX_HIP(ctx, hipMemcpy(nb, ptr, sizeof(T) * (size_t)keep, hipMemcpyDeviceToDevice));
-  if (ptr) RRTX_HIP(ctx, hipFree(ptr));
-  ptr = nb;
-  return RRTX_OK;
-}
-
 // room for n more edges in the mirror (the five arrays double from 4096, keeping what they hold); RRTX_E_CAPACITY
 // beyond the int32 id range.  Waits on the stream when it has to reallocate.
 int grow_edges(rrtx_ctx *ctx, int64_t n) {
@@ -271,16 +259,7 @@ int grow_nodes(rrtx_ctx *ctx, int64_t need) {
     if ((rc = regrow(ctx, ctx->sl_d[k], nc, ctx->n_nodes))) return rc;
   }
   if ((rc = regrow(ctx, ctx->nodes_pp, nc, ctx->n_nodes))) return rc;
-  {
-    double *old_aos = ctx->nodes_aos;
-    double *nb = nullptr;
-    hipError_t e = hipMalloc(&nb, sizeof(double) * 4 * (size_t)nc);
-    if (e != hipSuccess) return fail(ctx, RRTX_E_NOMEM, "hipMalloc of %lld node slots failed: %s", (long long)nc, hipGetErrorString(e));
-    if (ctx->n_nodes > 0 && old_aos)
-      RRTX_HIP(ctx, hipMemcpy(nb, old_aos, sizeof(double) * 4 * (size_t)ctx->n_nodes, hipMemcpyDeviceToDevice));
-    if (old_aos) RRTX_HIP(ctx, hipFree(old_aos));
-    ctx->nodes_aos = nb;
-  }
+  if ((rc = regrow(ctx, ctx->nodes_aos, 4 * nc, 4 * ctx->n_nodes))) return rc;   // (four doubles a node)
   if ((rc = regrow(ctx, ctx->sl_pp, nc, ctx->n_nodes))) return rc;
   if ((rc = regrow(ctx, ctx->sl_id, nc, ctx->n_nodes))) return rc;
   {
@@ -315,21 +294,18 @@ static bool host_registered(const rrtx_ctx *ctx, const void *p, size_t bytes) {
 static int arena_begin(rrtx_ctx *ctx, size_t need) {
   ctx->h_arena_used = 0;
   ctx->h_pending.clear();
-  if (need <= ctx->h_arena_bytes) return RRTX_OK;
+  if (need <= ctx->h_arena.bytes) return RRTX_OK;
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->h_arena) (void)hipHostFree(ctx->h_arena);
-  ctx->h_arena = nullptr; ctx->h_arena_bytes = 0;
   size_t nb = 1 << 20;
   while (nb < need) nb *= 2;
-  RRTX_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_arena), nb, hipHostMallocDefault));
-  ctx->h_arena_bytes = nb;
+  RRTX_HIP(ctx, ctx->h_arena.alloc(nb, hipHostMallocDefault));   // (nothing of a finished call is kept)
   return RRTX_OK;
 }
 static char *arena_take(rrtx_ctx *ctx, size_t bytes) {
   const size_t at = (ctx->h_arena_used + 63) & ~(size_t)63;
-  if (at + bytes > ctx->h_arena_bytes) return nullptr;
+  if (at + bytes > ctx->h_arena.bytes) return nullptr;
   ctx->h_arena_used = at + bytes;
-  return ctx->h_arena + at;
+  return ctx->h_arena.as<char>() + at;
 }
 // device -> caller array: straight DMA when the array is registered, else through the arena (copied out by
 // arena_flush after the stream has been synchronised)
@@ -412,24 +388,8 @@ static int stage_in_small(rrtx_ctx *ctx, DevBuf &buf, const void *host, size_t b
 }
 
 // ---- packed blocks: what a batched call holds per sample, in one allocation so that it moves in one transfer ----
-// A block is described once, as an ordered list of typed fields (the structs below).  The description gives the byte
-// size of the transfer and every field's address under any base: the device block or its copy in the pinned arena.
-template <class T>
-struct Field {
-  size_t off, count;
-  T *in(void *base) const { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
-  size_t bytes() const { return sizeof(T) * count; }
-  void to(T *dst, void *base) const { if (dst) std::memcpy(dst, in(base), bytes()); }          // (null: not asked for)
-  void from(const T *src, void *base) const { if (src) std::memcpy(in(base), src, bytes()); }  // (null: not given)
-};
-// `n` elements of T appended to a block of `bytes` bytes, at T's own alignment unless one is given
-template <class T>
-Field<T> take(size_t &bytes, size_t n, size_t align = alignof(T)) {
-  bytes = (bytes + align - 1) & ~(align - 1);
-  const Field<T> f{bytes, n};
-  bytes += f.bytes();
-  return f;
-}
+// A block is described once, as an ordered list of typed fields (Field / take of block_layout.hpp; the structs below):
+// that gives the byte size of the transfer and every field's address under any base, the device block or its pinned copy.
 // (a block is made from its sample count alone, B{n}: the fields are then initialised in the order they are declared,
 // which is the layout, and `bytes` grows with them to the size of the block)
 struct CandidatesBlock {            // rrtx_extend_candidates[_dubins]; the _self calls: its CSR prefix alone
@@ -620,6 +580,17 @@ std::mutex g_create_mu;
 
 using namespace rrtx;
 
+// The end of a context, also of one rrtx_create could not finish (no stream yet, or a node store grown in part): what is
+// not memory is undone here; every allocation is then released by the member that owns it.
+rrtx_ctx::~rrtx_ctx() {
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  drain_spans(this);
+  for (auto ev : event_pool) (void)hipEventDestroy(ev);
+  for (const auto &r : h_registered) (void)hipHostUnregister(const_cast<char *>(r.first));
+  if (own_stream) (void)hipStreamDestroy(own_stream);
+}
+
 #define CHECK_CTX_KEEP(ctx)            \
   ::rrtx::ApiRange _rrtx_api_range(__func__); \
   do {                                 \
@@ -673,7 +644,6 @@ int rrtx_create(rrtx_ctx **out, int dim, int device, int64_t node_capacity) {
   int rc = grow_nodes(ctx, node_capacity > 0 ? node_capacity : 1024);
   if (rc != RRTX_OK) {
     g_create_err = ctx->err;
-    (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return rc;
   }
@@ -683,55 +653,6 @@ int rrtx_create(rrtx_ctx **out, int dim, int device, int64_t node_capacity) {
 
 int rrtx_destroy(rrtx_ctx *ctx) {
   if (!ctx) return RRTX_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  drain_spans(ctx);
-  for (auto ev : ctx->event_pool) (void)hipEventDestroy(ev);
-  for (int k = 0; k < 4; ++k)
-    if (ctx->nodes[k]) (void)hipFree(ctx->nodes[k]);
-  for (int k = 0; k < 4; ++k)
-    if (ctx->nodes_f[k]) (void)hipFree(ctx->nodes_f[k]);
-  if (ctx->nodes_pp) (void)hipFree(ctx->nodes_pp);
-  if (ctx->nodes_aos) (void)hipFree(ctx->nodes_aos);
-  for (int k = 0; k < 4; ++k)
-    if (ctx->sl_f[k]) (void)hipFree(ctx->sl_f[k]);
-  for (int k = 0; k < 4; ++k)
-    if (ctx->sl_d[k]) (void)hipFree(ctx->sl_d[k]);
-  if (ctx->sl_pp) (void)hipFree(ctx->sl_pp);
-  if (ctx->sl_id) (void)hipFree(ctx->sl_id);
-  if (ctx->chunk_ext) (void)hipFree(ctx->chunk_ext);
-  ctx->d_absmax.release();
-  ctx->d_xrange.release();
-  DevBuf *bufs[] = {&ctx->d_sph, &ctx->d_sph_reach, &ctx->d_sph_reach_f, &ctx->d_sph_aux, &ctx->d_poly_off, &ctx->d_poly_vxy, &ctx->d_poly_slope, &ctx->d_poly_meta,
-                    &ctx->d_poly_orig, &ctx->d_poly_bbox, &ctx->d_poly_ytab, &ctx->d_poly_pbox, &ctx->d_poly_grid_start, &ctx->d_poly_grid_items, &ctx->d_poly_path_off, &ctx->d_poly_path, &ctx->ws_knn_off, &ctx->ws_knn_idx,
-                    &ctx->ws_knn_dist, &ctx->ws_knn_misc, &ctx->ws_q, &ctx->ws_q2, &ctx->ws_slots, &ctx->ws_copies,
-                    &ctx->ws_copy_meta, &ctx->ws_copies_f, &ctx->ws_recs, &ctx->ws_counts, &ctx->ws_bsum, &ctx->ws_scalars, &ctx->ws_scalars_nn, &ctx->ws_tmp,
-                    &ctx->ws_owner, &ctx->ws_dub_rec, &ctx->ws_dub_ckpt, &ctx->ws_out_off, &ctx->ws_out_idx, &ctx->ws_out_dist, &ctx->ws_out_u8a,
-                    &ctx->ws_out_u8b, &ctx->ws_out_i32, &ctx->ws_out_f64, &ctx->ws_partial, &ctx->ws_thr, &ctx->ws_mask, &ctx->ws_i32a, &ctx->ws_i32b,
-                    &ctx->ws_slab_hist, &ctx->ws_slab_start, &ctx->ws_slab_sr, &ctx->ws_slab_params, &ctx->ws_run_hist, &ctx->ws_run_sr,
-                    &ctx->ws_copies_s,
-                    &ctx->ws_meta_s, &ctx->ws_cb, &ctx->ws_qhist, &ctx->ws_qslot, &ctx->ws_bkt,
-                    &ctx->ws_ev_a, &ctx->ws_ev_cnt, &ctx->ws_confirm_args, &ctx->ws_sph_lists, &ctx->ws_poly_lists, &ctx->ws_self, &ctx->d_sph_sample,
-                    &ctx->ws_sweep_mark, &ctx->ws_sweep_flag, &ctx->ws_sweep_cnt, &ctx->ws_sweep_start,
-                    &ctx->ws_swb_tab, &ctx->ws_swb_word, &ctx->ws_swb_seg_id, &ctx->ws_swb_seg_word, &ctx->ws_swb_blk_n, &ctx->ws_swb_cnt,
-                    &ctx->ws_swb_pos, &ctx->ws_swb_base, &ctx->ws_swb_off, &ctx->ws_rel_stay, &ctx->ws_pswb_q, &ctx->ws_pswb_pos,
-                    &ctx->ws_pswb_cand_id, &ctx->ws_pswb_cand_word, &ctx->ws_pswb_hit, &ctx->ws_prel_stay,
-                    &ctx->gc.lmc, &ctx->gc.parent, &ctx->gc.stamp, &ctx->gc.flags, &ctx->gc.orph, &ctx->gc.anc, &ctx->gc.ids,
-                    &ctx->gc.in_cnt, &ctx->gc.in_start, &ctx->gc.in_cursor, &ctx->gc.in_tiles, &ctx->gc.in_src, &ctx->gc.in_w,
-                    &ctx->gc.in_pos, &ctx->gc.rep_lmc, &ctx->gc.rep_parent, &ctx->gc.delta_cnt, &ctx->gc.delta_pos, &ctx->ws_sel_cnt, &ctx->ws_sel_blk, &ctx->ws_sel_rwn, &ctx->ws_sel_rwv, &ctx->ws_sel_lmc,
-                    &ctx->ws_tgt_blk[0], &ctx->ws_tgt_blk[1], &ctx->ws_tgt_res,
-                    &ctx->ws_link_cnt, &ctx->ws_link_row, &ctx->ws_link_res, &ctx->ws_link_node, &ctx->ws_link_get, &ctx->ws_delta_node};
-  for (auto b : bufs) b->release();
-  if (ctx->node_lmc) (void)hipFree(ctx->node_lmc);
-  if (ctx->ge_start) (void)hipFree(ctx->ge_start);
-  if (ctx->ge_end) (void)hipFree(ctx->ge_end);
-  if (ctx->ge_dist) (void)hipFree(ctx->ge_dist);
-  if (ctx->ge_dist0) (void)hipFree(ctx->ge_dist0);
-  if (ctx->ge_dirty) (void)hipFree(ctx->ge_dirty);
-  if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
-  if (ctx->h_arena) (void)hipHostFree(ctx->h_arena);
-  for (const auto &r : ctx->h_registered) (void)hipHostUnregister(const_cast<char *>(r.first));
-  (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return RRTX_OK;
 }
@@ -914,7 +835,7 @@ int rrtx_nodes_append_dev(rrtx_ctx *ctx, const double *pos_dev, int64_t n) {
                      ctx->nodes_f[ctx->dim == 4 ? 3 : 2], ctx->nodes_pp, ctx->d_absmax.as<unsigned long long>(),
                      ctx->sl_f[0], ctx->sl_f[1], ctx->sl_f[2], ctx->sl_f[ctx->dim == 4 ? 3 : 2], ctx->sl_pp, ctx->sl_id,
                      ctx->sl_d[0], ctx->sl_d[1], ctx->sl_d[2], ctx->sl_d[ctx->dim == 4 ? 3 : 2], ctx->nodes_aos,
-                     reinterpret_cast<ChunkExt *>(ctx->chunk_ext), ctx->d_xrange.as<unsigned long long>(), as_run ? 1 : 0, rr);
+                     reinterpret_cast<ChunkExt *>(ctx->chunk_ext.get()), ctx->d_xrange.as<unsigned long long>(), as_run ? 1 : 0, rr);
   RRTX_HIP(ctx, hipGetLastError());
   if (as_run) {
     rc = slab_append_run(ctx, ctx->n_nodes, n);

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rrtx.h"
@@ -57,21 +58,74 @@ struct alignas(64) SweepQueryOwned { SweepQuery q; unsigned long long owner; dou
 // host-side mirror of exact_math.hpp's ChunkExt (this header is also read by plain C++)
 struct ChunkExtHost { unsigned long long xlo, xhi, ylo, yhi; };
 
-struct DevBuf {
+// ---- owners of device and pinned memory --------------------------------------
+// Every allocation of the library belongs to a member of one of these types and is released by its destructor; they
+// move and do not copy.  hipMalloc / hipFree / hipHostMalloc / hipHostFree are called here and nowhere else.
+template <hipError_t (*Free)(void *)>
+struct Owned {
   void *p = nullptr;
   size_t bytes = 0;
-  hipError_t ensure(size_t need) {
-    if (need <= bytes) return hipSuccess;
+  Owned() = default;
+  Owned(const Owned &) = delete;   // (and so no copy assignment either: a move assignment is declared)
+  Owned(Owned &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  Owned &operator=(Owned &&o) noexcept {   // (releases what it held)
+    if (this != &o) { release(); std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    return *this;
+  }
+  ~Owned() { release(); }
+  void release() { if (p) (void)Free(p); p = nullptr; bytes = 0; }
+  template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+struct DevBuf : Owned<hipFree> {
+  size_t grown(size_t need) const {   // what a need beyond `bytes` is rounded to: doubled from 4096 or from what is held
     size_t nb = bytes ? bytes : 4096;
     while (nb < need) nb *= 2;
+    return nb;
+  }
+  hipError_t ensure(size_t need) {     // room for `need` bytes; what the buffer held is not kept
+    if (need <= bytes) return hipSuccess;
+    const size_t nb = grown(need);
     if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; bytes = 0; }
     hipError_t e = hipMalloc(&p, nb);
     if (e == hipSuccess) bytes = nb;
     return e;
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-  template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+  // THE grow-and-keep routine: a new block of exactly `new_bytes`, the first `keep` bytes of the old one copied on `st`
+  // and waited for, the old block freed.  On failure the new block is freed and the old one stays.
+  hipError_t regrow(size_t new_bytes, size_t keep, hipStream_t st) {
+    DevBuf nb;
+    hipError_t e = hipMalloc(&nb.p, new_bytes);
+    if (e != hipSuccess) return e;
+    nb.bytes = new_bytes;
+    if (p && keep > 0) e = hipMemcpyAsync(nb.p, p, keep, hipMemcpyDeviceToDevice, st);
+    if (p && e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) *this = std::move(nb);
+    return e;
+  }
+  hipError_t ensure_keep(size_t need, size_t keep, hipStream_t st) {   // ensure, keeping the first `keep` bytes
+    return need <= bytes ? hipSuccess : regrow(grown(need), keep, st);
+  }
 };
+// A device array of T, read where a T * is expected and sized by its owner's policy (regrow: exactly `count` elements).
+// get() is for the places an implicit conversion does not reach: a deduced template parameter, a cast.
+template <class T>
+struct DevArray {
+  DevBuf buf;
+  T *get() const { return buf.as<T>(); }
+  operator T *() const { return get(); }
+  hipError_t regrow(size_t count, size_t keep, hipStream_t st) { return buf.regrow(sizeof(T) * count, sizeof(T) * keep, st); }
+};
+// pinned host memory (hipHostMalloc with the given flags); alloc replaces what is held
+struct PinnedBuf : Owned<hipHostFree> {
+  hipError_t alloc(size_t nb, unsigned flags) {
+    release();
+    const hipError_t e = hipHostMalloc(&p, nb, flags);
+    if (e == hipSuccess) bytes = nb;
+    return e;
+  }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_constructible<DevArray<double>>::value &&
+              !std::is_copy_constructible<PinnedBuf>::value, "an allocation has one owner");
 
 // cost propagation over the edge mirror (kernels_graph.hip): the state of the last solve stays on the device
 struct GraphCost {
@@ -103,8 +157,8 @@ struct rrtx_ctx {
   // host-pointer entry points: results leave the device through ONE pinned staging arena (hipHostMalloc; DMA at PCIe
   // rate, no driver-side staging of pageable memory) and are copied into the caller's arrays after the final sync --
   // unless the caller registered its arrays (rrtx_host_register), in which case the DMA goes straight to them
-  char *h_arena = nullptr;
-  size_t h_arena_bytes = 0, h_arena_used = 0;
+  rrtx::PinnedBuf h_arena;
+  size_t h_arena_used = 0;
   struct HostCopy { void *dst; const void *src; size_t bytes; };
   std::vector<HostCopy> h_pending;                       // arena -> caller copies to run after the next sync
   std::vector<std::pair<const char *, size_t>> h_registered;
@@ -112,13 +166,13 @@ struct rrtx_ctx {
   std::string err;
 
   // node SoA (fp64), one array per coordinate
-  double *nodes[4] = {nullptr, nullptr, nullptr, nullptr};
+  rrtx::DevArray<double> nodes[4];
   // the same coordinates, four doubles per node (x y z w): one 32-byte read per random node access
-  double *nodes_aos = nullptr;
+  rrtx::DevArray<double> nodes_aos;
   // fp32 shadow of the node SoA for the conservative range prefilter
   // (kernels_nn.hip, nn_scan_f32_kernel); never used to decide a result
-  float *nodes_f[4] = {nullptr, nullptr, nullptr, nullptr};
-  float *nodes_pp = nullptr;        // |p~|^2 of the shifted fp32 coordinates
+  rrtx::DevArray<float> nodes_f[4];
+  rrtx::DevArray<float> nodes_pp;   // |p~|^2 of the shifted fp32 coordinates
   double origin[4] = {0, 0, 0, 0};  // shift applied before the fp32 conversion (first node)
   bool origin_set = false;
   int64_t n_nodes = 0, cap_nodes = 0;
@@ -132,11 +186,11 @@ struct rrtx_ctx {
   // Inside a chunk the positions are lane-major: scan lane L owns positions 8 L .. 8 L + 7, so
   // its eight nodes are two 16-byte loads per array and the exact re-test of a flagged lane
   // reads eight consecutive doubles (sl_d: the same order in fp64).
-  float *sl_f[4] = {nullptr, nullptr, nullptr, nullptr};
-  double *sl_d[4] = {nullptr, nullptr, nullptr, nullptr};
-  float *sl_pp = nullptr;
-  int32_t *sl_id = nullptr;
-  rrtx::ChunkExtHost *chunk_ext = nullptr;   // x / y extent of every chunk (enc_ord), see exact_math.hpp ChunkExt
+  rrtx::DevArray<float> sl_f[4];
+  rrtx::DevArray<double> sl_d[4];
+  rrtx::DevArray<float> sl_pp;
+  rrtx::DevArray<int32_t> sl_id;
+  rrtx::DevArray<rrtx::ChunkExtHost> chunk_ext;   // x / y extent of every chunk (enc_ord), see exact_math.hpp ChunkExt
   int64_t cap_chunks = 0;
   int64_t sl_n_sorted = 0;
   double sl_run_chunks = 0.0;       // chunks of the tail that were appended as sorted runs
@@ -223,7 +277,7 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_qslot;                // bucket-slot table of the culled search without ghosts (QSlots)
   rrtx::DevBuf ws_bkt;      // per-query hit buckets (16-byte records)
   int bkt_mult = 2;         // bucket capacity in units of the average list length the caller made room for
-  unsigned *mailbox = nullptr;   // host-mapped words the finish kernel reports to: [0] overflow records of a call
+  rrtx::PinnedBuf mailbox;       // host-mapped words the finish kernel reports to: [0] overflow records of a call
   rrtx::DevBuf ws_ev_a, ws_ev_cnt, ws_confirm_args;   // per-wave entry slices, their counts, confirm arguments
   rrtx::DevBuf ws_recs;     // HitRec
   rrtx::DevBuf ws_counts;   // int32 count[nq], cursor[nq]
@@ -245,10 +299,10 @@ struct rrtx_ctx {
   rrtx::DevBuf ws_self;           // rrtx_extend_candidates_self[_dubins]: sample table, its fp32 shadow, row counts, max |q - origin|
 
   // device mirror of the planner's directed edges (obstacle sweeps, kernels_sweep.hip)
-  int32_t *ge_start = nullptr, *ge_end = nullptr;
-  double *ge_dist = nullptr;        // edge.dist of every mirrored edge (Inf = blocked); SimpleEdge cost by default
-  double *ge_dist0 = nullptr;       // edge.distOriginal: what append / set_dist wrote last (block leaves it alone)
-  uint8_t *ge_dirty = nullptr;      // edge cost touched since the last cost solve (set_dist / block)
+  rrtx::DevArray<int32_t> ge_start, ge_end;
+  rrtx::DevArray<double> ge_dist;   // edge.dist of every mirrored edge (Inf = blocked); SimpleEdge cost by default
+  rrtx::DevArray<double> ge_dist0;  // edge.distOriginal: what append / set_dist wrote last (block leaves it alone)
+  rrtx::DevArray<uint8_t> ge_dirty; // edge cost touched since the last cost solve (set_dist / block)
   rrtx::GraphCost gc;               // cost propagation state (kernels_graph.hip)
   int64_t ge_n = 0, ge_cap = 0;
   rrtx::DevBuf ws_sweep_mark, ws_sweep_flag, ws_sweep_cnt, ws_sweep_start;
@@ -270,7 +324,7 @@ struct rrtx_ctx {
   std::vector<int32_t> prel_stay_host;              // what ws_prel_stay is copied from (lives until the call's sync)
 
   // parent / rewire selection over the extend lists (kernels_select.hip)
-  double *node_lmc = nullptr;       // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
+  rrtx::DevArray<double> node_lmc;  // rrtLMC per node as rrtx_node_cost_set left it (+Inf: never set)
   int64_t node_lmc_cap = 0, node_lmc_n = 0;   // slots allocated; slots initialised (follows n_nodes)
   rrtx::DevBuf ws_sel_cnt;          // int32 rewire entries per sample
   rrtx::DevBuf ws_sel_blk;          // rrtx_extend_select: everything that is per sample, one block (SelectBlock, rrtx_capi.hip)
@@ -310,6 +364,8 @@ struct rrtx_ctx {
   int last_tile_form = 0;           // rrtx_last_tile_form: 0 none, 1 looped, 2 straight
   int64_t last_sweep_candidates = 0;
   int last_visit_slices = 0;        // entries of ws_ev_cnt holding its per-wave chunk counts
+
+  ~rrtx_ctx();                      // what is not memory (rrtx_capi.hip); the members then release what they own
 };
 
 namespace rrtx {
@@ -574,6 +630,14 @@ struct TargetRound {
 };
 int launch_target_round(rrtx_ctx *ctx, const TargetRound &T);
 int node_cost_ensure(rrtx_ctx *ctx);   // ctx->node_lmc covers every node (new slots +Inf)
+// a.regrow(count, keep) on the context's stream; RRTX_E_NOMEM when the allocation fails
+template <class T>
+int regrow(rrtx_ctx *ctx, DevArray<T> &a, int64_t count, int64_t keep) {
+  const hipError_t e = a.regrow((size_t)count, (size_t)keep, ctx->stream);
+  if (e == hipErrorOutOfMemory) return fail(ctx, RRTX_E_NOMEM, "hipMalloc of %lld array elements failed", (long long)count);
+  RRTX_HIP(ctx, e);
+  return RRTX_OK;
+}
 
 // make sure the packed obstacle tables on the device match the host truth
 int sync_spheres(rrtx_ctx *ctx, double robot_radius);
