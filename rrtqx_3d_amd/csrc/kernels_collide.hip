@@ -1843,6 +1843,17 @@ int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, 
   return RRTX_OK;
 }
 
+int launch_list_edges(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double robot_radius, double r_min, double r,
+                      NearTable near) {
+  if (ctx->dim == 4) return launch_candidate_dubins(ctx, L, q_dev, nq, r_min, robot_radius, near);
+  const double rl = (r >= 0.0) ? r : -1.0;
+  if (ctx->opt_extend_polygons)
+    return launch_candidate_edges_polygons(ctx, q_dev, nq, L.offsets, L.idx, L.owner, L.cap, robot_radius, L.e.hit_out, L.e.hit_in,
+                                           nullptr, rl, near.p, near.rows);
+  return launch_candidate_edges(ctx, q_dev, nq, L.offsets, L.idx, L.owner, L.cap, robot_radius, L.e.hit_out, L.e.hit_in, rl, nullptr,
+                                near.p, near.rows);
+}
+
 int launch_edges_polygons(rrtx_ctx *ctx, const double *p0_dev, const double *p1_dev, int64_t ne,
                           double robot_radius, int obstacle_or_minus1, int obs_begin, int obs_end,
                           uint8_t *hit_dev, int32_t *first_hit_dev) {

@@ -1544,14 +1544,10 @@ static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int 
 // Candidate Dubins edges of extend(): CSR entry e = (sample qi, node idx[e]); both directed edges
 // sample->near and near->sample are steered and checked (R/DRRT_Q.jl:1951-1963, 2600-2602 with
 // Edge = DubinsEdge).
-int launch_candidate_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
-                            const int32_t *idx_dev, const int32_t *owner_dev, int64_t cap, double r_min,
-                            double robot_radius, double *cost_out, double *cost_in, uint8_t *word_out,
-                            uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in, const double *near_cols,
-                            int64_t n_near) {
-  // near_cols / n_near: the table idx points into, four columns of n_near doubles one after the other (null: the
-  // context's nodes)
-  if (nq <= 0 || cap <= 0) return RRTX_OK;
+int launch_candidate_dubins(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double r_min, double robot_radius,
+                            NearTable near) {
+  // near: the table idx points into, four columns of near.rows doubles one after the other (null: the context's nodes)
+  if (nq <= 0 || L.cap <= 0) return RRTX_OK;
   if (ctx->dim != 4) return fail(ctx, RRTX_E_STATE, "Dubins steering needs a dim=4 [x y t theta] context");
   int rc = sync_polygons(ctx);
   if (rc) return rc;
@@ -1559,17 +1555,17 @@ int launch_candidate_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, const in
   const PolyTab tab = poly_tab(ctx);
   EdgeSrc src = {};
   src.mode = 1;
-  src.q = q_dev; src.offsets = offsets_dev; src.idx = idx_dev; src.owner = owner_dev; src.nq = nq;
+  src.q = q_dev; src.offsets = L.offsets; src.idx = L.idx; src.owner = L.owner; src.nq = nq;
   src.nx = ctx->nodes[0]; src.ny = ctx->nodes[1]; src.nz = ctx->nodes[2]; src.nw = ctx->nodes[3];
   src.n_nodes = (int)ctx->n_nodes;
-  if (near_cols) {
-    src.nx = near_cols; src.ny = near_cols + n_near; src.nz = near_cols + 2 * n_near; src.nw = near_cols + 3 * n_near;
-    src.n_nodes = (int)n_near;
+  if (near.p) {
+    src.nx = near.p; src.ny = near.p + near.rows; src.nz = near.p + 2 * near.rows; src.nw = near.p + 3 * near.rows;
+    src.n_nodes = (int)near.rows;
   }
-  src.cap = (long long)cap;
+  src.cap = (long long)L.cap;
   src.dir = 0;
-  return run_dubins_edges(ctx, src, (long long)cap, 0, r_min, robot_radius, tab, true, cost_out, word_out, hit_out, nullptr,
-                          cost_in, word_in, hit_in);
+  return run_dubins_edges(ctx, src, (long long)L.cap, 0, r_min, robot_radius, tab, true, L.e.cost_out, L.e.word_out, L.e.hit_out,
+                          nullptr, L.e.cost_in, L.e.word_in, L.e.hit_in);
 }
 
 int launch_detmath_eval(rrtx_ctx *ctx, int op, const double *x_dev, const double *y_dev, int64_t n, double *out_dev) {

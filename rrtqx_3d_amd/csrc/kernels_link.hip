@@ -161,9 +161,10 @@ __global__ void link_gather_kernel(const int32_t *__restrict__ ids, long long n,
 LinkArgs link_args(rrtx_ctx *ctx, const LinkLists &L) {
   LinkArgs a;
   a.nq = L.nq;
-  a.offsets = L.offsets; a.idx = L.idx; a.cost_out = L.cost_out; a.cost_in = L.cost_in;
-  a.hit_out = L.hit_out; a.hit_in = L.hit_in;
-  a.n_valid = L.n_valid_dev; a.cap = (long long)L.cap;
+  const ListsRO &V = L.lists;
+  a.offsets = V.offsets; a.idx = V.idx; a.cost_out = V.e.cost_out; a.cost_in = V.e.cost_in;
+  a.hit_out = V.e.hit_out; a.hit_in = V.e.hit_in;
+  a.n_valid = V.count; a.cap = (long long)V.cap;
   a.node_of = L.node_of; a.idx_is_batch = L.idx_is_batch ? 1 : 0;
   a.n_nodes = (long long)ctx->n_nodes;
   a.row_cnt = ctx->ws_link_cnt.as<int>();

@@ -771,14 +771,11 @@ int launch_nn_nearest(rrtx_ctx *ctx, const double *q_dev, int nq, int32_t *idx_d
   return launch_nn_nearest_screened(ctx, q_dev, nq, idx_dev, dist_dev);
 }
 
-int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
-                              const int32_t *idx_dev, const double *dist_dev, int32_t *nearest_idx_dev,
-                              double *nearest_dist_dev) {
-  (void)q_dev;
+int launch_nearest_from_lists(rrtx_ctx *ctx, const ListsRO &L, int nq, int32_t *nearest_idx_dev, double *nearest_dist_dev) {
   if (nq <= 0) return RRTX_OK;
   span_begin(ctx, KF_NN_FINISH);
   hipLaunchKernelGGL(nn_nearest_from_lists_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream,
-                     offsets_dev, idx_dev, dist_dev, nq, nearest_idx_dev, nearest_dist_dev);
+                     L.offsets, L.idx, L.key, nq, nearest_idx_dev, nearest_dist_dev);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
   return RRTX_OK;

@@ -133,9 +133,10 @@ int launch_select(rrtx_ctx *ctx, const SelectLaunch &L) {
   RRTX_HIP(ctx, ctx->ws_sel_cnt.ensure(sizeof(int) * (size_t)(L.nq > 0 ? L.nq : 1)));
   SelArgs a;
   a.nq = L.nq;
-  a.offsets = L.offsets; a.idx = L.idx; a.cost_out = L.cost_out; a.cost_in = L.cost_in;
-  a.hit_out = L.hit_out; a.hit_in = L.hit_in;
-  a.n_valid = L.n_valid_dev; a.cap = (long long)L.cap;
+  const ListsRO &V = L.lists;
+  a.offsets = V.offsets; a.idx = V.idx; a.cost_out = V.e.cost_out; a.cost_in = V.e.cost_in;
+  a.hit_out = V.e.hit_out; a.hit_in = V.e.hit_in;
+  a.n_valid = V.count; a.cap = (long long)V.cap;
   a.unsafe = L.sample_unsafe; a.lmc = L.lmc; a.n_lmc = (long long)L.n_lmc;
   a.parent_idx = L.parent_idx; a.parent_entry = L.parent_entry; a.lmc_new = L.lmc_new; a.status = L.status;
   a.rw_count = ctx->ws_sel_cnt.as<int>();

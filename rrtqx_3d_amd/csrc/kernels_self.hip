@@ -969,36 +969,32 @@ __global__ __launch_bounds__(kSelfThreads) void closest_rows4_kernel(const Close
 
 }  // namespace
 
-int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, const uint8_t *skip_dev,
-                        const uint8_t *want_dev, const int32_t *tree_idx_dev, int32_t *idx_dev, double *cost_dev,
-                        uint8_t *hit_out_dev, uint8_t *hit_in_dev, int32_t *count_dev, uint8_t *tree_hit_out_dev,
-                        uint8_t *tree_hit_in_dev) {
+int launch_closest_self(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, int k, double robot_radius,
+                        const uint8_t *skip_dev, const uint8_t *want_dev, int32_t *count_dev, const TreeColumn &tree) {
   if (nq <= 0) return RRTX_OK;
-  const ClosestSelfBlock B{(size_t)nq, (size_t)k, false};   // ws_self (block_layout.hpp)
+  const ClosestSelfBlock B{(size_t)nq, (size_t)k, false};   // ws_self (block_layout.hpp); L.owner holds B.owner_bytes
   const size_t n = B.n, cap = B.slots;
   RRTX_HIP(ctx, ctx->ws_self.ensure(B.bytes));
-  RRTX_HIP(ctx, ctx->ws_owner.ensure(B.owner_bytes));
   void *ws = ctx->ws_self.p;
   double4 *tab = B.tab.in_as<double4>(ws);
   float4 *shadow = B.shadow.in_as<float4>(ws);
   int64_t *slots_off = B.slots_off.in(ws), *rows_off = B.rows_off.in(ws);
   unsigned long long *absmax = B.absmax.in(ws);
-  int32_t *row_owner = B.row_owner.in(ws), *tree_near = tree_idx_dev ? B.tree_near.in(ws) : nullptr;
+  int32_t *row_owner = B.row_owner.in(ws), *tree_near = tree.tree_idx ? B.tree_near.in(ws) : nullptr;
   RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
   ClosestPlan p;
-  p.tab = tab; p.want = want_dev; p.tree_idx = tree_idx_dev; p.nq = nq; p.k = k;
+  p.tab = tab; p.want = want_dev; p.tree_idx = tree.tree_idx; p.nq = nq; p.k = k;
   p.rows = B.rows.in(ws); p.n_rows = B.n_rows.in(ws); p.tree_near = tree_near;
   p.slots_end = slots_off + n; p.rows_end = rows_off + n;
   ClosestRows a;
   a.tab = tab; a.shadow = shadow; a.absmax = absmax; a.rows = p.rows; a.n_rows = p.n_rows; a.nq = nq; a.k = k;
   a.ox = ctx->origin[0]; a.oy = ctx->origin[1]; a.oz = ctx->origin[2];
-  a.idx = idx_dev; a.count = count_dev; a.cost = cost_dev;
+  a.idx = L.idx; a.count = count_dev; a.cost = L.key;
   span_begin(ctx, KF_NN_SCAN);
   hipLaunchKernelGGL(self_table_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, q_dev, nq, skip_dev,
                      a.ox, a.oy, a.oz, tab, shadow, absmax);
-  hipLaunchKernelGGL(closest_fill_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, nq, k, idx_dev,
-                     cost_dev, hit_out_dev, hit_in_dev, count_dev, ctx->ws_owner.as<int32_t>(), row_owner, tree_hit_out_dev,
-                     tree_hit_in_dev);
+  hipLaunchKernelGGL(closest_fill_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, nq, k, L.idx,
+                     L.key, L.e.hit_out, L.e.hit_in, count_dev, L.owner, row_owner, tree.e.hit_out, tree.e.hit_in);
   hipLaunchKernelGGL(closest_plan_kernel, dim3(1), dim3(kPlanThreads), 0, ctx->stream, p);
   hipLaunchKernelGGL(closest_rows_kernel, dim3((unsigned)((nq + kClosestGroup - 1) / kClosestGroup)), dim3(kSelfThreads), 0,
                      ctx->stream, a);
@@ -1006,36 +1002,23 @@ int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, doubl
   RRTX_HIP(ctx, hipGetLastError());
   // both directed edges of every slot against the WHOLE obstacle list (r < 0), by the kernels of rrtx_extend_candidates:
   // slot e = (row e / k, sample idx[e]); an empty slot (idx -1) and everything past the last filled row is left alone
-  const double *table = reinterpret_cast<const double *>(tab);
-  int rc;
-  if (ctx->opt_extend_polygons)
-    rc = launch_candidate_edges_polygons(ctx, q_dev, nq, slots_off, idx_dev, ctx->ws_owner.as<int32_t>(), (int64_t)cap,
-                                         robot_radius, hit_out_dev, hit_in_dev, nullptr, -1.0, table, nq);
-  else
-    rc = launch_candidate_edges(ctx, q_dev, nq, slots_off, idx_dev, ctx->ws_owner.as<int32_t>(), (int64_t)cap, robot_radius,
-                                hit_out_dev, hit_in_dev, -1.0, nullptr, table, nq);
-  if (rc || !tree_idx_dev) return rc;
+  Lists slots = L;
+  slots.offsets = slots_off; slots.cap = (int64_t)cap;
+  int rc = launch_list_edges(ctx, slots, q_dev, nq, robot_radius, 0.0, -1.0, NearTable{B.tab.in(ws), nq});
+  if (rc || !tree.tree_idx) return rc;
   // the tree column: one entry a row, (row j, node tree_idx[j]); an index outside the tree is left alone by the kernels
   if (ctx->n_nodes <= 0 || !ctx->nodes_aos) return RRTX_OK;
-  if (ctx->opt_extend_polygons)
-    return launch_candidate_edges_polygons(ctx, q_dev, nq, rows_off, p.tree_near, row_owner, (int64_t)nq, robot_radius,
-                                           tree_hit_out_dev, tree_hit_in_dev, nullptr, -1.0);
-  return launch_candidate_edges(ctx, q_dev, nq, rows_off, p.tree_near, row_owner, (int64_t)nq, robot_radius, tree_hit_out_dev,
-                                tree_hit_in_dev, -1.0);
+  return launch_list_edges(ctx, Lists{rows_off, nullptr, tree_near, row_owner, nullptr, tree.e, nq}, q_dev, nq, robot_radius, 0.0,
+                           -1.0);
 }
 
-int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, double r_min,
-                               const uint8_t *skip_dev, const uint8_t *want_dev, const int32_t *tree_idx_dev,
-                               int32_t *idx_dev, double *key_dev, double *cost_out_dev, double *cost_in_dev,
-                               uint8_t *word_out_dev, uint8_t *word_in_dev, uint8_t *hit_out_dev, uint8_t *hit_in_dev,
-                               int32_t *count_dev, double *tree_cost_out_dev, double *tree_cost_in_dev,
-                               uint8_t *tree_word_out_dev, uint8_t *tree_word_in_dev, uint8_t *tree_hit_out_dev,
-                               uint8_t *tree_hit_in_dev) {
+int launch_closest_self_dubins(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, int k, double robot_radius,
+                               double r_min, const uint8_t *skip_dev, const uint8_t *want_dev, int32_t *count_dev,
+                               const TreeColumn &tree) {
   if (nq <= 0) return RRTX_OK;
-  const ClosestSelfBlock B{(size_t)nq, (size_t)k, true};   // ws_self (block_layout.hpp)
+  const ClosestSelfBlock B{(size_t)nq, (size_t)k, true};   // ws_self (block_layout.hpp); L.owner holds B.owner_bytes
   const size_t n = B.n, cap = B.slots;
   RRTX_HIP(ctx, ctx->ws_self.ensure(B.bytes));
-  RRTX_HIP(ctx, ctx->ws_owner.ensure(B.owner_bytes));
   void *ws = ctx->ws_self.p;
   double *col = B.tab.in(ws);
   float4 *shadow = B.shadow.in_as<float4>(ws);
@@ -1043,10 +1026,10 @@ int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k
   uint8_t *mark = B.mark.in(ws);
   int64_t *slots_off = B.slots_off.in(ws), *rows_off = B.rows_off.in(ws);
   unsigned long long *absmax = B.absmax.in(ws);
-  int32_t *row_owner = B.row_owner.in(ws), *tree_near = tree_idx_dev ? B.tree_near.in(ws) : nullptr;
+  int32_t *row_owner = B.row_owner.in(ws), *tree_near = tree.tree_idx ? B.tree_near.in(ws) : nullptr;
   RRTX_HIP(ctx, hipMemsetAsync(absmax, 0, sizeof(unsigned long long), ctx->stream));
   ClosestPlan4 p;
-  p.mark = mark; p.want = want_dev; p.tree_idx = tree_idx_dev; p.nq = nq; p.k = k;
+  p.mark = mark; p.want = want_dev; p.tree_idx = tree.tree_idx; p.nq = nq; p.k = k;
   p.rows = B.rows.in(ws); p.n_rows = B.n_rows.in(ws); p.tree_near = tree_near;
   p.slots_end = slots_off + n; p.rows_end = rows_off + n;
   ClosestRows4 a;
@@ -1057,14 +1040,14 @@ int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k
   a.wr.n_wraps = ctx->n_wraps;
   for (int w = 0; w < 3; ++w) { a.wr.wd[w] = ctx->wrap_dim[w]; a.wr.wp[w] = ctx->wrap_period[w]; }
   a.wr.thr_gt = __builtin_inf();             // no copy is skipped, so C covers every copy of every live sample; the first tau
-  a.idx = idx_dev; a.count = count_dev; a.key = key_dev;
+  a.idx = L.idx; a.count = count_dev; a.key = L.key;
   span_begin(ctx, KF_NN_SCAN);
   hipLaunchKernelGGL(self_table4_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, q_dev, nq, skip_dev,
                      a.wr, a.ox, a.oy, a.oz, a.ow, col, col + n, col + 2 * n, col + 3 * n, mark, shadow, spp, absmax);
-  hipLaunchKernelGGL(closest_fill4_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, nq, k, idx_dev,
-                     key_dev, cost_out_dev, cost_in_dev, word_out_dev, word_in_dev, hit_out_dev, hit_in_dev, count_dev,
-                     ctx->ws_owner.as<int32_t>(), row_owner, tree_cost_out_dev, tree_cost_in_dev, tree_word_out_dev,
-                     tree_word_in_dev, tree_hit_out_dev, tree_hit_in_dev);
+  hipLaunchKernelGGL(closest_fill4_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, nq, k, L.idx,
+                     L.key, L.e.cost_out, L.e.cost_in, L.e.word_out, L.e.word_in, L.e.hit_out, L.e.hit_in, count_dev,
+                     L.owner, row_owner, tree.e.cost_out, tree.e.cost_in, tree.e.word_out, tree.e.word_in, tree.e.hit_out,
+                     tree.e.hit_in);
   hipLaunchKernelGGL(closest_plan4_kernel, dim3(1), dim3(kPlanThreads), 0, ctx->stream, p);
   hipLaunchKernelGGL(closest_rows4_kernel, dim3((unsigned)((nq + kClosestGroup - 1) / kClosestGroup)), dim3(kSelfThreads), 0,
                      ctx->stream, a);
@@ -1073,20 +1056,18 @@ int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k
   // both directed Dubins edges of every slot, by the kernels of rrtx_extend_candidates_dubins: slot e = (row e / k, sample
   // idx[e]) with the sample columns as the near table; an empty slot (idx -1) and everything past the last filled row is
   // left alone
-  int rc = launch_candidate_dubins(ctx, q_dev, nq, slots_off, idx_dev, ctx->ws_owner.as<int32_t>(), (int64_t)cap, r_min,
-                                   robot_radius, cost_out_dev, cost_in_dev, word_out_dev, word_in_dev, hit_out_dev,
-                                   hit_in_dev, col, nq);
-  if (rc || !tree_idx_dev) return rc;
+  Lists slots = L;
+  slots.offsets = slots_off; slots.cap = (int64_t)cap;
+  int rc = launch_candidate_dubins(ctx, slots, q_dev, nq, r_min, robot_radius, NearTable{col, nq});
+  if (rc || !tree.tree_idx) return rc;
   // the tree column: one entry a row, (row j, node tree_idx[j]); an index outside the tree is left alone by the kernels
   if (ctx->n_nodes <= 0 || !ctx->nodes[0]) return RRTX_OK;
-  return launch_candidate_dubins(ctx, q_dev, nq, rows_off, p.tree_near, row_owner, (int64_t)nq, r_min, robot_radius,
-                                 tree_cost_out_dev, tree_cost_in_dev, tree_word_out_dev, tree_word_in_dev, tree_hit_out_dev,
-                                 tree_hit_in_dev);
+  return launch_candidate_dubins(ctx, Lists{rows_off, nullptr, tree_near, row_owner, nullptr, tree.e, nq}, q_dev, nq, r_min,
+                                 robot_radius);
 }
 
-int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev, int64_t *offsets_dev,
-                     int32_t *idx_dev, double *cost_dev, int32_t *owner_dev, int64_t cap, int64_t *needed_dev,
-                     const double **table_out) {
+int launch_self_join(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
+                     NearTable *table_out) {
   if (nq <= 0) return RRTX_OK;
   const SelfJoinBlock B{(size_t)nq, false};   // ws_self (block_layout.hpp)
   RRTX_HIP(ctx, ctx->ws_self.ensure(B.bytes));
@@ -1100,25 +1081,24 @@ int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const
   a.tab = tab; a.shadow = shadow; a.absmax = absmax; a.nq = nq;
   a.thr = thr_first_ge(r);
   a.ox = ctx->origin[0]; a.oy = ctx->origin[1]; a.oz = ctx->origin[2];
-  a.count = count; a.offsets = offsets_dev; a.cap = (long long)cap;
-  a.idx = idx_dev; a.owner = owner_dev; a.cost = cost_dev;
+  a.count = count; a.offsets = L.offsets; a.cap = (long long)L.cap;
+  a.idx = L.idx; a.owner = L.owner; a.cost = L.key;
   const int G = (nq + kSelfGroup - 1) / kSelfGroup;
   const dim3 grid((unsigned)((G + 1) / 2));
   span_begin(ctx, KF_NN_SCAN);
   hipLaunchKernelGGL(self_table_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, q_dev, nq, skip_dev,
                      a.ox, a.oy, a.oz, tab, shadow, absmax);
   hipLaunchKernelGGL(self_join_kernel<false>, grid, dim3(kSelfThreads), 0, ctx->stream, a);
-  launch_excl_scan<int64_t>(ctx->stream, count, offsets_dev, nq, needed_dev);
-  if (cap > 0) hipLaunchKernelGGL(self_join_kernel<true>, grid, dim3(kSelfThreads), 0, ctx->stream, a);
+  launch_excl_scan<int64_t>(ctx->stream, count, L.offsets, nq, L.count);
+  if (L.cap > 0) hipLaunchKernelGGL(self_join_kernel<true>, grid, dim3(kSelfThreads), 0, ctx->stream, a);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
-  if (table_out) *table_out = reinterpret_cast<const double *>(tab);
+  if (table_out) *table_out = NearTable{B.tab.in(ws), nq};
   return RRTX_OK;
 }
 
-int launch_self_join_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
-                            int64_t *offsets_dev, int32_t *idx_dev, double *key_dev, int32_t *owner_dev, int64_t cap,
-                            int64_t *needed_dev, const double **columns_out) {
+int launch_self_join_dubins(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
+                            NearTable *table_out) {
   if (nq <= 0) return RRTX_OK;
   const SelfJoinBlock B{(size_t)nq, true};   // ws_self (block_layout.hpp)
   const size_t n = B.n;
@@ -1136,8 +1116,8 @@ int launch_self_join_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, double r
   a.wr.n_wraps = ctx->n_wraps;
   for (int w = 0; w < 3; ++w) { a.wr.wd[w] = ctx->wrap_dim[w]; a.wr.wp[w] = ctx->wrap_period[w]; }
   a.wr.thr_gt = thr_first_gt(r);
-  a.count = B.count.in(ws); a.offsets = offsets_dev; a.cap = (long long)cap;
-  a.idx = idx_dev; a.owner = owner_dev; a.key = key_dev;
+  a.count = B.count.in(ws); a.offsets = L.offsets; a.cap = (long long)L.cap;
+  a.idx = L.idx; a.owner = L.owner; a.key = L.key;
   const int G = (nq + kSelfGroup - 1) / kSelfGroup;
   const dim3 grid((unsigned)((G + 1) / 2));
   span_begin(ctx, KF_NN_SCAN);
@@ -1145,11 +1125,11 @@ int launch_self_join_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, double r
                      a.wr, a.ox, a.oy, a.oz, a.ow, col, col + n, col + 2 * n, col + 3 * n,
                      B.mark.in(ws), B.shadow.in_as<float4>(ws), B.spp.in(ws), absmax);
   hipLaunchKernelGGL(self_join4_kernel<false>, grid, dim3(kSelfThreads), 0, ctx->stream, a);
-  launch_excl_scan<int64_t>(ctx->stream, a.count, offsets_dev, nq, needed_dev);
-  if (cap > 0) hipLaunchKernelGGL(self_join4_kernel<true>, grid, dim3(kSelfThreads), 0, ctx->stream, a);
+  launch_excl_scan<int64_t>(ctx->stream, a.count, L.offsets, nq, L.count);
+  if (L.cap > 0) hipLaunchKernelGGL(self_join4_kernel<true>, grid, dim3(kSelfThreads), 0, ctx->stream, a);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
-  if (columns_out) *columns_out = col;
+  if (table_out) *table_out = NearTable{col, nq};
   return RRTX_OK;
 }
 

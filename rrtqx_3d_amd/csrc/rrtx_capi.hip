@@ -491,11 +491,9 @@ int resolve_lmc(rrtx_ctx *ctx, const double *lmc_host, Lmc *lmc) {
 // columns one after the other in ws_out_dist, the flag bytes out / in in ws_out_u8a / _u8b with the words behind them.
 // cols = 1: SimpleEdge's one cost column, which is key, cost_out and cost_in alike; cols = 3: the Dubins key | cost_out |
 // cost_in.  words: the Dubins word columns (null without).  The addresses are taken after every ensure; lists that are
-// held (sel_hold_*) are found again with the arguments they were made with, which then ensure nothing anew.
-struct NeighbourLists {
-  int32_t *idx, *owner; double *key, *cost_out, *cost_in; uint8_t *word_out, *word_in, *hit_out, *hit_in; int64_t cap;
-};
-int neighbour_lists(rrtx_ctx *ctx, int64_t cap, int cols, bool words, NeighbourLists *L) {
+// held (sel_hold_*) are found again with the arguments they were made with, which then ensure nothing anew.  offsets and
+// count are the call's own (null here): it sets them once the block that holds them is ensured.
+int neighbour_lists(rrtx_ctx *ctx, int64_t cap, int cols, bool words, Lists *L) {
   const size_t n = (size_t)std::max<int64_t>(cap, 1);
   RRTX_HIP(ctx, ctx->ws_out_idx.ensure(sizeof(int32_t) * n));
   RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * n));
@@ -504,26 +502,27 @@ int neighbour_lists(rrtx_ctx *ctx, int64_t cap, int cols, bool words, NeighbourL
   RRTX_HIP(ctx, ctx->ws_out_u8b.ensure((words ? 1 + kWordBytes : 1) * n));
   double *key = ctx->ws_out_dist.as<double>();
   uint8_t *out = ctx->ws_out_u8a.as<uint8_t>(), *in = ctx->ws_out_u8b.as<uint8_t>();
-  *L = NeighbourLists{ctx->ws_out_idx.as<int32_t>(), ctx->ws_owner.as<int32_t>(), key, cols == 3 ? key + n : key,
-                      cols == 3 ? key + 2 * n : key, words ? out + n : nullptr, words ? in + n : nullptr, out, in, cap};
+  *L = Lists{nullptr, nullptr, ctx->ws_out_idx.as<int32_t>(), ctx->ws_owner.as<int32_t>(), key,
+             EdgeCols{cols == 3 ? key + n : key, cols == 3 ? key + 2 * n : key, words ? out + n : nullptr,
+                      words ? in + n : nullptr, out, in}, cap};
   return RRTX_OK;
 }
 // the caller's arrays for the columns of a call's lists (null: not asked for, or the call has no such column)
 struct ListsOut { int32_t *idx; double *key, *cost_out, *cost_in; uint8_t *word_out, *word_in, *hit_out, *hit_in; };
 // fn(caller's array, device column, bytes an entry) for every column
 template <class Fn>
-int each_column_out(const NeighbourLists &L, const ListsOut &to, Fn fn) {
+int each_column_out(const Lists &L, const ListsOut &to, Fn fn) {
   int rc = fn(to.key, L.key, sizeof(double));
-  if (!rc) rc = fn(to.cost_out, L.cost_out, sizeof(double));
-  if (!rc) rc = fn(to.cost_in, L.cost_in, sizeof(double));
+  if (!rc) rc = fn(to.cost_out, L.e.cost_out, sizeof(double));
+  if (!rc) rc = fn(to.cost_in, L.e.cost_in, sizeof(double));
   if (!rc) rc = fn(to.idx, L.idx, sizeof(int32_t));
-  if (!rc) rc = fn(to.word_out, L.word_out, kWordBytes);
-  if (!rc) rc = fn(to.word_in, L.word_in, kWordBytes);
-  if (!rc) rc = fn(to.hit_out, L.hit_out, 1);
-  return rc ? rc : fn(to.hit_in, L.hit_in, 1);
+  if (!rc) rc = fn(to.word_out, L.e.word_out, kWordBytes);
+  if (!rc) rc = fn(to.word_in, L.e.word_in, kWordBytes);
+  if (!rc) rc = fn(to.hit_out, L.e.hit_out, 1);
+  return rc ? rc : fn(to.hit_in, L.e.hit_in, 1);
 }
 // the first n entries of the columns the caller asked for, queued (d2h skips a null array)
-int lists_down(rrtx_ctx *ctx, const NeighbourLists &L, int64_t n, const ListsOut &to) {
+int lists_down(rrtx_ctx *ctx, const Lists &L, int64_t n, const ListsOut &to) {
   return each_column_out(L, to, [&](void *dst, const void *src, size_t entry) { return d2h(ctx, dst, src, entry * (size_t)n); });
 }
 // what d2h may take from the arena for up to `cap` entries of `entry` bytes, ...
@@ -533,7 +532,7 @@ size_t out_need(const void *dst, size_t entry, int64_t cap) {
 // ... and for the lists of a call
 size_t lists_need(const ListsOut &to, int64_t cap) {
   size_t need = 0;
-  each_column_out(NeighbourLists{}, to, [&](const void *dst, const void *, size_t entry) { need += out_need(dst, entry, cap); return 0; });
+  each_column_out(Lists{}, to, [&](const void *dst, const void *, size_t entry) { need += out_need(dst, entry, cap); return 0; });
   return need;
 }
 // the end of a call that queued n entries or slots: the transfers waited for, the staged ones copied to the caller
@@ -548,17 +547,18 @@ int lists_finish(rrtx_ctx *ctx, int64_t n) {
 // sized once from what the last search produced, and when an attempt produces more, grown to that with an eighth of
 // headroom and the attempt made once more.  `attempt` enqueues the search and what follows it over lists of L.cap
 // entries; the `bytes` at `dev`, which begin with the int64 count of entries the search produced, are then read back
-// into the arena at `host`.
+// into the arena at `host`.  offsets: the CSR of the attempt (ensured by the caller), which with the count completes L.
 template <class Attempt>
-int with_neighbour_lists(rrtx_ctx *ctx, const char *fn, int nq, int64_t at_least, int cols, void *host, const void *dev,
-                         size_t bytes, Attempt attempt) {
+int with_neighbour_lists(rrtx_ctx *ctx, const char *fn, int nq, int64_t at_least, int cols, int64_t *offsets, void *host,
+                         int64_t *dev, size_t bytes, Attempt attempt) {
   int64_t cap = ctx->sel_list_cap > 0 ? ctx->sel_list_cap
                                       : std::max<int64_t>(ctx->last_neighbors + ctx->last_neighbors / 8, std::max<int64_t>(64 * (int64_t)nq, 1024));
   cap = std::max(cap, at_least);
   for (int again = 0;; ++again) {
-    NeighbourLists L;
+    Lists L;
     int rc = neighbour_lists(ctx, cap, cols, false, &L);
     if (rc) return rc;
+    L.offsets = offsets; L.count = dev;
     ctx->sel_list_cap = cap;
     rc = attempt(L);
     if (rc) return rc;
@@ -1238,7 +1238,7 @@ int append_lists_dev(rrtx_ctx *ctx, const char *fn, LinkLists L, int64_t *first_
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const unsigned verdict = (unsigned)res[2];
   if (verdict & kLinkOverflow)
-    return fail(ctx, RRTX_E_CAPACITY, "%s: the extend call produced more entries than the lists hold (%lld)", fn, (long long)L.cap);
+    return fail(ctx, RRTX_E_CAPACITY, "%s: the extend call produced more entries than the lists hold (%lld)", fn, (long long)L.lists.cap);
   if (verdict & kLinkBadOffsets) return fail(ctx, RRTX_E_INVALID, "%s: offsets out of order or beyond the lists", fn);
   if (verdict & kLinkBadNode)
     return fail(ctx, RRTX_E_INVALID, "%s: node_of references a node outside [0, %lld)", fn, (long long)ctx->n_nodes);
@@ -1263,10 +1263,9 @@ int rrtx_graph_edges_append_lists_dev(rrtx_ctx *ctx, int nq, const int64_t *offs
   CHECK_CTX_KEEP(ctx);
   int rc = append_lists_args(ctx, "graph_edges_append_lists_dev", nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, cap, node_of);
   if (rc) return rc;
-  return append_lists_dev(ctx, "graph_edges_append_lists_dev",
-                          LinkLists{nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, n_valid_dev, cap, node_of,
-                                    idx_is_batch != 0, row_first},
-                          first_id, n_added);
+  const ListsRO L{offsets, n_valid_dev, idx, nullptr, nullptr, {cost_out, cost_in, nullptr, nullptr, hit_out, hit_in}, cap};
+  return append_lists_dev(ctx, "graph_edges_append_lists_dev", LinkLists{nq, L, node_of, idx_is_batch != 0, row_first}, first_id,
+                          n_added);
 }
 
 int rrtx_graph_edges_append_lists(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
@@ -1299,10 +1298,10 @@ int rrtx_graph_edges_append_lists(rrtx_ctx *ctx, int nq, const int64_t *offsets,
   RRTX_HIP(ctx, ctx->ws_link_row.ensure(sizeof(int64_t) * rows));
   const double *co = ctx->ws_out_dist.as<double>();
   rc = append_lists_dev(ctx, fn,
-                        LinkLists{nq, ctx->ws_out_off.as<int64_t>(), ctx->ws_out_idx.as<int32_t>(), co,
-                                  one_cost ? co : ctx->ws_out_f64.as<double>(), ctx->ws_out_u8a.as<uint8_t>(),
-                                  ctx->ws_out_u8b.as<uint8_t>(), nullptr, n_valid, ctx->ws_link_node.as<int32_t>(),
-                                  idx_is_batch != 0, ctx->ws_link_row.as<int64_t>()},
+                        LinkLists{nq, ListsRO{ctx->ws_out_off.as<int64_t>(), nullptr, ctx->ws_out_idx.as<int32_t>(), nullptr, nullptr,
+                                              {co, one_cost ? co : ctx->ws_out_f64.as<double>(), nullptr, nullptr,
+                                               ctx->ws_out_u8a.as<uint8_t>(), ctx->ws_out_u8b.as<uint8_t>()}, n_valid},
+                                  ctx->ws_link_node.as<int32_t>(), idx_is_batch != 0, ctx->ws_link_row.as<int64_t>()},
                         first_id, n_added);
   if (rc) return rc;
   if (row_first && (rc = d2h(ctx, row_first, ctx->ws_link_row.p, sizeof(int64_t) * rows))) return rc;
@@ -1331,11 +1330,10 @@ int rrtx_graph_edges_append_selected(rrtx_ctx *ctx, int nq, const int32_t *node_
   RRTX_HIP(ctx, ctx->ws_link_row.ensure(sizeof(int64_t) * rows));
   const SelectBlock B{(size_t)nq};
   char *blk = ctx->ws_sel_blk.as<char>();
-  NeighbourLists L;      // the held lists, as the select call made them
+  Lists L;               // the held lists, as the select call made them
   if ((rc = neighbour_lists(ctx, ctx->sel_list_cap, ctx->sel_hold_cols, false, &L))) return rc;
-  rc = append_lists_dev(ctx, fn,
-                        LinkLists{nq, B.offsets.in(blk), L.idx, L.cost_out, L.cost_in, L.hit_out, L.hit_in, B.counts.in(blk),
-                                  L.cap, ctx->ws_link_node.as<int32_t>(), false, ctx->ws_link_row.as<int64_t>()},
+  L.offsets = B.offsets.in(blk); L.count = B.counts.in(blk);
+  rc = append_lists_dev(ctx, fn, LinkLists{nq, read_only(L), ctx->ws_link_node.as<int32_t>(), false, ctx->ws_link_row.as<int64_t>()},
                         first_id, n_added);
   if (rc) return rc;
   if (row_first && (rc = d2h(ctx, row_first, ctx->ws_link_row.p, sizeof(int64_t) * rows))) return rc;
@@ -2054,6 +2052,18 @@ int rrtx_extend_candidates_dev(rrtx_ctx *ctx, const double *q, int nq, double r,
                                 hit_in, (r >= 0.0) ? r : -1.0, sample_unsafe);
 }
 
+// The samples of a batch among themselves into L, nq > 0: the join, then both directed edges of every entry by the
+// kernels of the preamble: the "near" end of entry e is row idx[e] of the sample table instead of a node; the per-sample
+// obstacle lists are built for this batch and ball.  A dim = 4 context: [x y t theta] and Dubins edges.
+// (dim decides the join and the edge type; extend_self_args / extend_self_dubins_args have refused the other dim, so it
+// agrees with the `dubins` flag by which extend_csr_host chose the columns)
+static int extend_self_lists(rrtx_ctx *ctx, const Lists &L, const double *q, int nq, double r, double robot_radius, double r_min,
+                             const uint8_t *skip) {
+  NearTable table;
+  int rc = ctx->dim == 4 ? launch_self_join_dubins(ctx, L, q, nq, r, skip, &table) : launch_self_join(ctx, L, q, nq, r, skip, &table);
+  return rc ? rc : launch_list_edges(ctx, L, q, nq, robot_radius, r_min, r, table);
+}
+
 // The host form of the calls that return a CSR, after their own refusals.  Everything that is per sample sits in ONE small
 // device block (CandidatesBlock), so that it leaves in one transfer; the per-entry arrays follow once the count is known.
 // Small transfers go through the context's pinned arena, large ones straight to the caller.  self: the _self calls, which
@@ -2066,7 +2076,7 @@ static int extend_csr_host(rrtx_ctx *ctx, const char *fn, bool self, bool dubins
   const CandidatesBlock B{(size_t)nq};
   const size_t blk_bytes = self ? B.csr_bytes : B.bytes;
   const size_t q_bytes = sizeof(double) * (size_t)nq * ctx->dim, skip_bytes = skip ? (size_t)nq : 0;
-  NeighbourLists L;
+  Lists L;
   int rc = neighbour_lists(ctx, cap, dubins ? 3 : 1, dubins, &L);
   if (rc) return rc;
   RRTX_HIP(ctx, ctx->ws_out_off.ensure(blk_bytes));
@@ -2077,18 +2087,14 @@ static int extend_csr_host(rrtx_ctx *ctx, const char *fn, bool self, bool dubins
   const uint8_t *skip_dev = skip ? ctx->ws_q2.as<uint8_t>() : nullptr;
   char *blk = ctx->ws_out_off.as<char>(), *host_blk;
   const bool want_nearest = nearest_idx && nearest_dist;
-  if (!self)
-    rc = rrtx_extend_candidates_dev(ctx, q_dev, nq, r, robot_radius, B.offsets.in(blk), L.idx, L.key, L.hit_out, L.hit_in, cap,
-                                    B.count.in(blk), want_nearest ? B.nearest_idx.in(blk) : nullptr,
+  L.offsets = B.offsets.in(blk); L.count = B.count.in(blk);
+  if (self)
+    rc = extend_self_lists(ctx, L, q_dev, nq, r, robot_radius, r_min, skip_dev);
+  else      // (the SimpleEdge preamble keeps its way through the public positional form)
+    rc = rrtx_extend_candidates_dev(ctx, q_dev, nq, r, robot_radius, L.offsets, L.idx, L.key, L.e.hit_out, L.e.hit_in, cap,
+                                    L.count, want_nearest ? B.nearest_idx.in(blk) : nullptr,
                                     want_nearest ? B.nearest_dist.in(blk) : nullptr,
                                     sample_unsafe ? B.sample_unsafe.in(blk) : nullptr);
-  else if (dubins)
-    rc = rrtx_extend_candidates_self_dubins_dev(ctx, q_dev, nq, r, robot_radius, r_min, skip_dev, B.offsets.in(blk), L.idx, L.key,
-                                                L.cost_out, L.cost_in, L.word_out, L.word_in, L.hit_out, L.hit_in, cap,
-                                                B.count.in(blk));
-  else
-    rc = rrtx_extend_candidates_self_dev(ctx, q_dev, nq, r, robot_radius, skip_dev, B.offsets.in(blk), L.idx, L.key, L.hit_out,
-                                         L.hit_in, cap, B.count.in(blk));
   if (rc) return rc;
   if ((rc = block_down(ctx, fn, blk, blk_bytes, &host_blk))) return rc;
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2139,17 +2145,9 @@ int rrtx_extend_candidates_self_dev(rrtx_ctx *ctx, const double *q, int nq, doub
   int rc = extend_self_args(ctx, q, nq, offsets, idx, cost, hit_out, hit_in, cap);
   if (rc || nq == 0) return rc;
   RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
-  const double *table = nullptr;
-  rc = launch_self_join(ctx, q, nq, r, skip, offsets, idx, cost, ctx->ws_owner.as<int32_t>(), cap, needed_dev, &table);
-  if (rc) return rc;
-  // both directed edges of every entry, by the kernels of rrtx_extend_candidates: the "near" end of entry e is row
-  // idx[e] of the sample table instead of a node; the per-sample obstacle lists are built for this batch and ball
-  const double rl = (r >= 0.0) ? r : -1.0;
-  if (ctx->opt_extend_polygons)
-    return launch_candidate_edges_polygons(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, robot_radius, hit_out,
-                                           hit_in, nullptr, rl, table, nq);
-  return launch_candidate_edges(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, robot_radius, hit_out, hit_in, rl,
-                                nullptr, table, nq);
+  const Lists L{offsets, needed_dev, idx, ctx->ws_owner.as<int32_t>(), cost,
+                EdgeCols{cost, cost, nullptr, nullptr, hit_out, hit_in}, cap};
+  return extend_self_lists(ctx, L, q, nq, r, robot_radius, 0.0, skip);
 }
 
 int rrtx_extend_candidates_self(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
@@ -2185,8 +2183,12 @@ int rrtx_extend_closest_self_dev(rrtx_ctx *ctx, const double *q, int nq, int k, 
   CHECK_CTX(ctx);
   int rc = extend_closest_args(ctx, q, nq, k, tree_idx, idx, cost, hit_out, hit_in, count, tree_hit_out, tree_hit_in);
   if (rc || nq == 0) return rc;
-  return launch_closest_self(ctx, q, nq, k, robot_radius, skip, want, tree_idx, idx, cost, hit_out, hit_in, count,
-                             tree_hit_out, tree_hit_in);
+  const int64_t slots = (int64_t)nq * k;
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)slots));
+  const Lists L{nullptr, nullptr, idx, ctx->ws_owner.as<int32_t>(), cost,
+                EdgeCols{cost, cost, nullptr, nullptr, hit_out, hit_in}, slots};
+  return launch_closest_self(ctx, L, q, nq, k, robot_radius, skip, want, count,
+                             TreeColumn{tree_idx, EdgeCols{nullptr, nullptr, nullptr, nullptr, tree_hit_out, tree_hit_in}});
 }
 
 int rrtx_extend_closest_self(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, const uint8_t *skip,
@@ -2201,17 +2203,18 @@ int rrtx_extend_closest_self(rrtx_ctx *ctx, const double *q, int nq, int k, doub
   const ClosestInBlock I{n};
   const ClosestBlock B{n};
   const ListsOut to{idx, cost, nullptr, nullptr, nullptr, nullptr, hit_out, hit_in};
-  NeighbourLists L;
+  Lists L;
   if ((rc = neighbour_lists(ctx, slots, 1, false, &L))) return rc;
   RRTX_HIP(ctx, ctx->ws_out_off.ensure(B.bytes));
   if ((rc = arena_begin(ctx, small_in(q_bytes) + block_need(I.bytes) + block_need(B.bytes) + lists_need(to, L.cap)))) return rc;
   if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
   if ((rc = closest_inputs_up(ctx, "extend_closest_self", I, skip, want, tree_idx))) return rc;
   char *in = ctx->ws_q2.as<char>(), *blk = ctx->ws_out_off.as<char>(), *host_blk;
-  rc = rrtx_extend_closest_self_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius, skip ? I.skip.in(in) : nullptr,
-                                    want ? I.want.in(in) : nullptr, tree_idx ? I.tree_idx.in(in) : nullptr, L.idx, L.key,
-                                    L.hit_out, L.hit_in, B.count.in(blk), tree_idx ? B.tree_hit_out.in(blk) : nullptr,
-                                    tree_idx ? B.tree_hit_in.in(blk) : nullptr);
+  TreeColumn tree{};     // (tree_idx null: no tree column)
+  if (tree_idx)
+    tree = TreeColumn{I.tree_idx.in(in), EdgeCols{nullptr, nullptr, nullptr, nullptr, B.tree_hit_out.in(blk), B.tree_hit_in.in(blk)}};
+  rc = launch_closest_self(ctx, L, ctx->ws_q.as<double>(), nq, k, robot_radius, skip ? I.skip.in(in) : nullptr,
+                           want ? I.want.in(in) : nullptr, B.count.in(blk), tree);
   if (rc) return rc;
   // (no count to wait for: the block and the slots come down behind one another)
   if ((rc = block_down(ctx, "extend_closest_self", blk, B.bytes, &host_blk))) return rc;
@@ -2235,24 +2238,17 @@ static int extend_dubins_args(rrtx_ctx *ctx, const double *q, int nq, const int6
   return RRTX_OK;
 }
 
-int rrtx_extend_candidates_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
-                                      double r_min, int64_t *offsets, int32_t *idx, double *key, double *cost_out,
-                                      double *cost_in, uint8_t *word_out, uint8_t *word_in, uint8_t *hit_out,
-                                      uint8_t *hit_in, int64_t cap, int64_t *needed_dev, int32_t *nearest_idx,
-                                      double *nearest_dist, uint8_t *sample_unsafe) {
-  CHECK_CTX(ctx);
-  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
-  if (rc || nq == 0) return rc;
-  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
+// The Dubins preamble into L, nq > 0: radius search, candidate Dubins edges, sample points, then the nearest scan under wraps.
+static int extend_dubins_lists(rrtx_ctx *ctx, const Lists &L, const double *q, int nq, double r, double robot_radius, double r_min,
+                               int32_t *nearest_idx, double *nearest_dist, uint8_t *sample_unsafe) {
   const bool want_nearest = nearest_idx && nearest_dist;
   // with wrapped dimensions a list key is the distance to the copy that found the node FIRST
   // (addToRangeList), not the minimum over the copies, so kdFindNearest cannot be read off the list
   const bool nearest_from_list = want_nearest && ctx->n_wraps == 0;
-  rc = launch_nn_radius(ctx, q, nullptr, r, nq, offsets, idx, key, cap, needed_dev, ctx->ws_owner.as<int32_t>(),
-                        nearest_from_list ? nearest_idx : nullptr, nearest_from_list ? nearest_dist : nullptr);
+  int rc = launch_nn_radius(ctx, q, nullptr, r, nq, L.offsets, L.idx, L.key, L.cap, L.count, L.owner,
+                            nearest_from_list ? nearest_idx : nullptr, nearest_from_list ? nearest_dist : nullptr);
   if (rc) return rc;
-  rc = launch_candidate_dubins(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, r_min, robot_radius, cost_out,
-                               cost_in, word_out, word_in, hit_out, hit_in);
+  rc = launch_candidate_dubins(ctx, L, q, nq, r_min, robot_radius);
   if (rc) return rc;
   if (sample_unsafe) {
     rc = launch_points_polygons(ctx, q, nq, robot_radius, sample_unsafe, nullptr);
@@ -2263,6 +2259,20 @@ int rrtx_extend_candidates_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, do
     if (rc) return rc;
   }
   return RRTX_OK;
+}
+
+int rrtx_extend_candidates_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
+                                      double r_min, int64_t *offsets, int32_t *idx, double *key, double *cost_out,
+                                      double *cost_in, uint8_t *word_out, uint8_t *word_in, uint8_t *hit_out,
+                                      uint8_t *hit_in, int64_t cap, int64_t *needed_dev, int32_t *nearest_idx,
+                                      double *nearest_dist, uint8_t *sample_unsafe) {
+  CHECK_CTX(ctx);
+  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
+  if (rc || nq == 0) return rc;
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
+  const Lists L{offsets, needed_dev, idx, ctx->ws_owner.as<int32_t>(), key,
+                EdgeCols{cost_out, cost_in, word_out, word_in, hit_out, hit_in}, cap};
+  return extend_dubins_lists(ctx, L, q, nq, r, robot_radius, r_min, nearest_idx, nearest_dist, sample_unsafe);
 }
 
 int rrtx_extend_candidates_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
@@ -2319,23 +2329,26 @@ int rrtx_extend_candidates_dubins(rrtx_ctx *ctx, const double *q, int nq, double
 }
 
 // ---- the samples of one Dubins extend batch among themselves (kernels_self.hip) ----------------------
+// (what both forms refuse, before anything is staged: the join packs flags into the top two bits of the owner word)
+static int extend_self_dubins_args(rrtx_ctx *ctx, const double *q, int nq, const int64_t *offsets, const int32_t *idx,
+                                   const double *key, const double *cost_out, const double *cost_in, const uint8_t *hit_out,
+                                   const uint8_t *hit_in, int64_t cap) {
+  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
+  if (rc) return rc;
+  if (nq >= (1 << 30)) return fail(ctx, RRTX_E_INVALID, "extend_candidates_self_dubins: at most 2^30 - 1 samples per call");
+  return RRTX_OK;
+}
 int rrtx_extend_candidates_self_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
                                            double r_min, const uint8_t *skip, int64_t *offsets, int32_t *idx, double *key,
                                            double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
                                            uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed_dev) {
   CHECK_CTX(ctx);
-  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
-  if (rc) return rc;
-  if (nq >= (1 << 30)) return fail(ctx, RRTX_E_INVALID, "extend_candidates_self_dubins: at most 2^30 - 1 samples per call");
-  if (nq == 0) return RRTX_OK;
+  int rc = extend_self_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
+  if (rc || nq == 0) return rc;
   RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)(cap > 0 ? cap : 1)));
-  const double *cols = nullptr;
-  rc = launch_self_join_dubins(ctx, q, nq, r, skip, offsets, idx, key, ctx->ws_owner.as<int32_t>(), cap, needed_dev, &cols);
-  if (rc) return rc;
-  // both directed edges of every entry, by the kernels of rrtx_extend_candidates_dubins: the "near" end of entry e is
-  // row idx[e] of the sample columns instead of a node
-  return launch_candidate_dubins(ctx, q, nq, offsets, idx, ctx->ws_owner.as<int32_t>(), cap, r_min, robot_radius, cost_out,
-                                 cost_in, word_out, word_in, hit_out, hit_in, cols, nq);
+  const Lists L{offsets, needed_dev, idx, ctx->ws_owner.as<int32_t>(), key,
+                EdgeCols{cost_out, cost_in, word_out, word_in, hit_out, hit_in}, cap};
+  return extend_self_lists(ctx, L, q, nq, r, robot_radius, r_min, skip);
 }
 
 int rrtx_extend_candidates_self_dubins(rrtx_ctx *ctx, const double *q, int nq, double r, double robot_radius,
@@ -2343,7 +2356,7 @@ int rrtx_extend_candidates_self_dubins(rrtx_ctx *ctx, const double *q, int nq, d
                                        double *cost_out, double *cost_in, uint8_t *word_out, uint8_t *word_in,
                                        uint8_t *hit_out, uint8_t *hit_in, int64_t cap, int64_t *needed) {
   CHECK_CTX(ctx);
-  int rc = extend_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
+  int rc = extend_self_dubins_args(ctx, q, nq, offsets, idx, key, cost_out, cost_in, hit_out, hit_in, cap);
   if (rc) return rc;
   return extend_csr_host(ctx, "extend_candidates_self_dubins", true, true, q, nq, r, robot_radius, r_min, skip, offsets,
                          ListsOut{idx, key, cost_out, cost_in, word_out, word_in, hit_out, hit_in}, cap, needed);
@@ -2376,10 +2389,13 @@ int rrtx_extend_closest_self_dubins_dev(rrtx_ctx *ctx, const double *q, int nq, 
   int rc = extend_closest_dubins_args(ctx, q, nq, k, tree_idx, idx, key, cost_out, cost_in, hit_out, hit_in, count,
                                       tree_cost_out, tree_cost_in, tree_hit_out, tree_hit_in);
   if (rc || nq == 0) return rc;
-  return launch_closest_self_dubins(ctx, q, nq, k, robot_radius, r_min, skip, want, tree_idx, idx, key, cost_out, cost_in,
-                                    word_out, word_in, hit_out, hit_in, count, tree_cost_out, tree_cost_in,
-                                    tree_idx ? tree_word_out : nullptr, tree_idx ? tree_word_in : nullptr, tree_hit_out,
-                                    tree_hit_in);
+  const int64_t slots = (int64_t)nq * k;
+  RRTX_HIP(ctx, ctx->ws_owner.ensure(sizeof(int32_t) * (size_t)slots));
+  const Lists L{nullptr, nullptr, idx, ctx->ws_owner.as<int32_t>(), key,
+                EdgeCols{cost_out, cost_in, word_out, word_in, hit_out, hit_in}, slots};
+  return launch_closest_self_dubins(ctx, L, q, nq, k, robot_radius, r_min, skip, want, count,
+                                    TreeColumn{tree_idx, EdgeCols{tree_cost_out, tree_cost_in, tree_idx ? tree_word_out : nullptr,
+                                                                  tree_idx ? tree_word_in : nullptr, tree_hit_out, tree_hit_in}});
 }
 
 int rrtx_extend_closest_self_dubins(rrtx_ctx *ctx, const double *q, int nq, int k, double robot_radius, double r_min,
@@ -2398,20 +2414,19 @@ int rrtx_extend_closest_self_dubins(rrtx_ctx *ctx, const double *q, int nq, int 
   const ClosestInBlock I{n};
   const ClosestDubinsBlock B{n};
   const ListsOut to{idx, key, cost_out, cost_in, word_out, word_in, hit_out, hit_in};
-  NeighbourLists L;
+  Lists L;
   if ((rc = neighbour_lists(ctx, slots, 3, true, &L))) return rc;
   RRTX_HIP(ctx, ctx->ws_out_off.ensure(B.bytes));
   if ((rc = arena_begin(ctx, small_in(q_bytes) + block_need(I.bytes) + block_need(B.bytes) + lists_need(to, L.cap)))) return rc;
   if ((rc = stage_in_small(ctx, ctx->ws_q, q, q_bytes))) return rc;
   if ((rc = closest_inputs_up(ctx, "extend_closest_self_dubins", I, skip, want, tree_idx))) return rc;
   char *in = ctx->ws_q2.as<char>(), *blk = ctx->ws_out_off.as<char>(), *host_blk;
-  rc = rrtx_extend_closest_self_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, k, robot_radius, r_min,
-                                           skip ? I.skip.in(in) : nullptr, want ? I.want.in(in) : nullptr,
-                                           tree_idx ? I.tree_idx.in(in) : nullptr, L.idx, L.key, L.cost_out, L.cost_in,
-                                           L.word_out, L.word_in, L.hit_out, L.hit_in, B.count.in(blk),
-                                           tree_idx ? B.tree_cost_out.in(blk) : nullptr, tree_idx ? B.tree_cost_in.in(blk) : nullptr,
-                                           tree_idx ? B.tree_word_out.in(blk) : nullptr, tree_idx ? B.tree_word_in.in(blk) : nullptr,
-                                           tree_idx ? B.tree_hit_out.in(blk) : nullptr, tree_idx ? B.tree_hit_in.in(blk) : nullptr);
+  TreeColumn tree{};     // (tree_idx null: no tree column)
+  if (tree_idx)
+    tree = TreeColumn{I.tree_idx.in(in), EdgeCols{B.tree_cost_out.in(blk), B.tree_cost_in.in(blk), B.tree_word_out.in(blk),
+                                                  B.tree_word_in.in(blk), B.tree_hit_out.in(blk), B.tree_hit_in.in(blk)}};
+  rc = launch_closest_self_dubins(ctx, L, ctx->ws_q.as<double>(), nq, k, robot_radius, r_min, skip ? I.skip.in(in) : nullptr,
+                                  want ? I.want.in(in) : nullptr, B.count.in(blk), tree);
   if (rc) return rc;
   // (no count to wait for: the block and the slots come down behind one another)
   if ((rc = block_down(ctx, "extend_closest_self_dubins", blk, B.bytes, &host_blk))) return rc;
@@ -2440,17 +2455,13 @@ int rrtx_pack_hits_dev(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit
 // ---- parent and rewire selection over the extend lists (kernels_select.hip) -----------------------
 // (the selection over lists on the device, rrtLMC a device array or null for the context's own: shared by the _dev entry
 // point and rrtx_extend_select, which runs it inside its own call)
-static int select_over_lists(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
-                             const double *cost_in, const uint8_t *hit_out, const uint8_t *hit_in,
-                             const int64_t *n_valid_dev, int64_t cap, const uint8_t *sample_unsafe, Lmc lmc,
-                             int32_t *parent_idx, int64_t *parent_entry, double *lmc_new, uint8_t *status,
-                             int64_t *rw_offsets, int32_t *rw_node, double *rw_value, int64_t rw_cap,
-                             int64_t *rw_needed_dev) {
-  int rc = lmc.dev ? RRTX_OK : resolve_lmc(ctx, nullptr, &lmc);
-  if (rc) return rc;
-  return launch_select(ctx, SelectLaunch{nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, n_valid_dev, cap,
-                                         sample_unsafe, lmc.dev, lmc.n, parent_idx, parent_entry, lmc_new, status, rw_offsets,
-                                         rw_node, rw_value, rw_cap, rw_needed_dev});
+static int select_over_lists(rrtx_ctx *ctx, SelectLaunch S) {
+  if (!S.lmc) {
+    Lmc own;
+    if (int rc = resolve_lmc(ctx, nullptr, &own)) return rc;
+    S.lmc = own.dev; S.n_lmc = own.n;
+  }
+  return launch_select(ctx, S);
 }
 
 int rrtx_extend_select_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const int32_t *idx, const double *cost_out,
@@ -2464,8 +2475,9 @@ int rrtx_extend_select_dev(rrtx_ctx *ctx, int nq, const int64_t *offsets, const 
       (nq > 0 && (!parent_idx || !parent_entry || !lmc_new || !status)) ||
       (cap > 0 && (!idx || !cost_out || !cost_in || !hit_out || !hit_in)) || (rw_cap > 0 && (!rw_node || !rw_value)))
     return fail(ctx, RRTX_E_INVALID, "extend_select: bad arguments");
-  return select_over_lists(ctx, nq, offsets, idx, cost_out, cost_in, hit_out, hit_in, n_valid_dev, cap, sample_unsafe,
-                           Lmc{lmc, ctx->n_nodes}, parent_idx, parent_entry, lmc_new, status, rw_offsets, rw_node, rw_value, rw_cap, rw_needed_dev);
+  const ListsRO L{offsets, n_valid_dev, idx, nullptr, nullptr, {cost_out, cost_in, nullptr, nullptr, hit_out, hit_in}, cap};
+  return select_over_lists(ctx, SelectLaunch{nq, L, sample_unsafe, lmc, ctx->n_nodes, parent_idx, parent_entry, lmc_new, status,
+                                             rw_offsets, rw_node, rw_value, rw_cap, rw_needed_dev});
 }
 
 int rrtx_node_cost_set(rrtx_ctx *ctx, int64_t first_index, const double *lmc, int64_t n) {
@@ -2546,25 +2558,24 @@ static int extend_select_host(rrtx_ctx *ctx, const char *fn, bool dubins, const 
   char *host_blk = arena_take(ctx, out_bytes);
   if (!host_blk) return fail(ctx, RRTX_E_NOMEM, "%s: staging arena", fn);
   const bool want_nearest = nearest_idx && nearest_dist;
-  NeighbourLists lists;
-  rc = with_neighbour_lists(ctx, fn, nq, 0, cols, host_blk, blk, out_bytes, [&](const NeighbourLists &L) {
+  Lists lists;
+  rc = with_neighbour_lists(ctx, fn, nq, 0, cols, B.offsets.in(blk), host_blk, B.counts.in(blk), out_bytes, [&](const Lists &L) {
     lists = L;
     int32_t *ni = want_nearest ? B.nearest_idx.in(blk) : nullptr;
     double *nd = want_nearest ? B.nearest_dist.in(blk) : nullptr;
     // (in a wrapped Dubins space the preamble ends with the full nearest scan: it writes the two columns of the select
     // block and its own search workspaces, never a list)
-    int rc = dubins ? rrtx_extend_candidates_dubins_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, r_min,
-                                                        B.offsets.in(blk), L.idx, L.key, L.cost_out, L.cost_in,
-                                                        nullptr, nullptr, L.hit_out, L.hit_in, L.cap, B.counts.in(blk), ni, nd,
-                                                        B.sample_unsafe.in(blk))
-                    : rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, B.offsets.in(blk), L.idx,
-                                                 L.key, L.hit_out, L.hit_in, L.cap, B.counts.in(blk), ni, nd,
-                                                 B.sample_unsafe.in(blk));
+    int rc;
+    if (dubins)
+      rc = extend_dubins_lists(ctx, L, ctx->ws_q.as<double>(), nq, r, robot_radius, r_min, ni, nd, B.sample_unsafe.in(blk));
+    else      // (the SimpleEdge preamble keeps its way through the public positional form)
+      rc = rrtx_extend_candidates_dev(ctx, ctx->ws_q.as<double>(), nq, r, robot_radius, L.offsets, L.idx, L.key, L.e.hit_out,
+                                      L.e.hit_in, L.cap, L.count, ni, nd, B.sample_unsafe.in(blk));
     if (rc) return rc;
-    return select_over_lists(ctx, nq, B.offsets.in(blk), L.idx, L.cost_out, L.cost_in, L.hit_out, L.hit_in, B.counts.in(blk), L.cap,
-                             B.sample_unsafe.in(blk), lmc_dev, B.parent_idx.in(blk), B.parent_entry.in(blk),
-                             B.lmc_new.in(blk), B.status.in(blk), B.rw_offsets.in(blk), ctx->ws_sel_rwn.as<int32_t>(),
-                             ctx->ws_sel_rwv.as<double>(), rw_cap, B.counts.in(blk) + 1);
+    return select_over_lists(ctx, SelectLaunch{nq, read_only(L), B.sample_unsafe.in(blk), lmc_dev.dev, lmc_dev.n,
+                                               B.parent_idx.in(blk), B.parent_entry.in(blk), B.lmc_new.in(blk), B.status.in(blk),
+                                               B.rw_offsets.in(blk), ctx->ws_sel_rwn.as<int32_t>(),
+                                               ctx->ws_sel_rwv.as<double>(), rw_cap, B.counts.in(blk) + 1});
   });
   if (rc) return rc;
   const int64_t total = B.counts.in(host_blk)[0], rw_total = B.counts.in(host_blk)[1];
@@ -2679,24 +2690,16 @@ int find_new_target(rrtx_ctx *ctx, const char *fn, bool dubins, const double *po
     if (round > 64) return fail(ctx, RRTX_E_STATE, "%s: %d poses still searching after 64 rounds", fn, n_act);
     char *cur = ctx->ws_tgt_blk[side].as<char>(), *nxt = ctx->ws_tgt_blk[side ^ 1].as<char>();
     const double *q_dev = Q.pose.in(cur);
-    rc = with_neighbour_lists(ctx, fn, nq, room, dubins ? 3 : 1, host_hdr, hdr_dev, R.hdr.bytes(), [&](const NeighbourLists &L) {
-      int rc = launch_nn_radius(ctx, q_dev, Q.thr.in(cur), 0.0, n_act, off_dev, L.idx, L.key, L.cap, hdr_dev, L.owner);
+    rc = with_neighbour_lists(ctx, fn, nq, room, dubins ? 3 : 1, off_dev, host_hdr, hdr_dev, R.hdr.bytes(), [&](const Lists &L) {
+      int rc = launch_nn_radius(ctx, q_dev, Q.thr.in(cur), 0.0, n_act, L.offsets, L.idx, L.key, L.cap, L.count, L.owner);
       if (rc) return rc;
-      if (dubins) {
-        rc = launch_candidate_dubins(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, r_min, robot_radius, L.cost_out,
-                                     L.cost_in, nullptr, nullptr, L.hit_out, L.hit_in);
-      } else if (ctx->opt_extend_polygons) {
-        rc = launch_candidate_edges_polygons(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, robot_radius, L.hit_out,
-                                             L.hit_in, nullptr, -1.0);
-      } else {      // (r < 0: the radii differ from pose to pose, every sphere is looked at)
-        rc = launch_candidate_edges(ctx, q_dev, n_act, off_dev, L.idx, L.owner, L.cap, robot_radius, L.hit_out, L.hit_in,
-                                    -1.0, nullptr);
-      }
+      // (r < 0: the radii differ from pose to pose, every obstacle is looked at)
+      rc = launch_list_edges(ctx, L, q_dev, n_act, robot_radius, r_min, -1.0);
       if (rc) return rc;
       TargetRound T;
       T.n_act = n_act; T.nq = nq; T.round = round; T.dim = ctx->dim; T.r_max = r_max;
-      T.offsets = off_dev; T.idx = L.idx; T.cost = L.cost_out; T.hit_out = L.hit_out;
-      T.n_valid = hdr_dev; T.cap = (long long)L.cap;
+      T.offsets = L.offsets; T.idx = L.idx; T.cost = L.e.cost_out; T.hit_out = L.e.hit_out;
+      T.n_valid = L.count; T.cap = (long long)L.cap;
       T.lmc = lmc_dev.dev; T.n_lmc = (long long)lmc_dev.n;
       T.q = q_dev; T.rad = Q.rad.in(cur); T.slot = Q.slot.in(cur);
       T.pending = R.pending.in(res);

@@ -421,6 +421,38 @@ double thr_first_ge(double r);
 double thr_first_gt(double r);
 double thr_point_clear(double robot_radius, double radius);
 
+// ---- a call's neighbour lists on the device, as ONE value ------------------------
+// W: the columns may be written (Lists); read-only otherwise (ListsRO, what the selection and the link kernels get).
+// The per-entry results of both directed edges of a list; null: the call has no such column.
+template <bool W>
+struct EdgeColsT {
+  template <class T> using P = std::conditional_t<W, T, const T> *;
+  P<double> cost_out, cost_in; P<uint8_t> word_out, word_in, hit_out, hit_in;
+};
+// The lists: the CSR (offsets of nq + 1 rows, *count = the entries the search produced, which may exceed cap), per entry
+// the near index, the owner row, the key and the edge columns, and the entries every column has room for.  SimpleEdge has
+// one double column, which is key, e.cost_out and e.cost_in alike.  A launcher reads the columns it needs and no other.
+// INVARIANT: a view is built after the last ensure of every buffer it points into, and a function that receives a view
+// ensures none of those buffers (ws_out_*, ws_owner, the block that holds offsets and count).  The SimpleEdge preamble
+// (rrtx_extend_candidates[_dev]), the range search and the two SimpleEdge edge launchers take positional pointers.
+template <bool W>
+struct ListsT {
+  template <class T> using P = std::conditional_t<W, T, const T> *;
+  P<int64_t> offsets, count; P<int32_t> idx, owner; P<double> key; EdgeColsT<W> e; int64_t cap;
+};
+using EdgeCols = EdgeColsT<true>;
+using Lists = ListsT<true>;
+using ListsRO = ListsT<false>;
+inline ListsRO read_only(const Lists &L) {
+  return ListsRO{L.offsets, L.count, L.idx, L.owner, L.key,
+                 {L.e.cost_out, L.e.cost_in, L.e.word_out, L.e.word_in, L.e.hit_out, L.e.hit_in}, L.cap};
+}
+// What idx points into: `rows` rows of a table the edge kernels read in their own layout (launch_candidate_edges and
+// _polygons: four doubles a row; launch_candidate_dubins: four columns of `rows` doubles).  Null: the context's nodes.
+struct NearTable { const double *p = nullptr; int64_t rows = 0; };
+// The tree column of the closest calls: one entry a row, (row j, node tree_idx[j]).  tree_idx null: no such column.
+struct TreeColumn { const int32_t *tree_idx; EdgeCols e; };
+
 // ---- launchers (device pointers, enqueue on ctx->stream) ----------------------
 // Fused extend() work of the range search (sphere list, culled search only): both directed edges of
 // every list entry and explicitPointCheck of the samples; r = radius the lists are built with.
@@ -486,13 +518,10 @@ int launch_sweep_finish(rrtx_ctx *ctx, const int32_t *ids_dev, long long n, cons
 int launch_sweep_gather(rrtx_ctx *ctx, const int32_t *ids_dev, long long n, double *p0_dev, double *p1_dev);
 void packed_range(const std::vector<int32_t> &orig, int begin, int end, int &pb, int &pe);
 std::vector<int32_t> active_positions(const std::vector<uint8_t> &active);
-// idx[e] is a row of near_cols (four columns of n_near doubles, x y t theta one after the other): the context's nodes
-// unless a table is given (the samples themselves, rrtx_extend_candidates_self_dubins)
-int launch_candidate_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
-                            const int32_t *idx_dev, const int32_t *owner_dev, int64_t cap, double r_min,
-                            double robot_radius, double *cost_out, double *cost_in, uint8_t *word_out,
-                            uint8_t *word_in, uint8_t *hit_out, uint8_t *hit_in, const double *near_cols = nullptr,
-                            int64_t n_near = 0);
+// Candidate Dubins edges of extend(): both directed edges of every entry of L steered and checked into L.e (words may be
+// null).  No sample pass; returns at cap <= 0.
+int launch_candidate_dubins(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double r_min, double robot_radius,
+                            NearTable near = {});
 int launch_detmath_eval(rrtx_ctx *ctx, int op, const double *x_dev, const double *y_dev, int64_t n, double *out_dev);
 int launch_dubins_trajectory(rrtx_ctx *ctx, const double *s_dev, const double *g_dev, int64_t ne, double r_min,
                              const int64_t *traj_off_dev, double *traj_xy_dev, int64_t cap_rows,
@@ -509,35 +538,31 @@ int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, 
                                     double robot_radius, uint8_t *hit_out_dev, uint8_t *hit_in_dev,
                                     uint8_t *sample_unsafe_dev, double r = -1.0, const double *near_aos = nullptr,
                                     int64_t n_near = 0);
-// the samples of a batch among themselves (kernels_self.hip): CSR of the earlier samples within r of every sample,
-// keys and owners; device pointers, *needed_dev = entries found, no entry at or beyond cap is written
-int launch_self_join(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev, int64_t *offsets_dev,
-                     int32_t *idx_dev, double *cost_dev, int32_t *owner_dev, int64_t cap, int64_t *needed_dev,
-                     const double **table_out);
+// both directed edges of every entry of a view, for the calls that are not the SimpleEdge preamble (the self and closest
+// calls, find_new_target): a dim = 4 context checks Dubins edges, a dim = 3 context SimpleEdges against the polygon list
+// (opt_extend_polygons) or the spheres, without a sample pass
+int launch_list_edges(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double robot_radius, double r_min, double r,
+                      NearTable near = {});
+// the samples of a batch among themselves (kernels_self.hip): into L the CSR of the earlier samples within r of every
+// sample, keys and owners; *L.count = entries found, no entry at or beyond L.cap is written.  *table_out = the samples
+// as the near table of launch_candidate_edges
+int launch_self_join(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
+                     NearTable *table_out);
 // the same in [x y t theta] with the context's wrapped dimensions: the copies of the later sample against the earlier
-// sample as it is, the key of the first copy that reaches it; *columns_out = the samples as four columns of nq doubles
-int launch_self_join_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
-                            int64_t *offsets_dev, int32_t *idx_dev, double *key_dev, int32_t *owner_dev, int64_t cap,
-                            int64_t *needed_dev, const double **columns_out);
-// the k nearest earlier samples of every wanted live sample (kernels_self.hip): nq x k slots, both edge flags of every
-// slot against the whole obstacle list, and the same flags for (sample, node tree_idx) when a tree column is given;
-// device pointers, bounded by nq, k and the node count on the device
-int launch_closest_self(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, const uint8_t *skip_dev,
-                        const uint8_t *want_dev, const int32_t *tree_idx_dev, int32_t *idx_dev, double *cost_dev,
-                        uint8_t *hit_out_dev, uint8_t *hit_in_dev, int32_t *count_dev, uint8_t *tree_hit_out_dev,
-                        uint8_t *tree_hit_in_dev);
+// sample as it is, the key of the first copy that reaches it; *table_out = the near table of launch_candidate_dubins
+int launch_self_join_dubins(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, double r, const uint8_t *skip_dev,
+                            NearTable *table_out);
+// the k nearest earlier samples of every wanted live sample (kernels_self.hip): L holds nq x k slots (offsets and count
+// are not used; owner: the row of every slot), both edge flags of every slot against the whole obstacle list, and the
+// same flags for (sample, node tree_idx) when a tree column is given; bounded by nq, k and the node count on the device
+int launch_closest_self(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, int k, double robot_radius,
+                        const uint8_t *skip_dev, const uint8_t *want_dev, int32_t *count_dev, const TreeColumn &tree);
 // the same in [x y t theta] with the context's wrapped dimensions: rows by the minimum over the later sample's copies,
 // per slot the key, both Dubins costs, words (may be null) and flag bytes, and the same fields of the tree column
-int launch_closest_self_dubins(rrtx_ctx *ctx, const double *q_dev, int nq, int k, double robot_radius, double r_min,
-                               const uint8_t *skip_dev, const uint8_t *want_dev, const int32_t *tree_idx_dev,
-                               int32_t *idx_dev, double *key_dev, double *cost_out_dev, double *cost_in_dev,
-                               uint8_t *word_out_dev, uint8_t *word_in_dev, uint8_t *hit_out_dev, uint8_t *hit_in_dev,
-                               int32_t *count_dev, double *tree_cost_out_dev, double *tree_cost_in_dev,
-                               uint8_t *tree_word_out_dev, uint8_t *tree_word_in_dev, uint8_t *tree_hit_out_dev,
-                               uint8_t *tree_hit_in_dev);
-int launch_nearest_from_lists(rrtx_ctx *ctx, const double *q_dev, int nq, const int64_t *offsets_dev,
-                              const int32_t *idx_dev, const double *dist_dev, int32_t *nearest_idx_dev,
-                              double *nearest_dist_dev);
+int launch_closest_self_dubins(rrtx_ctx *ctx, const Lists &L, const double *q_dev, int nq, int k, double robot_radius,
+                               double r_min, const uint8_t *skip_dev, const uint8_t *want_dev, int32_t *count_dev,
+                               const TreeColumn &tree);
+int launch_nearest_from_lists(rrtx_ctx *ctx, const ListsRO &L, int nq, int32_t *nearest_idx_dev, double *nearest_dist_dev);
 
 int launch_obstacle_sweep(rrtx_ctx *ctx, const double centre[3], double thr_lt, double thr_gt, const SphRec &ob,
                           int active, int32_t *out_dev, int64_t cap, long long **total_dev);
@@ -582,8 +607,7 @@ int launch_pack_hits(rrtx_ctx *ctx, const uint8_t *hit_out, const uint8_t *hit_i
 // findBestParent + rewire test over the lists of the extend preamble (kernels_select.hip); device pointers
 struct SelectLaunch {
   int nq;
-  const int64_t *offsets; const int32_t *idx; const double *cost_out, *cost_in; const uint8_t *hit_out, *hit_in;
-  const int64_t *n_valid_dev; int64_t cap;
+  ListsRO lists;
   const uint8_t *sample_unsafe; const double *lmc; int64_t n_lmc;
   int32_t *parent_idx; int64_t *parent_entry; double *lmc_new; uint8_t *status;
   int64_t *rw_offsets; int32_t *rw_node; double *rw_value; int64_t rw_cap; int64_t *rw_needed_dev;
@@ -594,7 +618,7 @@ int launch_select(rrtx_ctx *ctx, const SelectLaunch &L);
 // edges, verdict} in ctx->ws_link_res and the CSR of every sample's edges in row_first (nq + 1); the caller reads the
 // three words, refuses or grows the mirror, and launch_link_fill writes edges [first, first + total).
 enum : unsigned {
-  kLinkOverflow = 1,      // *n_valid_dev > cap
+  kLinkOverflow = 1,      // *lists.count > lists.cap
   kLinkBadNode = 2,       // node_of[j] >= the node count
   kLinkBadIndex = 4,      // a surviving entry's near node / batch position out of range
   kLinkBadOffsets = 8,    // offsets out of order or beyond cap
@@ -602,8 +626,7 @@ enum : unsigned {
 };
 struct LinkLists {
   int nq;
-  const int64_t *offsets; const int32_t *idx; const double *cost_out, *cost_in; const uint8_t *hit_out, *hit_in;
-  const int64_t *n_valid_dev; int64_t cap;
+  ListsRO lists;
   const int32_t *node_of; bool idx_is_batch;
   int64_t *row_first;
 };

@@ -74,6 +74,19 @@ def polygon_args(name, mode):
     return mv + stat, [6, 7, 6, 7, 6, 7] + [3] * len(stat), paths + [None] * len(stat)
 
 
+def two_polygons():
+    """(polygons, kinds, paths): one polygon that moves along its path and one static one of the "small" moving scene"""
+    polys, kinds, paths = polygon_args("small", "moving")
+    i = kinds.index(3)
+    return [polys[0], polys[i]], [kinds[0], 3], [paths[0], None]
+
+
+def transposed_share(ref, used, pairs):
+    """per pair (a, b) of fields: the share of the used entries in which ref[a] and ref[b] differ, i.e. in which a result
+    with the two columns transposed would differ from ref"""
+    return {a: float((np.asarray(ref[a])[used] != np.asarray(ref[b])[used]).mean()) for a, b in pairs}
+
+
 def lattice_samples():
     """600 samples, x y t multiples of 1/4 in [-4, 4] and theta a multiple of 1/4 in [0, 6.25]: the squared distances of
     the samples themselves are exact, so pairs at distance exactly r exist (they are not neighbours: KDdist < r), and

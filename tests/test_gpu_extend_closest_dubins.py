@@ -189,6 +189,28 @@ def test_tree_column_with_time(oracle):
         assert len(set(ref["tree_hit_out"].tolist())) >= 3
 
 
+def test_no_two_columns_can_be_transposed(oracle):
+    """65 samples over a tree of 257 nodes, k = 3, theta wrapped, one static and one moving polygon, time on: on the
+    oracle's answer alone cost_out / cost_in, word_out / word_in and hit_out / hit_in each differ in at least a quarter
+    of the used slots, and so do the three pairs of the tree column over the filled rows, so a call that hands two
+    columns of a pair out in each other's place cannot equal it"""
+    Q = S.random_samples("small")
+    tree = S.tree_points(257, S.RANDOM["small"][1])
+    ti = np.random.default_rng(8).integers(0, len(tree), len(Q)).astype(np.int32)
+    polys, kinds, paths = S.two_polygons()
+    ref = M.closest_reference(oracle, Q, 3, oracle.PolygonSet(polys, kinds=kinds, paths=paths), "moving", tree_idx=ti,
+                              tree_pts=tree)
+    pairs = (("cost_out", "cost_in"), ("word_out", "word_in"), ("hit_out", "hit_in"))
+    share = S.transposed_share(ref, ref["idx"] >= 0, pairs)
+    share.update(S.transposed_share(ref, ref["count"] > 0, [("tree_" + a, "tree_" + b) for a, b in pairs]))
+    assert (ref["idx"] >= 0).sum() >= 65 and min(share.values()) >= 0.25, share
+    with _context("small", "moving", tree=tree) as ctx:
+        ctx.polygons_set(polys, kinds=kinds, paths=paths)
+        got = ctx.extend_closest_self_dubins(Q, 3, RR, RMIN, tree_idx=ti)
+    for f in ALL:
+        assert np.array_equal(got[f], ref[f]), f
+
+
 @pytest.mark.parametrize("mode", ["flat", "time"])
 def test_entries_are_those_of_dubins_edges_check(mode):
     """byte for byte and bit for bit what rrtx_dubins_edges_check returns for the directed edge; with time bit 1 of a

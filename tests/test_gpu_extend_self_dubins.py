@@ -66,6 +66,23 @@ def test_scenes_with_time(oracle, b, mode):
         assert set(got["hit_out"].tolist()) | set(got["hit_in"].tolist()) == {0, 1, 2, 3}
 
 
+def test_no_two_columns_can_be_transposed(oracle):
+    """65 samples, theta wrapped, one static and one moving polygon, time on: on the oracle's answer alone cost_out /
+    cost_in, word_out / word_in and hit_out / hit_in each differ in at least a quarter of the entries, so a call that
+    hands two columns of a pair out in each other's place cannot equal it"""
+    Q, r = M.random_samples("small"), M.RANDOM["small"][2]
+    polys, kinds, paths = M.two_polygons()
+    ref = M.self_reference(oracle, Q, r, oracle.PolygonSet(polys, kinds=kinds, paths=paths), "moving")
+    pairs = (("cost_out", "cost_in"), ("word_out", "word_in"), ("hit_out", "hit_in"))
+    share = M.transposed_share(ref, np.ones(len(ref["idx"]), dtype=bool), pairs)
+    assert len(ref["idx"]) >= 65 and min(share.values()) >= 0.25, share
+    with _context("small", "moving") as ctx:
+        ctx.polygons_set(polys, kinds=kinds, paths=paths)
+        got = ctx.extend_candidates_self_dubins(Q, r, RR, RMIN)
+    for f in FIELDS:
+        assert np.array_equal(got[f], ref[f]), f
+
+
 @pytest.mark.parametrize("r", M.LATTICE_R)
 def test_lattice_scenes(oracle, r):
     """pairs at distance exactly r are no neighbours; duplicates are neighbours at key 0"""
