@@ -35,12 +35,12 @@ __device__ __forceinline__ double sq2(double ax, double ay, double bx, double by
 }
 
 // Julia Base.min/max on Float64: NaN-propagating, -0.0 < +0.0 (base/math.jl)
-__device__ __forceinline__ double jl_min(double x, double y) {
+__host__ __device__ __forceinline__ double jl_min(double x, double y) {
   bool sx = __builtin_signbit(x), sy = __builtin_signbit(y);
   if ((y < x) || (sy && !sx)) return (x != x) ? x : y;
   return (y != y) ? y : x;
 }
-__device__ __forceinline__ double jl_max(double x, double y) {
+__host__ __device__ __forceinline__ double jl_max(double x, double y) {
   bool sx = __builtin_signbit(x), sy = __builtin_signbit(y);
   if ((y > x) || (!sy && sx)) return (x != x) ? x : y;
   return (y != y) ? y : x;

@@ -5,6 +5,7 @@
 // gfx950 only.  Lane = edge (or point); the obstacle loop is wave-uniform so
 // obstacle records arrive through scalar loads; a wave leaves the loop as soon
 // as every lane has its answer (ballot early-out).
+#include "block_layout.hpp"
 #include "collide_device.hpp"
 
 #include <limits>
@@ -1444,96 +1445,71 @@ int sync_spheres(rrtx_ctx *ctx, double robot_radius) {
   const bool same_origin = ctx->sph_packed_origin[0] == ctx->origin[0] && ctx->sph_packed_origin[1] == ctx->origin[1] &&
                            ctx->sph_packed_origin[2] == ctx->origin[2];
   if (!ctx->sph_dirty && ctx->sph_packed_rr == robot_radius && same_origin) return RRTX_OK;
-  const int m = (int)ctx->sph_active.size();
-  std::vector<SphRec> rec, reach;
-  std::vector<double> radius, thr_in;
-  std::vector<int32_t> orig;
-  for (int i = 0; i < m; ++i) {
-    if (!ctx->sph_active[i]) continue;
-    const double *c = &ctx->sph[4 * (size_t)i];
-    SphRec r;
-    r.cx = c[0]; r.cy = c[1]; r.cz = c[2];
-    r.thr = thr_first_gt(robot_radius + c[3]);
-    rec.push_back(r);
-    // inflated reach for the conservative midpoint test (kernel: may_touch)
-    SphRec rb = r;
-    const double R = robot_radius + c[3];
-    const double cm = std::fmax(std::fmax(std::fabs(c[0]), std::fabs(c[1])), std::fabs(c[2]));
-    const bool usable = std::isfinite(R) && std::isfinite(cm) && cm < 1e100 && std::fabs(R) < 1e100;
-    rb.thr = usable ? (std::fmax(R, 0.0) * (1.0 + 1e-12) + 1e-12 * (cm + 1.0)) * (1.0 + 1e-12)
-                    : std::numeric_limits<double>::infinity();
-    reach.push_back(rb);
-    radius.push_back(c[3]);
-    thr_in.push_back(thr_first_gt(c[3]));
-    orig.push_back(i);
-  }
-  const int na = (int)rec.size();
-  ctx->sph_n_active = na;
+  const std::vector<int32_t> pos = active_positions(ctx->sph_active);
+  const int na = (int)pos.size();
+  ctx->sph_view = SphView{};        // (nothing in use: m = 0 and null pointers, whatever the buffer holds)
   if (na > 0) {
-    RRTX_HIP(ctx, ctx->d_sph.ensure(sizeof(SphRec) * na));
-    RRTX_HIP(ctx, ctx->d_sph_aux.ensure((sizeof(double) * 2 + sizeof(int32_t)) * na + 64));
-    // the packed tables may still be read by kernels in flight on the stream
-    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_sph.p, rec.data(), sizeof(SphRec) * na, hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, ctx->d_sph_reach.ensure(sizeof(SphRec) * na));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_sph_reach.p, reach.data(), sizeof(SphRec) * na, hipMemcpyHostToDevice));
+    const SphereTableBlock B{(size_t)na};
+    static_assert(sizeof(SphRec) == 4 * sizeof(double) && sizeof(SampleSph) == 8 * sizeof(double), "SphereTableBlock's records");
+    const HostImage image(B.bytes);
+    void *host = image.base;
+    SphRec *rec = B.rec.in_as<SphRec>(host), *reach = B.reach.in_as<SphRec>(host);
+    SampleSph *st = B.sample.in_as<SampleSph>(host);
+    double *radius = B.radius.in(host), *thr_in = B.thr_in.in(host);
+    std::copy(pos.begin(), pos.end(), B.orig.in(host));
     // fp32 reach table for the packed screen of candidate_edges_kernel: centres relative to the
     // context origin, pair-interleaved {cxA,cxB, cyA,cyB, czA,czB, RA,RB}, padded to groups of 8
     // obstacles with centres at +inf (never within reach).  R~ = RU[(R' + 3 eps |c|_1)(1 + 8 eps)].
-    {
-      const int ng = (na + 7) / 8;
-      std::vector<float> tf((size_t)ng * 32, std::numeric_limits<float>::infinity());
-      const double eps = 5.9604644775390625e-08;
-      for (int k = 0; k < na; ++k) {
-        const double cx = reach[k].cx - ctx->origin[0], cy = reach[k].cy - ctx->origin[1], cz = reach[k].cz - ctx->origin[2];
-        const double l1 = std::fabs(cx) + std::fabs(cy) + std::fabs(cz);
-        const double Rr = reach[k].thr;   // already inflated fp64 reach (or +inf)
-        double Rf = (Rr + 3.0 * eps * l1 + 1e-30) * (1.0 + 8.0 * eps);
-        float rf = (float)Rf;
-        if (!(rf >= Rf)) rf = std::nextafterf(rf, std::numeric_limits<float>::infinity());
-        if (!std::isfinite(Rf) || !(l1 < 1e30)) rf = std::numeric_limits<float>::infinity();
-        float *g = &tf[(size_t)(k / 8) * 32 + (size_t)((k % 8) / 2) * 8];
-        const int h = k & 1;
-        g[0 + h] = (float)cx; g[2 + h] = (float)cy; g[4 + h] = (float)cz; g[6 + h] = rf;
-        if (!std::isfinite(rf)) { g[0 + h] = 0.f; g[2 + h] = 0.f; g[4 + h] = 0.f; }   // reach +inf: always evaluated
-      }
-      // padding entries keep centre = +inf and R = +inf would pass; give them R = 0
-      for (int k = na; k < ng * 8; ++k) {
-        float *g = &tf[(size_t)(k / 8) * 32 + (size_t)((k % 8) / 2) * 8];
-        g[6 + (k & 1)] = 0.f;
-      }
-      RRTX_HIP(ctx, ctx->d_sph_reach_f.ensure(sizeof(float) * tf.size()));
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_sph_reach_f.p, tf.data(), sizeof(float) * tf.size(), hipMemcpyHostToDevice));
+    float *tf = B.reach_f.in(host);
+    std::fill(tf, tf + B.reach_f.count, std::numeric_limits<float>::infinity());
+    const double eps = 5.9604644775390625e-08;
+    for (int k = 0; k < na; ++k) {
+      const double *c = &ctx->sph[4 * (size_t)pos[k]];
+      SphRec r;
+      r.cx = c[0]; r.cy = c[1]; r.cz = c[2];
+      r.thr = thr_first_gt(robot_radius + c[3]);
+      rec[k] = r;
+      // inflated reach for the conservative midpoint test (kernel: may_touch)
+      SphRec rb = r;
+      const double R = robot_radius + c[3];
+      const double cm = std::fmax(std::fmax(std::fabs(c[0]), std::fabs(c[1])), std::fabs(c[2]));
+      const bool usable = std::isfinite(R) && std::isfinite(cm) && cm < 1e100 && std::fabs(R) < 1e100;
+      rb.thr = usable ? (std::fmax(R, 0.0) * (1.0 + 1e-12) + 1e-12 * (cm + 1.0)) * (1.0 + 1e-12)
+                      : std::numeric_limits<double>::infinity();
+      reach[k] = rb;
+      radius[k] = c[3];
+      thr_in[k] = thr_first_gt(c[3]);
+      const double cx = reach[k].cx - ctx->origin[0], cy = reach[k].cy - ctx->origin[1], cz = reach[k].cz - ctx->origin[2];
+      const double l1 = std::fabs(cx) + std::fabs(cy) + std::fabs(cz);
+      const double Rr = reach[k].thr;   // already inflated fp64 reach (or +inf)
+      double Rf = (Rr + 3.0 * eps * l1 + 1e-30) * (1.0 + 8.0 * eps);
+      float rf = (float)Rf;
+      if (!(rf >= Rf)) rf = std::nextafterf(rf, std::numeric_limits<float>::infinity());
+      if (!std::isfinite(Rf) || !(l1 < 1e30)) rf = std::numeric_limits<float>::infinity();
+      float *g = &tf[(size_t)(k / 8) * 32 + (size_t)((k % 8) / 2) * 8];
+      const int h = k & 1;
+      g[0 + h] = (float)cx; g[2 + h] = (float)cy; g[4 + h] = (float)cz; g[6 + h] = rf;
+      if (!std::isfinite(rf)) { g[0 + h] = 0.f; g[2 + h] = 0.f; g[4 + h] = 0.f; }   // reach +inf: always evaluated
+      st[k].cx = rec[k].cx; st[k].cy = rec[k].cy; st[k].cz = rec[k].cz;
+      st[k].thr_in = thr_in[k];
+      st[k].thr_pt = thr_point_clear(robot_radius, radius[k]);
+      st[k].reach = reach[k].thr;
+      st[k].pad0 = 0.0; st[k].pad1 = 0.0;
     }
-    {
-      std::vector<SampleSph> st((size_t)na);
-      for (int k = 0; k < na; ++k) {
-        st[k].cx = rec[k].cx; st[k].cy = rec[k].cy; st[k].cz = rec[k].cz;
-        st[k].thr_in = thr_in[k];
-        st[k].thr_pt = thr_point_clear(robot_radius, radius[k]);
-        st[k].reach = reach[k].thr;
-        st[k].pad0 = 0.0; st[k].pad1 = 0.0;
-      }
-      RRTX_HIP(ctx, ctx->d_sph_sample.ensure(sizeof(SampleSph) * na));
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_sph_sample.p, st.data(), sizeof(SampleSph) * na, hipMemcpyHostToDevice));
-    }
-    char *aux = ctx->d_sph_aux.as<char>();
-    RRTX_HIP(ctx, hipMemcpy(aux, radius.data(), sizeof(double) * na, hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, hipMemcpy(aux + sizeof(double) * na, thr_in.data(), sizeof(double) * na,
-                            hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, hipMemcpy(aux + sizeof(double) * 2 * na, orig.data(), sizeof(int32_t) * na,
-                            hipMemcpyHostToDevice));
+    // padding entries keep centre = +inf and R = +inf would pass; give them R = 0
+    for (int k = na; k < (int)B.reach_f.count / 4; ++k) tf[(size_t)(k / 8) * 32 + (size_t)((k % 8) / 2) * 8 + 6 + (k & 1)] = 0.f;
+    // the packed tables may still be read by kernels in flight on the stream
+    RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RRTX_HIP(ctx, ctx->d_sph_tab.ensure(B.bytes));
+    void *dev = ctx->d_sph_tab.p;
+    RRTX_HIP(ctx, hipMemcpy(dev, host, B.bytes, hipMemcpyHostToDevice));
+    ctx->sph_view = SphView{B.rec.in_as<SphRec>(dev), B.reach.in_as<SphRec>(dev), B.reach_f.in(dev), B.sample.in(dev),
+                            B.radius.in(dev), B.thr_in.in(dev), B.orig.in(dev), na};
   }
   ctx->sph_dirty = false;
   ctx->sph_packed_rr = robot_radius;
   for (int k = 0; k < 3; ++k) ctx->sph_packed_origin[k] = ctx->origin[k];
   return RRTX_OK;
-}
-
-static const double *sph_radius_dev(rrtx_ctx *ctx) { return ctx->d_sph_aux.as<double>(); }
-static const double *sph_thr_in_dev(rrtx_ctx *ctx) { return ctx->d_sph_aux.as<double>() + ctx->sph_n_active; }
-static const int32_t *sph_orig_dev(rrtx_ctx *ctx) {
-  return reinterpret_cast<const int32_t *>(ctx->d_sph_aux.as<double>() + 2 * (size_t)ctx->sph_n_active);
 }
 
 std::vector<int32_t> active_positions(const std::vector<uint8_t> &active) {
@@ -1607,37 +1583,30 @@ int sync_polygons(rrtx_ctx *ctx) {
   bool y_ok = true;
   for (double y : ytab) y_ok = y_ok && (y == y);
   if (y_ok) std::sort(ytab.begin(), ytab.end()); else ytab.clear();
-  ctx->poly_n_ytab = y_ok ? (int)ytab.size() : -1;
   const int na = (int)orig.size();
-  ctx->poly_n_active = na;
+  ctx->poly_view = PolyView{};      // (nothing in use: m = 0 and null pointers, whatever the buffer holds)
   RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (na > 0) {
-    RRTX_HIP(ctx, ctx->d_poly_meta.ensure(sizeof(double) * meta.size()));
-    RRTX_HIP(ctx, ctx->d_poly_off.ensure(sizeof(int32_t) * off.size()));
-    RRTX_HIP(ctx, ctx->d_poly_vxy.ensure(sizeof(double) * (vxy.size() + 2)));
-    RRTX_HIP(ctx, ctx->d_poly_orig.ensure(sizeof(int32_t) * na));
-    RRTX_HIP(ctx, ctx->d_poly_slope.ensure(sizeof(double) * (slope.size() + 1)));
-    if (!slope.empty())
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_slope.p, slope.data(), sizeof(double) * slope.size(), hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_meta.p, meta.data(), sizeof(double) * meta.size(), hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_off.p, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
-    if (!vxy.empty())
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_vxy.p, vxy.data(), sizeof(double) * vxy.size(), hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_orig.p, orig.data(), sizeof(int32_t) * na, hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, ctx->d_poly_bbox.ensure(sizeof(double) * bbox.size()));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_bbox.p, bbox.data(), sizeof(double) * bbox.size(), hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, ctx->d_poly_pbox.ensure(sizeof(double) * pbox.size()));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_pbox.p, pbox.data(), sizeof(double) * pbox.size(), hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, ctx->d_poly_ytab.ensure(sizeof(double) * (ytab.size() + 1)));
-    if (!ytab.empty())
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_ytab.p, ytab.data(), sizeof(double) * ytab.size(), hipMemcpyHostToDevice));
-    RRTX_HIP(ctx, ctx->d_poly_path_off.ensure(sizeof(int32_t) * path_off.size()));
-    RRTX_HIP(ctx, ctx->d_poly_path.ensure(sizeof(double) * (path.size() + 3)));
-    RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_path_off.p, path_off.data(), sizeof(int32_t) * path_off.size(), hipMemcpyHostToDevice));
-    if (!path.empty())
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_path.p, path.data(), sizeof(double) * path.size(), hipMemcpyHostToDevice));
+    const PolygonTableBlock B{(size_t)na, vxy.size() / 2, path.size() / 3, ytab.size()};
+    const HostImage image(B.bytes);
+    void *host = image.base;
+    std::copy(meta.begin(), meta.end(), B.meta.in(host));
+    std::copy(off.begin(), off.end(), B.off.in(host));
+    std::copy(vxy.begin(), vxy.end(), B.vxy.in(host));
+    std::copy(slope.begin(), slope.end(), B.vslope.in(host));
+    std::copy(orig.begin(), orig.end(), B.orig.in(host));
+    std::copy(bbox.begin(), bbox.end(), B.bbox.in(host));
+    std::copy(pbox.begin(), pbox.end(), B.pbox.in(host));
+    std::copy(ytab.begin(), ytab.end(), B.ytab.in(host));
+    std::copy(path_off.begin(), path_off.end(), B.path_off.in(host));
+    std::copy(path.begin(), path.end(), B.path.in(host));
+    RRTX_HIP(ctx, ctx->d_poly_tab.ensure(B.bytes));
+    void *dev = ctx->d_poly_tab.p;
+    RRTX_HIP(ctx, hipMemcpy(dev, host, B.bytes, hipMemcpyHostToDevice));
+    ctx->poly_view = PolyView{B.meta.in(dev), B.off.in(dev), B.vxy.in(dev), B.vslope.in(dev), B.orig.in(dev), B.bbox.in(dev),
+                              B.pbox.in(dev), B.ytab.in(dev), y_ok ? (int)ytab.size() : -1, B.path_off.in(dev), B.path.in(dev),
+                              na, moving};
   }
-  ctx->poly_has_moving = moving;
   ctx->poly_dirty = false;
   ctx->poly_h_meta.swap(meta);
   ctx->poly_h_bbox.swap(bbox);
@@ -1652,7 +1621,7 @@ int sync_polygons(rrtx_ctx *ctx) {
 // obstacle the point lies outside that box in x or in y: beyond reach for certain, outside the vertex box, and outside
 // the bound of the per-sample lists -- the three things the kernel's walk over the whole list would find out one by one.
 int sync_polygon_grid(rrtx_ctx *ctx, double pad_needed) {
-  const int na = ctx->poly_n_active;
+  const int na = ctx->poly_view.m;
   // (a wider pad than needed only lengthens the cell lists; calls with and without the per-sample lists share one grid)
   if (ctx->poly_grid_pad >= pad_needed && ctx->poly_grid_pad <= 4.0 * pad_needed + 8.0) return RRTX_OK;
   ctx->poly_grid_pad = -1.0;
@@ -1699,11 +1668,13 @@ int sync_polygon_grid(rrtx_ctx *ctx, double pad_needed) {
         }
     }
     if (pass == 1) {
+      const PolygonGridBlock B{(size_t)G * G, items.size()};
+      const HostImage image(B.bytes);
+      std::copy(start.begin(), start.end(), B.start.in(image.base));
+      std::copy(items.begin(), items.end(), B.items.in(image.base));
       RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      RRTX_HIP(ctx, ctx->d_poly_grid_start.ensure(sizeof(int32_t) * start.size()));
-      RRTX_HIP(ctx, ctx->d_poly_grid_items.ensure(sizeof(uint16_t) * items.size()));
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_grid_start.p, start.data(), sizeof(int32_t) * start.size(), hipMemcpyHostToDevice));
-      RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_grid_items.p, items.data(), sizeof(uint16_t) * items.size(), hipMemcpyHostToDevice));
+      RRTX_HIP(ctx, ctx->d_poly_grid.ensure(B.bytes));
+      RRTX_HIP(ctx, hipMemcpy(ctx->d_poly_grid.p, image.base, B.bytes, hipMemcpyHostToDevice));
     }
   }
   ctx->poly_grid_x0 = gx0; ctx->poly_grid_y0 = gy0; ctx->poly_grid_inv_wx = inv_wx; ctx->poly_grid_inv_wy = inv_wy;
@@ -1744,10 +1715,11 @@ int launch_edges_spheres(rrtx_ctx *ctx, const double *p0_dev, const double *p1_d
   int pb, pe;
   packed_range(active_positions(ctx->sph_active), obs_begin, obs_end, pb, pe);
   if (pe <= pb) return zero_outputs(ctx, ne, hit_dev, first_hit_dev);
+  const SphView &S = ctx->sph_view;
   span_begin(ctx, KF_EDGES);
   hipLaunchKernelGGL(edges_spheres_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream, p0_dev,
                      p1_dev, ctx->dim, sidx_dev, eidx_dev, ctx->nodes[0], ctx->nodes[1], ctx->nodes[2], (long long)ne,
-                     ctx->d_sph.as<SphRec>(), ctx->d_sph_reach.as<SphRec>(), maskp, sph_orig_dev(ctx), pb, pe, hit_dev,
+                     S.rec, S.reach, maskp, S.orig, pb, pe, hit_dev,
                      first_hit_dev);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
@@ -1764,7 +1736,8 @@ int launch_candidate_edges(rrtx_ctx *ctx, const double *q_dev, int nq, const int
   if (!near_aos) { near_aos = ctx->nodes_aos; n_near = ctx->n_nodes; }
   int rc = sync_spheres(ctx, robot_radius);
   if (rc) return rc;
-  const int m = ctx->sph_n_active;
+  const SphView &S = ctx->sph_view;
+  const int m = S.m;
   const bool use_lists = r >= 0.0 && m > 0;
   const double r_bound = r * (1.0 + 1e-12);
   const int32_t *lists = nullptr, *list_n = nullptr;
@@ -1775,7 +1748,7 @@ int launch_candidate_edges(rrtx_ctx *ctx, const double *q_dev, int nq, const int
     span_begin(ctx, KF_POINTS);
     if (m > 0) {
       hipLaunchKernelGGL(sample_spheres_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(64 * kSampleWaves), 0, ctx->stream,
-                         q_dev, ctx->dim, (long long)nq, ctx->d_sph_sample.as<SampleSph>(), m,
+                         q_dev, ctx->dim, (long long)nq, reinterpret_cast<const SampleSph *>(S.sample), m,
                          use_lists ? r_bound : 0.0, sample_unsafe_dev, l, ln);
     } else if (sample_unsafe_dev) {
       RRTX_HIP(ctx, hipMemsetAsync(sample_unsafe_dev, 0, (size_t)nq, ctx->stream));
@@ -1788,7 +1761,7 @@ int launch_candidate_edges(rrtx_ctx *ctx, const double *q_dev, int nq, const int
   // the grid covers the caller's capacity; lanes past offsets[nq] idle
   hipLaunchKernelGGL(candidate_edges_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, q_dev,
                      ctx->dim, offsets_dev, nq, idx_dev, owner_dev, reinterpret_cast<const double4 *>(near_aos),
-                     (int)n_near, (long long)cap, ctx->d_sph.as<SphRec>(), ctx->d_sph_reach_f.as<float>(), ctx->origin[0],
+                     (int)n_near, (long long)cap, S.rec, S.reach_f, ctx->origin[0],
                      ctx->origin[1], ctx->origin[2], m, lists, list_n, kSphListCap, r_bound, hit_out_dev, hit_in_dev);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
@@ -1807,10 +1780,11 @@ int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, 
   if (!near_aos) { near_aos = ctx->nodes_aos; n_near = ctx->n_nodes; }
   int rc = sync_polygons(ctx);
   if (rc) return rc;
+  const PolyView &V = ctx->poly_view;
   const double list_r = (r >= 0.0 && r - r == 0.0) ? r * (1.0 + 1e-8) : -1.0;
   const unsigned short *near_lists = nullptr, *near_cnt = nullptr;
   if (sample_unsafe_dev || (list_r >= 0.0 && cap > 0)) {
-    if (ctx->poly_n_active > 0) {
+    if (V.m > 0) {
       rc = launch_points_polygons(ctx, q_dev, nq, robot_radius, sample_unsafe_dev, nullptr, list_r, &near_lists, &near_cnt);
       if (rc) return rc;
     } else if (sample_unsafe_dev) {
@@ -1818,7 +1792,7 @@ int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, 
     }
   }
   if (cap <= 0) return RRTX_OK;
-  if (ctx->poly_n_active == 0) {
+  if (V.m == 0) {
     RRTX_HIP(ctx, hipMemsetAsync(hit_out_dev, 0, (size_t)cap, ctx->stream));
     RRTX_HIP(ctx, hipMemsetAsync(hit_in_dev, 0, (size_t)cap, ctx->stream));
     return RRTX_OK;
@@ -1831,13 +1805,11 @@ int launch_candidate_edges_polygons(rrtx_ctx *ctx, const double *q_dev, int nq, 
   // (without a time column a wave's scratch is 8 KB: five waves per SIMD, with the register budget cut to match)
   // the last eighth of the entries in waves of 32 (measured: 1/8 0.1314, 2/8 0.1319, 3/8 0.1326, 4/8 0.1347, none 0.1345 ms)
   const int tail_eighths = 1;
-  hipLaunchKernelGGL((ctx->poly_has_moving ? edges_polygons_kernel<true, 1, 4, true> : edges_polygons_kernel<true, 1, 5, false>),
+  hipLaunchKernelGGL((V.has_moving ? edges_polygons_kernel<true, 1, 4, true> : edges_polygons_kernel<true, 1, 5, false>),
                      dim3((unsigned)((cap + 63) / 64 + (tail_eighths ? (cap + 31) / 32 * tail_eighths / 8 + 2 : 0))), dim3(64), 0, ctx->stream,
-                     (const double *)nullptr, (const double *)nullptr, ctx->dim, 0ll, csr, ctx->d_poly_meta.as<double>(),
-                     ctx->d_poly_off.as<int32_t>(), ctx->d_poly_vxy.as<double>(), ctx->d_poly_slope.as<double>(),
-                     ctx->d_poly_path_off.as<int32_t>(),
-                     ctx->d_poly_path.as<double>(), ctx->poly_has_moving ? 1 : 0, ctx->d_poly_orig.as<int32_t>(), 0,
-                     ctx->poly_n_active, robot_radius, hit_out_dev, (int32_t *)nullptr, near_lists, near_cnt, list_r, tail_eighths);
+                     (const double *)nullptr, (const double *)nullptr, ctx->dim, 0ll, csr, V.meta, V.off, V.vxy, V.vslope,
+                     V.path_off, V.path, V.has_moving ? 1 : 0, V.orig, 0, V.m, robot_radius, hit_out_dev, (int32_t *)nullptr,
+                     near_lists, near_cnt, list_r, tail_eighths);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
   return RRTX_OK;
@@ -1868,12 +1840,11 @@ int launch_edges_polygons(rrtx_ctx *ctx, const double *p0_dev, const double *p1_
   int pb, pe;
   packed_range(active_positions(ctx->poly_active), obs_begin, obs_end, pb, pe);
   if (pe <= pb) return zero_outputs(ctx, ne, hit_dev, first_hit_dev);
+  const PolyView &V = ctx->poly_view;
   span_begin(ctx, KF_EDGES);
   hipLaunchKernelGGL((edges_polygons_kernel<false, 4, 4, true>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream, p0_dev,
-                     p1_dev, ctx->dim, (long long)ne, PolyCsr{}, ctx->d_poly_meta.as<double>(), ctx->d_poly_off.as<int32_t>(),
-                     ctx->d_poly_vxy.as<double>(), ctx->d_poly_slope.as<double>(), ctx->d_poly_path_off.as<int32_t>(),
-                     ctx->d_poly_path.as<double>(),
-                     ctx->poly_has_moving ? 1 : 0, ctx->d_poly_orig.as<int32_t>(), pb, pe, robot_radius, hit_dev,
+                     p1_dev, ctx->dim, (long long)ne, PolyCsr{}, V.meta, V.off, V.vxy, V.vslope, V.path_off, V.path,
+                     V.has_moving ? 1 : 0, V.orig, pb, pe, robot_radius, hit_dev,
                      first_hit_dev, (const unsigned short *)nullptr, (const unsigned short *)nullptr, 0.0, 0);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
@@ -1885,10 +1856,10 @@ int launch_points_spheres(rrtx_ctx *ctx, const double *p_dev, int64_t np, double
   if (np <= 0) return RRTX_OK;
   int rc = sync_spheres(ctx, robot_radius);
   if (rc) return rc;
+  const SphView &S = ctx->sph_view;
   span_begin(ctx, KF_POINTS);
   hipLaunchKernelGGL(points_spheres_kernel, dim3((unsigned)((np * kPtLanes + 255) / 256)), dim3(256), 0, ctx->stream, p_dev,
-                     ctx->dim, (long long)np, ctx->d_sph.as<SphRec>(), sph_radius_dev(ctx), sph_thr_in_dev(ctx),
-                     ctx->sph_n_active, robot_radius, quick, unsafe_dev, clearance_dev);
+                     ctx->dim, (long long)np, S.rec, S.radius, S.thr_in, S.m, robot_radius, quick, unsafe_dev, clearance_dev);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
   return RRTX_OK;
@@ -1902,17 +1873,18 @@ int launch_points_polygons(rrtx_ctx *ctx, const double *p_dev, int64_t np, doubl
   if (np <= 0) return RRTX_OK;
   int rc = sync_polygons(ctx);
   if (rc) return rc;
+  const PolyView &V = ctx->poly_view;
   unsigned short *lists = nullptr, *list_cnt = nullptr;
   // flag-only calls over obstacles that stand still: two points per wave with the reference's loop as the fall-back
   // inside the kernel; a wanted certificate or obstacles that move in time: the reference's loop, one point per wave
-  const bool flag_only = clearance_dev == nullptr && !ctx->poly_has_moving && ctx->poly_n_ytab >= 0 &&
-                         ctx->d_poly_bbox.as<double>() != nullptr;
+  // (an empty list has no tables: the reference's loop over nothing, whatever list came before)
+  const bool flag_only = clearance_dev == nullptr && !V.has_moving && V.n_ytab >= 0 && V.m > 0;
   if (!flag_only && unsafe_dev == nullptr && clearance_dev == nullptr) return RRTX_OK;   // (a call for the lists alone)
   span_begin(ctx, KF_POINTS);
   if (flag_only) {
     // list_r >= 0: also list, per point, the obstacles an edge of at most that length from the point can reach (the
     // fused extend preamble hands them to edges_polygons_kernel)
-    if (lists_out && list_cnt_out && list_r >= 0.0 && ctx->poly_n_active <= 65535) {
+    if (lists_out && list_cnt_out && list_r >= 0.0 && V.m <= 65535) {
       RRTX_HIP(ctx, ctx->ws_poly_lists.ensure(sizeof(unsigned short) * (size_t)np * (kPolyListCap + 1)));
       lists = ctx->ws_poly_lists.as<unsigned short>();
       list_cnt = lists + (size_t)np * kPolyListCap;
@@ -1921,21 +1893,20 @@ int launch_points_polygons(rrtx_ctx *ctx, const double *p_dev, int64_t np, doubl
     if (np >= 256) {                            // (a handful of points: not worth a grid build)
       rc = sync_polygon_grid(ctx, std::fabs(robot_radius) + (lists ? list_r : 0.0));
       if (rc) { span_end(ctx); return rc; }
-      if (ctx->poly_grid_pad >= 0.0)
+      if (ctx->poly_grid_pad >= 0.0) {
+        const PolygonGridBlock B{(size_t)ctx->poly_grid_g * ctx->poly_grid_g, 0};   // (no field's place depends on the item count)
         grid = PolyGrid{ctx->poly_grid_x0, ctx->poly_grid_y0, ctx->poly_grid_inv_wx, ctx->poly_grid_inv_wy, ctx->poly_grid_g,
-                        ctx->d_poly_grid_start.as<int32_t>(), ctx->d_poly_grid_items.as<uint16_t>()};
+                        B.start.in(ctx->d_poly_grid.p), B.items.in(ctx->d_poly_grid.p)};
+      }
     }
     hipLaunchKernelGGL(points_polygons_flag_kernel, dim3((unsigned)((np + 7) / 8)), dim3(256), 0, ctx->stream, p_dev,
-                       ctx->dim, (long long)np, ctx->d_poly_meta.as<double>(), ctx->d_poly_off.as<int32_t>(),
-                       ctx->d_poly_vxy.as<double>(), ctx->poly_n_active, robot_radius, unsafe_dev,
-                       ctx->d_poly_bbox.as<double>(), ctx->d_poly_ytab.as<double>(), ctx->poly_n_ytab, list_r, lists,
-                       list_cnt, grid);
+                       ctx->dim, (long long)np, V.meta, V.off, V.vxy, V.m, robot_radius, unsafe_dev, V.bbox, V.ytab, V.n_ytab,
+                       list_r, lists, list_cnt, grid);
     if (lists) { *lists_out = lists; *list_cnt_out = list_cnt; }
   } else
     hipLaunchKernelGGL(points_polygons_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, ctx->stream, p_dev,
-                       ctx->dim, (long long)np, ctx->d_poly_meta.as<double>(), ctx->d_poly_off.as<int32_t>(),
-                       ctx->d_poly_vxy.as<double>(), ctx->d_poly_path_off.as<int32_t>(), ctx->d_poly_path.as<double>(),
-                       ctx->poly_has_moving ? 1 : 0, ctx->poly_n_active, robot_radius, unsafe_dev, clearance_dev);
+                       ctx->dim, (long long)np, V.meta, V.off, V.vxy, V.path_off, V.path, V.has_moving ? 1 : 0, V.m, robot_radius,
+                       unsafe_dev, clearance_dev);
   span_end(ctx);
   RRTX_HIP(ctx, hipGetLastError());
   return RRTX_OK;

@@ -1430,21 +1430,13 @@ __global__ __launch_bounds__(256) void dubins_trajectory_rs_kernel(const double 
 }
 
 PolyTab poly_tab(rrtx_ctx *ctx) {
-  PolyTab t;
-  t.meta = ctx->d_poly_meta.as<double>();
-  t.off = ctx->d_poly_off.as<int32_t>();
-  t.vxy = ctx->d_poly_vxy.as<double>();
-  t.vslope = ctx->d_poly_slope.as<double>();
-  t.poff = ctx->d_poly_path_off.as<int32_t>();
-  t.path = ctx->d_poly_path.as<double>();
-  t.pbox = ctx->d_poly_pbox.as<double>();
-  t.m = ctx->poly_n_active;
-  return t;
+  const PolyView &V = ctx->poly_view;
+  return PolyTab{V.meta, V.off, V.vxy, V.vslope, V.path_off, V.path, V.pbox, V.m};
 }
 
 // obstacles that move in time are tested at the pieces' time stamps: only a space with time has them
 int check_space(rrtx_ctx *ctx) {
-  if (ctx->poly_has_moving && !ctx->opt_space_has_time)
+  if (ctx->poly_view.has_moving && !ctx->opt_space_has_time)
     return fail(ctx, RRTX_E_STATE, "Dubins edges against moving obstacles (kind 6/7) need the time-parameterised "
                                    "trajectory: set RRTX_OPT_SPACE_HAS_TIME (CSpace.spaceHasTime)");
   return RRTX_OK;
@@ -1479,7 +1471,7 @@ static int run_dubins_edges(rrtx_ctx *ctx, const EdgeSrc &src, long long n, int 
   double *rec2 = both ? rec + kRecDoubles * (size_t)chunk : nullptr;
   const int has_time = ctx->opt_space_has_time ? 1 : 0;
   // the running-sum time column: only a moving obstacle ever reads a piece's stamps
-  const bool rsum = check && has_time && ctx->opt_dubins_time_column == RRTX_TIME_COLUMN_RUNNING_SUM && ctx->poly_has_moving;
+  const bool rsum = check && has_time && ctx->opt_dubins_time_column == RRTX_TIME_COLUMN_RUNNING_SUM && ctx->poly_view.has_moving;
   double *ckpt = nullptr;
   if (rsum) {
     RRTX_HIP(ctx, ctx->ws_dub_ckpt.ensure(sizeof(double) * kCkptMax * (size_t)chunk));

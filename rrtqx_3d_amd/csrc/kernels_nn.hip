@@ -1382,9 +1382,10 @@ void radius_args(rrtx_ctx *ctx, const RadiusPlan &p, int flip, const ExtendFuse 
   d.pf.sph = nullptr; d.pf.m_sph = -1; d.pf.root_rule = ctx->opt_root_rule;
   d.xd.r_bound = -1.0;
   if (p.fuse) {                           // (sphere list; the caller has synced the tables)
-    d.xd.sph = ctx->d_sph.as<SphRec>(); d.xd.stab = ctx->d_sph_sample.as<SampleSph>();
-    d.xd.reach_f = ctx->d_sph_reach_f.as<float>(); d.xd.naos = reinterpret_cast<const double4 *>(ctx->nodes_aos.get());
-    d.xd.ox = ctx->origin[0]; d.xd.oy = ctx->origin[1]; d.xd.oz = ctx->origin[2]; d.xd.m = ctx->sph_n_active;
+    const SphView &S = ctx->sph_view;
+    d.xd.sph = S.rec; d.xd.stab = reinterpret_cast<const SampleSph *>(S.sample);
+    d.xd.reach_f = S.reach_f; d.xd.naos = reinterpret_cast<const double4 *>(ctx->nodes_aos.get());
+    d.xd.ox = ctx->origin[0]; d.xd.oy = ctx->origin[1]; d.xd.oz = ctx->origin[2]; d.xd.m = S.m;
     d.xd.r_bound = (ext->r >= 0.0 && d.xd.m > 0) ? ext->r * (1.0 + 1e-12) : -1.0;
     d.xd.sample_unsafe = ext->sample_unsafe;
     d.pf.sph = d.xd.sph; d.pf.m_sph = d.xd.m;

@@ -532,7 +532,7 @@ int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, in
   const int nb = (int)((ne + kSweepBlock - 1) / kSweepBlock);
   const int ng = (k + kSweepGroup - 1) / kSweepGroup;
   const int kg_max = std::min(k, kSweepGroup);        // (edge ids are int32: kg_max * nb < 2^27 counts, an int for the scan)
-  const int na = release ? ctx->sph_n_active : 0;
+  const int na = release ? ctx->sph_view.m : 0;
   if (release && (size_t)na != ctx->rel_stay_host.size()) return fail(ctx, RRTX_E_STATE, "obstacle_release_batch: stay mask of %zu for %d spheres in use", ctx->rel_stay_host.size(), na);
   RRTX_HIP(ctx, ctx->ws_swb_tab.ensure(sizeof(SweepObs) * (size_t)k));
   if (release) RRTX_HIP(ctx, ctx->ws_rel_stay.ensure((size_t)(na > 0 ? na : 1)));
@@ -560,7 +560,7 @@ int launch_sphere_burst(rrtx_ctx *ctx, int k, bool release, int32_t *out_dev, in
                        ctx->nodes[2], n, tab, kg, word);
     if (release)
       hipLaunchKernelGGL(release_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_dist, ctx->ge_start, ctx->ge_end,
-                         ne, n, word, ctx->nodes_aos, tab, kg, nb, ctx->d_sph.as<SphRec>(), ctx->ws_rel_stay.as<uint8_t>(), na,
+                         ne, n, word, ctx->nodes_aos, tab, kg, nb, ctx->sph_view.rec, ctx->ws_rel_stay.as<uint8_t>(), na,
                          seg_id, seg_word, blk_n, cnt);
     else
       hipLaunchKernelGGL(sweep_edges_words_kernel, dim3(nb), dim3(kSweepBlock), 0, st, ctx->ge_start, ctx->ge_end, ne, n, word,
@@ -654,18 +654,16 @@ int launch_polygon_burst(rrtx_ctx *ctx, int k, double r_min, double robot_radius
         const int rc = launch_dubins_check_words(ctx, cand_id, cand_word, n_c, r_min, robot_radius, ppos, kg, hit_word, stay, n_stay);
         if (rc) return rc;
       } else {
+        const PolyView &V = ctx->poly_view;
         span_begin(ctx, KF_EDGES);
         const dim3 grid((unsigned)((n_c + 255) / 256));
         if (release)
           hipLaunchKernelGGL(release_polygon_words_kernel, grid, dim3(256), 0, st, cand_id, cand_word, (long long)n_c, ctx->ge_start,
-                             ctx->ge_end, n, ctx->nodes_aos, ctx->d_poly_meta.as<double>(), ctx->d_poly_off.as<int32_t>(),
-                             ctx->d_poly_vxy.as<double>(), ctx->d_poly_path_off.as<int32_t>(), ctx->d_poly_path.as<double>(), ppos,
-                             robot_radius, hit_word, stay, n_stay, ctx->poly_n_active);
+                             ctx->ge_end, n, ctx->nodes_aos, V.meta, V.off, V.vxy, V.path_off, V.path, ppos, robot_radius, hit_word, stay,
+                             n_stay, V.m);
         else
           hipLaunchKernelGGL(sweep_polygon_words_kernel, grid, dim3(256), 0, st, cand_id, cand_word, (long long)n_c, ctx->ge_start,
-                             ctx->ge_end, n, ctx->nodes_aos, ctx->d_poly_meta.as<double>(), ctx->d_poly_off.as<int32_t>(),
-                             ctx->d_poly_vxy.as<double>(), ctx->d_poly_path_off.as<int32_t>(), ctx->d_poly_path.as<double>(), ppos,
-                             robot_radius, hit_word);
+                             ctx->ge_end, n, ctx->nodes_aos, V.meta, V.off, V.vxy, V.path_off, V.path, ppos, robot_radius, hit_word);
         span_end(ctx);
       }
     }

@@ -915,20 +915,21 @@ int rrtx_polygons_set(rrtx_ctx *ctx, const int32_t *vert_off, const double *vxy,
       for (int k = 0; k < 3; ++k) ctx->poly_cr[3 * (size_t)i + k] = centre_radius[3 * (size_t)i + k];
       continue;
     }
-    // Obstacle(kind, polygon) ctor, R/DRRT_data_structures.jl:229-241
+    // Obstacle(kind, polygon) ctor, R/DRRT_data_structures.jl:229-241: Julia's maximum / minimum, which keep a NaN
+    // (a polygon with a NaN vertex has a NaN circle, which the bounding-circle tests never rule out)
     const int b = vert_off[i], e = vert_off[i + 1];
     if (e <= b) continue;
     double maxx = vxy[2 * b], minx = maxx, maxy = vxy[2 * b + 1], miny = maxy;
     for (int v = b + 1; v < e; ++v) {
-      maxx = std::fmax(maxx, vxy[2 * v]); minx = std::fmin(minx, vxy[2 * v]);
-      maxy = std::fmax(maxy, vxy[2 * v + 1]); miny = std::fmin(miny, vxy[2 * v + 1]);
+      maxx = jl_max(maxx, vxy[2 * v]); minx = jl_min(minx, vxy[2 * v]);
+      maxy = jl_max(maxy, vxy[2 * v + 1]); miny = jl_min(miny, vxy[2 * v + 1]);
     }
     const double px = (maxx + minx) / 2.0, py = (maxy + miny) / 2.0;
     double best = 0.0;
     for (int v = b; v < e; ++v) {
       double dx = vxy[2 * v] - px, dy = vxy[2 * v + 1] - py;
       double s = dx * dx + dy * dy;
-      if (v == b || s > best) best = s;
+      best = v == b ? s : jl_max(best, s);
     }
     ctx->poly_cr[3 * (size_t)i + 0] = px;
     ctx->poly_cr[3 * (size_t)i + 1] = py;

@@ -144,6 +144,33 @@ struct GraphCost {
   DevBuf delta_cnt, delta_pos;                      // differing nodes per workgroup, their exclusive scan
 };
 
+// ---- the packed obstacle tables on the device, as the launch sites read them ---------
+// One view per list: const device pointers into the list's one block (SphereTableBlock / PolygonTableBlock,
+// block_layout.hpp) and its counts.  sync_spheres / sync_polygons rewrite the context's view at their end, after the
+// block's ensure (the invariant of Lists below).  Nothing in use: m = 0 and null pointers, whatever the buffer holds.
+struct SphView {
+  const SphRec *rec = nullptr, *reach = nullptr;   // exact records; centre + inflated reach (conservative skip test)
+  const float *reach_f = nullptr;                  // fp32, origin-relative, pair-interleaved groups of 8 (the packed screen)
+  const double *sample = nullptr;                  // SampleSph (collide_device.hpp) by its scalars, 8 a sphere
+  const double *radius = nullptr, *thr_in = nullptr;
+  const int32_t *orig = nullptr;                   // list position of every packed sphere
+  int m = 0;                                       // spheres in use
+};
+struct PolyView {
+  const double *meta = nullptr;                    // per obstacle in use {cx, cy, radius, kind}
+  const int32_t *off = nullptr;                    // vertex CSR
+  const double *vxy = nullptr, *vslope = nullptr;  // per vertex v: slope of the side that ends at v (R/DRRT.jl:1178)
+  const int32_t *orig = nullptr;                   // list position of every packed obstacle
+  // the exact box of the obstacle's vertices (xmin, xmax, ymin, ymax); the box of its centre over its whole path
+  // (kinds 6 / 7; a point otherwise); the sorted y of every vertex of the kind-3 polygons (n_ytab < 0: no table)
+  const double *bbox = nullptr, *pbox = nullptr, *ytab = nullptr;
+  int n_ytab = 0;
+  const int32_t *path_off = nullptr;               // kinds 6 / 7: rows of (dx, dy, t), CSR over the packed obstacles
+  const double *path = nullptr;
+  int m = 0;                                       // obstacles in use
+  bool has_moving = false;                         // one of them is of kind 6 or 7
+};
+
 enum KernelFamily { KF_NN_SCAN = 0, KF_NN_FINISH, KF_NN_NEAREST, KF_EDGES, KF_POINTS, KF_DUBINS, KF_DUBINS_STEER, KF_COUNT };
 
 struct TimedSpan { hipEvent_t a, b; int family; };
@@ -226,32 +253,19 @@ struct rrtx_ctx {
   std::vector<uint8_t> sph_active;  // m
   bool sph_dirty = true;
   double sph_packed_rr = -1.0;      // robot radius the packed thresholds were built for
-  int sph_n_active = 0;
-  rrtx::DevBuf d_sph;               // SphRec[n_active]
-  rrtx::DevBuf d_sph_reach;         // SphRec[n_active]: centre + inflated reach (conservative skip test)
-  rrtx::DevBuf d_sph_reach_f;       // fp32, origin-relative, pair-interleaved copy for the packed screen
-  double sph_packed_origin[3] = {0, 0, 0};
-  rrtx::DevBuf d_sph_aux;           // double radius[n_active] then int32 orig[n_active]
-  rrtx::DevBuf d_sph_sample;        // SampleSph[n_active]: one record per sphere for sample_spheres_kernel
-
+  rrtx::DevBuf d_sph_tab;           // SphereTableBlock (block_layout.hpp): the packed tables, one allocation and one upload
+  rrtx::SphView sph_view;           // ... as the launch sites read them; rewritten by every sync_spheres
+  double sph_packed_origin[3] = {0, 0, 0};   // origin the fp32 reach groups are relative to
   // polygon obstacles
   std::vector<int32_t> poly_off;    // m+1
   std::vector<double> poly_vxy;
   std::vector<double> poly_cr;      // m x 3
   std::vector<uint8_t> poly_kind, poly_active;
   bool poly_dirty = true;
-  int poly_n_active = 0;
-  rrtx::DevBuf d_poly_slope;   // per vertex v: slope of the side that ends at v, (y_v - y_prev) / (x_v - x_prev) (R/DRRT.jl:1178)
-  rrtx::DevBuf d_poly_off, d_poly_vxy, d_poly_meta; // meta: per active obstacle {cx, cy, radius, kind} doubles
-  rrtx::DevBuf d_poly_orig;
-  // flag-only point checks (points_polygons_kernel's fast path): per packed obstacle the exact bounding box of its
-  // vertices (xmin, xmax, ymin, ymax); the sorted y coordinates of every vertex of the packed kind-3 polygons
-  rrtx::DevBuf d_poly_bbox, d_poly_ytab;
-  rrtx::DevBuf d_poly_pbox;    // per packed obstacle: box of its centre over its whole path (kinds 6 / 7; a point otherwise)
-  int poly_n_ytab = 0;
-  // uniform grid over the packed obstacles for the flag-only point check (kernels_collide.hip, sync_polygon_grid): per cell
-  // the obstacles whose bounding circle or box, padded by poly_grid_pad, reaches the cell
-  rrtx::DevBuf d_poly_grid_start, d_poly_grid_items;
+  rrtx::DevBuf d_poly_tab;          // PolygonTableBlock (block_layout.hpp): the packed tables, one allocation and one upload
+  rrtx::PolyView poly_view;         // ... as the launch sites read them; rewritten by every sync_polygons
+  // uniform grid over the packed obstacles for the flag-only point check (sync_polygon_grid, PolygonGridBlock): per cell
+  rrtx::DevBuf d_poly_grid;         // the obstacles whose bounding circle or box, padded by poly_grid_pad, reaches the cell
   std::vector<double> poly_h_meta, poly_h_bbox;      // host copies of the packed records the grid is built from
   double poly_grid_pad = -1.0;                        // < 0: no grid
   double poly_grid_x0 = 0.0, poly_grid_y0 = 0.0, poly_grid_inv_wx = 0.0, poly_grid_inv_wy = 0.0;
@@ -262,8 +276,6 @@ struct rrtx_ctx {
   // kinds 6 / 7 (polygons moving in time): per obstacle rows of (dx, dy, t), CSR over all m obstacles
   std::vector<int32_t> poly_path_off;
   std::vector<double> poly_path;
-  rrtx::DevBuf d_poly_path_off, d_poly_path;   // packed over the active obstacles like d_poly_off
-  bool poly_has_moving = false;                // an active obstacle of kind 6 or 7 exists
 
   // workspaces
   rrtx::DevBuf ws_q;        // staged queries / points

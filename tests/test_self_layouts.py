@@ -6,7 +6,12 @@ the kernels cannot.
 
 The offsets come from a stand-alone program (tests/self_layouts_print.cpp: its own main, the block descriptions and no
 HIP header) built with the host compiler; a second build with -fsanitize=address,undefined runs as a program of its own
-and must print the same."""
+and must print the same.
+
+The three obstacle-table blocks (SphereTableBlock, PolygonTableBlock, PolygonGridBlock) have no earlier arithmetic to
+be equal to: each table was a buffer of its own.  They are held to their rules instead: every field on a multiple of
+256 bytes, the fields in declaration order and apart once their slack is counted, `bytes` the end of the last field,
+the slack what the separate buffers carried, the fp32 reach groups whole."""
 import os
 import shutil
 import subprocess
@@ -119,3 +124,54 @@ def test_the_layouts_are_aligned_for_their_types(want):
         for (block, field), off in offs.items():
             if field in align:
                 assert off % align[field] == 0, (key, block, field, off)
+
+
+# ---- the obstacle tables ---------------------------------------------------------------------------------------------
+NAS = (0, 1, 7, 8, 9, 64, 65535)
+COUNTS = (0, 1, 300)          # vertices, path rows and ytab entries
+SPHERE_FIELDS = ("rec", "reach", "reach_f", "sample", "radius", "thr_in", "orig")
+POLYGON_FIELDS = ("meta", "off", "vxy", "vslope", "orig", "bbox", "pbox", "ytab", "path_off", "path")
+GRID_FIELDS = ("start", "items")
+
+
+def _tables(tmp_path, name, extra):
+    exe = str(tmp_path / ("tables_" + name))
+    r = subprocess.run([_compiler(), "-std=c++17", "-O1", "-Wall", *extra, SRC, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    cases = [(na, nv, rows, ny) for na in NAS for nv in COUNTS for rows in COUNTS for ny in COUNTS]
+    r = subprocess.run([exe, "tables", *[str(v) for c in cases for v in c]], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, r.stdout[-2000:] + r.stderr
+    lines = r.stdout.splitlines()
+    slack = dict(zip(lines[0].split()[1::2], map(int, lines[0].split()[2::2])))
+    got = {}
+    for line in lines[1:]:
+        block, na, nv, rows, ny, field, off, count, size = line.split()
+        got.setdefault((block, int(na), int(nv), int(rows), int(ny)), []).append((field, int(off), int(count), int(size)))
+    assert sorted({k[1:] for k in got}) == sorted(cases) and len(got) == 3 * len(cases)
+    return slack, got
+
+
+@pytest.mark.parametrize("name, extra", [("plain", []), ("sanitized", ["-g", "-fsanitize=address,undefined",
+                                                                       "-fno-sanitize-recover=all"])])
+def test_obstacle_table_blocks_keep_their_rules(tmp_path, name, extra):
+    slack, got = _tables(tmp_path, name, extra)
+    assert slack == dict(vxy=2, vslope=1, path=3, ytab=1, sph_aux_bytes=64, align=256)
+    for (block, na, nv, rows, ny), fields in got.items():
+        names = tuple(f for f, _, _, _ in fields)
+        assert names == dict(spheres=SPHERE_FIELDS, polygons=POLYGON_FIELDS, grid=GRID_FIELDS)[block] + ("bytes",)
+        end = 0
+        for field, off, count, size in fields[:-1]:
+            assert off % 256 == 0, (block, na, field, off)
+            assert off >= end, (block, na, field, off, end)        # declaration order, apart from the field before
+            end = off + count * size                                # (count includes the slack)
+        assert fields[-1][1] == end, (block, na, fields[-1], end)  # bytes = end of the last field
+        have = {f: (count, size) for f, _, count, size in fields[:-1]}
+        if block == "spheres":
+            want = dict(rec=(4 * na, 8), reach=(4 * na, 8), reach_f=(32 * ((na + 7) // 8), 4), sample=(8 * na, 8),
+                        radius=(na + 64 // 8, 8), thr_in=(na + 64 // 8, 8), orig=(na + 64 // 4, 4))
+        elif block == "polygons":
+            want = dict(meta=(4 * na, 8), off=(na + 1, 4), vxy=(2 * nv + 2, 8), vslope=(nv + 1, 8), orig=(na, 4),
+                        bbox=(4 * na, 8), pbox=(4 * na, 8), ytab=(ny + 1, 8), path_off=(na + 1, 4), path=(3 * rows + 3, 8))
+        else:
+            want = dict(start=(na + 1, 4), items=(nv, 2))
+        assert have == want, (block, na, nv, rows, ny)
