@@ -286,8 +286,10 @@ int rrtx_edges_check_idx(rrtx_ctx *ctx, const int32_t *start_idx, const int32_t 
 /* Obstacle sweep against a device mirror of the planner's directed edges.
  * rrtx_graph_edges_append registers edges start -> end (node indices; what RRTNodeNeighborIterator
  * walks: the out-neighbour edges and the parent edge of every node) and returns the id of the first
- * one; ids are consecutive.  The mirror may be a superset of the live graph (edges the planner has
- * dropped are simply ignored by the caller).  rrtx_obstacle_sweep is the edge loop of addNewObstacle
+ * one; ids are consecutive.  The sweeps and releases tolerate a mirror that is a superset of the live graph (they
+ * only list ids, and the caller ignores those of edges it has dropped); the cost propagation does not, so the edges
+ * the planner culls are dropped on the device with rrtx_graph_edges_cull and removed with rrtx_graph_edges_compact
+ * (below, after rrtx_graph_cost_update_delta).  rrtx_obstacle_sweep is the edge loop of addNewObstacle
  * (R/DRRT_Q.jl:3195-3290): nodes within search_range (= robotRadius + delta + ob.radius) of sphere
  * `obstacle`'s centre -- kdFindWithinRange, root with <= -- and, among the registered edges that
  * START at such a node, those for which explicitEdgeCheck(S, edge, ob) is true.  edge_ids receives
@@ -508,6 +510,47 @@ int rrtx_graph_cost_update(rrtx_ctx *ctx, int root_idx, double *lmc /* n_nodes *
  *     edge ids die with the mirror). */
 int rrtx_graph_cost_update_delta(rrtx_ctx *ctx, int root_idx, int store, int32_t *node, double *lmc, int32_t *parent_edge,
                                  int64_t cap, int64_t *needed, int32_t *passes);
+/* cullCurrentNeighbors over the mirror (R/DRRT_Q.jl:2388-2403), and the removal of what it dropped.
+ * RRT^X bounds every node's degree: whenever a node is rewired or has its rrtLMC recalculated it drops its CURRENT
+ * out-neighbours whose edge.dist exceeds the ball, which shrinks as the tree grows, and keeps its INITIAL ones.
+ * Node indices are insertion order and extend() alone makes edges -- new -> neighbour is the new node's initial
+ * out-neighbour, neighbour -> new the older node's current one -- so A MIRRORED EDGE IS A CURRENT OUT-EDGE OF ITS START
+ * NODE IFF start < end.  That holds for what rrtx_graph_edges_append_selected / _append_lists[_dev] produce (tree lists,
+ * self lists, the closestNode rule) and classifies what rrtx_graph_edges_append registers the same way; a self loop is
+ * never current.
+ * rrtx_graph_edges_cull: cullCurrentNeighbors(node, ball) for the k nodes listed (a node listed twice is fine), or
+ * for every node when nodes is NULL and k is 0.  Every mirrored edge that is not yet culled, whose start node is
+ * listed, with start < end and dist > ball becomes CULLED.  The comparison is IEEE on the edge.dist the mirror holds
+ * (whatever wrote it, in any dimension): a NaN cost is kept, dist == ball is kept, a blocked edge (+Inf) is culled.
+ * A culled edge gets dist = distOriginal = +Inf, is marked as touched for the next rrtx_graph_cost_update exactly as
+ * rrtx_graph_edges_block marks it, and carries a culled flag of its own.  To every other call it is an edge blocked for
+ * good: the next rrtx_graph_cost_update[_delta] orphans the nodes whose parent edge it was and solves again;
+ * rrtx_graph_edges_unblock and the `unblock` of the release calls restore +Inf; until the mirror is compacted the
+ * sweeps and releases may still list its id.  Writing a finite cost to a culled id with rrtx_graph_edges_set_dist
+ * does not clear the flag: the edge relaxes again, and rrtx_graph_edges_compact refuses (RRTX_E_STATE) for as long as
+ * a solve uses it as a parent edge.  *n_culled (may be NULL) = the edges this call culled; the same call again culls
+ * 0.  ball NaN or negative, k < 0, k > 0 with nodes NULL, a node outside the tree: RRTX_E_INVALID, nothing written.  An
+ * empty mirror, or k == 0 with nodes given: RRTX_OK and 0.
+ * WHAT THIS IS NOT: inside the reference's queue loop a finite ball depends on pop order -- a node can be improved
+ * through a long edge before it is itself popped and culled.  The device offers the order-independent object, the
+ * fixed point over the culled graph (cull, then rrtx_graph_cost_update), and does not claim equality with
+ * reduceInconsistency run with a finite hyberBallRad.
+ * rrtx_graph_edges_compact removes the culled edges.  Survivors keep their order: new id = old id - (culled edges
+ * with a lower id); start, end, dist, distOriginal and a pending touched mark move together, no survivor is culled,
+ * rrtx_graph_edges_count shrinks and the next append starts there.  remap (may be NULL; else remap_cap >= the edge count
+ * at entry, RRTX_E_CAPACITY with nothing changed otherwise) receives remap[old] = new, -1 for a removed edge.  The
+ * kept solver state is carried over: the parent edges are renumbered on the device, so is the baseline of
+ * rrtx_graph_cost_update_delta -- a baseline entry whose edge was removed becomes a value no id equals, and that node
+ * is reported by the next delta -- and the next solve rebuilds its in-edge index.  PRECONDITION, decided on the
+ * device: when a kept solve still has a culled edge as some node's parent edge (compaction straight after a cull; a
+ * culled id revived with set_dist) the call is RRTX_E_STATE -- run rrtx_graph_cost_update first -- and nothing
+ * changes.  Without a kept solve it always goes through.  *n_removed (may be NULL) = edges removed.
+ * rrtx_graph_edges_get_culled: culled[i] = 1 when edge first_id + i is culled, else 0 (rrtx_graph_edges_get cannot
+ * tell a cull from set_dist(+Inf)); a range outside the mirror is RRTX_E_INVALID.  rrtx_graph_edges_clear clears the
+ * flags with the mirror.  The three calls keep the lists of rrtx_extend_select (HOLD RULE below). */
+int rrtx_graph_edges_cull(rrtx_ctx *ctx, double ball, const int32_t *nodes, int64_t k, int64_t *n_culled);
+int rrtx_graph_edges_compact(rrtx_ctx *ctx, int32_t *remap, int64_t remap_cap, int64_t *n_removed);
+int rrtx_graph_edges_get_culled(rrtx_ctx *ctx, int64_t first_id, int64_t n, uint8_t *culled);
 /* explicitPointCheck (R/DRRT_Q.jl:1520-1556; quick=0: explicitPointCheck3D,
  * :1558-1590).  unsafe[i] in {0,1}; clearance[i] = the returned certificate
  * (0.0 when unsafe); clearance may be NULL when only the flag is wanted (the

@@ -894,6 +894,46 @@ function unblockEdges(tree::HipTree, ids::Vector{Int32})
       (Ptr{Cvoid}, Ptr{Int32}, Int64), tree.ctx, ids, length(ids)))
 end
 
+# cullCurrentNeighbors(node, hyberBallRad) (R/DRRT_Q.jl:2388-2403) over the registered edges, for the nodes given
+# (nothing: every node of the tree): a node's current out-neighbour edges -- registered edges that start at it and end at
+# a node inserted later -- whose edge.dist exceeds the ball are dropped (dist = distOriginal = Inf from then on, touched
+# for the next costUpdateDelta); its initial ones stay.  Returns the number of edges dropped by this call.
+function cullCurrentNeighbors(tree::HipTree, nodes, hyberBallRad::Float64)
+  culled = Ref{Int64}(0)
+  if nodes === nothing
+    rrtx_check(tree, ccall((:rrtx_graph_edges_cull, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Cdouble, Ptr{Int32}, Int64, Ref{Int64}), tree.ctx, hyberBallRad, Ptr{Int32}(C_NULL), 0, culled))
+  else
+    which = Int32[tree.indexOf[nd] for nd in nodes]
+    push!(which, Int32(0))                    # (an empty list is still a list: a pointer that is not NULL)
+    GC.@preserve which rrtx_check(tree, ccall((:rrtx_graph_edges_cull, LIBRRTX), Cint,
+        (Ptr{Cvoid}, Cdouble, Ptr{Int32}, Int64, Ref{Int64}), tree.ctx, hyberBallRad, which, length(which) - 1, culled))
+  end
+  return Int(culled[])
+end
+
+# Removes the edges cullCurrentNeighbors dropped; the others keep their order.  Returns (remap, edges removed):
+# remap[old id + 1] = new id (0-based), -1 for a removed edge -- the caller renumbers the ids it holds with it; the
+# device renumbers the parent edges and the baseline costUpdateDelta reports against.  Run costUpdateDelta between a cull
+# and this: the device refuses (RRTX_E_STATE) while a dropped edge is still some node's parent edge.
+function compactRegisteredEdges(tree::HipTree)
+  ne = Int(ccall((:rrtx_graph_edges_count, LIBRRTX), Int64, (Ptr{Cvoid},), tree.ctx))
+  remap = Vector{Int32}(undef, max(ne, 1))
+  removed = Ref{Int64}(0)
+  GC.@preserve remap rrtx_check(tree, ccall((:rrtx_graph_edges_compact, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Ptr{Int32}, Int64, Ref{Int64}), tree.ctx, remap, length(remap), removed))
+  return remap[1:ne], Int(removed[])
+end
+
+# 1 for every registered edge of [firstId, firstId + n) that cullCurrentNeighbors dropped (registeredEdges cannot tell
+# a dropped edge from one whose cost was set to Inf)
+function culledEdges(tree::HipTree, firstId::Int, n::Int)
+  out = Vector{UInt8}(undef, max(n, 1))
+  GC.@preserve out rrtx_check(tree, ccall((:rrtx_graph_edges_get_culled, LIBRRTX), Cint,
+      (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}), tree.ctx, firstId, n, out))
+  return out[1:n]
+end
+
 # The state propogateDescendants + reduceInconsistency (R/DRRT_Q.jl:2703-2817) reach with changeThresh = 0.0
 # once the queue is empty: rrtLMC of every node, and the registered id of its parent edge (-1: root / orphan).
 # The caller writes them back: node.rrtLMC = node.rrtTreeCost = lmc[i+1]; makeParentOf along edge parent[i+1].

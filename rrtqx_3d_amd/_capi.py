@@ -134,6 +134,9 @@ SYMBOLS = [
     ("rrtx_graph_cost_update", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("rrtx_graph_cost_update_dev", C.c_int, [_VP, C.c_int, _VP, _VP]),
     ("rrtx_graph_cost_update_delta", C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int64, c_int64_p, _VP]),
+    ("rrtx_graph_edges_cull", C.c_int, [_VP, C.c_double, _VP, C.c_int64, c_int64_p]),
+    ("rrtx_graph_edges_compact", C.c_int, [_VP, _VP, C.c_int64, c_int64_p]),
+    ("rrtx_graph_edges_get_culled", C.c_int, [_VP, C.c_int64, C.c_int64, _VP]),
     ("rrtx_set_dubins_velocity", C.c_int, [_VP, C.c_double, C.c_double]),
     ("rrtx_dubins_steer_full", C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_double, _VP, _VP, _VP, _VP, _VP]),
     ("rrtx_dubins_edges_check", C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_double, C.c_double, _VP, _VP, _VP, _VP]),

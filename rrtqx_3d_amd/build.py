@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, "librrtx_hip.so")
 LIB_CLK = os.path.join(HERE, "librrtx_hip_clk.so")
 
 SOURCES = ["rrtx_capi.hip", "kernels_link.hip", "kernels_nn.hip", "kernels_finish.hip", "kernels_nearest.hip", "kernels_slab.hip", "kernels_sweep.hip", "kernels_graph.hip", "kernels_collide.hip",
-           "kernels_dubins.hip", "kernels_select.hip", "kernels_target.hip", "kernels_self.hip"]
+           "kernels_dubins.hip", "kernels_select.hip", "kernels_target.hip", "kernels_self.hip", "kernels_cull.hip"]
 HEADERS = ["rrtx_internal.hpp", "exact_math.hpp", "nn_device.hpp", "collide_device.hpp", "wave_device.hpp", "list_walk.hpp", "block_layout.hpp", os.path.join("..", "..", "include", "rrtx.h"),
            os.path.join("..", "..", "include", "rrtx_detmath.h")]
 

@@ -866,6 +866,38 @@ class Context:
                                                    _capi._ptr(end), _capi._ptr(dist), _capi._ptr(dist0)))
         return start, end, dist, dist0
 
+    def graph_edges_cull(self, ball: float, nodes=None) -> int:
+        """rrtx_graph_edges_cull: cullCurrentNeighbors(node, ball) over the mirror for the nodes listed (None: every
+        node) -- every edge with start listed, start < end and dist > ball becomes culled (dist = distOriginal = +Inf,
+        touched for the next cost update).  Returns the number of edges this call culled."""
+        culled = C.c_int64()
+        if nodes is None:
+            ia, k = None, 0
+        else:
+            given = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+            k = given.shape[0]
+            ia = given if k else np.zeros(1, dtype=np.int32)      # (an empty list is still a list: a pointer that is not NULL)
+        self._check(self._lib.rrtx_graph_edges_cull(self._h, float(ball), _capi._ptr(ia), k, C.byref(culled)))
+        return culled.value
+
+    def graph_edges_compact(self, want_remap: bool = True):
+        """rrtx_graph_edges_compact: the culled edges leave the mirror, survivors keep their order.  Returns
+        (remap or None, n_removed): remap[old id] = new id, -1 for a removed edge.  RRTX_E_STATE when a kept cost solve
+        still uses a culled edge as a parent edge (run graph_cost_update first)."""
+        ne = self.n_graph_edges
+        remap = np.empty(ne, dtype=np.int32) if want_remap else None
+        removed = C.c_int64()
+        self._check(self._lib.rrtx_graph_edges_compact(self._h, _capi._ptr(remap) if ne else None, ne, C.byref(removed)))
+        return remap, removed.value
+
+    def graph_edges_culled(self, first_id: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """rrtx_graph_edges_get_culled: one byte per edge of [first_id, first_id + n) (n None: to the end of the mirror),
+        1 = culled"""
+        n = self.n_graph_edges - int(first_id) if n is None else int(n)
+        out = np.empty(max(n, 0), dtype=np.uint8)
+        self._check(self._lib.rrtx_graph_edges_get_culled(self._h, int(first_id), n, _capi._ptr(out)))
+        return out
+
     def _edge_ids_call(self, fn, edge_ids):
         ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
         self._check(fn(self._h, _capi._ptr(ids), ids.shape[0]))

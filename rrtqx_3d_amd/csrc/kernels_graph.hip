@@ -34,7 +34,7 @@ namespace rrtx {
 namespace {
 
 constexpr unsigned long long kInfBits = 0x7ff0000000000000ull;
-constexpr int32_t kNoParent = 0x7fffffff;
+constexpr int32_t kNoParent = kNoParentEdge;
 constexpr int kGroupMax = 32;        // most passes launched between two reads of the "changed" flags
 constexpr int kFlagInts = 64;        // [0, kGroupMax): pass flags, 40: orphan roots seen, 41: a parent edge of cost 0, 42: seed pass
 constexpr int kFlagOrphans = 40, kFlagZeroCost = 41, kFlagSeed = 42;
@@ -515,9 +515,10 @@ static int graph_cost_impl(rrtx_ctx *ctx, int root, bool update, double *lmc_dev
     if (host_flags[kFlagZeroCost]) resume = false;
   }
   span_begin(ctx, KF_EDGES);
-  // the CSR of in-edges: rebuilt for a full solve, or when the tail of newer edges has grown large
+  // the CSR of in-edges: rebuilt for a full solve, when there is none (the first solve; after a compaction of the
+  // mirror, whose update resumes), or when the tail of newer edges has grown large
   const long long tail = ne - gc.in_ne;
-  if (gc.in_ne > ne || (!resume && (tail > 0 || gc.in_nn == 0)) || tail > 262144 + gc.in_ne / 8) {
+  if (gc.in_ne > ne || gc.in_nn == 0 || (!resume && tail > 0) || tail > 262144 + gc.in_ne / 8) {
     int rc = build_in_csr(ctx, n, ne);
     if (rc) return rc;
   }

@@ -241,6 +241,8 @@ int grow_edges(rrtx_ctx *ctx, int64_t n) {
   if ((rc = regrow(ctx, ctx->ge_dist, nc, ctx->ge_n))) return rc;
   if ((rc = regrow(ctx, ctx->ge_dist0, nc, ctx->ge_n))) return rc;
   if ((rc = regrow(ctx, ctx->ge_dirty, nc, ctx->ge_n))) return rc;
+  if ((rc = regrow(ctx, ctx->ge_culled, nc, ctx->ge_n))) return rc;
+  RRTX_HIP(ctx, hipMemsetAsync(ctx->ge_culled + ctx->ge_n, 0, (size_t)(nc - ctx->ge_n), ctx->stream));   // no new edge is culled
   ctx->ge_cap = nc;
   return RRTX_OK;
 }
@@ -1151,6 +1153,7 @@ int64_t rrtx_graph_edges_count(rrtx_ctx *ctx) { return ctx ? ctx->ge_n : 0; }
 
 int rrtx_graph_edges_clear(rrtx_ctx *ctx) {
   CHECK_CTX_KEEP(ctx);
+  if (ctx->ge_n > 0) RRTX_HIP(ctx, hipMemsetAsync(ctx->ge_culled, 0, (size_t)ctx->ge_n, ctx->stream));
   ctx->ge_n = 0;
   graph_cost_forget(ctx);
   graph_delta_forget(ctx);
@@ -1207,6 +1210,40 @@ int rrtx_graph_edges_block(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
 int rrtx_graph_edges_unblock(rrtx_ctx *ctx, const int32_t *edge_ids, int64_t n) {
   CHECK_CTX_KEEP(ctx);
   return graph_edges_block_host(ctx, "graph_edges_unblock", true, edge_ids, n);
+}
+
+// ---- cullCurrentNeighbors over the mirror, and its compaction (kernels_cull.hip) --------------------------------
+int rrtx_graph_edges_cull(rrtx_ctx *ctx, double ball, const int32_t *nodes, int64_t k, int64_t *n_culled) {
+  CHECK_CTX_KEEP(ctx);
+  if (n_culled) *n_culled = 0;
+  if (!(ball >= 0.0)) return fail(ctx, RRTX_E_INVALID, "graph_edges_cull: the ball is negative or NaN");
+  if (k < 0 || (k > 0 && !nodes)) return fail(ctx, RRTX_E_INVALID, "graph_edges_cull: bad arguments");
+  for (int64_t i = 0; nodes && i < k; ++i)
+    if (nodes[i] < 0 || nodes[i] >= ctx->n_nodes)
+      return fail(ctx, RRTX_E_INVALID, "graph_edges_cull: node %d outside [0, %lld)", nodes[i], (long long)ctx->n_nodes);
+  if (ctx->ge_n == 0 || (nodes && k == 0)) return RRTX_OK;
+  return launch_edges_cull(ctx, ball, nodes, k, n_culled);
+}
+
+int rrtx_graph_edges_compact(rrtx_ctx *ctx, int32_t *remap, int64_t remap_cap, int64_t *n_removed) {
+  CHECK_CTX_KEEP(ctx);
+  if (n_removed) *n_removed = 0;
+  if (remap && remap_cap < ctx->ge_n)
+    return fail(ctx, RRTX_E_CAPACITY, "graph_edges_compact: remap has room for %lld of %lld edge ids", (long long)remap_cap,
+                (long long)ctx->ge_n);
+  if (ctx->ge_n == 0) return RRTX_OK;
+  return launch_edges_compact(ctx, remap, n_removed);
+}
+
+int rrtx_graph_edges_get_culled(rrtx_ctx *ctx, int64_t first_id, int64_t n, uint8_t *culled) {
+  CHECK_CTX_KEEP(ctx);
+  if (n < 0 || first_id < 0 || first_id > ctx->ge_n || n > ctx->ge_n - first_id || (n > 0 && !culled))
+    return fail(ctx, RRTX_E_INVALID, "graph_edges_get_culled: edges [%lld, %lld) of %lld", (long long)first_id,
+                (long long)(first_id + n), (long long)ctx->ge_n);
+  if (n == 0) return RRTX_OK;
+  RRTX_HIP(ctx, copy_out(ctx, culled, ctx->ge_culled + first_id, (size_t)n));
+  RRTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RRTX_OK;
 }
 
 // ---- neighbour lists -> mirror edges on the device (kernels_link.hip) -------------------------------------------

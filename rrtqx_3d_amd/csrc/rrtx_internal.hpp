@@ -127,6 +127,11 @@ struct PinnedBuf : Owned<hipHostFree> {
 static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_constructible<DevArray<double>>::value &&
               !std::is_copy_constructible<PinnedBuf>::value, "an allocation has one owner");
 
+// a node without a parent edge in GraphCost::parent (the root, an orphan); and what rrtx_graph_edges_compact leaves in
+// GraphCost::rep_parent for a parent edge it removed: neither -1 (none) nor an edge id, so the next delta reports the node
+constexpr int32_t kNoParentEdge = 0x7fffffff;
+constexpr int32_t kRemovedEdge = -2;
+
 // cost propagation over the edge mirror (kernels_graph.hip): the state of the last solve stays on the device
 struct GraphCost {
   DevBuf lmc, parent, stamp, flags, orph, anc, ids;
@@ -314,7 +319,7 @@ struct rrtx_ctx {
   rrtx::DevArray<int32_t> ge_start, ge_end;
   rrtx::DevArray<double> ge_dist;   // edge.dist of every mirrored edge (Inf = blocked); SimpleEdge cost by default
   rrtx::DevArray<double> ge_dist0;  // edge.distOriginal: what append / set_dist wrote last (block leaves it alone)
-  rrtx::DevArray<uint8_t> ge_dirty; // edge cost touched since the last cost solve (set_dist / block)
+  rrtx::DevArray<uint8_t> ge_dirty; // edge cost touched since the last cost solve (set_dist / block / cull)
   rrtx::GraphCost gc;               // cost propagation state (kernels_graph.hip)
   int64_t ge_n = 0, ge_cap = 0;
   rrtx::DevBuf ws_sweep_mark, ws_sweep_flag, ws_sweep_cnt, ws_sweep_start;
@@ -376,6 +381,13 @@ struct rrtx_ctx {
   int last_tile_form = 0;           // rrtx_last_tile_form: 0 none, 1 looped, 2 straight
   int64_t last_sweep_candidates = 0;
   int last_visit_slices = 0;        // entries of ws_ev_cnt holding its per-wave chunk counts
+
+  // cull and compaction of the edge mirror (kernels_cull.hip).  Last in the context, so that no member above moves:
+  // a byte per mirrored edge beside ge_dirty (1: rrtx_graph_edges_cull dropped the edge; zero at and beyond ge_n), and
+  // the workspaces: a byte per node (1 = listed) and the staged list, counts per workgroup and their scan,
+  // remap[old id], {a culled parent edge, the new solved_edges}
+  rrtx::DevArray<uint8_t> ge_culled;
+  rrtx::DevBuf ws_cull_map, ws_cull_nodes, ws_cull_cnt, ws_cull_pos, ws_cull_remap, ws_cull_res;
 
   ~rrtx_ctx();                      // what is not memory (rrtx_capi.hip); the members then release what they own
 };
@@ -606,6 +618,11 @@ int launch_graph_touch(rrtx_ctx *ctx, long long first, long long n);
 // edge.dist = Inf (restore = false) or edge.distOriginal (restore = true) for the edges ids[i], all in [0, ge_n)
 int launch_graph_block(rrtx_ctx *ctx, bool restore, const int32_t *ids_host, long long n);      // synchronises
 int launch_graph_block_dev(rrtx_ctx *ctx, bool restore, const int32_t *ids_dev, long long n);   // ids already on the device
+// cullCurrentNeighbors over the mirror and the removal of what it culled (kernels_cull.hip); both synchronise.
+// cull: nodes_host null = every node, else k validated node indices; the mirror is not empty.  compact: remap_host null
+// or room for ge_n ids; RRTX_E_STATE with nothing changed when a kept solve has a culled parent edge.
+int launch_edges_cull(rrtx_ctx *ctx, double ball, const int32_t *nodes_host, long long k, int64_t *n_culled);
+int launch_edges_compact(rrtx_ctx *ctx, int32_t *remap_host, int64_t *n_removed);
 int launch_graph_cost(rrtx_ctx *ctx, int root, bool update, double *lmc_dev, int32_t *parent_dev, int *passes_out);
 void graph_cost_forget(rrtx_ctx *ctx);
 int launch_graph_delta(rrtx_ctx *ctx, int root, bool store, int32_t *node_dev, double *lmc_dev, int32_t *par_dev, long long cap,

@@ -957,6 +957,30 @@ def unblockEdges(KD: HipTree, ids):
     KD.ctx.graph_edges_unblock(ids)
 
 
+def cullCurrentNeighbors(KD: HipTree, nodes: Optional[Iterable[RRTNode]], hyberBallRad_: float) -> int:
+    """cullCurrentNeighbors(node, hyberBallRad) (R/DRRT_Q.jl:2388-2403) over the registered edges, for every node of
+    `nodes` (None: every node of the tree): the node's current out-neighbour edges -- registered edges that start at it
+    and end at a node inserted later -- whose edge.dist exceeds the ball are dropped; its initial ones stay.  A dropped
+    edge reads dist = distOriginal = Inf from then on and orphans what hung on it at the next costToRoot update /
+    costUpdateDelta; compactRegisteredEdges removes it.  Returns the number of edges dropped by this call."""
+    return KD.ctx.graph_edges_cull(hyberBallRad_, None if nodes is None else [nd.index for nd in nodes])
+
+
+def compactRegisteredEdges(KD: HipTree) -> Tuple[np.ndarray, int]:
+    """Removes the edges cullCurrentNeighbors dropped; the others keep their order.  Returns (remap, edges removed):
+    remap[old id] = new id, -1 for a removed edge.  This module keeps no registered id of its own -- the ids
+    registerEdges* and the sweeps return live with the caller, who renumbers them through remap; the device renumbers
+    the parent edges and the baseline costUpdateDelta reports against.  Run a cost update between a cull and this (the
+    device refuses while a dropped edge is still some node's parent edge)."""
+    return KD.ctx.graph_edges_compact()
+
+
+def culledEdges(KD: HipTree, first_id: int = 0, n: Optional[int] = None) -> np.ndarray:
+    """1 for every registered edge of [first_id, first_id + n) (n None: to the last one) that cullCurrentNeighbors
+    dropped: registeredEdges cannot tell a dropped edge from one whose cost was set to Inf."""
+    return KD.ctx.graph_edges_culled(first_id, n)
+
+
 def registerEdgesFromLists(KD: HipTree, lists: dict, nodeOf, selfLists: bool = False) -> Tuple[int, int, np.ndarray]:
     """What extend() links for a batch (R/DRRT_Q.jl:2560-2640), registered on the device from the host lists of
     extend_candidates* (a dict with offsets, idx, hit_out, hit_in and cost, or cost_out / cost_in for Dubins lists):
