@@ -289,7 +289,9 @@ __global__ __launch_bounds__(256) void nn_confirm_kernel(ConfirmArgs a, const in
 // index, positions base + 8 lane .. + 7; 2: lane-major GROUPS, every lane its own eight consecutive
 // positions p_lane .. + 7 (lanes outside the wave mask vm hold nothing and file nothing).
 // LQ: the records of copies q0 .. q0 + 15 come from the tile's LDS table lq (padded with never_pass records to 16)
-// instead of copies_f; they are moved to scalar registers like the scalar loads' results.
+// instead of copies_f.  1: they are moved to scalar registers like the scalar loads' results (four v_readfirstlane
+// per record); 2: they stay in the vector registers the LDS reads return (every lane holds the same record; the
+// packed FMAs select the lane's own copy of the component), which saves those moves.
 template <int D>
 __device__ __forceinline__ typename QRecFT<D>::type uniform_qrecf(const typename QRecFT<D>::type &f) {
   typename QRecFT<D>::type u = f;
@@ -300,7 +302,7 @@ __device__ __forceinline__ typename QRecFT<D>::type uniform_qrecf(const typename
   u.thr = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f.thr)));
   return u;
 }
-template <int D, int MODE, bool LQ = false>
+template <int D, int MODE, int LQ = 0, bool ONE_END_TEST = false>
 __device__ __forceinline__ void scan_chunk_f32(const float *__restrict__ fx, const float *__restrict__ fy,
                                                const float *__restrict__ fz, const float *__restrict__ fw,
                                                const float *__restrict__ fpp, const int base, const int node_end,
@@ -335,9 +337,13 @@ __device__ __forceinline__ void scan_chunk_f32(const float *__restrict__ fx, con
         w[4 * v] = 0.f; w[4 * v + 1] = 0.f; w[4 * v + 2] = 0.f; w[4 * v + 3] = 0.f;
       }
     }
+    // (ONE_END_TEST: only the lanes of the tree's last group can reach beyond node_end, so the wave asks once
+    // whether any of its lanes does before it tests the eight positions one by one)
+    if (!ONE_END_TEST || __ballot((int)p0 + (kScanFU - 1) >= node_end) != 0ull) {
 #pragma unroll
-    for (int u = 0; u < kScanFU; ++u)
-      if ((int)p0 + u >= node_end) { x[u] = 0.f; y[u] = 0.f; z[u] = 0.f; w[u] = 0.f; pp[u] = kInf; }
+      for (int u = 0; u < kScanFU; ++u)
+        if ((int)p0 + u >= node_end) { x[u] = 0.f; y[u] = 0.f; z[u] = 0.f; w[u] = 0.f; pp[u] = kInf; }
+    }
   } else {
 #pragma unroll
     for (int u = 0; u < kScanFU; ++u) {
@@ -358,7 +364,8 @@ __device__ __forceinline__ void scan_chunk_f32(const float *__restrict__ fx, con
     typename QRecFT<D>::type c[kQPI];
 #pragma unroll
     for (int k = 0; k < kQPI; ++k) {
-      if constexpr (LQ) c[k] = uniform_qrecf<D>(lq[q - q0 + k]);
+      if constexpr (LQ == 2) c[k] = lq[q - q0 + k];
+      else if constexpr (LQ == 1) c[k] = uniform_qrecf<D>(lq[q - q0 + k]);
       else c[k] = copies_f[q + k];
     }
     unsigned long long mk[kQPI];      // wave masks stay on the SALU (no short-circuit control flow)
@@ -691,6 +698,15 @@ __device__ __forceinline__ void load_qhist16(const int *__restrict__ qhist, int 
 // Both loop bodies are the same text for both forms; only the loop heads, the list reset between passes and the
 // barrier before the next tile differ.  What the looped form hoists out of the two loops and keeps (or spills) for
 // the whole kernel is then computed where it is used.
+//
+// The lean pass over the straight form ("tile kernel, lean"): same launches, buffers, records, atomics,
+// barriers and fences; fewer instructions and fewer dependent round trips on the path of wave 0, which every other
+// wave of the workgroup waits for.  A measuring build puts cuts back one at a time (-DRRTX_TILE_PUT_BACK=mask,
+// profiles/tile_lean_ablation.txt): 1 the two-level placement search, 2 the screen's copy records in vector registers,
+// 4 one test per wave for positions beyond the last node, 8 the grid description requested before the reach.
+#ifndef RRTX_TILE_PUT_BACK
+#define RRTX_TILE_PUT_BACK 0
+#endif
 template <int D, bool EXT, bool SL, bool ONE>
 __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     const float *__restrict__ fx, const float *__restrict__ fy, const float *__restrict__ fz,
@@ -700,6 +716,10 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     const ConfirmArgs a, const ConfirmArgs *__restrict__ ca, const TileGrid tg, const ExtendDev x,
     int *__restrict__ visits, const int n_copies_known, const TilePlace tp) {
   __shared__ TileLds<D> sm;
+  constexpr bool kLeanSearch = ONE && !(RRTX_TILE_PUT_BACK & 1);
+  constexpr int kLQ = !SL ? 0 : (ONE && !(RRTX_TILE_PUT_BACK & 2)) ? 2 : 1;
+  constexpr bool kGridEarly = ONE && !(RRTX_TILE_PUT_BACK & 8);
+  constexpr bool kOneEndTest = ONE && !(RRTX_TILE_PUT_BACK & 4);
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int part = blockIdx.x % n_parts;
@@ -723,6 +743,12 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     int wn = 0;                             // wave-uniform: entries in the slice
 
     RRTX_TILE_CLK(0);
+    // (straight form) wave 0 asks for the grid description of step 2a early: the scalar load is under way while the
+    // wave waits for its copies' counters and records and works out the reach, instead of starting behind the
+    // reach's barrier.  It is issued where the wave next waits for vector loads, not LDS reads (which would wait
+    // for the scalar load as well): between search and counters with the slot table, else before the copies.
+    SlabParams sp_early = {};
+    const bool sp_now = kGridEarly && tg.groups && min(n_chunks, tg.n_sorted_chunks) > 0;
     int slot = -1;                          // SL, wave 0, lane l < q1 - q0: table slot of the copy at position q0 + l
     if constexpr (SL) {
       // ---- 0. placement: which copies hold positions [q0, q1) of the bucket order.  Every thread adds up its
@@ -749,6 +775,7 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
       if (wave == 0) {
         const int pos = q0 + lane;
         int rk = -1, bk = 0;
+        int T = 0, p = 0;
         if (pos < q1) {
           const int w1 = sm.wcnt[0], w2 = w1 + sm.wcnt[1], w3 = w2 + sm.wcnt[2];
           // start of thread T's buckets (non-decreasing in T); the last T with start <= pos holds pos
@@ -756,11 +783,38 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
             const int w = T >> 6;
             return sm.list[kTileB + T] + (w == 0 ? 0 : (w == 1 ? w1 : (w == 2 ? w2 : w3)));
           };
-          int T = 0;
+          if constexpr (kLeanSearch) {
+            // two levels of sixteen: the fifteen starts at T = 16, 32, ..., 240 are read together (one LDS round trip,
+            // addresses and wave sums known at compile time), then the fifteen inside that block of sixteen (one
+            // wave's, since 16 divides 64).  The starts do not decrease, so counting those <= pos finds the last one.
 #pragma unroll
-          for (int st = 128; st > 0; st >>= 1)
-            if (start_of(T + st) <= pos) T += st;
-          int p = start_of(T);
+            for (int k = 1; k < 16; ++k) {
+              const int s = sm.list[kTileB + 16 * k] + (k < 4 ? 0 : (k < 8 ? w1 : (k < 12 ? w2 : w3)));
+              T += (s <= pos) ? 16 : 0;
+            }
+            const int w = T >> 6, wsum = w == 0 ? 0 : (w == 1 ? w1 : (w == 2 ? w2 : w3));
+            const int *blk16 = &sm.list[kTileB + T];
+            const int in_wave = pos - wsum;
+            p = blk16[0];
+            int inside = 0;
+#pragma unroll
+            for (int k = 1; k < 16; ++k) {
+              const int s = blk16[k];
+              const bool le = s <= in_wave;
+              inside += le ? 1 : 0;
+              p = le ? s : p;
+            }
+            T += inside;
+            p += wsum;
+          } else {
+#pragma unroll
+            for (int st = 128; st > 0; st >>= 1)
+              if (start_of(T + st) <= pos) T += st;
+            p = start_of(T);
+          }
+        }
+        if (sp_now) sp_early = *tg.sp;
+        if (pos < q1) {
           const int b0 = min(T * per, tp.n_buckets), b1 = min(b0 + per, tp.n_buckets);
           int h[16];
           load_qhist16(tp.qhist, per, b0, b1, h);
@@ -804,6 +858,9 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
     if (wave == 0) {
       double lo = __builtin_inf(), hi = -__builtin_inf(), ylo = __builtin_inf(), yhi = -__builtin_inf();
       double zlo = __builtin_inf(), zhi = -__builtin_inf();
+      if constexpr (!SL) {
+        if (sp_now) sp_early = *tg.sp;
+      }
       if constexpr (SL) {
         if (lane >= q1 - q0 && lane < kTileB) sm.cf[lane] = never_pass_qrecf<D>();   // padding of the screen's reads
       }
@@ -881,7 +938,9 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
             //      x and y: slab_of is monotone).  Lane = cell within reach, in position order; a group
             //      shared by two runs is listed once (prefix maximum of the runs' last groups).  Groups
             //      of whole sorted chunks only: the chunk the sorted part ends in goes by extent below.
-            const SlabParams sp = *tg.sp;
+            // sp_early was loaded under sp_now, which is this branch's condition only with cb == 0 and ce == n_chunks
+            static_assert(!kGridEarly || ONE, "the early grid description is the straight form's");
+            const SlabParams sp = kGridEarly ? sp_early : *tg.sp;
             const int Kz = tg.kz;
             const int cx0 = slab_of(lo, sp.x0, sp.inv_wx, sp.Kx), cx1 = slab_of(hi, sp.x0, sp.inv_wx, sp.Kx);
             const int cy0 = slab_of(ylo, sp.y0, sp.inv_wy, sp.Ky), cy1 = slab_of(yhi, sp.y0, sp.inv_wy, sp.Ky);
@@ -999,8 +1058,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
               const TileEmit<D, EXT> emit_now{sm, a.hs, SL ? nullptr : a.meta, x, q0};
               drain_slice_to<D, true>(mine, wn, n_nodes, a, emit_now, sm.cp, q0);
             }
-            scan_chunk_f32<D, 2, SL>(fx, fy, fz, fw, fpp, 0, n_nodes, copies_f, q0, q1, mine, wn, p_lane, __ballot(valid),
-                                     sm.cf);
+            scan_chunk_f32<D, 2, kLQ, kOneEndTest>(fx, fy, fz, fw, fpp, 0, n_nodes, copies_f, q0, q1, mine, wn, p_lane,
+                                                   __ballot(valid), sm.cf);
             visited += min(64, G - 64 * u);
           }
         }
@@ -1018,8 +1077,8 @@ __global__ __launch_bounds__(kScanThreads, 4) void nn_tile_kernel(
             const TileEmit<D, EXT> emit_now{sm, a.hs, SL ? nullptr : a.meta, x, q0};
             drain_slice_to<D, true>(mine, wn, n_nodes, a, emit_now, sm.cp, q0);
           }
-          scan_chunk_f32<D, 1, SL>(fx, fy, fz, fw, fpp, chunk * kChunkF, n_nodes, copies_f, q0, q1, mine, wn, 0u, ~0ull,
-                                   sm.cf);
+          scan_chunk_f32<D, 1, kLQ, kOneEndTest>(fx, fy, fz, fw, fpp, chunk * kChunkF, n_nodes, copies_f, q0, q1, mine, wn,
+                                                 0u, ~0ull, sm.cf);
           visited += kChunkF / 8;
         }
         if constexpr (ONE) break;

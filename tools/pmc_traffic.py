@@ -16,12 +16,17 @@ d, kern, line = sys.argv[1], sys.argv[2], sys.argv[3]
 bench = json.loads(open(line).read().strip().splitlines()[-1])
 
 
+# the name as bench.py asks for it ("nn_tile_kernel<3, true>"); the kernel's template list may have grown since
+want = kern.replace(" ", "")
+want = want[:-1] if want.endswith(">") else want
+
+
 def get(fname, counter):
     p = os.path.join(d, fname)
     if not os.path.exists(p):
         return None, 0
     for r in csv.DictReader(open(p)):
-        if r["counter"] == counter and kern.replace(" ", "") in r["kernel"].replace(" ", ""):
+        if r["counter"] == counter and want in r["kernel"].replace(" ", ""):
             return float(r["avg_per_launch"]), int(r["launches"])
     return None, 0
 
